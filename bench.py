@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of closest_hit on the 1M-triangle instanced TLAS (BASELINE.json config C3).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step` = wall time of the K timed steps / K).
+--full adds, after the same steps, the roofline, the CPU baseline with its bit-exact check against the last timed step, and the extras
+(other workloads, sizes and options; --no-cpu-baseline / --no-extras leave parts out).  --dump-outputs DIR writes the hit records of the
+last timed step (dump_outputs); the rays of every step are seeded, so two runs with the same arguments trace the same rays.
 
 A step = one closest_hit pass over one batch of 4 194 304 synthetic primary rays (2048 x 2048 pinhole) against
 256 transformed instances of one 4 096-triangle BLAS (1 048 576 triangles), rays and scene already resident in
@@ -49,6 +54,14 @@ COUNTS_FILE = os.path.join("profiles", "c3_reference_counts.json")  # reference-
 # Fallback when the counts file is missing (same numbers, measured by the oracle in round 1)
 C3_NODE_FETCHES_PER_RAY = 33.006
 C3_INST_ENTRIES_PER_RAY = 1.922
+METRIC = "Mrays/s closest_hit (1M-tri TLAS)"
+MAX_FRESH_BATCHES = 512   # ray buffers the timed path keeps resident (134 MB each at the default size); more launches than that take them in rotation
+# --dump-outputs: at most this many rays' hit records (52 B each as float32 / float64: 55 MB), a fixed sample drawn with this seed
+DUMP_SAMPLE = 1 << 20
+DUMP_SEED = 0xC3D0
+# u32 fields are written as float64 (exact), f32 fields as float32; the padding word is left out
+DUMP_FIELDS = (("hit", np.float64), ("t", np.float32), ("primitive_id", np.float64), ("instance_custom_index", np.float64),
+               ("bary_u", np.float32), ("bary_v", np.float32), ("instance_id", np.float64))
 
 
 def kernel_fingerprint():
@@ -203,6 +216,31 @@ def make_workload_roofline(entry, launch_ms, n_rays, fingerprint_ok, source=WORK
     return out
 
 
+def print_line(out):
+    """The ONE JSON line, last thing on stdout.  RCCL prints its version banner through C stdio, which would otherwise be flushed at exit,
+    AFTER the JSON line: flushed first."""
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except Exception:  # noqa: BLE001
+        pass
+    sys.stdout.flush()
+    print(json.dumps(out), flush=True)
+
+
+def dump_outputs(out_dir, hits):
+    """--dump-outputs: the hit records a caller of the timed path receives (rc.HIT_DT), one DIR/<field>.npy per field plus
+    DIR/ray_index.npy, the rays they belong to.  A batch above DUMP_SAMPLE rays is sampled without replacement with DUMP_SEED, so that
+    two runs with the same arguments write the same rays' records."""
+    n = len(hits)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    sel = hits[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ray_index.npy"), idx.astype(np.float64))
+    for name, dt in DUMP_FIELDS:
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(sel[name], dtype=dt))
+
+
 def self_launch(args, argv):
     """`python bench.py --gpus N` with N > 1 and no rank environment: start N rank processes (fresh children: this process never
     touches a GPU) and relay rank 0's output.  Exit code = the worst child's."""
@@ -229,11 +267,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--res", type=int, default=2048, help="primary rays = res x res")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the roofline, the CPU baseline and its bit-exact check, and the extras (other workloads, sizes and "
+                         "options); without it the run sets up, warms up, times the steps and prints the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hit records of the last timed step as DIR/<field>.npy (float32 / float64; a fixed seeded sample of "
+                         f"{DUMP_SAMPLE} rays when the batch is larger, their indices in ray_index.npy)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL over xGMI; gloo only for dry runs)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: exercises the launcher, the process group and the JSON line (CPU tests)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args, sys.argv[1:]))
@@ -279,10 +325,7 @@ def main():
     t.sync()
     n_tris = t.n_primitives() * t.n_instances()
 
-    rays = sc.c3_primary_rays(cfg, args.res, args.res)
-    n = len(rays)
-    d_rays = torch.from_numpy(rays.view(np.uint8).reshape(-1)).cuda()
-    d_hits = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
+    n = args.res * args.res
     stream = torch.cuda.current_stream()
 
     # the headline is what a caller sees for a batch it traces for the FIRST time.  Every warm-up and timed step traces its OWN
@@ -293,9 +336,11 @@ def main():
     # earlier launches) is extras.c3_repeated_batch -> "repeated_value".
     CLOCK_WARM = 40   # untimed launches in front of the W warm-up steps (below): first launches of their own batches too, so that EVERY dispatch of the
                       # trace kernel in this command -- what `rocprofv3 --kernel-trace --stats` averages -- is what the timed steps are
-    n_fresh = CLOCK_WARM + args.warmup + args.steps
-    if n_fresh > 512:
-        raise SystemExit("--warmup + --steps above 472: every launch traces its own 32 B/ray batch (134 MB at the default size); lower them")
+    n_launch = CLOCK_WARM + args.warmup + args.steps
+    # every launch traces its own 32 B/ray batch (134 MB at the default size) up to MAX_FRESH_BATCHES launches; beyond that the batches come back in
+    # rotation, each after MAX_FRESH_BATCHES - 1 others -- far more than the device's 4 remembered batches and the 256 MiB Infinity Cache hold
+    n_fresh = min(n_launch, MAX_FRESH_BATCHES)
+    rotation = ", taken in rotation" if n_launch > n_fresh else ""
 
     def fresh_batch(seed):
         """c3_primary_rays(jitter_seed=...) restated on the device (float64 like the numpy version; the batch used for the bit-exact check is
@@ -326,7 +371,7 @@ def main():
     torch.cuda.synchronize()
 
     def step(i):
-        t.trace_device(fresh[i].data_ptr(), d_hits_fresh.data_ptr(), n, mode="closest", stream=stream.cuda_stream)
+        t.trace_device(fresh[i % n_fresh].data_ptr(), d_hits_fresh.data_ptr(), n, mode="closest", stream=stream.cuda_stream)
 
     def fence():
         torch.cuda.synchronize()
@@ -369,16 +414,35 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
     rc.lib().rc_range_pop()
+    if use_dist:
+        tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+    value, ms_per_step = round(world * n * args.steps / elapsed / 1e6, 1), round(elapsed / args.steps * 1e3, 4)
+    kernel_name = {-1: "auto (phased persistent, top level in LDS)", 0: "simple", 1: "persistent", 2: "voted", 3: "phased", 4: "phased + top level in LDS, 1024-thread workgroups",
+                   5: "phased + top level in LDS", 6: "phased + tops of the TLAS / BLAS in LDS"}.get(t.get_option("kernel"), "option")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_hits_fresh.cpu().numpy().view(rc.HIT_DT))
+    if not args.full:
+        # a plain run ends here: the headline line only (the roofline, the CPU baseline, the bit-exact check and the extras are --full's)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print_line({"metric": METRIC, "value": value, "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+                        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                        "config": {"workload": "C3: TLAS of 256 rotated/scaled instances of one 4096-triangle BLAS (1 048 576 triangles), "
+                                               f"{n} pinhole primary rays per GPU per step, closest_hit",
+                                   "scheduling": f"first launch of the batch: every warm-up and timed step traces its own batch of rays ({n_fresh} different buffers{rotation})",
+                                   "triangles": int(n_tris), "rays_per_step_per_gpu": n, "kernel": kernel_name, "parallelism": f"replicas x{world} (rays sharded, no collective)"},
+                        "full": False})
+        return
     if own_events:
         per_step = t.recent_kernel_ms(args.steps)
         assert len(per_step) == args.steps and all(x > 0 for x in per_step), per_step
         launch_ms = float(np.mean(per_step))
     else:
         launch_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
-    if use_dist:
-        tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
     # what the library did with the LAST timed step (the claim-order header of the launch shape, read through the dev option the tests use):
     # "fresh" = the batch was not a repeat of a remembered one -> natural order, nothing recorded; "paused" = the shape's batches have not
     # repeated for 8 launches in a row, so its launches currently go out without even looking at their rays
@@ -390,9 +454,12 @@ def main():
         order_state = {"last_step_fresh": int(hdr[4]), "last_step_used_a_learned_order": int(hdr[1]), "last_step_recorded": int(hdr[5]), "pause_launches_left": int(hdr[38])}
     except Exception as e:  # noqa: BLE001
         order_state = {"error": str(e)[:100]}
-    last_fresh_rays = fresh[-1].cpu().numpy().view(rc.RAY_DT).copy()   # the last timed step's batch and its output: checked against the oracle below
+    last_fresh_rays = fresh[(n_launch - 1) % n_fresh].cpu().numpy().view(rc.RAY_DT).copy()   # the last timed step's batch and its output: checked against the oracle below
     last_fresh_hits = d_hits_fresh.cpu().numpy().view(rc.HIT_DT).copy()
     del fresh
+    rays = sc.c3_primary_rays(cfg, args.res, args.res)
+    d_rays = torch.from_numpy(rays.view(np.uint8).reshape(-1)).cuda()
+    d_hits = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
     t.trace_device(d_rays.data_ptr(), d_hits.data_ptr(), n, mode="closest", stream=stream.cuda_stream)  # the unjittered batch: the extras' reference output
     torch.cuda.synchronize()
     hits = d_hits.cpu().numpy().view(rc.HIT_DT)
@@ -1141,18 +1208,18 @@ def main():
         roofline = make_roofline(launch_ms, n, node_f, inst_f, counts_source, load_json(COUNTER_FILE) or {}, t.get_option("kernel"), args.res == 2048,
                                  mix=load_json(MIX_FILE), fingerprint=kernel_fingerprint())
         out = {
-            "metric": "Mrays/s closest_hit (1M-tri TLAS)", "value": round(world * n * args.steps / elapsed / 1e6, 1), "unit": "Mrays/s",
+            "metric": METRIC, "value": value, "unit": "Mrays/s",
             # `value` is the FIRST launch of a batch (every timed step traces rays never seen before).  Beside it, from the extras
             # of the same run (same scene, same ray count, 1 GPU): repeated_value = one buffer replayed with its learned claim order (rounds 1-5's
             # `value`); same_buffer_natural_order_value = one cache-warm buffer with the order switched off (rounds 4-5's first_touch_value);
             # moving_camera_value = a camera that moves every frame
             "repeated_value": None, "same_buffer_natural_order_value": None, "moving_camera_value": None,
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": True,
             "config": {"workload": "C3: TLAS of 256 rotated/scaled instances of one 4096-triangle BLAS (1 048 576 triangles), "
                                    f"{n} pinhole primary rays per GPU per step, closest_hit",
                        "scheduling": "first launch of the batch: every warm-up and timed step traces its OWN batch of rays (the C3 camera, each ray through a random point of its pixel; "
-                                     f"{n_fresh} different 32 B/ray buffers resident in HBM), default options as shipped -- a batch the library has not seen runs in natural claim order "
+                                     f"{n_fresh} different 32 B/ray buffers resident in HBM{rotation}), default options as shipped -- a batch the library has not seen runs in natural claim order "
                                      "and records nothing.  repeated_value: ONE buffer replayed, the order in which its 128-ray chunks are claimed learned from its earlier launches "
                                      "(option cost_order: the batch is recognised on the device by sample rays)",
                        "last_timed_step": order_state,
@@ -1160,7 +1227,7 @@ def main():
                                      "would test no triangle (DESIGN 4.1); every hit record identical with the option off (gpu_matches_bit_exact below is against the CPU oracle); "
                                      "the roofline's VALU counters are those of this kernel, the algorithmic bytes are the reference algorithm's",
                        "triangles": int(n_tris), "rays_per_step_per_gpu": n, "hit_fraction": round(hit_frac, 4),
-                       "kernel": {-1: "auto (phased persistent, top level in LDS)", 0: "simple", 1: "persistent", 2: "voted", 3: "phased", 4: "phased + top level in LDS, 1024-thread workgroups", 5: "phased + top level in LDS", 6: "phased + tops of the TLAS / BLAS in LDS"}.get(t.get_option("kernel"), "option"), "parallelism": f"replicas x{world} (rays sharded, no collective)"},
+                       "kernel": kernel_name, "parallelism": f"replicas x{world} (rays sharded, no collective)"},
             "roofline": roofline,
             "cpu_baseline": cpu_baseline,
             "extras": extras,
@@ -1171,17 +1238,10 @@ def main():
     def emit():
         if out is None:
             return
-        # RCCL prints its version banner through C stdio, which would otherwise be flushed at exit, AFTER the JSON line
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except Exception:  # noqa: BLE001
-            pass
-        sys.stdout.flush()
         out["repeated_value"] = (extras.get("c3_repeated_batch") or {}).get("mrays_s")
         out["same_buffer_natural_order_value"] = (extras.get("c3_cost_order_off") or {}).get("mrays_s")
         out["moving_camera_value"] = (extras.get("c3_moving_camera") or {}).get("mrays_s")
-        print(json.dumps(out), flush=True)  # the ONE JSON line, last thing on stdout
+        print_line(out)
 
     if not args.no_extras and args.backend == "nccl":
         # The view-factor extra is the only measurement with collectives in it.  It runs first among the extras, with the headline

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 R=${1:-r06}
 O=gpurun_out/$R; P=$O/profiles
 mkdir -p $O $P
-CMD="python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras"
+CMD="python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $CMD > $O/stats.log 2>&1
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TA_TA_BUSY_sum TD_TD_BUSY_sum" "GRBM_GUI_ACTIVE GRBM_COUNT" \
@@ -16,12 +16,12 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TA_TA_BUSY_sum 
   i=$((i+1))
   rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/pmc_$i -- $CMD > $O/pmc_$i.log 2>&1
 done
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 python3 - "$R" <<'PY'
 import csv, glob, json, sys, collections, shutil, os
 R = sys.argv[1]
 O, P = f"gpurun_out/{R}", f"gpurun_out/{R}/profiles"
-out = {"command": "rocprofv3 --pmc <set> --kernel-trace --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras (one pass per counter set; FETCH_SIZE and WRITE_SIZE in separate passes)",
+out = {"command": "rocprofv3 --pmc <set> --kernel-trace --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras (one pass per counter set; FETCH_SIZE and WRITE_SIZE in separate passes)",
        "workload": "BASELINE C3: 4 194 304 primary rays, closest_hit, 1 048 576-triangle instanced TLAS"}
 agg = collections.defaultdict(list)
 meta = {}

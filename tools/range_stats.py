@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Kernel time per roctx range: joins rocprofv3's marker trace with its kernel trace.
 
-    rocprofv3 --marker-trace --kernel-trace --output-format csv -d OUT -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline
+    rocprofv3 --marker-trace --kernel-trace --output-format csv -d OUT -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline
     python3 tools/range_stats.py OUT > profiles/r05_bench_with_extras_by_range.csv
 
 Every C-ABI entry point of the library is a range named after itself (rc_capi.hip, guarded()); bench.py wraps its phases in ranges of its own

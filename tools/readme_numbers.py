@@ -5,7 +5,7 @@
     python3 tools/readme_numbers.py --write    # replace the block between the markers in README.md
 
 Source: the record of the highest round among the driver's BENCH_rNN.json (its `parsed` line) and the builder's profiles/rNN_bench.json
-(`python3 bench.py` on one MI355X with the round's counter files in place); the driver's wins a tie.  Figures are truncated, never rounded up.
+(`python3 bench.py --full` on one MI355X with the round's counter files in place); the driver's wins a tie.  Figures are truncated, never rounded up.
 tests/test_readme_numbers.py checks that README.md holds exactly the block of the source it names and that the source is of the newest round."""
 import glob
 import json
