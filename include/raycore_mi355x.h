@@ -419,6 +419,29 @@ int rc_compact_hits_device(rc_scene* scene, const rc_hit* d_hits, uint64_t n, ui
  * per hit, origin = hit_point + shading_normal * bias, direction = reflect(-ray.d, shading_normal), t_max = Inf; misses get the
  * reference's dummy ray (d = (0,0,1), t_max = 0).  Material tests (metallic / roughness) stay with the caller. */
 int rc_reflection_rays_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, float bias, rc_ray* d_out, void* stream);
+/* rc_bounce_rays_device: diffuse (cosine-weighted) bounce rays, n_out output slots.  Output slot i continues source slot s:
+ *  - d_src == NULL (slot-aligned): s = i, k = 0; d_src_count must be NULL and wrap 0.
+ *  - d_src != NULL: c = *d_src_count is read ON THE DEVICE when the kernel runs (e.g. the count rc_compact_hits_device wrote earlier on
+ *    the same stream), so the call needs no host read-back and can be captured.  c == 0: every slot is dead.  wrap == 0: s = d_src[i]
+ *    for i < c, slots i >= c are dead (a live-first queue).  wrap == 1: s = d_src[i % c], k = i / c (round robin).
+ *  - A slot whose source missed (d_hits[s].hit == 0) is dead too.
+ * Path identity: path = path_base + (d_path_in ? d_path_in[s] : s); d_path_out (optional) receives lo32(path) per slot and
+ * RC_INVALID_ID for dead slots, ready to be the next bounce's d_path_in (with path_base 0).  The random numbers depend only on
+ * (path, k, bounce, seed), so they do not change when the queue is compacted or the batch is split into chunks or shards.
+ * A live slot: (p, n) = the hit point and geometric world normal facing the ray origin (as rc_hit_points_device); origin p + n * bias,
+ * t_min 0, t_max Inf; u1, u2 = the first two words of Philox4x32-10(counter = (lo32 path, hi32 path, k, 0x424E0000 | bounce),
+ * key = (lo32 seed, hi32 seed)) as 24-bit floats in [0, 1); direction = cosine_sample_hemisphere(u1, u2) (src/math.jl:1-21,
+ * concentric disk, Float32(pi), cos / sin evaluated in f64 and rounded once) in the basis get_orthogonal_basis(n) (src/math.jl:143-156):
+ * d = (u*dx + v*dy) + n*z, not renormalised, every expression left to right without contraction.
+ * A dead slot gets o = (0,0,0), d = (0,0,1), t_min = 0, t_max = -1.  Unlike the shadow stage's t_max = 0 dummy -- a [0, 0] interval can
+ * still hit a triangle through the origin at t = 0 -- an interval with t_max < 0 misses under both rc_trace_closest_device and
+ * rc_trace_any_device (any_hit starts from t_min = 0).
+ * RC_ERR_INVALID_ARGUMENT: a NULL scene, d_rays, d_hits or d_out (the last three while n_out > 0); only one of d_src / d_src_count;
+ * wrap without d_src; bounce >= 65536; n_out >= 2^32.  RC_ERR_NOT_SYNCED on an unsynced scene.  n_out == 0 writes nothing.
+ * No allocation, copy or synchronisation: capture-safe and re-entrant like the other stages. */
+int rc_bounce_rays_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count,
+                          int wrap, const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n_out, uint64_t seed,
+                          uint32_t bounce, float bias, rc_ray* d_out, void* stream);
 
 /* Scene files.  The reference has no on-disk format; this one keeps what a rebuild would recompute (per geometry: sorted
  * primitives, BVH2 nodes, mesh attributes; plus instance descriptors and the handle table).  rc_scene_save needs a synced

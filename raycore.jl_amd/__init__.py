@@ -4,6 +4,7 @@
 contains a dot and cannot be imported by that name.
 """
 from . import scenes  # noqa: F401  (pure numpy; usable without the library)
+from . import wavefront  # noqa: F401  (torch is imported when a frame is built)
 from ._capi import HIT_DT, LIB_PATH, RAY_DT, SYMBOLS, TRIANGLE_DT, RaycoreError, lib  # noqa: F401
 from .api import (BLAS4, CONTACT_DT, CollisionResult, ContactPair, collide_instances, collide_instances_any, EMPTY_TRIANGLE, RAYHIT_DT, INVALID_HANDLE, any_hit4, build_blas4, closest_hit4, Bounds3, Ray, RayHit, StaticTLAS, TLAS, TLAS_from_items,  # noqa: F401
                   TLAS_from_meshes, TLASHandle, Triangle, adapt, any_hit, closest_hit, generate_ray_grid,

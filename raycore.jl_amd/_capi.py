@@ -107,6 +107,7 @@ SYMBOLS = [
     ("rc_primary_rays_lookat_device", _int, [_vp, _vp, _vp, _vp, _vp, C.c_float, C.c_float, _u32, _u32, _u32, _u64, _int, _vp, _vp]),
     ("rc_reflection_rays_device", _int, [_vp, _vp, _vp, _u64, C.c_float, _vp, _vp]),
     ("rc_compact_hits_device", _int, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    ("rc_bounce_rays_device", _int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _u64, _u64, _u64, _u32, C.c_float, _vp, _vp]),
     ("rc_scene_save", _int, [_vp, C.c_char_p]),
     ("rc_scene_load", _int, [_int, C.c_char_p, C.POINTER(_vp)]),
     ("rc_instance_buffer_device", _int, [_vp, _u32, C.POINTER(_vp), _pu32]),

@@ -259,6 +259,16 @@ class TLAS:
         """Ascending indices of the hit rays + their count (device u32): queue compaction between wavefront stages."""
         check(lib().rc_compact_hits_device(self._h, ptr(d_hits), int(n), ptr(d_indices), ptr(d_count), ptr(stream)))
 
+    def bounce_rays_device(self, d_rays, d_hits, n_out, d_out, seed=0, bounce=0, bias=1e-3, d_src=None, d_src_count=None, wrap=False,
+                           d_path_in=None, d_path_out=None, path_base=0, stream=None):
+        """Diffuse (cosine-weighted) bounce rays into n_out device RTRay slots (rc_bounce_rays_device): slot-aligned, or gathered through
+        d_src / d_src_count (a device u32 count, e.g. compact_hits_device's; wrap=True reuses the sources round robin).  Dead slots get
+        t_max = -1; d_path_out receives each slot's path id (RC_INVALID_ID when dead)."""
+        check(lib().rc_bounce_rays_device(self._h, ptr(d_rays), ptr(d_hits), ptr(d_src) if d_src else None,
+                                          ptr(d_src_count) if d_src_count else None, 1 if wrap else 0, ptr(d_path_in) if d_path_in else None,
+                                          ptr(d_path_out) if d_path_out else None, int(path_base), int(n_out), int(seed), int(bounce), float(bias),
+                                          ptr(d_out), ptr(stream) if stream else None))
+
     def shading_attributes_device(self, d_hits, n, d_normals=None, d_uvs=None, stream=None):
         """Interpolated shading normal / uv per hit on device buffers (docs/src/wavefront-renderer.jl:382-387)."""
         check(lib().rc_shading_attributes_device(self._h, ptr(d_hits), int(n), ptr(d_normals), ptr(d_uvs), ptr(stream)))

@@ -1464,6 +1464,22 @@ int rc_shadow_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hit
     });
 }
 
+int rc_bounce_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
+                          const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n_out, uint64_t seed, uint32_t bounce, float bias,
+                          rc_ray* d_out, void* stream) {
+    if (!s || (n_out && (!d_rays || !d_hits || !d_out))) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!d_src != !d_src_count) return fail(RC_ERR_INVALID_ARGUMENT, "rc_bounce_rays_device: d_src and d_src_count go together");
+    if (wrap && !d_src) return fail(RC_ERR_INVALID_ARGUMENT, "rc_bounce_rays_device: wrap needs d_src");
+    if (bounce >= 65536u) return fail(RC_ERR_INVALID_ARGUMENT, "rc_bounce_rays_device: bounce must be below 65536");
+    if (n_out >= (1ull << 32)) return fail(RC_ERR_INVALID_ARGUMENT, "rc_bounce_rays_device: n_out must be below 2^32");
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        rc_launch_bounce_rays(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), d_src, d_src_count, wrap, d_path_in,
+                              d_path_out, path_base, n_out, seed, bounce, bias, reinterpret_cast<RcRay*>(d_out), (hipStream_t)stream);
+    });
+}
+
 // (the HIP runtime accepts a second hipHostRegister of the same range silently; the library keeps its own table so that the two
 // calls have defined semantics: one registration per array, unregister only what was registered through this interface)
 static std::mutex g_host_reg_mutex;

@@ -176,7 +176,9 @@ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint
 __device__ inline float u32_to_unit(uint32_t x) { return (float)(x >> 8) * 0x1.0p-24f; }
 
 // ---- f64 trig with a fixed operation order (fdlibm kernels), valid for the ranges the sampler needs -----
-__device__ inline void sincos_f64(double x, double& s, double& c) {  // 0 <= x <= 2 pi
+// Also exact on [-pi/4, 0) (the diffuse bounce's theta): there x * two_over_pi + 0.5 lies in (-1, 0.5) (about -5e-9 at x = -pi/4 after
+// rounding), the truncating cast gives k = 0, r = x exactly, and the fdlibm kernels are valid for |r| <= pi/4.
+__device__ inline void sincos_f64(double x, double& s, double& c) {  // -pi/4 <= x <= 2 pi
     const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17, two_over_pi = 6.36619772367581382433e-01;
     int k = (int)(x * two_over_pi + 0.5);
     double r = (x - (double)k * pio2_hi) - (double)k * pio2_lo;
@@ -224,19 +226,24 @@ __device__ inline float3_ normalize3(float3_ a) {
     return mk3((a.x / n), (a.y / n), (a.z / n));
 }
 
-// The ray view_factors! shoots for (source primitive, ray index) (:83-92 + src/math.jl:125-174)
-__device__ inline RcRay view_factor_ray(const RcPrim& tri, uint32_t src, uint32_t ray_idx, uint32_t k0, uint32_t k1) {
-    float3_ p1 = mk3(tri.v[0], tri.v[1], tri.v[2]), p2 = mk3(tri.v[3], tri.v[4], tri.v[5]), p3 = mk3(tri.v[6], tri.v[7], tri.v[8]);
-    float3_ normal = normalize3(cross3(sub3(p2, p1), sub3(p3, p1)));  // GB.orthogonal_vector + normalize (:86-87)
-    // get_orthogonal_basis (src/math.jl:143-156)
+// get_orthogonal_basis (src/math.jl:143-156): argmin(abs.(normal)) keeps the FIRST minimum on ties.
+__device__ inline void orthogonal_basis(const float3_ normal, float3_& bu, float3_& bv) {
     float3_ n = normalize3(normal);
     float ax = fabsf(normal.x), ay = fabsf(normal.y), az = fabsf(normal.z);
     int mi = 1; float mv = ax;
     if (ay < mv) { mi = 2; mv = ay; }
     if (az < mv) { mi = 3; mv = az; }
     float3_ cand = mi == 1 ? mk3(1, 0, 0) : (mi == 2 ? mk3(0, 1, 0) : mk3(0, 0, 1));
-    float3_ bv = normalize3(cross3(n, cand));
-    float3_ bu = normalize3(cross3(bv, n));
+    bv = normalize3(cross3(n, cand));
+    bu = normalize3(cross3(bv, n));
+}
+
+// The ray view_factors! shoots for (source primitive, ray index) (:83-92 + src/math.jl:125-174)
+__device__ inline RcRay view_factor_ray(const RcPrim& tri, uint32_t src, uint32_t ray_idx, uint32_t k0, uint32_t k1) {
+    float3_ p1 = mk3(tri.v[0], tri.v[1], tri.v[2]), p2 = mk3(tri.v[3], tri.v[4], tri.v[5]), p3 = mk3(tri.v[6], tri.v[7], tri.v[8]);
+    float3_ normal = normalize3(cross3(sub3(p2, p1), sub3(p3, p1)));  // GB.orthogonal_vector + normalize (:86-87)
+    float3_ bu, bv;
+    orthogonal_basis(normal, bu, bv);
     uint32_t rnd[4];
     philox4x32_10(ray_idx, src, 0u, 0u, k0, k1, rnd);
     float r1 = u32_to_unit(rnd[0]), r2 = u32_to_unit(rnd[1]), xi1 = u32_to_unit(rnd[2]), xi2 = u32_to_unit(rnd[3]);
@@ -443,6 +450,66 @@ __global__ void k_shadow_rays(SceneView v, const RcRay* rays, const RcHit* hits,
         float4* q = reinterpret_cast<float4*>(out + i);
         q[0] = make_float4(s.ox, s.oy, s.oz, s.tmin);
         q[1] = make_float4(s.dx, s.dy, s.dz, s.tmax);
+    }
+}
+
+// cosine_sample_hemisphere (src/math.jl:1-21, concentric disk) in the frame (bu, bv, n), combined as random_hemisphere_uniform does
+// (u*x + v*y + n*z, not renormalised).  pi is Float32(pi); cos / sin of theta in [-pi/4, 3pi/4] through sincos_f64, rounded once.
+__device__ inline float3_ cosine_hemisphere_dir(const float3_ n, float u1, float u2) {
+    const float pi = 3.1415927f;
+    const float ox = 2.0f * u1 - 1.0f, oy = 2.0f * u2 - 1.0f;
+    float dx = 0.0f, dy = 0.0f;
+    if (!(ox == 0.0f && oy == 0.0f)) {  // offset ≈ 0f0 with the default tolerances is exact zero
+        float r, theta;
+        if (fabsf(ox) > fabsf(oy)) { r = ox; theta = ((oy / ox) * pi) / 4.0f; }
+        else { r = oy; theta = pi / 2.0f - ((ox / oy) * pi) / 4.0f; }
+        double st, ct;
+        sincos_f64((double)theta, st, ct);
+        dx = r * (float)ct; dy = r * (float)st;
+    }
+    const float z = __builtin_sqrtf(fmaxf(0.0f, (1.0f - dx * dx) - dy * dy));
+    float3_ bu, bv;
+    orthogonal_basis(n, bu, bv);
+    return add3(add3(scale3(bu, dx), scale3(bv, dy)), scale3(n, z));
+}
+
+// Diffuse bounce: output slot i continues the path of source slot s (s = i, or d_src[i] for i < count, or d_src[i % count] round robin
+// with k = i / count), from hit_point + normal * bias in a cosine-weighted direction about the geometric normal.  The uniforms are
+// Philox4x32-10(counter = (lo32 path, hi32 path, k, 0x424E0000 | bounce), key = seed): a path's bounce does not depend on compaction,
+// chunking or sharding.  Dead slots (no source, or a miss) get o = 0, d = (0,0,1), [t_min, t_max] = [0, -1], which misses everything.
+__global__ void k_bounce_rays(SceneView v, const RcRay* rays, const RcHit* hits, const uint32_t* src, const uint32_t* src_count, int wrap,
+                              const uint32_t* path_in, uint32_t* path_out, uint64_t path_base, uint32_t n, uint32_t k0, uint32_t k1,
+                              uint32_t tag, float bias, RcRay* out) {
+    const uint32_t c = src ? *src_count : 0u;
+    for (uint64_t i64 = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i64 < n; i64 += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t i = (uint32_t)i64;
+        bool live = true;
+        uint32_t s = i, k = 0;
+        if (src) {
+            if (c == 0u || (!wrap && i >= c)) live = false;
+            else if (wrap) { s = src[i % c]; k = i / c; }
+            else s = src[i];
+        }
+        RcRay b{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
+        uint32_t path_id = 0xFFFFFFFFu;  // RC_INVALID_ID
+        if (live) {
+            const RcHit h = hits[s];
+            if (h.hit) {
+                const uint64_t path = path_base + (path_in ? (uint64_t)path_in[s] : (uint64_t)s);
+                path_id = (uint32_t)path;
+                float3_ p, nn;
+                hit_frame(v, rays[s], h, p, nn);
+                const float3_ o = add3(p, scale3(nn, bias));
+                uint32_t rnd[4];
+                philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), k, tag, k0, k1, rnd);
+                const float3_ d = cosine_hemisphere_dir(nn, u32_to_unit(rnd[0]), u32_to_unit(rnd[1]));
+                b = RcRay{o.x, o.y, o.z, 0.f, d.x, d.y, d.z, INFINITY};
+            }
+        }
+        float4* q = reinterpret_cast<float4*>(out + i);
+        q[0] = make_float4(b.ox, b.oy, b.oz, b.tmin);
+        q[1] = make_float4(b.dx, b.dy, b.dz, b.tmax);
+        if (path_out) path_out[i] = path_id;
     }
 }
 
@@ -770,6 +837,17 @@ void rc_launch_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits
     if (n == 0) return;
     uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cus * 8);
     hipLaunchKernelGGL(k_shadow_rays, dim3(blocks), dim3(256), 0, stream, rc_scene_view_static(s), d_rays, d_hits, n, light[0], light[1], light[2], bias, d_out);
+    RC_HIP(hipGetLastError());
+    rc_note_stage_launch(s, stream);
+}
+
+void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
+                           const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n, uint64_t seed, uint32_t bounce, float bias,
+                           RcRay* d_out, hipStream_t stream) {
+    if (n == 0) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cus * 8);
+    hipLaunchKernelGGL(k_bounce_rays, dim3(blocks), dim3(256), 0, stream, rc_scene_view_static(s), d_rays, d_hits, d_src, d_src_count, wrap ? 1 : 0,
+                       d_path_in, d_path_out, path_base, (uint32_t)n, (uint32_t)seed, (uint32_t)(seed >> 32), 0x424E0000u | bounce, bias, d_out);
     RC_HIP(hipGetLastError());
     rc_note_stage_launch(s, stream);
 }

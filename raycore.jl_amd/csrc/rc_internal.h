@@ -437,3 +437,7 @@ void rc_trace_host_impl(rc_scene* s, const rc_ray* rays, rc_hit* hits, uint64_t 
 void rc_launch_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out, hipStream_t stream);
 void rc_launch_hit_points(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, float* d_points, float* d_normals, hipStream_t stream);
 void rc_launch_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float light[3], float bias, RcRay* d_out, hipStream_t stream);
+// Diffuse (cosine-weighted) bounce rays, slot-aligned or gathered through d_src / *d_src_count (read on the device); n < 2^32, bounce < 2^16
+void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
+                           const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n, uint64_t seed, uint32_t bounce, float bias,
+                           RcRay* d_out, hipStream_t stream);

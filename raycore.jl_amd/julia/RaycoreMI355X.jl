@@ -423,6 +423,16 @@ shadow_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitRe
                     bias::Float32 = 0.01f0, stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_shadow_rays_device, LIB), Cint, (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, Ptr{Float32}, Cfloat, Ptr{RTRay}, Ptr{Cvoid}),
                 a.owner.ptr, d_rays, d_hits, n, Float32[light...], bias, d_out, stream))
+"Diffuse (cosine-weighted) bounce rays: slot-aligned, or gathered through `d_src` / `d_src_count` (a device count; `wrap` = round robin)."
+bounce_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n_out::Integer, d_out::Ptr{RTRay};
+                    seed::UInt64 = UInt64(0), bounce::Integer = 0, bias::Float32 = 1f-3, d_src::Ptr{UInt32} = Ptr{UInt32}(C_NULL),
+                    d_src_count::Ptr{UInt32} = Ptr{UInt32}(C_NULL), wrap::Bool = false, d_path_in::Ptr{UInt32} = Ptr{UInt32}(C_NULL),
+                    d_path_out::Ptr{UInt32} = Ptr{UInt32}(C_NULL), path_base::Integer = 0, stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_bounce_rays_device, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, Ptr{UInt32}, Ptr{UInt32}, Cint, Ptr{UInt32}, Ptr{UInt32}, UInt64, UInt64, UInt64,
+                 UInt32, Cfloat, Ptr{RTRay}, Ptr{Cvoid}),
+                a.owner.ptr, d_rays, d_hits, d_src, d_src_count, wrap ? 1 : 0, d_path_in, d_path_out, path_base, n_out, seed, bounce, bias,
+                d_out, stream))
 reflection_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n::Integer, d_out::Ptr{RTRay};
                         bias::Float32 = 0.01f0, stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_reflection_rays_device, LIB), Cint, (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, Cfloat, Ptr{RTRay}, Ptr{Cvoid}),

@@ -1,0 +1,144 @@
+"""An on-device wavefront path frame over the stage kernels (the shape of docs/src/wavefront-renderer.jl:185-600, without shading).
+
+One frame: primary rays (generate_primary_rays_lookat!) -> closest_hit, then per depth b: shadow rays toward a point light -> any_hit,
+and while b + 1 < depth: [hit compaction] -> diffuse bounce rays -> closest_hit.  Every stage runs on one stream, with no host
+synchronisation and no parallel branches, so a frame can be captured into one graph and replayed.  Materials, BSDFs and image
+accumulation stay with the caller.
+
+Buffers are torch tensors on the accel's device: ray / hit records are uint8 tensors of 32 bytes per slot (RTRay / RTHitResult, view them
+with RAY_DT / HIT_DT), path ids and counts are int32 tensors holding u32 values.
+"""
+import numpy as np
+
+from ._capi import RaycoreError
+
+RC_INVALID_ID = 0xFFFFFFFF
+
+
+def lookat_camera(eye, target, width, height, fov_deg=45.0, up=(0.0, 1.0, 0.0)):
+    """Camera basis for primary_rays_lookat_device: dict(pos, right, up, forward, half_width, half_height), float32."""
+    eye = np.asarray(eye, np.float64)
+    f = np.asarray(target, np.float64) - eye
+    f /= np.linalg.norm(f)
+    r = np.cross(f, np.asarray(up, np.float64))
+    r /= np.linalg.norm(r)
+    u = np.cross(r, f)
+    half_h = np.tan(np.radians(fov_deg) / 2)
+    return {"pos": eye.astype(np.float32), "right": r.astype(np.float32), "up": u.astype(np.float32), "forward": f.astype(np.float32),
+            "half_width": float(np.float32(half_h * width / height)), "half_height": float(np.float32(half_h))}
+
+
+def _stream(stream):
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream()
+
+
+class WavefrontPaths:
+    """Owns the device buffers of a `depth`-deep path frame of width*height*samples paths on `accel` (a synced TLAS) and enqueues it.
+
+    Per depth b (0-based): rays[b] / hits[b] (the closest-hit stage), shadow_rays[b] / shadow_hits[b] (any_hit toward `light`) and
+    path_ids[b] (the path each slot of rays[b] continues; path_ids[0] is the primary ray index, dead slots hold RC_INVALID_ID).
+    compact=True gathers the hits into a live-first queue (compact_hits_device) before each bounce, so the live slots come first and the
+    dead tail is traced as rays that miss; compact=False keeps slot i on path i.  A path's bounce directions depend only on
+    (seed, path id, depth), so both modes produce the same (path id -> hit) records."""
+
+    def __init__(self, accel, width, height, samples, depth, camera, light, seed=0, bias=1e-3, compact=True):
+        import torch
+        if depth < 1:
+            raise ValueError("depth must be at least 1")
+        self.accel, self.width, self.height, self.samples, self.depth = accel, int(width), int(height), int(samples), int(depth)
+        self.n = self.width * self.height * self.samples
+        if self.n == 0 or self.n >= 2 ** 31:
+            raise ValueError("width * height * samples must be in [1, 2^31)")
+        self.camera = {k: (np.asarray(v, np.float32) if k in ("pos", "right", "up", "forward") else float(v)) for k, v in camera.items()}
+        self.light = np.ascontiguousarray(light, dtype=np.float32)
+        self.seed, self.bias, self.compact = int(seed), float(bias), bool(compact)
+        dev = torch.device("cuda", accel.device)
+        rec = lambda: torch.zeros(self.n * 32, dtype=torch.uint8, device=dev)  # noqa: E731
+        self.rays = [rec() for _ in range(depth)]
+        self.hits = [rec() for _ in range(depth)]
+        self.shadow_rays = [rec() for _ in range(depth)]
+        self.shadow_hits = [rec() for _ in range(depth)]
+        self.path_ids = [torch.arange(self.n, dtype=torch.int32, device=dev)] + [
+            torch.full((self.n,), -1, dtype=torch.int32, device=dev) for _ in range(depth - 1)]
+        self.indices = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        # the buffers are initialised on the allocating stream; a frame may run on any other: wait for them once, here
+        torch.cuda.current_stream(dev).synchronize()
+        self._streams = set()
+        self.graph = None
+        self._graph_stream = None
+
+    def buffers(self):
+        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + self.path_ids + [self.indices, self.count]
+
+    def run(self, stream=None):
+        """Enqueue one frame on `stream` (a torch.cuda.Stream; None = the current stream).  No host synchronisation.  The first frame on
+        a stream must run eagerly, before any capture on it."""
+        s = _stream(stream)
+        st = s.cuda_stream
+        if st not in self._streams:  # the caching allocator must not hand the buffers out again while this stream may still use them
+            for buf in self.buffers():
+                buf.record_stream(s)
+            self._streams.add(st)
+        a, c, n = self.accel, self.camera, self.n
+        a.primary_rays_lookat_device(c["pos"], c["right"], c["up"], c["forward"], c["half_width"], c["half_height"], self.width, self.height,
+                                     self.rays[0].data_ptr(), samples=self.samples, seed=self.seed, jitter=True, stream=st)
+        a.trace_device(self.rays[0].data_ptr(), self.hits[0].data_ptr(), n, stream=st)
+        for b in range(self.depth):
+            a.shadow_rays_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.light, self.shadow_rays[b].data_ptr(),
+                                 bias=self.bias, stream=st)
+            a.trace_device(self.shadow_rays[b].data_ptr(), self.shadow_hits[b].data_ptr(), n, mode="any", stream=st)
+            if b + 1 >= self.depth:
+                break
+            src = cnt = None
+            if self.compact:
+                a.compact_hits_device(self.hits[b].data_ptr(), n, self.indices.data_ptr(), self.count.data_ptr(), stream=st)
+                src, cnt = self.indices.data_ptr(), self.count.data_ptr()
+            a.bounce_rays_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.rays[b + 1].data_ptr(), seed=self.seed,
+                                 bounce=b, bias=self.bias, d_src=src, d_src_count=cnt, d_path_in=self.path_ids[b].data_ptr(),
+                                 d_path_out=self.path_ids[b + 1].data_ptr(), stream=st)
+            a.trace_device(self.rays[b + 1].data_ptr(), self.hits[b + 1].data_ptr(), n, stream=st)
+
+    def capture(self, stream):
+        """Record one frame into a torch.cuda.CUDAGraph on `stream`, which must have run the frame eagerly before (the trace needs its
+        stack spill area, the compaction its scratch: include/raycore_mi355x.h, "hipGraph capture").  The graph holds 2 * depth of the
+        scene's 16 captured launches until the caller destroys it and hands them back (accel.set_option("release_captures", 1))."""
+        import torch
+        if self._graph_stream is not None:
+            raise RaycoreError(1, "WavefrontPaths.capture: this frame is already captured")
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=stream):
+            self.run(stream)
+        self.graph, self._graph_stream = g, stream
+        return g
+
+    def replay(self):
+        """Replay the captured frame (asynchronous, like run)."""
+        if self.graph is None:
+            raise RaycoreError(1, "WavefrontPaths.replay: capture() a frame first")
+        self.graph.replay()
+
+    def traced_rays(self):
+        """Ray slots one frame traces: per depth one closest-hit pass (primary or bounce) and one any-hit pass (shadow) over every slot,
+        dead ones included."""
+        return self.n * 2 * self.depth
+
+
+def c4_bounce_rays_device(accel, d_rays, d_hits, n_primary, n_rays, d_out, seed=0xC4, stream=None):
+    """C4's incoherent diffuse bounce rays made on the device: the n_primary primary hits are compacted and reused round robin
+    (rc_bounce_rays_device with wrap=1) to fill n_rays output slots at d_out, origin = hit point + 1e-3 * normal, path id = the primary
+    ray's index.  `stream`: a torch.cuda.Stream (None = the current one).  Returns the (indices, count) tensors the call reads on the
+    device; they are also recorded on the stream, so dropping them is safe."""
+    import torch
+    s = _stream(stream)
+    dev = torch.device("cuda", accel.device)
+    indices = torch.empty(max(int(n_primary), 1), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    if s != torch.cuda.current_stream(dev):
+        indices.record_stream(s)
+        count.record_stream(s)
+    accel.compact_hits_device(d_hits, int(n_primary), indices.data_ptr(), count.data_ptr(), stream=s.cuda_stream)
+    accel.bounce_rays_device(d_rays, d_hits, int(n_rays), d_out, seed=seed, bounce=0, bias=1e-3, d_src=indices.data_ptr(),
+                             d_src_count=count.data_ptr(), wrap=True, stream=s.cuda_stream)
+    return indices, count
