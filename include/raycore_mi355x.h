@@ -15,7 +15,7 @@
  *    non-zero status into ErrorException (test/test_tlas_stress.jl:585-617 expects that type).
  *  - The caller owns every host buffer it passes.  The library owns all device memory behind the opaque
  *    rc_scene handle and frees it in rc_scene_destroy (replaces free!, src/instanced-bvh.jl:383-399).
- *  - Threading.  Mutations (rc_add_*, rc_update_*, rc_delete, rc_sync, rc_set_option, rc_blas4_build, rc_refit_device) on one scene
+ *  - Threading.  Mutations (rc_add_*, rc_update_*, rc_delete, rc_sync, rc_set_option, rc_blas4_build, rc_refit_device*) on one scene
  *    must be externally serialised and must not overlap queries.  QUERIES ON A SYNCED SCENE ARE RE-ENTRANT: any number of host threads
  *    may call rc_trace_closest / rc_trace_any (each call stages through its own stream and buffers; a fifth concurrent call waits for a
  *    staging context) and the *_device entry points (rc_trace_*_device, rc_get_illumination_device, rc_view_factors_device,
@@ -25,6 +25,10 @@
  *    host-buffer queries (rc_get_illumination, rc_view_factors*, rc_collide_instances, rc_trace_*4) are safe to call concurrently and run
  *    one at a time per scene.  rc_compact_hits_device and rc_collide_instances_device use scene-owned scratch: keep their calls on one
  *    scene on one stream.  rc_last_kernel_ms reports the calling thread's latest launch.  No global mutable state.
+ *    rc_update_transforms_device and rc_refit_device_async are mutations too, enqueued on the caller's stream: work enqueued LATER ON THE
+ *    SAME STREAM sees the new scene; *_device queries on other streams or threads must be ordered behind them by the caller (events), as
+ *    for any mutation; the host-buffer queries wait for them on the host (see rc_refit_device_async).  A captured update / refit holds device addresses that a REBUILDING rc_sync invalidates, like the address
+ *    rc_instance_buffer_device returns.
  *  - hipGraph capture: trace / driver launches on a capturing stream are captured (no events, a counter slot of their own that eager
  *    launches never use); the stream must have run one eager launch on the scene before (stack spill area), see INTEGRATION.md.
  *    Entry points that allocate, copy or free (scene create / destroy / sync, the host-buffer queries) may run on any thread while a
@@ -159,7 +163,8 @@ int rc_sync(rc_scene* scene, int* action);
  * number of flat primitives / TLAS nodes / BLAS nodes after the last sync. */
 int rc_counts(rc_scene* scene, uint32_t* n_live_instances, uint32_t* n_total_instances, uint32_t* n_geometries,
               uint32_t* n_prims, uint32_t* n_tlas_nodes, uint32_t* n_blas_nodes);
-/* world_bound(tlas) (src/instanced-bvh.jl:2147-2149): out = {min xyz, max xyz}. */
+/* world_bound(tlas) (src/instanced-bvh.jl:2147-2149): out = {min xyz, max xyz}.  After rc_refit_device_async the call first waits for
+ * the refit and reads the root box back (see there). */
 int rc_world_bound(rc_scene* scene, float out[6]);
 /* wait_for_gpu! (src/instanced-bvh.jl:2418-2421).  Also the place where asynchronous launches (the *_device entry points) report a
  * traversal-stack overflow (RC_ERR_STACK_OVERFLOW): the host-buffer entry points check after every call, the device ones cannot. */
@@ -459,6 +464,41 @@ int rc_scene_load(int device, const char* path, rc_scene** out);
  * mutation).  The address is valid until the next rebuilding rc_sync. */
 int rc_instance_buffer_device(rc_scene* scene, uint32_t handle, rc_instance_desc** d_descs, uint32_t* count);
 int rc_refit_device(rc_scene* scene, int recompute_inverse);
+
+/* update_transforms!(tlas, handle, transforms) with a backend-resident array (src/instanced-bvh.jl:784-794,
+ * update_instance_transforms_offset_kernel!, src/instanced-bvh-kernels.jl:455-476), and refit_tlas! (:2197-2222), both enqueued on the
+ * caller's `stream` with no host wait: update -> refit -> trace can run back to back on one stream and be captured into one graph.
+ *
+ * rc_update_transforms_device: d_xforms = m x 12 f32 in device memory on the scene's device (Mat3x4f bytes as in rc_update_transforms,
+ * 4-byte aligned), m = the handle's instance count.  One kernel writes, for every instance of the handle, transform = d_xforms[i],
+ * inv_transform = mat3x4_inverse(transform) (the bytes rc_update_transforms computes on the host) -- blas_index, instance_id and flags
+ * stay -- and everything the refit derives per instance (traversal record, entry-cull sphere, TLAS leaf box).  d_xforms is read WHEN THE
+ * KERNEL RUNS, not when the call is made: a captured call picks up the array's current contents on every replay.  The scene becomes
+ * transforms-dirty from the device: queries fail with RC_ERR_NOT_SYNCED until rc_refit_device_async (or rc_sync, which then refits from
+ * the device descriptors, action 1) has been called; the host mirror of the descriptors is refreshed lazily (rc_get_instances, ...).
+ * Errors, all before anything is enqueued: RC_ERR_INVALID_ARGUMENT (NULL scene or d_xforms, m != the handle's count),
+ * RC_ERR_INVALID_HANDLE (unknown or deleted handle), RC_ERR_NOT_SYNCED (never synced, or pending host-side mutations: the descriptors'
+ * device positions are those of the last sync).
+ *
+ * rc_refit_device_async: bottom-up refit of the TLAS and its traversal copy on `stream`.  After rc_update_transforms_device calls the
+ * per-instance data is already in place; with none since the last refit (descriptors rewritten through rc_instance_buffer_device, with
+ * their inverses) it is derived from the descriptors first, as rc_refit_device(scene, 0) does.  Do not mix the two ways between two refits.
+ * No allocation, copy, event or synchronisation: legal on a capturing stream, once the stream has run it eagerly (like the trace).
+ * THE WORLD BOUND stays in device memory: the host copy is refreshed lazily.  rc_world_bound, the ray grid / illumination drivers,
+ * rc_scene_save and the multi-device replica check wait for the refit and read the root box back first; on a stream that is being
+ * captured they fail with RC_ERR_NOT_SYNCED ("stale world bound") instead of using an old one -- call rc_world_bound before the capture.
+ * The HOST-BUFFER queries (rc_trace_closest / rc_trace_any, rc_get_illumination, rc_view_factors*, rc_collide_instances*, the *_multi
+ * calls, the rc_export_* calls) run on streams of the library's own, which a caller cannot order behind its stream: they wait on the
+ * host for every EAGER update / refit enqueued so far (a flag test when none is pending), as do rc_sync and rc_refit_device.  Only the
+ * *_device queries on OTHER streams are the caller's to order (events).
+ * While a graph that captured an update or a refit may live (until a rebuilding rc_sync or "release_captures"), its replays change the
+ * scene at times the library does not see: the caller waits for a replay before any host-side read or host-buffer query, and every read
+ * of the world bound or of the host mirror of the descriptors then fetches it from the device again.
+ * The batch-recognition scale of the trace launches (claim ordering) may use the last known bound: it cannot change a hit.
+ * Reading the mirror (rc_get_instances, ...) between an update and its refit is harmless: the update stays pending.
+ * rc_scene_destroy waits for eager updates / refits still in flight (their stream must still exist), not for graph replays. */
+int rc_update_transforms_device(rc_scene* scene, uint32_t handle, const float* d_xforms, uint32_t m, void* stream);
+int rc_refit_device_async(rc_scene* scene, void* stream);
 
 /* Page-lock (pin) a caller-owned host array so that the host-buffer entry points (rc_trace_closest / rc_trace_any, rc_add_blas,
  * rc_view_factors ...) move it by DMA at the full PCIe rate instead of through the driver's staging copies: the option a Julia

@@ -316,6 +316,30 @@ class TLAS:
         check(lib().rc_refit_device(self._h, 1 if recompute_inverse else 0))
         return self
 
+    def update_transforms_device(self, handle, d_xforms, stream=None):
+        """update_transforms!(tlas, handle, transforms) for transforms that live in device memory (rc_update_transforms_device): a
+        contiguous float32 torch tensor of shape (m, 12) or (m, 3, 4) on the scene's device, or a raw device pointer to m x 12 floats
+        (m = the handle's instance count).  Enqueued on `stream` (a raw stream handle; None = the null stream); the tensor is read when
+        the kernel runs.  Follow with refit_device_async() on the same stream, or sync()."""
+        if hasattr(d_xforms, "data_ptr"):
+            t = d_xforms
+            if str(t.dtype) != "torch.float32" or not t.is_contiguous() or not t.is_cuda or t.device.index != self.device:
+                raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, "transforms tensor must be contiguous float32 on the scene's device")
+            if not (t.dim() >= 2 and (tuple(t.shape[1:]) == (12,) or tuple(t.shape[1:]) == (3, 4))):
+                raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, f"transforms tensor must have shape (m, 12) or (m, 3, 4), got {tuple(t.shape)}")
+            m, p = int(t.shape[0]), t.data_ptr()
+        else:
+            m, p = self.n_instances(handle), d_xforms
+        check(lib().rc_update_transforms_device(self._h, handle.id, ptr(p) if p else None, m, ptr(stream) if stream else None))
+        return self
+
+    def refit_device_async(self, stream=None):
+        """refit_tlas!(tlas) enqueued on `stream` with no host wait (rc_refit_device_async): later work on the same stream sees the new
+        scene, and so do the host-buffer queries (trace(), get_illumination(), ...), which wait for it on the host; *_device queries on
+        OTHER streams are the caller's to order.  world_bound() and the drivers that need it read it back lazily."""
+        check(lib().rc_refit_device_async(self._h, ptr(stream) if stream else None))
+        return self
+
     def sync(self):  # sync!, :894-921
         a = C.c_int()
         check(lib().rc_sync(self._h, C.byref(a)))

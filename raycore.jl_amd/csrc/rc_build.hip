@@ -501,6 +501,14 @@ __global__ void k_tlas_morton(const RcInstanceDesc* inst, const RcBlasDesc* desc
     vals[i] = i;
 }
 
+// The world box of an instance as a TLAS leaf keeps it: the eight corners of the BLAS's root box under `transform`, in corner order.
+__device__ inline void tlas_leaf_box(const float* transform, const RcBlasDesc& b, float3_& mn, float3_& mx) {
+    mn = mk3(INFINITY, INFINITY, INFINITY); mx = mk3(-INFINITY, -INFINITY, -INFINITY);
+    for (int c = 1; c <= 8; ++c) {
+        float3_ wc = xf_point(transform, corner(b.root_min, b.root_max, c));
+        mn = min3v(mn, wc); mx = max3v(mx, wc);
+    }
+}
 // create_tlas_leaf_nodes_kernel! (src/instanced-bvh-kernels.jl:332-375).  sorted == nullptr => refit path:
 // update_tlas_leaf_aabbs_kernel! (:487-519), the instance index is read back from child1.
 __global__ void k_tlas_leaves(RcNode* nodes, const uint32_t* sorted, const RcInstanceDesc* inst, const RcBlasDesc* descs,
@@ -511,11 +519,8 @@ __global__ void k_tlas_leaves(RcNode* nodes, const uint32_t* sorted, const RcIns
     uint32_t orig = sorted ? sorted[j - 1] : nd->child1;
     const RcInstanceDesc& in = inst[orig];
     const RcBlasDesc& b = descs[in.blas_index - 1];
-    float3_ mn = mk3(INFINITY, INFINITY, INFINITY), mx = mk3(-INFINITY, -INFINITY, -INFINITY);
-    for (int c = 1; c <= 8; ++c) {
-        float3_ wc = xf_point(in.transform, corner(b.root_min, b.root_max, c));
-        mn = min3v(mn, wc); mx = max3v(mx, wc);
-    }
+    float3_ mn, mx;
+    tlas_leaf_box(in.transform, b, mn, mx);
     nd->f[0] = mn.x; nd->f[1] = mn.y; nd->f[2] = mn.z; nd->f[3] = mx.x; nd->f[4] = mx.y; nd->f[5] = mx.z;
     nd->f[6] = nd->f[7] = nd->f[8] = nd->f[9] = nd->f[10] = nd->f[11] = 0.0f;
     nd->child0 = RC_INVALID_NODE;
@@ -657,22 +662,19 @@ __global__ void k_cull_radius(const RcPrim* prims, uint32_t n, const RcBlasDesc*
 //   a coplanar ray anywhere in the TLAS leaf's box gets the reference's NaN hit) get A = +inf; rays with a non-finite component or |d|^2
 //   outside [1e-2, 1e6] carry a NaN that fails the comparison (rc_traverse_core.h).  tests/test_gpu_entry_cull.py aims rays at every one of
 //   these edges and compares cull on / off / oracle bit for bit; mutants of the constants are caught by it.
-__global__ void k_inst_recs(const RcInstanceDesc* inst, const RcBlasDesc* descs, const uint32_t* blas_nprims, uint32_t n, RcInstRec* out,
-                            const uint32_t* cull_r_bits, float4* cull_out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const RcInstanceDesc& in = inst[i];
+// (one derivation, two callers: k_inst_recs over descriptors that are in memory, k_update_instances over the ones it is writing)
+__device__ inline RcInstRec inst_rec_of(const float* inv, uint32_t blas_index, uint32_t instance_id, const RcBlasDesc& bd, const uint32_t* blas_nprims) {
     RcInstRec r;
 #pragma unroll
-    for (int k = 0; k < 12; ++k) r.inv[k] = in.inv_transform[k];
-    const RcBlasDesc& bd = descs[in.blas_index - 1];
+    for (int k = 0; k < 12; ++k) r.inv[k] = inv[k];
     r.nodes_offset = bd.nodes_offset;
     r.prims_offset = bd.primitives_offset;
-    r.custom_index = in.instance_id;
-    r.n_prims = blas_nprims[in.blas_index - 1];
-    out[i] = r;
-    if (!cull_out) return;
-    const float* m = in.inv_transform;  // rows [a b c | t]: local = Minv * world + t
+    r.custom_index = instance_id;
+    r.n_prims = blas_nprims[blas_index - 1];
+    return r;
+}
+__device__ inline void entry_cull_sphere(const float* m, const RcBlasDesc& bd, uint32_t n_prims, uint32_t r_bits, float4& out0, float4& out1) {
+    // m = the inverse transform, rows [a b c | t]: local = Minv * world + t
     const double a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[4], a11 = m[5], a12 = m[6], a20 = m[8], a21 = m[9], a22 = m[10];
     const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
     const double det = a00 * c00 + a01 * c01 + a02 * c02;
@@ -694,16 +696,81 @@ __global__ void k_inst_recs(const RcInstanceDesc* inst, const RcBlasDesc* descs,
     const double lx = 0.5 * ((double)bd.root_min[0] + bd.root_max[0]) - m[3], ly = 0.5 * ((double)bd.root_min[1] + bd.root_max[1]) - m[7],
                  lz = 0.5 * ((double)bd.root_min[2] + bd.root_max[2]) - m[11];
     const double cx = w[0] * lx + w[1] * ly + w[2] * lz, cy = w[3] * lx + w[4] * ly + w[5] * lz, cz = w[6] * lx + w[7] * ly + w[8] * lz;
-    const double rl = (double)__uint_as_float(cull_r_bits[in.blas_index - 1]);
+    const double rl = (double)__uint_as_float(r_bits);
     const double rw = rl * sW * 1.00001;
     const double lc1 = fabs(0.5 * ((double)bd.root_min[0] + bd.root_max[0])) + fabs(0.5 * ((double)bd.root_min[1] + bd.root_max[1])) +
                        fabs(0.5 * ((double)bd.root_min[2] + bd.root_max[2]));  // |c'|_1: a mesh far from its own origin has large LOCAL coordinates, and the slab test rounds in those
     double A = 1.01 * rw + 8.0e-5 * (fabs(cx) + fabs(cy) + fabs(cz) + rw + sW * lc1);
     const double B = 4.0e-5 * sW;
-    const bool ok = r.n_prims >= 2u && sW <= 100.0 && sW * sI <= 16.0 && A < 1.0e30 && fabs(cx) < 1.0e30 && fabs(cy) < 1.0e30 && fabs(cz) < 1.0e30;  // (NaN anywhere: false)
+    const bool ok = n_prims >= 2u && sW <= 100.0 && sW * sI <= 16.0 && A < 1.0e30 && fabs(cx) < 1.0e30 && fabs(cy) < 1.0e30 && fabs(cz) < 1.0e30;  // (NaN anywhere: false)
     if (!ok) A = INFINITY;
-    cull_out[2 * i] = make_float4((float)cx, (float)cy, (float)cz, (float)A * (ok ? 1.000001f : 1.0f));
-    cull_out[2 * i + 1] = make_float4(ok ? (float)B * 1.000001f : 0.0f, 0.f, 0.f, 0.f);
+    out0 = make_float4((float)cx, (float)cy, (float)cz, (float)A * (ok ? 1.000001f : 1.0f));
+    out1 = make_float4(ok ? (float)B * 1.000001f : 0.0f, 0.f, 0.f, 0.f);
+}
+__global__ void k_inst_recs(const RcInstanceDesc* inst, const RcBlasDesc* descs, const uint32_t* blas_nprims, uint32_t n, RcInstRec* out,
+                            const uint32_t* cull_r_bits, float4* cull_out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const RcInstanceDesc& in = inst[i];
+    const RcBlasDesc& bd = descs[in.blas_index - 1];
+    const RcInstRec r = inst_rec_of(in.inv_transform, in.blas_index, in.instance_id, bd, blas_nprims);
+    out[i] = r;
+    if (!cull_out) return;
+    float4 c0, c1;
+    entry_cull_sphere(in.inv_transform, bd, r.n_prims, cull_r_bits[in.blas_index - 1], c0, c1);
+    cull_out[2 * i] = c0;
+    cull_out[2 * i + 1] = c1;
+}
+
+// Device-side update_transforms! (update_instance_transforms_offset_kernel!, src/instanced-bvh-kernels.jl:455-476) fused with everything a
+// refit derives PER INSTANCE from the new transform: for instance first + i it reads xforms[i] once and writes the descriptor's transform and
+// inverse (blas_index, instance_id and flags stay), the traversal record, the entry-cull sphere and the box of the instance's TLAS leaf --
+// what k_update_inverses, k_inst_recs and k_tlas_leaves produce in three passes over the 108-byte descriptors, bit for bit (the same
+// device functions).  leaf_of[instance] = sorted position (1-based) of its leaf, topology only (k_inst_leaf, rc_build_tlas).
+// The transforms go through LDS so that a wave reads consecutive dwords whatever the alignment of `xforms`; the 108-byte descriptors are
+// written dword by dword like everywhere else, the 64-byte records and nodes with 16-byte stores.
+__global__ __launch_bounds__(kBlock) void k_update_instances(const float* __restrict__ xforms, uint32_t first, uint32_t m, RcInstanceDesc* inst,
+                                                             const RcBlasDesc* __restrict__ descs, const uint32_t* __restrict__ blas_nprims,
+                                                             const uint32_t* __restrict__ cull_r_bits, const uint32_t* __restrict__ leaf_of,
+                                                             RcInstRec* recs, float4* cull_out, RcNode* nodes, uint32_t n) {
+    __shared__ float l_x[kBlock * 12];
+    const uint32_t base = blockIdx.x * kBlock;
+    const uint32_t words = (m - base < (uint32_t)kBlock ? m - base : (uint32_t)kBlock) * 12u;
+    for (uint32_t w = threadIdx.x; w < words; w += kBlock) l_x[w] = xforms[(size_t)base * 12u + w];
+    __syncthreads();
+    const uint32_t i = base + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t g = first + i;
+    float x[12], inv[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) x[k] = l_x[threadIdx.x * 12 + k];
+    rc_mat3x4_inverse_hd(x, inv);
+    RcInstanceDesc& d = inst[g];
+    const uint32_t blas_index = d.blas_index, instance_id = d.instance_id;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { d.transform[k] = x[k]; d.inv_transform[k] = inv[k]; }
+    const RcBlasDesc bd = descs[blas_index - 1];
+    const RcInstRec r = inst_rec_of(inv, blas_index, instance_id, bd, blas_nprims);
+    uint4* q = reinterpret_cast<uint4*>(&recs[g]);
+    q[0] = make_uint4(__float_as_uint(r.inv[0]), __float_as_uint(r.inv[1]), __float_as_uint(r.inv[2]), __float_as_uint(r.inv[3]));
+    q[1] = make_uint4(__float_as_uint(r.inv[4]), __float_as_uint(r.inv[5]), __float_as_uint(r.inv[6]), __float_as_uint(r.inv[7]));
+    q[2] = make_uint4(__float_as_uint(r.inv[8]), __float_as_uint(r.inv[9]), __float_as_uint(r.inv[10]), __float_as_uint(r.inv[11]));
+    q[3] = make_uint4(r.nodes_offset, r.prims_offset, r.custom_index, r.n_prims);
+    float4 c0, c1;
+    entry_cull_sphere(inv, bd, r.n_prims, cull_r_bits[blas_index - 1], c0, c1);
+    cull_out[2 * (size_t)g] = c0;
+    cull_out[2 * (size_t)g + 1] = c1;
+    float3_ mn, mx;
+    tlas_leaf_box(x, bd, mn, mx);
+    const uint32_t j = leaf_of[g];  // in 1..n
+    RcNode* nd = &nodes[(n - 1 + j) - 1];  // the rest of the leaf (zeros, child0 = invalid, child1 = g, parent) is topology and stays
+    *reinterpret_cast<float4*>(nd->f) = make_float4(mn.x, mn.y, mn.z, mx.x);
+    *reinterpret_cast<float2*>(nd->f + 4) = make_float2(mx.y, mx.z);
+}
+// leaf_of[sorted[j - 1]] = j: where each instance's leaf sits in the Morton order of the last rebuild
+__global__ void k_inst_leaf(const uint32_t* sorted, uint32_t n, uint32_t* leaf_of) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) leaf_of[sorted[j]] = j + 1u;
 }
 
 // stable sortperm of the 30-bit keys (Base.sortperm / AK.sortperm, src/instanced-bvh.jl:1399, 1533-1540).  rocPRIM's default switches
@@ -735,10 +802,11 @@ void emit_tree(rc_scene* s, RcNode* nodes, uint32_t n, DevBuf<uint4>& ranges) {
     else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, s->stream, nodes, 1u);  // single leaf: empty node, the leaf kernel fills the payload
 }
 
-void run_refit(rc_scene* s, RcNode* nodes, const RcPrim* prims, uint32_t n, int tlas, const DevBuf<uint4>& ranges) {
+void run_refit(rc_scene* s, RcNode* nodes, const RcPrim* prims, uint32_t n, int tlas, const DevBuf<uint4>& ranges, hipStream_t st, uint32_t* flags = nullptr) {
     if (n < 2) return;
-    RC_HIP(hipMemsetAsync(s->flags.p, 0, sizeof(uint32_t) * (n - 1), s->stream));
-    hipLaunchKernelGGL(k_refit, dim3((n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, s->stream, nodes, prims, s->flags.p, ranges.p, n, tlas);
+    if (!flags) flags = s->flags.p;
+    RC_HIP(hipMemsetAsync(flags, 0, sizeof(uint32_t) * (n - 1), st));
+    hipLaunchKernelGGL(k_refit, dim3((n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, nodes, prims, flags, ranges.p, n, tlas);
 }
 
 void host_root_aabb(const RcNode& root, bool tlas, float mn[3], float mx[3]) {
@@ -888,7 +956,7 @@ void rc_build_blas(rc_scene* s, uint32_t n, Blas& out, bool keep_face_map) {
     }
     emit_tree(s, out.nodes.p, n, s->range_tmp);
     hipLaunchKernelGGL(k_blas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, out.nodes.p, out.prims.p, n);
-    run_refit(s, out.nodes.p, out.prims.p, n, 0, s->range_tmp);
+    run_refit(s, out.nodes.p, out.prims.p, n, 0, s->range_tmp, s->stream);
     rc_timing_scene_end(s, s->stream);
     RcNode root;
     RC_HIP(hipMemcpyAsync(&root, out.nodes.p, sizeof(RcNode), hipMemcpyDeviceToHost, s->stream));
@@ -899,10 +967,10 @@ void rc_build_blas(rc_scene* s, uint32_t n, Blas& out, bool keep_face_map) {
 
 // rebuild_bvh! minus compaction (src/instanced-bvh.jl:968-992): build_tlas_topology (:1485-1594) +
 // The TLAS part of the traversal copy (behind the BLAS nodes), renumbered when the scene keeps the TLAS's top in LDS (tlas_top_k).
-static void pack_tlas(rc_scene* s) {
+static void pack_tlas(rc_scene* s, hipStream_t st) {
     const uint32_t n = (s->n_tlas_nodes + 1) / 2;
-    if (s->tlas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, s->stream, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, s->tlas_remap.p, false);
-    else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, s->stream, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, 0u);
+    if (s->tlas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, s->tlas_remap.p, false);
+    else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, 0u);
 }
 
 // build_flat_blas_arrays! (:470-517) + the traversal instance records.
@@ -981,7 +1049,10 @@ void rc_build_tlas(rc_scene* s) {
     RC_HIP(hipMemsetAsync(s->blas_cull_bits.p, 0, sizeof(uint32_t) * (nb ? nb : 1), s->stream));
     if (nb && tp) hipLaunchKernelGGL(k_cull_radius, dim3(grid_for(tp)), dim3(kBlock), 0, s->stream, s->flat_prims.p, tp, s->d_descs.p, nb, s->blas_cull_bits.p);
     s->n_static_instances = n;
+    s->captured_update = false;
+    s->captured_refit = false;  // (a graph that captured a refit of the old arrays is dead: its addresses are gone)
     if (n == 0) {  // :969-977
+        s->bound_stale = false;
         s->n_tlas_nodes = 0;
         for (int k = 0; k < 3; ++k) { s->root_min[k] = INFINITY; s->root_max[k] = -INFINITY; }
         RC_HIP(hipStreamSynchronize(s->stream));
@@ -1002,18 +1073,22 @@ void rc_build_tlas(rc_scene* s) {
     emit_tree(s, s->tlas_nodes.p, n, s->tlas_ranges);
     // n == 1 (:1553-1570): the single leaf holds the scene AABB == the instance's world AABB (same min/max set)
     hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->tlas_nodes.p, s->vals_b.p, s->d_instances.p, s->d_descs.p, n);
-    run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges);
+    run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges, s->stream);
+    s->tlas_flags.reserve(n);  // arrival counters of the asynchronous refit: its own, because s->flags is also the BLAS builds' (other stream)
+    s->inst_leaf.reserve(n);  // instance -> leaf (rc_update_instances_async): topology only, like the renumbering below
+    hipLaunchKernelGGL(k_inst_leaf, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, (const uint32_t*)s->vals_b.p, n, s->inst_leaf.p);
     if (s->tlas_top_k) {  // the renumbering depends on the topology only: computed here, reused by every refit
         s->tlas_remap.reserve(n - 1);
         hipLaunchKernelGGL(k_iota1, dim3(grid_for(n - 1)), dim3(kBlock), 0, s->stream, s->tlas_remap.p, n - 1);
         hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, s->stream, s->tlas_nodes.p, n, s->tlas_top_k, s->tlas_remap.p);
     }
-    pack_tlas(s);
+    pack_tlas(s, s->stream);
     RcNode root;
     RC_HIP(hipMemcpyAsync(&root, s->tlas_nodes.p, sizeof(RcNode), hipMemcpyDeviceToHost, s->stream));
     RC_HIP(hipStreamSynchronize(s->stream));
     RC_HIP(hipGetLastError());
     host_root_aabb(root, true, s->root_min, s->root_max);
+    s->bound_stale = false;
 }
 
 // refit_tlas! (src/instanced-bvh.jl:2197-2222): new transforms -> leaf AABBs -> bottom-up refit, in place
@@ -1032,11 +1107,84 @@ void rc_refit_tlas(rc_scene* s, bool from_device, bool recompute_inverse) {
     hipLaunchKernelGGL(k_inst_recs, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->d_instances.p, s->d_descs.p, s->d_blas_nprims.p, n, s->inst_recs.p,
                        (const uint32_t*)s->blas_cull_bits.p, s->inst_cull.p);
     hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->tlas_nodes.p, (const uint32_t*)nullptr, s->d_instances.p, s->d_descs.p, n);
-    run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges);
-    pack_tlas(s);
+    run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges, s->stream);
+    pack_tlas(s, s->stream);
     RcNode root;
     RC_HIP(hipMemcpyAsync(&root, s->tlas_nodes.p, sizeof(RcNode), hipMemcpyDeviceToHost, s->stream));
     RC_HIP(hipStreamSynchronize(s->stream));
     RC_HIP(hipGetLastError());
     host_root_aabb(root, true, s->root_min, s->root_max);
+    s->bound_stale = false;
+}
+
+// ---- the asynchronous update: everything on the caller's stream, nothing read back ------------------------------------------------------
+static bool stream_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return cs == hipStreamCaptureStatusActive;
+}
+static void note_async_mutation(rc_scene* s, hipStream_t st) {
+    if (stream_capturing(st)) return;  // (replays are the caller's to wait for)
+    s->async_stream = st;
+    s->async_pending = true;
+}
+
+void rc_update_instances_async(rc_scene* s, uint32_t first, uint32_t m, const float* d_xforms, hipStream_t st) {
+    const uint32_t n = (uint32_t)s->instances.size();
+    if (m == 0) return;
+    hipLaunchKernelGGL(k_update_instances, dim3(grid_for(m)), dim3(kBlock), 0, st, d_xforms, first, m, s->d_instances.p, (const RcBlasDesc*)s->d_descs.p,
+                       (const uint32_t*)s->d_blas_nprims.p, (const uint32_t*)s->blas_cull_bits.p, (const uint32_t*)s->inst_leaf.p, s->inst_recs.p,
+                       s->inst_cull.p, s->tlas_nodes.p, n);
+    RC_HIP(hipGetLastError());
+    if (stream_capturing(st)) s->captured_update = true;
+    note_async_mutation(s, st);
+}
+
+// refit_tlas! on `st` without the root read-back.  per_instance: the descriptors were rewritten by the caller's own kernels
+// (rc_instance_buffer_device), so the records, spheres and leaf boxes are derived from them first; after rc_update_instances_async they
+// are already in place.
+void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
+    const uint32_t n = (uint32_t)s->instances.size();
+    if (n == 0) return;
+    if (per_instance) {
+        hipLaunchKernelGGL(k_inst_recs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, s->d_blas_nprims.p, n, s->inst_recs.p,
+                           (const uint32_t*)s->blas_cull_bits.p, s->inst_cull.p);
+        hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, st, s->tlas_nodes.p, (const uint32_t*)nullptr, s->d_instances.p, s->d_descs.p, n);
+    }
+    run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges, st, s->tlas_flags.p);
+    pack_tlas(s, st);
+    RC_HIP(hipGetLastError());
+    s->host_instances_stale = true;
+    s->bound_stale = true;
+    if (stream_capturing(st)) s->captured_refit = true;  // every replay moves the root box again: the host copy is never trusted while the graph may live
+    note_async_mutation(s, st);
+}
+
+// Host wait for the EAGER asynchronous updates and refits enqueued so far.  Replays of a graph that captured them are the caller's to
+// wait for (a graph can be launched on any stream): the readers below then re-read what the device holds.
+void rc_wait_async_mutations(rc_scene* s) {
+    if (!s->async_pending) return;
+    RC_HIP(hipSetDevice(s->device));
+    if (stream_capturing(s->async_stream))
+        throw RcError(6, "the scene was updated asynchronously on a stream that is now being captured: its host-side state (world bound, instance mirror) is stale and cannot be refreshed during the capture");
+    if (hipStreamSynchronize(s->async_stream) != hipSuccess) {  // (the caller destroyed the stream: its work is waited for with the device's)
+        (void)hipGetLastError();
+        RC_HIP(hipDeviceSynchronize());
+    }
+    s->async_pending = false;
+}
+
+void rc_ensure_world_bound(rc_scene* s, hipStream_t for_stream) {
+    if (!s->bound_stale && !s->captured_refit) return;
+    std::lock_guard<std::mutex> lk(s->launch_mu);  // queries are re-entrant: one of them refreshes, the others find it done (callers take no launch guard before this)
+    if (!s->bound_stale && !s->captured_refit) return;
+    if (s->n_tlas_nodes == 0) { s->bound_stale = false; return; }
+    if (for_stream && stream_capturing(for_stream))
+        throw RcError(6, "stale world bound: the scene was refitted asynchronously (rc_refit_device_async) and this call lays its rays out from the world bound, which cannot be read back while the stream is being captured -- call rc_world_bound before the capture");
+    RC_HIP(hipSetDevice(s->device));
+    rc_wait_async_mutations(s);
+    RcNode root;
+    rc_copy_now(&root, s->tlas_nodes.p, sizeof(RcNode), hipMemcpyDeviceToHost);
+    host_root_aabb(root, true, s->root_min, s->root_max);
+    s->bound_stale = false;
 }

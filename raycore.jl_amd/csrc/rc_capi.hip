@@ -124,17 +124,26 @@ void compact_instances(rc_scene* s) {
 // The host mirror of tlas.instances is authoritative except after a device-side rewrite (rc_refit_device): pull it back
 // before anything reads or edits it.
 void sync_host_instances(rc_scene* s) {
-    if (!s->host_instances_stale) return;
+    // (captured_update: replays of a graph rewrite the descriptors at times the host does not see, so the mirror is pulled on every use --
+    // unless it holds edits of its own that the next rc_sync has yet to upload)
+    if (!s->host_instances_stale && !(s->captured_update && s->has_static && !s->mirror_edited)) return;
     RC_HIP(hipSetDevice(s->device));
+    rc_wait_async_mutations(s);
     RC_HIP(hipStreamSynchronize(s->stream));
     if (!s->instances.empty())
         rc_copy_now(s->instances.data(), s->d_instances.p, sizeof(RcInstanceDesc) * s->instances.size(), hipMemcpyDeviceToHost);
-    s->host_instances_stale = false;
+    s->host_instances_stale = false;  // (device_dirty stays: a read of the mirror is no mutation, the update still waits for its refit)
 }
 
 void require_synced(rc_scene* s) {
     if (!s->has_static || s->dirty || s->transforms_dirty)
         throw RcError(RC_ERR_NOT_SYNCED, "scene has pending mutations: call rc_sync before tracing (Adapt.adapt does this per dispatch)");
+}
+// The host-buffer queries run on streams of the library's own, which the caller cannot order behind an asynchronous update / refit it
+// enqueued on a stream of its own: they wait for it here (one flag test when nothing is pending).
+void require_synced_host(rc_scene* s) {
+    require_synced(s);
+    rc_wait_async_mutations(s);
 }
 
 // The scene's stack-overflow word is sticky: kernels only ever set it, and it is cleared here when it is reported -- so a launch can
@@ -299,6 +308,7 @@ int rc_scene_destroy(rc_scene* s) {
         if (s->slots[i].recorded && s->slots[i].t1) (void)hipEventSynchronize(s->slots[i].t1);
     for (auto& c : s->call_ctx) if (c && c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto a : s->aux_streams) if (a) (void)hipStreamSynchronize(a);
+    if (s->async_pending) (void)hipStreamSynchronize(s->async_stream);  // an asynchronous update / refit nobody has waited for yet
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     (void)hipGetLastError();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -439,7 +449,7 @@ int rc_export_triangles(rc_scene* s, rc_triangle* out, uint32_t capacity, uint32
     if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
     return guarded([&] {
         use_device(s);
-        require_synced(s);
+        require_synced_host(s);
         if (count) *count = s->n_flat_prims;
         if (!out || s->n_flat_prims == 0) return;
         if (capacity < s->n_flat_prims) throw RcError(RC_ERR_INVALID_ARGUMENT, "export buffer too small");
@@ -468,6 +478,7 @@ int rc_add_instances_with_inverse(rc_scene* s, uint32_t blas_id, const float* xf
         sync_host_instances(s);
         if (blas_id >= s->blas.size()) throw RcError(RC_ERR_INVALID_ARGUMENT, "blas_id out of range");
         HandleRange r{(uint32_t)s->instances.size(), m};
+        s->mirror_edited = true;
         for (uint32_t i = 0; i < m; ++i) {  // :670-674
             RcInstanceDesc d;
             d.blas_index = blas_id + 1;
@@ -496,6 +507,7 @@ int rc_update_transforms(rc_scene* s, uint32_t handle, const float* xforms, uint
         HandleRange& r = live_range(s, handle);
         if (m != r.count) throw RcError(RC_ERR_INVALID_ARGUMENT, "Transform count (" + std::to_string(m) + ") != instance count (" + std::to_string(r.count) + ")");
         if (!xforms) throw RcError(RC_ERR_INVALID_ARGUMENT, "xforms is NULL");
+        s->mirror_edited = true;
         for (uint32_t i = 0; i < m; ++i) {  // update_instance_transforms_offset_kernel! (src/instanced-bvh-kernels.jl:455-476)
             RcInstanceDesc& d = s->instances[r.first + i];
             memcpy(d.transform, xforms + 12 * (size_t)i, 48);
@@ -564,6 +576,16 @@ int rc_sync(rc_scene* s, int* action) {
     if (!s->dirty && !s->transforms_dirty && s->has_static) return RC_OK;  // :898-900, no device sync
     return guarded([&] {
         use_device(s);
+        if (s->has_static && !s->dirty && s->device_dirty && s->host_instances_stale) {
+            // rc_update_transforms_device since the last refit: the device descriptors are the new ones and the mirror is stale -- refit from
+            // them (the per-instance passes run again: they reproduce what the update kernel wrote); the mirror is refreshed when someone reads it
+            rc_wait_async_mutations(s);
+            rc_refit_tlas(s, true, false);
+            s->device_dirty = false;
+            s->transforms_dirty = false;
+            if (action) *action = 1;
+            return;
+        }
         sync_host_instances(s);
         if (s->dirty || !s->has_static) {  // rebuild_bvh! + rebuild_static_tlas! (:902-905, :911-915)
             if (!s->deleted_handles.empty()) compact_instances(s);
@@ -577,6 +599,8 @@ int rc_sync(rc_scene* s, int* action) {
             s->transforms_dirty = false;
             if (action) *action = 1;
         }
+        s->mirror_edited = false;  // the device holds what the mirror holds
+        s->device_dirty = false;
     });
 }
 
@@ -598,6 +622,10 @@ int rc_counts(rc_scene* s, uint32_t* n_live, uint32_t* n_total, uint32_t* n_geom
 
 int rc_world_bound(rc_scene* s, float out[6]) {
     if (!s || !out) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (s->bound_stale || s->captured_refit) {  // after rc_refit_device_async: wait for the refit, read the root back
+        const int rc = guarded([&] { rc_ensure_world_bound(s); });
+        if (rc != RC_OK) return rc;
+    }
     memcpy(out, s->root_min, 12);
     memcpy(out + 3, s->root_max, 12);
     return RC_OK;
@@ -623,13 +651,13 @@ int rc_wait(rc_scene* s) {
 
 int rc_export_tlas_nodes(rc_scene* s, rc_bvh_node* out, uint32_t capacity, uint32_t* count) {
     if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
-    return guarded([&] { use_device(s); require_synced(s); export_nodes(s, s->tlas_nodes.p, s->n_tlas_nodes, out, capacity, count); });
+    return guarded([&] { use_device(s); require_synced_host(s); export_nodes(s, s->tlas_nodes.p, s->n_tlas_nodes, out, capacity, count); });
 }
 int rc_export_blas_nodes(rc_scene* s, rc_bvh_node* out, uint32_t capacity, uint32_t* count) {
     if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
     return guarded([&] {
         use_device(s);
-        require_synced(s);
+        require_synced_host(s);
         if (count) *count = s->n_flat_nodes;
         if (!out || s->n_flat_nodes == 0) return;
         if (capacity < s->n_flat_nodes) throw RcError(RC_ERR_INVALID_ARGUMENT, "export buffer too small");
@@ -662,7 +690,7 @@ int rc_export_prims(rc_scene* s, rc_prim* out, uint32_t capacity, uint32_t* coun
     if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
     return guarded([&] {
         use_device(s);
-        require_synced(s);
+        require_synced_host(s);
         if (count) *count = s->n_flat_prims;
         if (!out || s->n_flat_prims == 0) return;
         if (capacity < s->n_flat_prims) throw RcError(RC_ERR_INVALID_ARGUMENT, "export buffer too small");
@@ -770,7 +798,7 @@ static void trace_host_pipelined(rc_scene* s, CallCtx& cx, const rc_ray* rays, r
 // One device's share of a host-buffer batch (throws; the C-ABI wrappers and rc_multi.hip's per-device threads catch).
 extern "C++" void rc_trace_host_impl(rc_scene* s, const rc_ray* rays, rc_hit* hits, uint64_t n, int any) {
     use_device(s);
-    require_synced(s);
+    require_synced_host(s);
     if (n == 0) return;
     if (!rays || !hits) throw RcError(RC_ERR_INVALID_ARGUMENT, "rays/hits is NULL");
     CtxLease lease(s);  // this call's own stream and staging buffers: host-buffer trace calls are re-entrant on a synced scene
@@ -940,7 +968,7 @@ int rc_collide_instances(rc_scene* s, rc_contact_pair* out, uint64_t capacity, u
     if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
     return guarded([&] {
         use_device(s);
-        require_synced(s);
+        require_synced_host(s);
         std::lock_guard<std::mutex> one_at_a_time(s->host_call_mu);
         uint64_t total = rc_collide_instances_launch(s, nullptr, 0, s->stream);
         if (count) *count = total;
@@ -957,7 +985,7 @@ int rc_collide_instances_any(rc_scene* s, uint32_t handle_a, uint32_t handle_b, 
     if (!s || !overlap) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
     return guarded([&] {
         use_device(s);
-        require_synced(s);
+        require_synced_host(s);
         const HandleRange ra = live_range(s, handle_a), rb = live_range(s, handle_b);
         const uint32_t n = s->n_static_instances;
         *overlap = 0;
@@ -1012,6 +1040,7 @@ int rc_scene_save(rc_scene* s, const char* path) {
         sync_host_instances(s);
         use_device(s);
         require_synced(s);  // compaction has run: no deleted handles, no unreferenced geometry
+        rc_ensure_world_bound(s);  // (also waits for an asynchronous refit still in flight)
         RC_HIP(hipStreamSynchronize(s->stream));
         FileCloser fc{fopen(path, "wb")};
         if (!fc.f) throw RcError(RC_ERR_INVALID_ARGUMENT, std::string("cannot open ") + path);
@@ -1166,9 +1195,43 @@ int rc_refit_device(rc_scene* s, int recompute_inverse) {
     return guarded([&] {
         use_device(s);
         require_synced(s);
+        rc_wait_async_mutations(s);  // (an asynchronous update / refit on a caller's stream comes first)
         rc_timing_scene_begin(s, s->stream);
         rc_refit_tlas(s, true, recompute_inverse != 0);
         rc_timing_scene_end(s, s->stream);
+    });
+}
+
+// update_transforms!(tlas, handle, transforms) for a device array (src/instanced-bvh.jl:784-794): one kernel on the caller's stream that
+// reads the transforms WHEN IT RUNS and writes descriptors, traversal records, entry-cull spheres and leaf boxes (k_update_instances).
+int rc_update_transforms_device(rc_scene* s, uint32_t handle, const float* d_xforms, uint32_t m, void* stream) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    return guarded([&] {
+        const HandleRange r = live_range(s, handle);
+        if (m != r.count) throw RcError(RC_ERR_INVALID_ARGUMENT, "Transform count (" + std::to_string(m) + ") != instance count (" + std::to_string(r.count) + ")");
+        if (!d_xforms) throw RcError(RC_ERR_INVALID_ARGUMENT, "d_xforms is NULL");
+        if (!s->has_static || s->dirty || s->mirror_edited)
+            throw RcError(RC_ERR_NOT_SYNCED, "rc_update_transforms_device writes the descriptors where the last rc_sync put them: the scene has pending host-side mutations, call rc_sync first");
+        use_device(s);
+        rc_update_instances_async(s, r.first, m, d_xforms, (hipStream_t)stream);
+        s->host_instances_stale = true;
+        s->device_dirty = true;
+        s->transforms_dirty = true;
+    });
+}
+
+// refit_tlas! (src/instanced-bvh.jl:2197-2222) on the caller's stream: no read-back, no host wait; the world bound is refreshed lazily.
+int rc_refit_device_async(rc_scene* s, void* stream) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    return guarded([&] {
+        if (!s->has_static || s->dirty || s->mirror_edited)
+            throw RcError(RC_ERR_NOT_SYNCED, "scene has pending host-side mutations: call rc_sync (rc_refit_device_async commits device-side updates only)");
+        use_device(s);
+        // device_dirty: every change since the last refit came through rc_update_transforms_device, whose kernel has already written the
+        // per-instance data; otherwise the descriptors were rewritten through rc_instance_buffer_device and it is derived from them here
+        rc_refit_tlas_async(s, !s->device_dirty, (hipStream_t)stream);
+        s->device_dirty = false;
+        s->transforms_dirty = false;
     });
 }
 
@@ -1198,6 +1261,8 @@ int rc_set_option(rc_scene* s, const char* name, int64_t value) {
             std::lock_guard<std::mutex> g(s->launch_mu);
             s->capture_slots.clear();
             s->last_capture = -1;
+            if (s->captured_refit) { s->captured_refit = false; s->bound_stale = true; }  // (no replay can move the root box any more: one more read-back settles it)
+            if (s->captured_update) { s->captured_update = false; s->host_instances_stale = s->host_instances_stale || !s->mirror_edited; }
         }
     }
     else if (k == "release_capture") {  // ONE captured launch handed back: value = the token option "last_capture_token" returned right after that capture
@@ -1315,7 +1380,7 @@ int rc_get_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, floa
     if (!s || !viewdir || !out_counts) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
     return guarded([&] {
         use_device(s);
-        require_synced(s);
+        require_synced_host(s);
         std::lock_guard<std::mutex> one_at_a_time(s->host_call_mu);
         uint32_t np = s->n_flat_prims;
         s->f32_stage.reserve(np ? np : 1);
@@ -1346,7 +1411,7 @@ int rc_view_factors_rows_host(rc_scene* s, uint32_t rays_per_triangle, uint64_t 
     if (!s || !out_matrix) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
     return guarded([&] {
         use_device(s);
-        require_synced(s);
+        require_synced_host(s);
         if (ld < s->n_flat_prims) throw RcError(RC_ERR_INVALID_ARGUMENT, "leading dimension smaller than the number of primitives");
         std::lock_guard<std::mutex> one_at_a_time(s->host_call_mu);
         rc_timing_fixed(s, rc_view_factors_rows_to_host(s, rays_per_triangle, seed, row_begin, row_end, out_matrix, ld));

@@ -595,6 +595,7 @@ GridParams grid_params(rc_scene* s, const float viewdir[3], uint32_t grid) {
 }  // namespace
 
 void rc_launch_ray_grid(rc_scene* s, const float viewdir[3], uint32_t grid, RcRay* d_rays, hipStream_t stream) {
+    rc_ensure_world_bound(s, stream);  // the grid is laid out from the world bound: after an asynchronous refit it is read back first
     GridParams g = grid_params(s, viewdir, grid);
     uint64_t n = (uint64_t)grid * grid;
     uint32_t blocks = (uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)s->n_cus * 8);
@@ -614,6 +615,7 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
                             float* d_counts, hipStream_t stream) {
     if (ray_end <= ray_begin) return;
     check_buffer_range(s);
+    rc_ensure_world_bound(s, stream);
     GridParams g = grid_params(s, viewdir, grid);
     const bool partial = rc_partial_driver_ok(s);
     const bool lds = partial || rc_lds_driver_ok(s);

@@ -207,6 +207,26 @@ struct rc_scene {
     uint32_t next_handle_id = 1;
     bool dirty = true, transforms_dirty = false, has_static = false;
     bool host_instances_stale = false;  // descriptors were rewritten on the device (rc_instance_buffer_device + rc_refit_device)
+    // ---- host state of the mutable scene.  Who sets / who clears / who refuses:
+    //  dirty             set: push, delete, geometry update, load.        cleared: rebuilding rc_sync.          refused while set: every query, rc_update_transforms_device, rc_refit_device_async
+    //  transforms_dirty  set: rc_update_transforms(_device).              cleared: rc_sync, rc_refit_device_async.  refused while set: every query (RC_ERR_NOT_SYNCED)
+    //  mirror_edited     set: push, rc_update_transforms (the host mirror holds edits the device lacks).  cleared: rc_sync (upload).
+    //                    refused while set: rc_update_transforms_device, rc_refit_device_async; the mirror is never pulled from the device
+    //  device_dirty      set: rc_update_transforms_device (the DEVICE descriptors are newer than the last refit; the update kernel has written the
+    //                    per-instance data).  cleared: rc_refit_device_async, rc_sync.  Survives a pull of the mirror (a read is no mutation).
+    //                    rc_sync with device_dirty && host_instances_stale refits from the device; otherwise the mirror equals the device and is uploaded
+    //  host_instances_stale  set: rc_refit_device, rc_update_transforms_device, rc_refit_device_async.  cleared: sync_host_instances (pull), which every
+    //                    reader / editor of the mirror calls first.  Implies !mirror_edited
+    //  bound_stale       set: rc_refit_device_async.  cleared: rc_ensure_world_bound (read-back), rc_sync.  While set, a driver that needs the bound
+    //                    fails on a capturing stream
+    //  captured_update / captured_refit  set: the call was captured into a graph.  cleared: rebuilding rc_sync, option "release_captures".  While set,
+    //                    the mirror (unless mirror_edited) / the bound are re-read from the device on every use: replays happen unseen
+    //  async_pending + async_stream  set: an EAGER update / refit was enqueued there.  cleared: rc_wait_async_mutations (stream synchronise), which the
+    //                    host-buffer queries, the mirror pull, the bound read-back, rc_sync, rc_refit_device and rc_scene_destroy call first
+    bool mirror_edited = false, device_dirty = false;
+    bool bound_stale = false, captured_update = false, captured_refit = false;
+    bool async_pending = false;
+    hipStream_t async_stream = nullptr;
 
     // StaticTLAS (src/instanced-bvh.jl:155-168): the adapted form owned by rc_sync
     DevBuf<RcNode> tlas_nodes;
@@ -218,6 +238,8 @@ struct rc_scene {
     uint32_t n_static_instances = 0;
     DevBuf<RcNode> flat_nodes;
     uint32_t n_flat_nodes = 0;
+    DevBuf<uint32_t> tlas_flags;       // arrival counters of rc_refit_tlas_async (n - 1 words; `flags` below belongs to the builds on the scene's own stream)
+    DevBuf<uint32_t> inst_leaf;        // instance -> sorted position (1-based) of its TLAS leaf: topology only, built by rc_build_tlas for k_update_instances
     DevBuf<uint32_t> tlas_remap;       // same for the TLAS's internal nodes (top levels too large for the full LDS kernels), kept for refits
     uint32_t tlas_top_k = 0;
     uint32_t tlas_top_k32 = 0, blas_top_k32 = 0;  // what the kernels with 32-bit lane stacks (smaller node planes) stage of the same renumbering: prefixes of tlas_top_k / blas_top_k
@@ -344,6 +366,10 @@ void rc_launch_shading_attributes(rc_scene* s, const RcHit* d_hits, uint64_t n, 
 void rc_build_tlas(rc_scene* s);   // build_tlas_topology + flat arrays -> StaticTLAS
 void rc_refit_tlas(rc_scene* s, bool from_device = false, bool recompute_inverse = false);   // refit_tlas!
 void rc_mat3x4_inverse(const float m[12], float out[12]);
+void rc_update_instances_async(rc_scene* s, uint32_t first, uint32_t m, const float* d_xforms, hipStream_t stream);  // transforms -> descriptors, records, cull spheres, leaf boxes
+void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t stream);  // refit_tlas! on `stream`, no read-back: leaves the world bound stale
+void rc_wait_async_mutations(rc_scene* s);                      // host wait for what the two above enqueued (throws while their stream is being captured)
+void rc_ensure_world_bound(rc_scene* s, hipStream_t for_stream = nullptr);  // root_min / root_max current, or an error when `for_stream` is being captured
 
 // rc_traverse.hip
 // learn_order = false: this launch is one piece of a larger batch (the chunked host-buffer path): the next launch of the same size traces OTHER rays,

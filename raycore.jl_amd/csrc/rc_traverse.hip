@@ -959,6 +959,7 @@ bool rc_cost_order_setup(rc_scene* s, uint64_t n, int any_hit, hipStream_t strea
         h->records_asked += 1;
         if (h->rebuild_credit < 1) h->rebuild_credit = 1;  // (the next launch gets the rebuild pair)
     }
+    // (after rc_refit_device_async this is the last bound the host read back: it only scales the batch-recognition samples, never a hit)
     const float ex = s->root_max[0] - s->root_min[0], ey = s->root_max[1] - s->root_min[1], ez = s->root_max[2] - s->root_min[2];
     const float l2 = ex * ex + ey * ey + ez * ez;
     c.inv_l2 = (l2 > 0.f && l2 < 1e30f) ? 1.0f / l2 : 0.f;

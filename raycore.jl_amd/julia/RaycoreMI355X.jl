@@ -463,6 +463,16 @@ end
 Raycore.refit_tlas!(t::MI355XTLAS; recompute_inverse::Bool = true) =
     (check(ccall((:rc_refit_device, LIB), Cint, (Ptr{Cvoid}, Cint), t.ptr, recompute_inverse ? 1 : 0)); t)
 
+# update_transforms!(tlas, handle, transforms) with a backend-resident array (src/instanced-bvh.jl:784-794): `d_transforms` points at
+# m Mat3x4f (48 bytes each) in device memory, read when the kernel runs on `stream`; commit with refit_tlas_async! on the same stream
+# (no host wait: update -> refit -> trace can be captured into one graph), or with sync!.
+function Raycore.update_transforms!(t::MI355XTLAS, h::TLASHandle, d_transforms::Ptr{Float32}, m::Integer; stream::Ptr{Cvoid} = C_NULL)
+    check(ccall((:rc_update_transforms_device, LIB), Cint, (Ptr{Cvoid}, UInt32, Ptr{Float32}, UInt32, Ptr{Cvoid}), t.ptr, h.id, d_transforms, m, stream))
+    return t
+end
+refit_tlas_async!(t::MI355XTLAS; stream::Ptr{Cvoid} = C_NULL) =
+    (check(ccall((:rc_refit_device_async, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), t.ptr, stream)); t)
+
 # collide_instances / collide_instances_any (src/collision.jl:189-262)
 function Raycore.collide_instances(t::MI355XTLAS)
     n = Ref{UInt64}(0)

@@ -40,9 +40,13 @@ class WavefrontPaths:
     path_ids[b] (the path each slot of rays[b] continues; path_ids[0] is the primary ray index, dead slots hold RC_INVALID_ID).
     compact=True gathers the hits into a live-first queue (compact_hits_device) before each bounce, so the live slots come first and the
     dead tail is traced as rays that miss; compact=False keeps slot i on path i.  A path's bounce directions depend only on
-    (seed, path id, depth), so both modes produce the same (path id -> hit) records."""
+    (seed, path id, depth), so both modes produce the same (path id -> hit) records.
 
-    def __init__(self, accel, width, height, samples, depth, camera, light, seed=0, bias=1e-3, compact=True):
+    dynamic: a list of (handle, transforms tensor) pairs -- float32 (m, 12) or (m, 3, 4) on the accel's device.  Every frame then starts
+    with update_transforms_device for each pair and one refit_device_async on the frame's stream, before the primary rays: the frame
+    shows whatever the tensors hold when it runs, also when it is a replay of the captured graph."""
+
+    def __init__(self, accel, width, height, samples, depth, camera, light, seed=0, bias=1e-3, compact=True, dynamic=None):
         import torch
         if depth < 1:
             raise ValueError("depth must be at least 1")
@@ -53,6 +57,7 @@ class WavefrontPaths:
         self.camera = {k: (np.asarray(v, np.float32) if k in ("pos", "right", "up", "forward") else float(v)) for k, v in camera.items()}
         self.light = np.ascontiguousarray(light, dtype=np.float32)
         self.seed, self.bias, self.compact = int(seed), float(bias), bool(compact)
+        self.dynamic = list(dynamic) if dynamic else []
         dev = torch.device("cuda", accel.device)
         rec = lambda: torch.zeros(self.n * 32, dtype=torch.uint8, device=dev)  # noqa: E731
         self.rays = [rec() for _ in range(depth)]
@@ -70,7 +75,7 @@ class WavefrontPaths:
         self._graph_stream = None
 
     def buffers(self):
-        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + self.path_ids + [self.indices, self.count]
+        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic]
 
     def run(self, stream=None):
         """Enqueue one frame on `stream` (a torch.cuda.Stream; None = the current stream).  No host synchronisation.  The first frame on
@@ -82,6 +87,10 @@ class WavefrontPaths:
                 buf.record_stream(s)
             self._streams.add(st)
         a, c, n = self.accel, self.camera, self.n
+        if self.dynamic:
+            for handle, xf in self.dynamic:
+                a.update_transforms_device(handle, xf, stream=st)
+            a.refit_device_async(stream=st)
         a.primary_rays_lookat_device(c["pos"], c["right"], c["up"], c["forward"], c["half_width"], c["half_height"], self.width, self.height,
                                      self.rays[0].data_ptr(), samples=self.samples, seed=self.seed, jitter=True, stream=st)
         a.trace_device(self.rays[0].data_ptr(), self.hits[0].data_ptr(), n, stream=st)
