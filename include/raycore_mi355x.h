@@ -216,7 +216,8 @@ int rc_trace_any_device_batches(rc_scene* scene, const rc_ray* const* d_rays, rc
  * host thread joins the device's NUMA node and faults in its own row block; default 1), "release_captures" (set to 1 when the hipGraphs that
  * captured launches of this scene have been destroyed: frees their stack spill regions and counter slots, 16 per scene; get: how many are held),
  * "blas_top" (1 = a scene with a single BLAS keeps that BLAS's top internal
- * nodes in LDS; takes effect at the next structural rc_sync), "onesweep_min" (key count from which
+ * nodes in LDS; takes effect at the next structural rc_sync), "tlas_rebuild_fused" (1 = rc_rebuild_tlas_device_async rebuilds scenes of
+ * 2 .. 256 instances with its single-workgroup kernel, 0 = always with the chain of build kernels), "onesweep_min" (key count from which
  * the builds sort with Onesweep radix passes instead of a merge sort), "stats" (dev counters),
  * "timeline_ptr" (dev: device address of 8 x u64 per wave that kernel 5 fills with its waves' event
  * times, tools/archive/timeline_probe.py; 0 = off).
@@ -499,6 +500,32 @@ int rc_refit_device(rc_scene* scene, int recompute_inverse);
  * rc_scene_destroy waits for eager updates / refits still in flight (their stream must still exist), not for graph replays. */
 int rc_update_transforms_device(rc_scene* scene, uint32_t handle, const float* d_xforms, uint32_t m, void* stream);
 int rc_refit_device_async(rc_scene* scene, void* stream);
+
+/* rebuild_bvh!(tlas) (src/instanced-bvh.jl:968-992; build_tlas_topology, :1485-1594) from the instances' CURRENT DEVICE-SIDE transforms, enqueued on
+ * the caller's `stream` with no host wait: rc_refit_device_async, except that the topology is built anew -- Morton codes from the new
+ * instance boxes, stable sort, Karras tree, refit -- instead of kept from the last rc_sync.  For animations that carry instances far from
+ * where they were sorted: a refitted tree's boxes grow and overlap, and the structural rc_sync that would repair it uploads the host
+ * mirror, waits on the host and kills every captured update / refit.
+ * RESULT: everything the trace reads is byte-identical to what a fresh scene holds after rc_sync, given the same BLASes and the same
+ * instances pushed in the same order with these transforms: TLAS nodes (rc_export_tlas_nodes), world bound, and therefore every hit
+ * record, exact ties and any_hit included.
+ * IN PLACE: no buffer address changes and the node count, kernel choice and LDS plan depend on the instance count alone, so graphs that
+ * captured updates, refits (also of this scene's WavefrontPaths frames) or traces stay valid and see the new tree on their next replay.
+ * It rewrites the TLAS nodes and their traversal copy, the topology records later refits walk, the instance -> leaf table
+ * rc_update_transforms_device scatters through, and the renumbering of the TLAS's top (scenes of more than 256 instances).
+ * Scene state: as rc_refit_device_async.  After rc_update_transforms_device calls the per-instance data is in place; with none since the
+ * last refit / rebuild it is derived from the descriptors first.  Clears transforms-dirty; leaves the world bound and the host mirror to
+ * the same lazy refresh; host-buffer queries, rc_sync (then a no-op), rc_world_bound, the exports, rc_scene_save and the collision calls
+ * behave as after an asynchronous refit.  A later rc_update_transforms + rc_sync refits on the new topology.
+ * No allocation, host copy, event or synchronisation (its scratch, the sort's temporary storage included, is reserved by rc_sync and is
+ * not shared with BLAS builds, which may run beside it on the scene's own stream): legal on a capturing stream, once the stream has run
+ * it eagerly.
+ * TWO DEVICE PATHS, same bytes: scenes of 2 .. 256 instances (the bound of the LDS-resident top level, where no renumbering exists) are
+ * rebuilt by ONE workgroup in one dispatch, everything staged in LDS; larger ones, a single instance, and any scene with option
+ * "tlas_rebuild_fused" = 0 run the build's chain of kernels (about a dozen dispatches and the sort's).
+ * n == 0: success, nothing enqueued.  Errors, all before anything is enqueued: RC_ERR_INVALID_ARGUMENT (NULL scene), RC_ERR_NOT_SYNCED
+ * (never synced, or pending host-side mutations).  Structural changes (instances or geometry added / deleted) stay with rc_sync. */
+int rc_rebuild_tlas_device_async(rc_scene* scene, void* stream);
 
 /* Page-lock (pin) a caller-owned host array so that the host-buffer entry points (rc_trace_closest / rc_trace_any, rc_add_blas,
  * rc_view_factors ...) move it by DMA at the full PCIe rate instead of through the driver's staging copies: the option a Julia

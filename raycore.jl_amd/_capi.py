@@ -114,6 +114,7 @@ SYMBOLS = [
     ("rc_refit_device", _int, [_vp, _int]),
     ("rc_update_transforms_device", _int, [_vp, _u32, _vp, _u32, _vp]),
     ("rc_refit_device_async", _int, [_vp, _vp]),
+    ("rc_rebuild_tlas_device_async", _int, [_vp, _vp]),
     ("rc_host_register", _int, [_vp, _vp, _u64]),
     ("rc_host_unregister", _int, [_vp, _vp]),
     ("rc_last_kernel_ms", _int, [_vp, _pf]),

@@ -340,6 +340,14 @@ class TLAS:
         check(lib().rc_refit_device_async(self._h, ptr(stream) if stream else None))
         return self
 
+    def rebuild_device_async(self, stream=None):
+        """rebuild_bvh!(tlas) from the instances' current device-side transforms, enqueued on `stream` with no host wait
+        (rc_rebuild_tlas_device_async): refit_device_async() with the topology built anew, so the scene traces exactly like a fresh one
+        synced with these transforms.  In place: graphs that captured updates, refits or traces of this scene stay valid.  Option
+        "tlas_rebuild_fused" (default 1) picks the single-workgroup kernel for scenes of 2 .. 256 instances."""
+        check(lib().rc_rebuild_tlas_device_async(self._h, ptr(stream) if stream else None))
+        return self
+
     def sync(self):  # sync!, :894-921
         a = C.c_int()
         check(lib().rc_sync(self._h, C.byref(a)))

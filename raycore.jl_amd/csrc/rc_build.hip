@@ -286,9 +286,8 @@ __device__ inline int delta(int i1, int i2, const uint32_t* codes, int n) {
 
 // emit_topology_kernel! (src/instanced-bvh-kernels.jl:119-152) = find_span_for_node + find_split_in_span
 // (src/instanced-bvh.jl:1232-1290)
-__global__ void k_topology(RcNode* nodes, const uint32_t* codes, int n, uint4* meta) {
-    int idx = blockIdx.x * blockDim.x + threadIdx.x + 1;
-    if (idx >= n) return;
+// (a device function: k_topology runs it over arrays in memory, k_rebuild_tlas_fused over arrays in LDS)
+__device__ inline void topology_node(int idx, RcNode* nodes, const uint32_t* codes, int n, uint4* meta) {
     int d_left = delta(idx, idx - 1, codes, n);
     int d_right = delta(idx, idx + 1, codes, n);
     int d = d_right > d_left ? 1 : -1;
@@ -331,6 +330,11 @@ __global__ void k_topology(RcNode* nodes, const uint32_t* codes, int n, uint4* m
     nodes[child0 - 1].parent = (uint32_t)idx;
     nodes[child1 - 1].parent = (uint32_t)idx;
     if (idx == 1) nodes[0].parent = RC_INVALID_NODE;
+}
+__global__ void k_topology(RcNode* nodes, const uint32_t* codes, int n, uint4* meta) {
+    int idx = blockIdx.x * blockDim.x + threadIdx.x + 1;
+    if (idx >= n) return;
+    topology_node(idx, nodes, codes, n, meta);
 }
 
 // create_leaf_nodes_kernel! (src/instanced-bvh-kernels.jl:198-226)
@@ -378,6 +382,12 @@ __device__ inline f2v load2_coherent(const float* p) {
 // index lies in the window too (a Karras node's index is inside its range).  Those nodes use an LDS arrival counter and LDS box
 // slots, and the second arrival writes the finished node with plain stores.  Only the few nodes that span windows (about
 // 2 log2(window) per workgroup) go through device-scope atomics and write-through stores.  Measured on 4 M triangles: 0.79 ms -> see DESIGN.
+//
+// join_boxes: the union of a subtree box with its sibling's in the reference's operand order, min.(aabb0, aabb1) (:1144-1147)
+__device__ inline void join_boxes(bool first_slot, float3_& mn, float3_& mx, float3_ smn, float3_ smx) {
+    mn = first_slot ? min3v(mn, smn) : min3v(smn, mn);
+    mx = first_slot ? max3v(mx, smx) : max3v(smx, mx);
+}
 constexpr int kRefitBlock = 1024;
 __global__ __launch_bounds__(kRefitBlock) void k_refit(RcNode* nodes, const RcPrim* prims, uint32_t* flags, const uint4* meta, uint32_t n, int tlas) {
     __shared__ uint32_t l_flags[kRefitBlock];
@@ -432,8 +442,7 @@ __global__ __launch_bounds__(kRefitBlock) void k_refit(RcNode* nodes, const RcPr
             } else {
                 q[0] = make_float4(smn.x, smn.y, smn.z, smx.x); q[1] = make_float4(smx.y, smx.z, mn.x, mn.y); q[2] = make_float4(mn.z, mx.x, mx.y, mx.z);
             }
-            mn = first_slot ? min3v(mn, smn) : min3v(smn, mn);  // union in the reference's operand order: min.(aabb0, aabb1) (:1144-1147)
-            mx = first_slot ? max3v(mx, smx) : max3v(smx, mx);
+            join_boxes(first_slot, mn, mx, smn, smx);
         } else {
             // ---- spans windows: device-scope protocol
             const uint4 m = meta[parent - 1];  // topology was written by earlier launches
@@ -449,8 +458,7 @@ __global__ __launch_bounds__(kRefitBlock) void k_refit(RcNode* nodes, const RcPr
             float3_ smn, smx;
             if (first_slot) { f2v a = load2_coherent(sib); f4v b = load4_coherent(sib + 2); smn = mk3(a.x, a.y, b.x); smx = mk3(b.y, b.z, b.w); }
             else { f4v a = load4_coherent(sib); f2v b = load2_coherent(sib + 4); smn = mk3(a.x, a.y, a.z); smx = mk3(a.w, b.x, b.y); }
-            mn = first_slot ? min3v(mn, smn) : min3v(smn, mn);
-            mx = first_slot ? max3v(mx, smx) : max3v(smx, mx);
+            join_boxes(first_slot, mn, mx, smn, smx);
         }
         cur = parent;
         parent = next_parent;
@@ -464,19 +472,21 @@ __device__ inline float3_ corner(const float* mn, const float* mx, int c) {
 }
 
 // compute_instance_aabbs_kernel! (src/instanced-bvh-kernels.jl:38-78) + scene reduction (:1502-1511)
+__device__ inline void instance_world_box(const float* transform, const RcBlasDesc& b, float3_& mn, float3_& mx) {
+    float3_ c1 = xf_point(transform, corner(b.root_min, b.root_max, 1));
+    mn = c1; mx = c1;
+    for (int c = 2; c <= 8; ++c) {
+        float3_ wc = xf_point(transform, corner(b.root_min, b.root_max, c));
+        mn = min3v(mn, wc); mx = max3v(mx, wc);
+    }
+}
 __global__ void k_instance_aabbs(const RcInstanceDesc* inst, const RcBlasDesc* descs, uint32_t n, float* aabbs,
                                  uint32_t* partials) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     float3_ mn = mk3(INFINITY, INFINITY, INFINITY), mx = mk3(-INFINITY, -INFINITY, -INFINITY);
     if (i < n) {
         const RcInstanceDesc& in = inst[i];
-        const RcBlasDesc& b = descs[in.blas_index - 1];
-        float3_ c1 = xf_point(in.transform, corner(b.root_min, b.root_max, 1));
-        mn = c1; mx = c1;
-        for (int c = 2; c <= 8; ++c) {
-            float3_ wc = xf_point(in.transform, corner(b.root_min, b.root_max, c));
-            mn = min3v(mn, wc); mx = max3v(mx, wc);
-        }
+        instance_world_box(in.transform, descs[in.blas_index - 1], mn, mx);
         aabbs[6 * i + 0] = mn.x; aabbs[6 * i + 1] = mn.y; aabbs[6 * i + 2] = mn.z;
         aabbs[6 * i + 3] = mx.x; aabbs[6 * i + 4] = mx.y; aabbs[6 * i + 5] = mx.z;
     }
@@ -484,20 +494,22 @@ __global__ void k_instance_aabbs(const RcInstanceDesc* inst, const RcBlasDesc* d
 }
 
 // calculate_tlas_morton_codes_kernel! (src/instanced-bvh-kernels.jl:295-327); extent clamped >= 1e-6 (:1517-1521)
-__global__ void k_tlas_morton(const RcInstanceDesc* inst, const RcBlasDesc* descs, uint32_t n, const uint32_t* enc,
-                              uint32_t* keys, uint32_t* vals) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+__device__ inline uint32_t tlas_morton_of(const float* transform, const RcBlasDesc& b, const uint32_t* enc) {
     float3_ smin = mk3(dec_f32(enc[0]), dec_f32(enc[1]), dec_f32(enc[2]));
     float3_ smax = mk3(dec_f32(enc[3]), dec_f32(enc[4]), dec_f32(enc[5]));
     float3_ e = sub3(smax, smin);
     float3_ extent = mk3(jl_max(e.x, 1e-6f), jl_max(e.y, 1e-6f), jl_max(e.z, 1e-6f));
-    const RcInstanceDesc& in = inst[i];
-    const RcBlasDesc& b = descs[in.blas_index - 1];
     float3_ lc = scale3(add3(mk3(b.root_min[0], b.root_min[1], b.root_min[2]), mk3(b.root_max[0], b.root_max[1], b.root_max[2])), 0.5f);
-    float3_ wc = xf_point(in.transform, lc);
+    float3_ wc = xf_point(transform, lc);
     float3_ d = sub3(wc, smin);
-    keys[i] = morton30(mk3(d.x / extent.x, d.y / extent.y, d.z / extent.z));
+    return morton30(mk3(d.x / extent.x, d.y / extent.y, d.z / extent.z));
+}
+__global__ void k_tlas_morton(const RcInstanceDesc* inst, const RcBlasDesc* descs, uint32_t n, const uint32_t* enc,
+                              uint32_t* keys, uint32_t* vals) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const RcInstanceDesc& in = inst[i];
+    keys[i] = tlas_morton_of(in.transform, descs[in.blas_index - 1], enc);
     vals[i] = i;
 }
 
@@ -509,6 +521,16 @@ __device__ inline void tlas_leaf_box(const float* transform, const RcBlasDesc& b
         mn = min3v(mn, wc); mx = max3v(mx, wc);
     }
 }
+// (every word of the leaf but `parent`, which belongs to the topology)
+__device__ inline void tlas_leaf_node(RcNode* nd, uint32_t orig, const float* transform, const RcBlasDesc& b) {
+    float3_ mn, mx;
+    tlas_leaf_box(transform, b, mn, mx);
+    nd->f[0] = mn.x; nd->f[1] = mn.y; nd->f[2] = mn.z; nd->f[3] = mx.x; nd->f[4] = mx.y; nd->f[5] = mx.z;
+    nd->f[6] = nd->f[7] = nd->f[8] = nd->f[9] = nd->f[10] = nd->f[11] = 0.0f;
+    nd->child0 = RC_INVALID_NODE;
+    nd->child1 = orig;
+    nd->pad = 0;
+}
 // create_tlas_leaf_nodes_kernel! (src/instanced-bvh-kernels.jl:332-375).  sorted == nullptr => refit path:
 // update_tlas_leaf_aabbs_kernel! (:487-519), the instance index is read back from child1.
 __global__ void k_tlas_leaves(RcNode* nodes, const uint32_t* sorted, const RcInstanceDesc* inst, const RcBlasDesc* descs,
@@ -518,14 +540,7 @@ __global__ void k_tlas_leaves(RcNode* nodes, const uint32_t* sorted, const RcIns
     RcNode* nd = &nodes[(n - 1 + j) - 1];
     uint32_t orig = sorted ? sorted[j - 1] : nd->child1;
     const RcInstanceDesc& in = inst[orig];
-    const RcBlasDesc& b = descs[in.blas_index - 1];
-    float3_ mn, mx;
-    tlas_leaf_box(in.transform, b, mn, mx);
-    nd->f[0] = mn.x; nd->f[1] = mn.y; nd->f[2] = mn.z; nd->f[3] = mx.x; nd->f[4] = mx.y; nd->f[5] = mx.z;
-    nd->f[6] = nd->f[7] = nd->f[8] = nd->f[9] = nd->f[10] = nd->f[11] = 0.0f;
-    nd->child0 = RC_INVALID_NODE;
-    nd->child1 = orig;
-    nd->pad = 0;
+    tlas_leaf_node(nd, orig, in.transform, descs[in.blas_index - 1]);
 }
 
 // ---- single-BLAS scenes: breadth-first renumbering of the BLAS's top internal nodes in the traversal copy (rc_traverse_core.h,
@@ -773,20 +788,120 @@ __global__ void k_inst_leaf(const uint32_t* sorted, uint32_t n, uint32_t* leaf_o
     if (j < n) leaf_of[sorted[j]] = j + 1u;
 }
 
+// ---- the whole TLAS rebuild as ONE workgroup (rc_rebuild_tlas_async; 2 <= n <= kFusedInst = kTlasLdsInst instances, the scenes whose top
+// level the trace keeps in LDS and never renumbers: tlas_top_k == 0).  The chain of rc_build_tlas is a dozen dispatches plus the sort's, each
+// with microseconds of work at this size; here thread i owns instance i, then sorted leaf i + 1 and internal node i + 1, and the tree is
+// assembled in LDS and written out once.  Same bytes as the chain, because the arithmetic IS the chain's (the device functions above):
+//  * scene bounds: min / max on the order-preserving encoding is exact in any order; with one block, k_reduce_partials folds a single
+//    partial, which is the identity;
+//  * sort: thread i counts the pairs (code, index) below its own -- a total order, so the result is the one stable permutation by code,
+//    rocPRIM's; n broadcast reads of LDS per thread;
+//  * refit: the in-window protocol of k_refit (LDS arrival counters, the second arrival carries the union up) with the box slots in the
+//    LDS copy of the node itself.  Every word of nodes 1..2n-1 is written before the copy-out: child / pad / parent words by topology_node,
+//    leaves by tlas_leaf_node, both boxes of every internal node by its two arrivals.
+constexpr int kFusedInst = rc::kTlasLdsInst;
+__global__ __launch_bounds__(kFusedInst) void k_rebuild_tlas_fused(const RcInstanceDesc* __restrict__ inst, const RcBlasDesc* __restrict__ descs, uint32_t n,
+                                                                   RcNode* __restrict__ nodes, RcNode* __restrict__ packed, uint4* __restrict__ ranges,
+                                                                   uint32_t* __restrict__ leaf_of) {
+    __shared__ RcNode l_nodes[2 * kFusedInst - 1];
+    __shared__ uint4 l_meta[(kFusedInst - 1) + kFusedInst / 4];  // k_topology's compact records, then one parent word per leaf
+    __shared__ float l_x[kFusedInst * 12];
+    __shared__ uint32_t l_blas[kFusedInst], l_codes[kFusedInst], l_sorted_codes[kFusedInst], l_sorted[kFusedInst], l_flags[kFusedInst];
+    __shared__ uint32_t l_enc[8];
+    const uint32_t t = threadIdx.x;
+    for (uint32_t w = t; w < n * 12u; w += kFusedInst) l_x[w] = inst[w / 12u].transform[w % 12u];
+    if (t < n) l_blas[t] = inst[t].blas_index;
+    l_flags[t] = 0u;
+    __syncthreads();
+    float3_ mn = mk3(INFINITY, INFINITY, INFINITY), mx = mk3(-INFINITY, -INFINITY, -INFINITY);
+    if (t < n) instance_world_box(&l_x[t * 12u], descs[l_blas[t] - 1], mn, mx);
+    block_reduce_bounds(mn, mx, l_enc);  // (block 0's partial: words 0..5)
+    __syncthreads();
+    uint32_t code = 0u;
+    if (t < n) { code = tlas_morton_of(&l_x[t * 12u], descs[l_blas[t] - 1], l_enc); l_codes[t] = code; }
+    __syncthreads();
+    if (t < n) {
+        uint32_t rank = 0u;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t c = l_codes[j];
+            rank += (c < code || (c == code && j < t)) ? 1u : 0u;
+        }
+        l_sorted_codes[rank] = code;
+        l_sorted[rank] = t;
+    }
+    __syncthreads();
+    if (t + 1u < n) topology_node((int)t + 1, l_nodes, l_sorted_codes, (int)n, l_meta);
+    if (t < n) {
+        const uint32_t orig = l_sorted[t];
+        tlas_leaf_node(&l_nodes[n - 1u + t], orig, &l_x[orig * 12u], descs[l_blas[orig] - 1]);
+        leaf_of[orig] = t + 1u;  // k_inst_leaf
+    }
+    __syncthreads();
+    if (t < n) {
+        uint32_t cur = n + t;  // 1-based index of sorted leaf t + 1
+        const RcNode& lf = l_nodes[cur - 1u];
+        mn = mk3(lf.f[0], lf.f[1], lf.f[2]); mx = mk3(lf.f[3], lf.f[4], lf.f[5]);
+        uint32_t parent = reinterpret_cast<const uint32_t*>(l_meta + (n - 1u))[t];
+        while (parent != RC_INVALID_NODE) {
+            const uint4 m = l_meta[parent - 1u];  // range, child0, parent
+            const bool first_slot = m.z == cur;
+            float* mine = l_nodes[parent - 1u].f + (first_slot ? 0 : 6);
+            mine[0] = mn.x; mine[1] = mn.y; mine[2] = mn.z; mine[3] = mx.x; mine[4] = mx.y; mine[5] = mx.z;
+            const uint32_t old = __hip_atomic_fetch_add(&l_flags[parent - 1u], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (old != 1u) break;
+            const float* sib = l_nodes[parent - 1u].f + (first_slot ? 6 : 0);
+            join_boxes(first_slot, mn, mx, mk3(sib[0], sib[1], sib[2]), mk3(sib[3], sib[4], sib[5]));
+            cur = parent;
+            parent = m.w;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < 2u * n - 1u; i += kFusedInst) {  // canonical node and traversal copy (k_pack_nodes), 16-byte stores
+        const RcNode nd = l_nodes[i];
+        const RcNode pk = rc_pack_node(nd);
+        uint4* q = reinterpret_cast<uint4*>(&nodes[i]);
+        uint4* r = reinterpret_cast<uint4*>(&packed[i]);
+        q[0] = make_uint4(__float_as_uint(nd.f[0]), __float_as_uint(nd.f[1]), __float_as_uint(nd.f[2]), __float_as_uint(nd.f[3]));
+        q[1] = make_uint4(__float_as_uint(nd.f[4]), __float_as_uint(nd.f[5]), __float_as_uint(nd.f[6]), __float_as_uint(nd.f[7]));
+        q[2] = make_uint4(__float_as_uint(nd.f[8]), __float_as_uint(nd.f[9]), __float_as_uint(nd.f[10]), __float_as_uint(nd.f[11]));
+        q[3] = make_uint4(nd.child0, nd.child1, nd.parent, nd.pad);
+        r[0] = make_uint4(__float_as_uint(pk.f[0]), __float_as_uint(pk.f[1]), __float_as_uint(pk.f[2]), __float_as_uint(pk.f[3]));
+        r[1] = make_uint4(__float_as_uint(pk.f[4]), __float_as_uint(pk.f[5]), __float_as_uint(pk.f[6]), __float_as_uint(pk.f[7]));
+        r[2] = make_uint4(__float_as_uint(pk.f[8]), __float_as_uint(pk.f[9]), __float_as_uint(pk.f[10]), __float_as_uint(pk.f[11]));
+        r[3] = make_uint4(pk.child0, pk.child1, pk.parent, pk.pad);
+    }
+    if (t + 1u < n) ranges[t] = l_meta[t];  // the topology the later refits read
+    if (t < n) reinterpret_cast<uint32_t*>(ranges + (n - 1u))[t] = reinterpret_cast<const uint32_t*>(l_meta + (n - 1u))[t];
+}
+
 // stable sortperm of the 30-bit keys (Base.sortperm / AK.sortperm, src/instanced-bvh.jl:1399, 1533-1540).  rocPRIM's default switches
 // from Onesweep to a merge sort at <= 1 Mi items (block sort + log2(n / 1024) partition/merge launch pairs: 146 us for 1 M keys); both
 // are stable, so the permutation is the same and the switch point is ours to choose (opt.onesweep_min).
+struct SortBufs {
+    uint32_t *keys_a, *keys_b, *vals_a, *vals_b;
+    DevBuf<unsigned char>* tmp;
+};
+// The size query is a host call that depends on n and the configuration alone.  bytes == nullptr: query, reserve, sort.  *bytes == 0: query
+// and reserve only, the size is returned (rc_build_tlas, on behalf of the rebuild that may not allocate).  Otherwise: sort with storage of
+// that size, reserved earlier -- no query, no allocation.
 template <size_t MergeLimit>
-static void sort_pairs_cfg(rc_scene* s, uint32_t n) {
+static void sort_pairs_cfg(const SortBufs& b, uint32_t n, hipStream_t st, size_t* bytes) {
     using Cfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, MergeLimit>;
-    size_t tmp = 0;
-    RC_HIP(rocprim::radix_sort_pairs<Cfg>(nullptr, tmp, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, n, 0u, 30u, s->stream));
-    s->sort_tmp.reserve(tmp ? tmp : 1);
-    RC_HIP(rocprim::radix_sort_pairs<Cfg>(s->sort_tmp.p, tmp, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, n, 0u, 30u, s->stream));
+    size_t tmp = bytes ? *bytes : 0;
+    if (!tmp) {
+        RC_HIP(rocprim::radix_sort_pairs<Cfg>(nullptr, tmp, b.keys_a, b.keys_b, b.vals_a, b.vals_b, n, 0u, 30u, st));
+        if (!tmp) tmp = 1;
+        b.tmp->reserve(tmp);
+        if (bytes) { *bytes = tmp; return; }
+    }
+    RC_HIP(rocprim::radix_sort_pairs<Cfg>(b.tmp->p, tmp, b.keys_a, b.keys_b, b.vals_a, b.vals_b, n, 0u, 30u, st));
+}
+static void sort_pairs_with(const SortBufs& b, uint32_t n, bool onesweep, hipStream_t st, size_t* bytes) {
+    if (onesweep) sort_pairs_cfg<4096>(b, n, st, bytes);
+    else sort_pairs_cfg<(size_t)1 << 30>(b, n, st, bytes);
 }
 void sort_pairs(rc_scene* s, uint32_t n) {
-    if ((int64_t)n >= s->opt.onesweep_min) sort_pairs_cfg<4096>(s, n);
-    else sort_pairs_cfg<(size_t)1 << 30>(s, n);
+    sort_pairs_with(SortBufs{s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, &s->sort_tmp}, n, (int64_t)n >= s->opt.onesweep_min, s->stream, nullptr);
 }
 
 void reserve_build_scratch(rc_scene* s, uint32_t n) {
@@ -1075,6 +1190,15 @@ void rc_build_tlas(rc_scene* s) {
     hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->tlas_nodes.p, s->vals_b.p, s->d_instances.p, s->d_descs.p, n);
     run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges, s->stream);
     s->tlas_flags.reserve(n);  // arrival counters of the asynchronous refit: its own, because s->flags is also the BLAS builds' (other stream)
+    {   // scratch of rc_rebuild_tlas_async, TLAS-only for the same reason; the sort's storage is sized here, where a host call may allocate
+        auto& r = s->rebuild;
+        r.keys_a.reserve(n); r.keys_b.reserve(n); r.vals_a.reserve(n); r.vals_b.reserve(n);
+        r.enc.reserve(8); r.partials.reserve((size_t)grid_for(n) * 6); r.aabbs.reserve(6 * (size_t)n);
+        r.n = n;
+        r.onesweep = (int64_t)n >= s->opt.onesweep_min;
+        r.sort_bytes = 0;
+        sort_pairs_with(SortBufs{r.keys_a.p, r.keys_b.p, r.vals_a.p, r.vals_b.p, &r.sort_tmp}, n, r.onesweep, s->stream, &r.sort_bytes);
+    }
     s->inst_leaf.reserve(n);  // instance -> leaf (rc_update_instances_async): topology only, like the renumbering below
     hipLaunchKernelGGL(k_inst_leaf, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, (const uint32_t*)s->vals_b.p, n, s->inst_leaf.p);
     if (s->tlas_top_k) {  // the renumbering depends on the topology only: computed here, reused by every refit
@@ -1157,6 +1281,45 @@ void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
     s->host_instances_stale = true;
     s->bound_stale = true;
     if (stream_capturing(st)) s->captured_refit = true;  // every replay moves the root box again: the host copy is never trusted while the graph may live
+    note_async_mutation(s, st);
+}
+
+// rebuild_bvh! (src/instanced-bvh.jl:968-992, build_tlas_topology :1485-1594) on `st` from the descriptors the device holds: what
+// rc_build_tlas does from k_instance_aabbs on, in place -- same buffers, same addresses, so captured updates, refits and traces stay valid
+// -- with the scratch reserved at sync time and without the root read-back.  per_instance as for rc_refit_tlas_async.
+void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
+    const uint32_t n = (uint32_t)s->instances.size();
+    if (n == 0) return;
+    auto& r = s->rebuild;
+    if (r.n != n) throw RcError(4, "rebuild scratch does not match the instance count");  // (reserved by every rebuilding rc_sync)
+    if (per_instance)
+        hipLaunchKernelGGL(k_inst_recs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, s->d_blas_nprims.p, n, s->inst_recs.p,
+                           (const uint32_t*)s->blas_cull_bits.p, s->inst_cull.p);
+    RcNode* packed = s->flat_nodes.p + s->n_flat_nodes;
+    if (s->opt.tlas_rebuild_fused && n >= 2 && n <= (uint32_t)kFusedInst && s->tlas_top_k == 0) {
+        hipLaunchKernelGGL(k_rebuild_tlas_fused, dim3(1), dim3(kFusedInst), 0, st, (const RcInstanceDesc*)s->d_instances.p, (const RcBlasDesc*)s->d_descs.p, n,
+                           s->tlas_nodes.p, packed, s->tlas_ranges.p, s->inst_leaf.p);
+    } else {
+        hipLaunchKernelGGL(k_instance_aabbs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, n, r.aabbs.p, r.partials.p);
+        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(384), 0, st, r.partials.p, grid_for(n), r.enc.p);
+        hipLaunchKernelGGL(k_tlas_morton, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, n, r.enc.p, r.keys_a.p, r.vals_a.p);
+        size_t bytes = r.sort_bytes;
+        sort_pairs_with(SortBufs{r.keys_a.p, r.keys_b.p, r.vals_a.p, r.vals_b.p, &r.sort_tmp}, n, r.onesweep, st, &bytes);
+        if (n > 1) hipLaunchKernelGGL(k_topology, dim3(grid_for(n - 1)), dim3(kBlock), 0, st, s->tlas_nodes.p, r.keys_b.p, (int)n, s->tlas_ranges.p);
+        else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, st, s->tlas_nodes.p, 1u);
+        hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, st, s->tlas_nodes.p, (const uint32_t*)r.vals_b.p, s->d_instances.p, s->d_descs.p, n);
+        run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges, st, s->tlas_flags.p);
+        hipLaunchKernelGGL(k_inst_leaf, dim3(grid_for(n)), dim3(kBlock), 0, st, (const uint32_t*)r.vals_b.p, n, s->inst_leaf.p);
+        if (s->tlas_top_k) {
+            hipLaunchKernelGGL(k_iota1, dim3(grid_for(n - 1)), dim3(kBlock), 0, st, s->tlas_remap.p, n - 1);
+            hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, st, s->tlas_nodes.p, n, s->tlas_top_k, s->tlas_remap.p);
+        }
+        pack_tlas(s, st);
+    }
+    RC_HIP(hipGetLastError());
+    s->host_instances_stale = true;
+    s->bound_stale = true;
+    if (stream_capturing(st)) s->captured_refit = true;  // (replays move the root box, as a captured refit's do)
     note_async_mutation(s, st);
 }
 

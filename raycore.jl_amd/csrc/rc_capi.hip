@@ -1235,6 +1235,20 @@ int rc_refit_device_async(rc_scene* s, void* stream) {
     });
 }
 
+// rebuild_bvh! (src/instanced-bvh.jl:968-992; build_tlas_topology, :1485-1594) on the caller's stream: the refit above with the topology built
+// anew from the device-side transforms, in place.
+int rc_rebuild_tlas_device_async(rc_scene* s, void* stream) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    return guarded([&] {
+        if (!s->has_static || s->dirty || s->mirror_edited)
+            throw RcError(RC_ERR_NOT_SYNCED, "scene has pending host-side mutations: call rc_sync (rc_rebuild_tlas_device_async rebuilds from device-side transforms only)");
+        use_device(s);
+        rc_rebuild_tlas_async(s, !s->device_dirty, (hipStream_t)stream);
+        s->device_dirty = false;
+        s->transforms_dirty = false;
+    });
+}
+
 int rc_set_option(rc_scene* s, const char* name, int64_t value) {
     if (!s || !name) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
     std::string k(name);
@@ -1247,6 +1261,7 @@ int rc_set_option(rc_scene* s, const char* name, int64_t value) {
     else if (k == "pool") s->opt.pool = value <= 0 ? 0 : (value < 16 ? 16 : (value > (1 << 20) ? (1 << 20) : value));  // 0 = default (128 rays per claim)
     else if (k == "onesweep_min") s->opt.onesweep_min = value < 0 ? 0 : value;
     else if (k == "blas_top") s->opt.blas_top = value != 0;
+    else if (k == "tlas_rebuild_fused") s->opt.tlas_rebuild_fused = value != 0;
     else if (k == "claim_shards") { int64_t p2 = 1; while (p2 * 2 <= value && p2 * 2 <= kClaimShards) p2 *= 2; s->opt.claim_shards = p2; }  // a power of two
     else if (k == "host_pipeline") s->opt.host_pipeline = value != 0;
     else if (k == "taper") s->opt.taper = value < 0 ? 0 : (value > 64 ? 64 : value);
@@ -1299,6 +1314,7 @@ int rc_get_option(rc_scene* s, const char* name, int64_t* value) {
     else if (k == "stack16") *value = s->opt.stack16;
     else if (k == "stack16_in_use") *value = (s->small_trees && s->opt.stack16) ? 1 : 0;
     else if (k == "blas_top") *value = s->opt.blas_top;
+    else if (k == "tlas_rebuild_fused") *value = s->opt.tlas_rebuild_fused;
     else if (k == "claim_drift") {
         // dev: chunk counters, over all slots, that are not back at zero once the device is idle -- always 0 unless the
         // every-wave-fails-exactly-once accounting of rc_claim_chunk is broken

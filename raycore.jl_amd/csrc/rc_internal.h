@@ -158,6 +158,7 @@ struct TraceOptions {
     int64_t claim_shards = 16; // phased kernels: chunk counters in use (a power of two <= kClaimShards)
     int64_t vf_first_touch = 1;          // ROWS on several devices: each device's host thread joins the device's NUMA node and faults in its own row block (rc_multi.hip)
     int64_t vf_chunk_bytes = 192 << 20;  // host-matrix view factors (rc_multi.hip): device block per row chunk -- large enough for full-rate launches and 2-D copies, small enough that the exposed first trace / last copy are a few ms
+    int64_t tlas_rebuild_fused = 1;  // rc_rebuild_tlas_device_async on scenes of at most kTlasLdsInst instances: 1 = one workgroup builds the whole TLAS in LDS (k_rebuild_tlas_fused), 0 = the chain of rc_build_tlas's kernels
     int64_t timeline_ptr = 0;  // dev: device address of 8 x u64 per wave (n_cus x 24 waves) that kernel 5 fills with its waves' event times; 0 = off
 };
 
@@ -209,15 +210,15 @@ struct rc_scene {
     bool host_instances_stale = false;  // descriptors were rewritten on the device (rc_instance_buffer_device + rc_refit_device)
     // ---- host state of the mutable scene.  Who sets / who clears / who refuses:
     //  dirty             set: push, delete, geometry update, load.        cleared: rebuilding rc_sync.          refused while set: every query, rc_update_transforms_device, rc_refit_device_async
-    //  transforms_dirty  set: rc_update_transforms(_device).              cleared: rc_sync, rc_refit_device_async.  refused while set: every query (RC_ERR_NOT_SYNCED)
+    //  transforms_dirty  set: rc_update_transforms(_device).              cleared: rc_sync, rc_refit_device_async, rc_rebuild_tlas_device_async.  refused while set: every query (RC_ERR_NOT_SYNCED)
     //  mirror_edited     set: push, rc_update_transforms (the host mirror holds edits the device lacks).  cleared: rc_sync (upload).
     //                    refused while set: rc_update_transforms_device, rc_refit_device_async; the mirror is never pulled from the device
     //  device_dirty      set: rc_update_transforms_device (the DEVICE descriptors are newer than the last refit; the update kernel has written the
-    //                    per-instance data).  cleared: rc_refit_device_async, rc_sync.  Survives a pull of the mirror (a read is no mutation).
+    //                    per-instance data).  cleared: rc_refit_device_async, rc_rebuild_tlas_device_async, rc_sync.  Survives a pull of the mirror (a read is no mutation).
     //                    rc_sync with device_dirty && host_instances_stale refits from the device; otherwise the mirror equals the device and is uploaded
     //  host_instances_stale  set: rc_refit_device, rc_update_transforms_device, rc_refit_device_async.  cleared: sync_host_instances (pull), which every
     //                    reader / editor of the mirror calls first.  Implies !mirror_edited
-    //  bound_stale       set: rc_refit_device_async.  cleared: rc_ensure_world_bound (read-back), rc_sync.  While set, a driver that needs the bound
+    //  bound_stale       set: rc_refit_device_async, rc_rebuild_tlas_device_async.  cleared: rc_ensure_world_bound (read-back), rc_sync.  While set, a driver that needs the bound
     //                    fails on a capturing stream
     //  captured_update / captured_refit  set: the call was captured into a graph.  cleared: rebuilding rc_sync, option "release_captures".  While set,
     //                    the mirror (unless mirror_edited) / the bound are re-read from the device on every use: replays happen unseen
@@ -239,6 +240,16 @@ struct rc_scene {
     DevBuf<RcNode> flat_nodes;
     uint32_t n_flat_nodes = 0;
     DevBuf<uint32_t> tlas_flags;       // arrival counters of rc_refit_tlas_async (n - 1 words; `flags` below belongs to the builds on the scene's own stream)
+    // scratch of rc_rebuild_tlas_async (a caller's stream): copies of the build scratch below, which BLAS builds on the scene's own stream use
+    // at the same time.  Reserved by rc_build_tlas for its instance count `n`, the sort's temporary storage included (`sort_bytes` for `onesweep`)
+    struct RebuildScratch {
+        DevBuf<uint32_t> keys_a, keys_b, vals_a, vals_b, enc, partials;
+        DevBuf<float> aabbs;
+        DevBuf<unsigned char> sort_tmp;
+        size_t sort_bytes = 0;
+        bool onesweep = false;
+        uint32_t n = 0;
+    } rebuild;
     DevBuf<uint32_t> inst_leaf;        // instance -> sorted position (1-based) of its TLAS leaf: topology only, built by rc_build_tlas for k_update_instances
     DevBuf<uint32_t> tlas_remap;       // same for the TLAS's internal nodes (top levels too large for the full LDS kernels), kept for refits
     uint32_t tlas_top_k = 0;
@@ -368,6 +379,7 @@ void rc_refit_tlas(rc_scene* s, bool from_device = false, bool recompute_inverse
 void rc_mat3x4_inverse(const float m[12], float out[12]);
 void rc_update_instances_async(rc_scene* s, uint32_t first, uint32_t m, const float* d_xforms, hipStream_t stream);  // transforms -> descriptors, records, cull spheres, leaf boxes
 void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t stream);  // refit_tlas! on `stream`, no read-back: leaves the world bound stale
+void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t stream);  // rebuild_bvh! on `stream` from the device descriptors, in place, no read-back
 void rc_wait_async_mutations(rc_scene* s);                      // host wait for what the two above enqueued (throws while their stream is being captured)
 void rc_ensure_world_bound(rc_scene* s, hipStream_t for_stream = nullptr);  // root_min / root_max current, or an error when `for_stream` is being captured
 

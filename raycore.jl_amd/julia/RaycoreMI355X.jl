@@ -472,6 +472,11 @@ function Raycore.update_transforms!(t::MI355XTLAS, h::TLASHandle, d_transforms::
 end
 refit_tlas_async!(t::MI355XTLAS; stream::Ptr{Cvoid} = C_NULL) =
     (check(ccall((:rc_refit_device_async, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), t.ptr, stream)); t)
+# rebuild_bvh!(tlas) (src/instanced-bvh.jl:968-992) from the device-side transforms, enqueued on `stream`: the asynchronous refit with a
+# fresh topology, in place -- captured refits and traces of this scene stay valid.  (The reference's one-argument rebuild_bvh! is what
+# sync! does after structural changes; this method is the one for instances that moved far from where they were sorted.)
+Raycore.rebuild_bvh!(t::MI355XTLAS, stream::Ptr{Cvoid}) =
+    (check(ccall((:rc_rebuild_tlas_device_async, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), t.ptr, stream)); t)
 
 # collide_instances / collide_instances_any (src/collision.jl:189-262)
 function Raycore.collide_instances(t::MI355XTLAS)

@@ -44,12 +44,19 @@ class WavefrontPaths:
 
     dynamic: a list of (handle, transforms tensor) pairs -- float32 (m, 12) or (m, 3, 4) on the accel's device.  Every frame then starts
     with update_transforms_device for each pair and one refit_device_async on the frame's stream, before the primary rays: the frame
-    shows whatever the tensors hold when it runs, also when it is a replay of the captured graph."""
+    shows whatever the tensors hold when it runs, also when it is a replay of the captured graph.
 
-    def __init__(self, accel, width, height, samples, depth, camera, light, seed=0, bias=1e-3, compact=True, dynamic=None):
+    rebuild=True (needs `dynamic`): the head of every frame calls rebuild_device_async instead of refit_device_async, so every frame
+    traces the tree a fresh sync would build from the tensors' transforms.  A caller who wants a rebuild only every K frames keeps the
+    default and calls accel.rebuild_device_async(stream) eagerly between replays of the captured refit frame: the rebuild works in place,
+    so the captured graph stays valid and refits the new topology from then on."""
+
+    def __init__(self, accel, width, height, samples, depth, camera, light, seed=0, bias=1e-3, compact=True, dynamic=None, rebuild=False):
         import torch
         if depth < 1:
             raise ValueError("depth must be at least 1")
+        if rebuild and not dynamic:
+            raise ValueError("rebuild=True needs dynamic: the rebuild follows the transform updates at the head of the frame")
         self.accel, self.width, self.height, self.samples, self.depth = accel, int(width), int(height), int(samples), int(depth)
         self.n = self.width * self.height * self.samples
         if self.n == 0 or self.n >= 2 ** 31:
@@ -58,6 +65,7 @@ class WavefrontPaths:
         self.light = np.ascontiguousarray(light, dtype=np.float32)
         self.seed, self.bias, self.compact = int(seed), float(bias), bool(compact)
         self.dynamic = list(dynamic) if dynamic else []
+        self.rebuild = bool(rebuild)
         dev = torch.device("cuda", accel.device)
         rec = lambda: torch.zeros(self.n * 32, dtype=torch.uint8, device=dev)  # noqa: E731
         self.rays = [rec() for _ in range(depth)]
@@ -90,7 +98,10 @@ class WavefrontPaths:
         if self.dynamic:
             for handle, xf in self.dynamic:
                 a.update_transforms_device(handle, xf, stream=st)
-            a.refit_device_async(stream=st)
+            if self.rebuild:
+                a.rebuild_device_async(stream=st)
+            else:
+                a.refit_device_async(stream=st)
         a.primary_rays_lookat_device(c["pos"], c["right"], c["up"], c["forward"], c["half_width"], c["half_height"], self.width, self.height,
                                      self.rays[0].data_ptr(), samples=self.samples, seed=self.seed, jitter=True, stream=st)
         a.trace_device(self.rays[0].data_ptr(), self.hits[0].data_ptr(), n, stream=st)
