@@ -56,6 +56,7 @@ extern "C" {
 #define RC_ERR_EMPTY_GEOMETRY 5   /* "Geometry has no valid triangles" (src/instanced-bvh.jl:601) */
 #define RC_ERR_NOT_SYNCED 6
 #define RC_ERR_STACK_OVERFLOW 7
+#define RC_ERR_GEOMETRY_CHANGED 8 /* an in-place geometry update met another face count (rc_update_geometry_device_async); reported by rc_wait */
 
 #define RC_INVALID_ID 0xFFFFFFFFu
 
@@ -526,6 +527,53 @@ int rc_refit_device_async(rc_scene* scene, void* stream);
  * n == 0: success, nothing enqueued.  Errors, all before anything is enqueued: RC_ERR_INVALID_ARGUMENT (NULL scene), RC_ERR_NOT_SYNCED
  * (never synced, or pending host-side mutations).  Structural changes (instances or geometry added / deleted) stay with rc_sync. */
 int rc_rebuild_tlas_device_async(rc_scene* scene, void* stream);
+
+/* update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) with backend-resident vertices: build_blas (:1376-1443) -- degenerate
+ * filter, Morton codes, stable sort, gather, Karras tree, leaves, refit -- enqueued on the caller's `stream` with no host wait, for meshes
+ * whose vertices move every frame (skinning, cloth, simulation output).  update -> [rc_update_transforms_device] -> refit -> trace can run
+ * back to back on one stream and be captured into one graph.
+ *
+ * rc_update_geometry_device_async: d_verts = n x 9 f32 soup in device memory on the scene's device, d_meta = n u32 or NULL (NULL: face
+ * index 1..n, assigned BEFORE the degenerate filter, as in rc_add_blas).  Both are read WHEN THE KERNELS RUN, not when the call is made: a
+ * captured call picks up the arrays' current contents on every replay.
+ * IN PLACE: the number of non-degenerate faces must equal the BLAS's current n_prims (n itself may differ, degenerate faces included).
+ * Then no address, offset, node count, kernel choice or LDS plan changes, and graphs that captured traces, updates, refits or rebuilds of
+ * this scene stay valid.  RESULT: everything is byte-identical to what a fresh scene holds after rc_sync given the new soup: the BLAS's
+ * nodes and primitives (rc_export_blas_nodes, rc_export_prims; a later structural rc_sync copies from them), their slices of the traversal
+ * copy, the root box (rc_export_blas_descs), the entry-cull radius, in a single-BLAS scene the renumbering of the BLAS's top, the shading
+ * attributes of the slice if they had been built, the face map of a mesh, and, for every instance of this geometry (through whichever
+ * handle), traversal record, entry-cull sphere and TLAS leaf box.
+ * The face count is compared ON THE DEVICE.  On a mismatch, or zero valid faces, nothing that a trace, an export or a later sync reads is
+ * modified and a sticky status makes the next rc_wait return RC_ERR_GEOMETRY_CHANGED, once; the scene then still traces the old geometry.
+ * Scene state afterwards: exactly as after rc_update_transforms_device -- transforms-dirty from the device, queries fail with
+ * RC_ERR_NOT_SYNCED until rc_refit_device_async, rc_rebuild_tlas_device_async or rc_sync (which then refits, action 1); it composes in
+ * either order with rc_update_transforms_device on the same stream before that refit.  The HOST copies of the root box are refreshed
+ * lazily under the rules of the asynchronous refit: rc_export_blas_descs, rc_scene_save and a structural rc_sync wait for the update and
+ * read the box back first, and fail while the update's stream is being captured; while a graph that captured an update may live (until a
+ * rebuilding rc_sync or "release_captures") they read it back on every use.
+ * At call time the geometry's BLAS4 is dropped (rc_trace_*4 behave as for a geometry whose BLAS4 was never built, until rc_blas4_build)
+ * and the view-factor source order is invalidated.  A captured update refreshes the shading attributes only if they existed at capture
+ * time: while such a graph may live, a call that would have to build them fails with RC_ERR_NOT_SYNCED -- use
+ * rc_shading_attributes_device once before capturing.  A captured update also holds the addresses of the geometry's OWN arrays: a host-side
+ * rc_update_geometry / rc_update_geometry_mesh of that geometry frees them at once -- the graph is dead from that call on, not only
+ * from the next rebuilding rc_sync (which is where a deleted geometry goes).
+ * SCRATCH: the call's own (not the BLAS-build scratch of the scene's stream), the sort's temporary storage included, sized for the
+ * largest n seen and shared by the scene's geometries -- enqueue these calls on one stream at a time.  An eager call may grow it; a call
+ * on a capturing stream that would have to grow it fails before enqueuing anything.  Otherwise no allocation, host copy, event or
+ * synchronisation: legal on a capturing stream once that stream has run it eagerly (with the same n).
+ * Errors, all before anything is enqueued: RC_ERR_INVALID_ARGUMENT (NULL scene or d_verts, n == 0, a scratch growth needed on a
+ * capturing stream), RC_ERR_INVALID_HANDLE (unknown or deleted handle, a handle without instances), RC_ERR_NOT_SYNCED (never synced, or
+ * pending host-side mutations).
+ *
+ * rc_update_mesh_vertices_device_async: the same for a geometry added through rc_add_mesh*: d_verts = nv x 3 f32 new vertex positions,
+ * d_normals = nv x 3 f32 new normals or NULL (keep the stored ones).  Indices, uvs and metadata are kept; the faces are expanded through
+ * the stored indices and the face map is rebuilt, so rc_shading_attributes_device and rc_reflection_rays_device see the new normals.  In a
+ * scene read by rc_scene_load the first call on a geometry recovers the per-face metadata from the surviving primitives (an allocation:
+ * eager only; a face that was degenerate when the file was written gets its index as metadata should it become valid).  nv != the mesh's vertex
+ * count, or a geometry that is not a mesh: RC_ERR_INVALID_ARGUMENT.
+ * Out of scope: a BLAS refit without the re-sort, a changed triangle count, geometry added or deleted -- those stay with rc_sync. */
+int rc_update_geometry_device_async(rc_scene* scene, uint32_t handle, const float* d_verts, const uint32_t* d_meta, uint32_t n, void* stream);
+int rc_update_mesh_vertices_device_async(rc_scene* scene, uint32_t handle, const float* d_verts, const float* d_normals, uint32_t nv, void* stream);
 
 /* Page-lock (pin) a caller-owned host array so that the host-buffer entry points (rc_trace_closest / rc_trace_any, rc_add_blas,
  * rc_view_factors ...) move it by DMA at the full PCIe rate instead of through the driver's staging copies: the option a Julia

@@ -32,6 +32,7 @@ assert RAY_DT.itemsize == 32 and HIT_DT.itemsize == 32 and NODE_DT.itemsize == 6
 assert INSTANCE_DT.itemsize == 108 and DESC_DT.itemsize == 32 and PRIM_DT.itemsize == 40
 
 RC_OK, RC_ERR_INVALID_ARGUMENT, RC_ERR_INVALID_HANDLE, RC_ERR_NO_DEVICE = 0, 1, 2, 3
+RC_ERR_GEOMETRY_CHANGED = 8  # reported once by rc_wait after an in-place geometry update that met another face count
 RC_INVALID_ID = 0xFFFFFFFF
 
 # every symbol include/raycore_mi355x.h declares: (name, restype, argtypes)
@@ -115,6 +116,8 @@ SYMBOLS = [
     ("rc_update_transforms_device", _int, [_vp, _u32, _vp, _u32, _vp]),
     ("rc_refit_device_async", _int, [_vp, _vp]),
     ("rc_rebuild_tlas_device_async", _int, [_vp, _vp]),
+    ("rc_update_geometry_device_async", _int, [_vp, _u32, _vp, _vp, _u32, _vp]),
+    ("rc_update_mesh_vertices_device_async", _int, [_vp, _u32, _vp, _vp, _u32, _vp]),
     ("rc_host_register", _int, [_vp, _vp, _u64]),
     ("rc_host_unregister", _int, [_vp, _vp]),
     ("rc_last_kernel_ms", _int, [_vp, _pf]),
@@ -126,6 +129,8 @@ _lib = None
 
 class RaycoreError(RuntimeError):
     """Raised for every non-zero status of the C ABI (the Julia wrapper raises ErrorException)."""
+
+    RC_ERR_GEOMETRY_CHANGED = RC_ERR_GEOMETRY_CHANGED
 
     def __init__(self, code, message):
         super().__init__(message)

@@ -348,6 +348,52 @@ class TLAS:
         check(lib().rc_rebuild_tlas_device_async(self._h, ptr(stream) if stream else None))
         return self
 
+    def _device_f32(self, t, what, inner):
+        """(rows, address) of a contiguous float32 torch tensor on the scene's device whose trailing shape multiplies to `inner`."""
+        if str(t.dtype) != "torch.float32" or not t.is_contiguous() or not t.is_cuda or t.device.index != self.device:
+            raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, f"{what} tensor must be contiguous float32 on the scene's device")
+        if t.dim() < 2 or int(np.prod(t.shape[1:])) != inner:
+            raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, f"{what} tensor must have {inner} floats per row, got shape {tuple(t.shape)}")
+        return int(t.shape[0]), t.data_ptr()
+
+    def update_geometry_device_async(self, handle, d_verts, n=None, d_meta=None, stream=None):
+        """update!(tlas, handle, new_geometry) for a soup that lives in device memory (rc_update_geometry_device_async): a contiguous
+        float32 torch tensor of shape (n, 9) or (n, 3, 3) on the scene's device, or a raw device pointer with `n`; d_meta an int32 /
+        uint32 tensor of n words (or a raw pointer), None = face index 1..n.  The BLAS is rebuilt on `stream` and committed in place when
+        the soup has as many non-degenerate faces as the BLAS has primitives; otherwise nothing changes and the next wait_for_gpu() raises
+        RaycoreError with code RC_ERR_GEOMETRY_CHANGED.  The tensors are read when the kernels run.  Follow with refit_device_async() or
+        rebuild_device_async() on the same stream, or sync()."""
+        if hasattr(d_verts, "data_ptr"):
+            rows, p = self._device_f32(d_verts, "soup", 9)
+            n = rows if n is None else int(n)
+            if n > rows:
+                raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, f"n = {n} exceeds the soup tensor's {rows} faces")
+        else:
+            if n is None:
+                raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, "n is required with a raw device pointer")
+            n, p = int(n), d_verts
+        pm = d_meta
+        if hasattr(d_meta, "data_ptr"):
+            if str(d_meta.dtype) not in ("torch.int32", "torch.uint32") or not d_meta.is_contiguous() or not d_meta.is_cuda or d_meta.device.index != self.device or d_meta.numel() < n:
+                raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, "metadata tensor must be contiguous int32 / uint32 on the scene's device, one word per face")
+            pm = d_meta.data_ptr()
+        check(lib().rc_update_geometry_device_async(self._h, handle.id, ptr(p) if p else None, ptr(pm) if pm else None, n, ptr(stream) if stream else None))
+        self._prims_cache = None
+        return self
+
+    def update_mesh_vertices_device_async(self, handle, d_verts, d_normals=None, stream=None):
+        """The same for a geometry added through add_mesh (rc_update_mesh_vertices_device_async): new vertex positions, float32 (nv, 3)
+        on the scene's device, and optionally new normals of the same shape (None keeps the stored ones).  Indices, uvs and metadata stay."""
+        nv, p = self._device_f32(d_verts, "vertex", 3)
+        pn = None
+        if d_normals is not None:
+            nn, pn = self._device_f32(d_normals, "normal", 3)
+            if nn != nv:
+                raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, f"{nn} normals for {nv} vertices")
+        check(lib().rc_update_mesh_vertices_device_async(self._h, handle.id, ptr(p), ptr(pn) if pn else None, nv, ptr(stream) if stream else None))
+        self._prims_cache = None
+        return self
+
     def sync(self):  # sync!, :894-921
         a = C.c_int()
         check(lib().rc_sync(self._h, C.byref(a)))

@@ -181,26 +181,28 @@ __global__ void k_expand_mesh(const float* verts, const uint32_t* indices, const
 
 // normals (9 floats) + uv (6 floats) of every primitive of one BLAS: build_triangle (:555-566).  Soup geometry has no mesh
 // attributes: geometric normal on all three vertices, default uv.
-__global__ void k_fill_attrs(const RcPrim* prims, uint32_t n, const float* normals, const float* uvs, const uint32_t* indices,
-                             const uint32_t* src_face, float* out) {
-    uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    float* o = out + 15 * (size_t)j;
+// (a device function: k_fill_attrs runs it over a whole BLAS, k_deform_commit over the primitives it is committing; face = the source face of primitive `p`)
+__device__ inline void fill_attrs_one(const RcPrim& p, const float* normals, const float* uvs, const uint32_t* indices, uint32_t face, float* o) {
     o[9] = 0.f; o[10] = 0.f; o[11] = 1.f; o[12] = 0.f; o[13] = 1.f; o[14] = 1.f;  // default uv (:561-565)
     if (normals) {
-        const uint32_t* idx = indices + 3 * (size_t)src_face[j];
+        const uint32_t* idx = indices + 3 * (size_t)face;
         for (int k = 0; k < 3; ++k) {
             const size_t v = idx[k];
             o[3 * k] = normals[3 * v]; o[3 * k + 1] = normals[3 * v + 1]; o[3 * k + 2] = normals[3 * v + 2];
             if (uvs) { o[9 + 2 * k] = uvs[2 * v]; o[10 + 2 * k] = uvs[2 * v + 1]; }
         }
     } else {
-        const RcPrim p = prims[j];
         const float3_ v0 = mk3(p.v[0], p.v[1], p.v[2]), v1 = mk3(p.v[3], p.v[4], p.v[5]), v2 = mk3(p.v[6], p.v[7], p.v[8]);
         const float3_ c = cross3(sub3(v1, v0), sub3(v2, v0));
         const float len = __builtin_sqrtf(dot3(c, c));
         for (int k = 0; k < 3; ++k) { o[3 * k] = c.x / len; o[3 * k + 1] = c.y / len; o[3 * k + 2] = c.z / len; }
     }
+}
+__global__ void k_fill_attrs(const RcPrim* prims, uint32_t n, const float* normals, const float* uvs, const uint32_t* indices,
+                             const uint32_t* src_face, float* out) {
+    uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    fill_attrs_one(prims[j], normals, uvs, indices, normals ? src_face[j] : 0u, out + 15 * (size_t)j);
 }
 
 // Triangle{UInt32} (src/triangle_mesh.jl:1-7), 136 bytes = 34 words: vertices 9, normals 9, tangents 9 (NaN), uv 6, metadata
@@ -616,6 +618,19 @@ __global__ void k_pack_nodes(const RcNode* src, RcNode* dst, uint32_t n, uint32_
 // centre to the farthest corner of the triangle's own box).  The reference reaches a triangle only through a slab test of that box, so a
 // ray that stays clear of this sphere -- by more than the slab test's rounding and its 1e-5 direction clamp can move it, see
 // k_inst_recs -- reaches no triangle of the BLAS.  Radii are >= 0: their bit patterns order like the values, and a NaN sorts above all.
+// (one primitive's share, as float bits; a device function: k_cull_radius folds it over every BLAS of the scene, k_deform_commit over the one it commits)
+__device__ inline uint32_t cull_radius_bits(const float* v, const float* root_min, const float* root_max) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float c = 0.5f * (root_min[k] + root_max[k]);
+        const float a = fminf(fminf(v[k], v[3 + k]), v[6 + k]), b = fmaxf(fmaxf(v[k], v[3 + k]), v[6 + k]);
+        const float m = fmaxf(fabsf(a - c), fabsf(b - c));
+        acc += m * m;
+        if (!(v[k] == v[k]) || !(v[3 + k] == v[3 + k]) || !(v[6 + k] == v[6 + k])) acc = NAN;  // (fmin / fmax drop NaNs: keep them)
+    }
+    return __float_as_uint(sqrtf(acc) * 1.000001f);
+}
 __global__ void k_cull_radius(const RcPrim* prims, uint32_t n, const RcBlasDesc* descs, uint32_t nb, uint32_t* out_bits) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool tail = i >= n;  // (threads past the end repeat the last primitive: every thread reaches the barriers below)
@@ -623,19 +638,9 @@ __global__ void k_cull_radius(const RcPrim* prims, uint32_t n, const RcBlasDesc*
     uint32_t lo = 0, hi = nb;  // the BLAS whose primitive range holds i: the last one whose offset is <= i
     while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (descs[mid].primitives_offset <= i) lo = mid; else hi = mid; }
     const RcBlasDesc& d = descs[lo];
-    const float* v = prims[i].v;
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float c = 0.5f * (d.root_min[k] + d.root_max[k]);
-        const float a = fminf(fminf(v[k], v[3 + k]), v[6 + k]), b = fmaxf(fmaxf(v[k], v[3 + k]), v[6 + k]);
-        const float m = fmaxf(fabsf(a - c), fabsf(b - c));
-        acc += m * m;
-        if (!(v[k] == v[k]) || !(v[3 + k] == v[3 + k]) || !(v[6 + k] == v[6 + k])) acc = NAN;  // (fmin / fmax drop NaNs: keep them)
-    }
     // one atomic per workgroup when the whole workgroup sits in one BLAS (the usual case: a 34 M-triangle BLAS would otherwise queue
     // 34 M atomics on one address), per lane otherwise
-    const uint32_t bits = __float_as_uint(sqrtf(acc) * 1.000001f);
+    const uint32_t bits = cull_radius_bits(prims[i].v, d.root_min, d.root_max);
     __shared__ uint32_t sh_first, sh_same, sh_max;
     if (threadIdx.x == 0) { sh_first = lo; sh_same = 1u; sh_max = 0u; }
     __syncthreads();
@@ -924,7 +929,7 @@ void run_refit(rc_scene* s, RcNode* nodes, const RcPrim* prims, uint32_t n, int 
     hipLaunchKernelGGL(k_refit, dim3((n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, nodes, prims, flags, ranges.p, n, tlas);
 }
 
-void host_root_aabb(const RcNode& root, bool tlas, float mn[3], float mx[3]) {
+__host__ __device__ inline void host_root_aabb(const RcNode& root, bool tlas, float mn[3], float mx[3]) {
     bool interior = root.child0 != RC_INVALID_NODE;
     float3_ a, b;
     if (interior) {
@@ -985,6 +990,9 @@ void rc_expand_mesh(rc_scene* s, const float* d_verts, const uint32_t* d_indices
 
 void rc_ensure_flat_attrs(rc_scene* s) {
     if (s->flat_attrs_valid) return;
+    if (s->captured_deform)  // (the graph baked "no attribute array" in: its replays would leave the one built here stale)
+        throw RcError(6, "shading attributes cannot be built while a graph that captured a geometry update may live: use rc_shading_attributes_device once before the capture, or release the graph (\"release_captures\")");
+    rc_wait_async_mutations(s);  // (an asynchronous geometry update on a caller's stream may still be writing the primitives read below)
     s->flat_attrs.reserve(15 * (size_t)(s->n_flat_prims ? s->n_flat_prims : 1));
     for (size_t i = 0; i < s->blas.size(); ++i) {
         const Blas& b = s->blas[i];
@@ -1166,6 +1174,9 @@ void rc_build_tlas(rc_scene* s) {
     s->n_static_instances = n;
     s->captured_update = false;
     s->captured_refit = false;  // (a graph that captured a refit of the old arrays is dead: its addresses are gone)
+    s->captured_deform = false;
+    s->blas_bounds_stale = false;  // (rc_sync refreshed the host copies before this rebuild read them)
+    for (auto& b : s->blas) b.root_on_device = false;
     if (n == 0) {  // :969-977
         s->bound_stale = false;
         s->n_tlas_nodes = 0;
@@ -1350,4 +1361,229 @@ void rc_ensure_world_bound(rc_scene* s, hipStream_t for_stream) {
     rc_copy_now(&root, s->tlas_nodes.p, sizeof(RcNode), hipMemcpyDeviceToHost);
     host_root_aabb(root, true, s->root_min, s->root_max);
     s->bound_stale = false;
+}
+
+// ---- update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) on the caller's stream: build_blas (:1376-1443) from a device soup,
+// committed IN PLACE.  The chain is rc_ingest_faces + rc_build_blas without their two read-backs, over scratch of its own (s->deform), into
+// a staged tree; the host cannot learn the valid-face count without waiting, so the chain runs with the BLAS's current count and the three
+// kernels below -- the only ones that touch anything a trace, an export or a later sync reads -- first compare it with the count the
+// filter found (deform_ok: the scan's last element + the last flag).  On a mismatch they write nothing but the sticky status word; the
+// staged tree was then built over the wrong number of slots, which costs time and nothing else (every index stays inside the scratch).
+namespace {
+
+__device__ inline bool deform_ok(const uint32_t* flags, const uint32_t* pos, uint32_t n, uint32_t n_prims) {
+    return pos[n - 1] + flags[n - 1] == n_prims;  // (n_prims >= 1: zero valid faces never match)
+}
+
+struct DeformCommit {
+    const uint32_t *flags, *pos;  // the filter's flags and their exclusive scan, n entries
+    uint32_t n, n_prims;
+    const RcNode* new_nodes;      // staged tree (2 n_prims - 1) and Morton-sorted primitives
+    const RcPrim* new_prims;
+    const uint32_t *perm, *slot_face;  // sorted slot -> compacted slot -> source face (mesh only)
+    RcNode *blas_nodes, *flat_nodes;   // the geometry's own arrays and its slices of the flat ones
+    RcPrim *blas_prims, *flat_prims;
+    uint32_t* src_face;           // mesh only
+    float* flat_attrs;            // nullptr: the attribute array is not valid, leave it
+    const float *normals, *uvs;   // per vertex, nullptr for a soup; normals = the NEW ones when the call brings some
+    const uint32_t* indices;
+    float* normals_keep;          // where new normals are kept for later structural syncs (nullptr: none given)
+    uint32_t n_normal_words;
+    const uint32_t* remap;        // breadth-first renumbering of the top (single-BLAS scenes), or nullptr
+    RcBlasDesc* desc;
+    uint32_t *cull_accum, *status;
+};
+
+// The commit of ONE BLAS: thread i copies node i into the geometry's own array and, packed (and renumbered), into the traversal copy;
+// threads below n_prims also commit primitive i, its attributes and source face, and fold its share of the entry-cull radius -- about the
+// centre of the NEW root box, which every thread derives from the staged root -- into one word (zeroed by the chain's memset); thread 0
+// writes the root box into the device descriptor.
+__global__ __launch_bounds__(kBlock) void k_deform_commit(DeformCommit c) {
+    __shared__ uint32_t sh_max;
+    const bool ok = deform_ok(c.flags, c.pos, c.n, c.n_prims);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n_nodes = 2u * c.n_prims - 1u;
+    if (!ok) {
+        if (i == 0) atomicOr(c.status, 1u);
+        return;  // (uniform: every thread of the grid reads the same two words)
+    }
+    if (threadIdx.x == 0) sh_max = 0u;
+    __syncthreads();
+    float rmin[3], rmax[3];
+    host_root_aabb(c.new_nodes[0], false, rmin, rmax);
+    if (i < n_nodes) {
+        RcNode nd = c.new_nodes[i];
+        c.blas_nodes[i] = nd;
+        uint32_t at = i;
+        if (c.remap && i + 1u < c.n_prims) {  // k_pack_nodes_remap
+            if (nd.child0 < c.n_prims) nd.child0 = c.remap[nd.child0 - 1];
+            if (nd.child1 < c.n_prims) nd.child1 = c.remap[nd.child1 - 1];
+            at = c.remap[i] - 1u;
+        }
+        c.flat_nodes[at] = i + 1u >= c.n_prims ? rc_pack_leaf(nd) : rc_pack_node(nd);
+    }
+    if (i < c.n_prims) {
+        const RcPrim p = c.new_prims[i];
+        c.blas_prims[i] = p;
+        c.flat_prims[i] = p;
+        uint32_t face = 0u;
+        if (c.src_face) { face = c.slot_face[c.perm[i]]; c.src_face[i] = face; }
+        if (c.flat_attrs) fill_attrs_one(p, c.normals, c.uvs, c.indices, face, c.flat_attrs + 15 * (size_t)i);
+        atomicMax(&sh_max, cull_radius_bits(p.v, rmin, rmax));
+    }
+    if (c.normals_keep)
+        for (uint32_t w = i; w < c.n_normal_words; w += gridDim.x * blockDim.x) c.normals_keep[w] = c.normals[w];
+    if (i == 0) {
+        for (int k = 0; k < 3; ++k) { c.desc->root_min[k] = rmin[k]; c.desc->root_max[k] = rmax[k]; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && blockIdx.x * blockDim.x < c.n_prims) atomicMax(c.cull_accum, sh_max);
+}
+
+// What k_inst_recs and k_tlas_leaves derive from a BLAS's descriptor and cull radius, for the instances of ONE BLAS (through whichever
+// handle): traversal record, entry-cull sphere, TLAS leaf box.  Thread 0 also publishes the radius the commit folded.
+__global__ void k_deform_instances(const uint32_t* flags, const uint32_t* pos, uint32_t n_faces, uint32_t n_prims, uint32_t blas_index,
+                                   const RcInstanceDesc* inst, const RcBlasDesc* descs, const uint32_t* blas_nprims, const uint32_t* cull_accum,
+                                   uint32_t* blas_cull_bits, const uint32_t* leaf_of, RcInstRec* recs, float4* cull_out, RcNode* nodes, uint32_t n) {
+    if (!deform_ok(flags, pos, n_faces, n_prims)) return;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t r_bits = *cull_accum;
+    if (i == 0) blas_cull_bits[blas_index - 1] = r_bits;
+    if (i >= n) return;
+    const RcInstanceDesc& in = inst[i];
+    if (in.blas_index != blas_index) return;
+    const RcBlasDesc bd = descs[blas_index - 1];
+    const RcInstRec r = inst_rec_of(in.inv_transform, blas_index, in.instance_id, bd, blas_nprims);
+    recs[i] = r;
+    float4 c0, c1;
+    entry_cull_sphere(in.inv_transform, bd, r.n_prims, r_bits, c0, c1);
+    cull_out[2 * (size_t)i] = c0;
+    cull_out[2 * (size_t)i + 1] = c1;
+    float3_ mn, mx;
+    tlas_leaf_box(in.transform, bd, mn, mx);
+    RcNode* nd = &nodes[(n - 1 + leaf_of[i]) - 1];  // the box only: the rest of the leaf is topology (k_update_instances)
+    nd->f[0] = mn.x; nd->f[1] = mn.y; nd->f[2] = mn.z; nd->f[3] = mx.x; nd->f[4] = mx.y; nd->f[5] = mx.z;
+}
+
+// metadata by source face out of the sorted primitives (the word k_expand_mesh gave each face when the mesh was added); faces the filter
+// dropped keep the default the caller put there
+__global__ void k_face_meta_of(const RcPrim* prims, const uint32_t* src_face, uint32_t n, uint32_t* face_meta) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) face_meta[src_face[j]] = prims[j].meta;
+}
+
+}  // namespace
+
+void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_verts, const uint32_t* d_meta, uint32_t n, const float* d_mesh_verts,
+                              const float* d_mesh_normals, hipStream_t st) {
+    Blas& b = s->blas[blas_idx];
+    auto& D = s->deform;
+    const uint32_t np = b.n_prims, cap_n = std::max(n, np);
+    const bool mesh = d_mesh_verts != nullptr, capturing = stream_capturing(st);
+    const bool onesweep = (int64_t)np >= s->opt.onesweep_min;
+    const unsigned nb = std::min(grid_for(np), 1024u);
+    // ---- scratch: grown by eager calls only
+    auto need = [&](auto& buf, size_t count) {
+        if (count <= buf.cap) return;
+        if (capturing) throw RcError(1, "the scratch of the geometry update is too small for this call and cannot grow while the stream is being captured: run the call eagerly once first");
+        buf.reserve(count);
+    };
+    need(D.flags, cap_n); need(D.pos, cap_n); need(D.compact, cap_n);
+    if (mesh) { need(D.slot_face, cap_n); need(D.soup, 9 * (size_t)n); }
+    need(D.keys_a, np); need(D.keys_b, np); need(D.vals_a, np); need(D.vals_b, np);
+    need(D.enc, 8); need(D.partials, (size_t)nb * 6); need(D.arrive, np);
+    if (s->blas_top_k > 0 && s->blas.size() == 1) need(D.remap, np - 1);
+    need(D.prims, np); need(D.nodes, 2 * (size_t)np - 1); need(D.ranges, np > 1 ? (size_t)(np - 1) + (np + 3) / 4 : 1);
+    if (!D.scan_bytes.count(n) || !D.sort_bytes.count(np)) {
+        if (capturing) throw RcError(1, "the geometry update has not run eagerly with these counts yet: its scan / sort storage cannot be sized while the stream is being captured");
+        size_t scan = 0, sort = 0;
+        RC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan, D.flags.p, D.pos.p, (int)n, st));
+        sort_pairs_with(SortBufs{D.keys_a.p, D.keys_b.p, D.vals_a.p, D.vals_b.p, &D.tmp}, np, onesweep, st, &sort);  // (size query + reserve, nothing enqueued)
+        D.scan_bytes[n] = scan ? scan : 1;
+        D.sort_bytes[np] = sort;
+    }
+    size_t scan_bytes = D.scan_bytes[n], sort_bytes = D.sort_bytes[np];
+    need(D.tmp, std::max(scan_bytes, sort_bytes));
+    if (mesh && b.m_face_meta.cap < b.n_mesh_faces) {
+        // a scene loaded from a file carries no per-face metadata: recovered from the surviving primitives through the face map (faces the
+        // filter had dropped get the default, their index)
+        if (capturing) throw RcError(1, "the first rc_update_mesh_vertices_device_async of a loaded geometry recovers its per-face metadata and cannot be captured: run the call eagerly once first");
+        b.m_face_meta.reserve(b.n_mesh_faces);
+        hipLaunchKernelGGL(k_iota1, dim3(grid_for(b.n_mesh_faces)), dim3(kBlock), 0, st, b.m_face_meta.p, b.n_mesh_faces);
+        hipLaunchKernelGGL(k_face_meta_of, dim3(grid_for(np)), dim3(kBlock), 0, st, (const RcPrim*)b.prims.p, (const uint32_t*)b.src_face.p, np, b.m_face_meta.p);
+    }
+    // ---- rc_ingest_faces
+    if (mesh) {  // (the kernel's per-face metadata output is not needed -- the compaction reads m_face_meta itself -- and lands in D.pos, which the scan overwrites)
+        hipLaunchKernelGGL(k_expand_mesh, dim3(grid_for(n)), dim3(kBlock), 0, st, d_mesh_verts, (const uint32_t*)b.m_indices.p, (const uint32_t*)nullptr, true, n, D.soup.p, D.pos.p);
+        d_verts = D.soup.p;
+        d_meta = b.m_face_meta.p;
+    }
+    hipLaunchKernelGGL(k_flag_valid_faces, dim3(grid_for(n)), dim3(kBlock), 0, st, d_verts, n, D.flags.p);
+    RC_HIP(hipcub::DeviceScan::ExclusiveSum(D.tmp.p, scan_bytes, D.flags.p, D.pos.p, (int)n, st));
+    hipLaunchKernelGGL(k_compact_faces, dim3(grid_for(n)), dim3(kBlock), 0, st, d_verts, d_meta, (const uint32_t*)D.flags.p, (const uint32_t*)D.pos.p, n, D.compact.p, mesh ? D.slot_face.p : (uint32_t*)nullptr);
+    // ---- rc_build_blas over np slots, into the staged arrays
+    hipLaunchKernelGGL(k_blas_scene_bounds, dim3(nb), dim3(kBlock), 0, st, (const RcPrim*)D.compact.p, np, D.partials.p);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(384), 0, st, (const uint32_t*)D.partials.p, nb, D.enc.p);
+    hipLaunchKernelGGL(k_blas_morton, dim3(grid_for(np)), dim3(kBlock), 0, st, (const RcPrim*)D.compact.p, np, (const uint32_t*)D.enc.p, D.keys_a.p, D.vals_a.p);
+    sort_pairs_with(SortBufs{D.keys_a.p, D.keys_b.p, D.vals_a.p, D.vals_b.p, &D.tmp}, np, onesweep, st, &sort_bytes);
+    hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(np)), dim3(kBlock), 0, st, (const RcPrim*)D.compact.p, (const uint32_t*)D.vals_b.p, np, D.prims.p);
+    if (np > 1) hipLaunchKernelGGL(k_topology, dim3(grid_for(np - 1)), dim3(kBlock), 0, st, D.nodes.p, (const uint32_t*)D.keys_b.p, (int)np, D.ranges.p);
+    else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, st, D.nodes.p, 1u);
+    hipLaunchKernelGGL(k_blas_leaves, dim3(grid_for(np)), dim3(kBlock), 0, st, D.nodes.p, (const RcPrim*)D.prims.p, np);
+    RC_HIP(hipMemsetAsync(D.arrive.p, 0, sizeof(uint32_t) * np, st));  // word 0: the cull radius being folded; then the refit's arrival counters
+    if (np > 1) hipLaunchKernelGGL(k_refit, dim3((np + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, D.nodes.p, (const RcPrim*)D.prims.p, D.arrive.p + 1, (const uint4*)D.ranges.p, np, 0);
+    const bool renumber = s->blas_top_k > 0 && s->blas.size() == 1;
+    if (renumber) {  // the renumbering follows the new topology (rc_build_tlas): staged too, the commit packs through it
+        hipLaunchKernelGGL(k_iota1, dim3(grid_for(np - 1)), dim3(kBlock), 0, st, D.remap.p, np - 1);
+        hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, st, (const RcNode*)D.nodes.p, np, s->blas_top_k, D.remap.p);
+    }
+    // ---- commit, then the instances of this BLAS
+    const RcBlasDesc& hd = s->descs[blas_idx];
+    DeformCommit c;
+    c.flags = D.flags.p; c.pos = D.pos.p; c.n = n; c.n_prims = np;
+    c.new_nodes = D.nodes.p; c.new_prims = D.prims.p; c.perm = D.vals_b.p; c.slot_face = D.slot_face.p;
+    c.blas_nodes = b.nodes.p; c.flat_nodes = s->flat_nodes.p + hd.nodes_offset;
+    c.blas_prims = b.prims.p; c.flat_prims = s->flat_prims.p + hd.primitives_offset;
+    c.src_face = mesh ? b.src_face.p : nullptr;
+    c.flat_attrs = s->flat_attrs_valid ? s->flat_attrs.p + 15 * (size_t)hd.primitives_offset : nullptr;
+    c.normals = b.has_attrs ? (d_mesh_normals ? d_mesh_normals : b.m_normals.p) : nullptr;
+    c.uvs = b.has_uvs ? b.m_uvs.p : nullptr;
+    c.indices = b.m_indices.p;
+    c.normals_keep = d_mesh_normals ? b.m_normals.p : nullptr;
+    c.n_normal_words = 3 * b.n_mesh_verts;
+    c.remap = renumber ? D.remap.p : nullptr;
+    c.desc = s->d_descs.p + blas_idx;
+    c.cull_accum = D.arrive.p;
+    c.status = rc_geometry_status_word(s);
+    hipLaunchKernelGGL(k_deform_commit, dim3(grid_for(2 * (uint64_t)np - 1)), dim3(kBlock), 0, st, c);
+    const uint32_t ni = (uint32_t)s->instances.size();
+    hipLaunchKernelGGL(k_deform_instances, dim3(grid_for(ni)), dim3(kBlock), 0, st, (const uint32_t*)D.flags.p, (const uint32_t*)D.pos.p, n, np, blas_idx + 1,
+                       (const RcInstanceDesc*)s->d_instances.p, (const RcBlasDesc*)s->d_descs.p, (const uint32_t*)s->d_blas_nprims.p, (const uint32_t*)D.arrive.p,
+                       s->blas_cull_bits.p, (const uint32_t*)s->inst_leaf.p, s->inst_recs.p, s->inst_cull.p, s->tlas_nodes.p, ni);
+    RC_HIP(hipGetLastError());
+    b.root_on_device = true;
+    s->blas_bounds_stale = true;
+    if (capturing) s->captured_deform = true;
+    note_async_mutation(s, st);
+}
+
+// The host copies of the root boxes an asynchronous geometry update left on the device (descs, Blas::root_min / root_max): read back for
+// the geometries that were updated in place since, after a host wait for the eager updates.  While a graph that captured one may live, on
+// every use.
+void rc_ensure_blas_bounds(rc_scene* s) {
+    if (!s->blas_bounds_stale && !s->captured_deform) return;
+    std::lock_guard<std::mutex> lk(s->launch_mu);  // exports are re-entrant: one of them refreshes, the others find it done (rc_ensure_world_bound)
+    if (!s->blas_bounds_stale && !s->captured_deform) return;
+    RC_HIP(hipSetDevice(s->device));
+    rc_wait_async_mutations(s);
+    const size_t nb = std::min(s->descs.size(), s->blas.size());
+    std::vector<RcBlasDesc> dev(nb);
+    rc_copy_now(dev.data(), s->d_descs.p, sizeof(RcBlasDesc) * nb, hipMemcpyDeviceToHost);
+    for (size_t i = 0; i < nb; ++i) {
+        Blas& b = s->blas[i];
+        if (!b.root_on_device) continue;  // (a geometry replaced on the host since holds the newer box)
+        memcpy(b.root_min, dev[i].root_min, 12); memcpy(b.root_max, dev[i].root_max, 12);
+        memcpy(s->descs[i].root_min, dev[i].root_min, 12); memcpy(s->descs[i].root_max, dev[i].root_max, 12);
+        if (!s->captured_deform) b.root_on_device = false;
+    }
+    s->blas_bounds_stale = false;
 }

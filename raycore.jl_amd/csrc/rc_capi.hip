@@ -398,6 +398,8 @@ static void build_mesh_blas(rc_scene* s, const float* verts, const float* normal
     s->vert_stage.reserve(9 * (size_t)(nf ? nf : 1));
     s->meta_stage.reserve(nf ? nf : 1);
     rc_expand_mesh(s, d_verts.p, b.m_indices.p, face_meta && n_meta ? d_vmeta.p : nullptr, meta_per_face, nf, s->vert_stage.p, s->meta_stage.p);
+    b.m_face_meta.reserve(nf ? nf : 1);  // the word of every face, dropped ones included: what an in-place vertex update expands with
+    if (nf) RC_HIP(hipMemcpyAsync(b.m_face_meta.p, s->meta_stage.p, sizeof(uint32_t) * (size_t)nf, hipMemcpyDeviceToDevice, s->stream));
     const uint32_t valid = rc_ingest_faces(s, s->vert_stage.p, s->meta_stage.p, nf, true);
     if (valid == 0) throw RcError(RC_ERR_EMPTY_GEOMETRY, "Geometry has no valid triangles");  // :601
     rc_build_blas(s, valid, b, true);  // synchronises the stream: the temporaries above may go
@@ -588,6 +590,7 @@ int rc_sync(rc_scene* s, int* action) {
         }
         sync_host_instances(s);
         if (s->dirty || !s->has_static) {  // rebuild_bvh! + rebuild_static_tlas! (:902-905, :911-915)
+            rc_ensure_blas_bounds(s);  // (root boxes an asynchronous geometry update left on the device)
             if (!s->deleted_handles.empty()) compact_instances(s);
             rc_build_tlas(s);
             s->dirty = false;
@@ -645,6 +648,12 @@ int rc_wait(rc_scene* s) {
                 rc_memset_now(rc_status_word(s), 0, 4);
                 throw RcError(RC_ERR_STACK_OVERFLOW, "traversal stack overflow in an earlier asynchronous launch (tree deeper than 128 levels)");
             }
+            // ... nor can an in-place geometry update whose soup no longer had the BLAS's face count: reported here once, nothing was changed
+            rc_copy_now(&st, rc_geometry_status_word(s), 4, hipMemcpyDeviceToHost);
+            if (st) {
+                rc_memset_now(rc_geometry_status_word(s), 0, 4);
+                throw RcError(RC_ERR_GEOMETRY_CHANGED, "an asynchronous geometry update found a number of non-degenerate faces other than the BLAS's primitive count: it changed nothing, the scene holds the old geometry");
+            }
         }
     });
 }
@@ -680,6 +689,7 @@ int rc_export_blas_descs(rc_scene* s, rc_blas_desc* out, uint32_t capacity, uint
     if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
     return guarded([&] {
         require_synced(s);
+        rc_ensure_blas_bounds(s);
         if (count) *count = (uint32_t)s->descs.size();
         if (!out) return;
         if (capacity < s->descs.size()) throw RcError(RC_ERR_INVALID_ARGUMENT, "export buffer too small");
@@ -899,6 +909,7 @@ int rc_blas4_build(rc_scene* s, uint32_t blas_id, uint32_t* n_nodes) {
         use_device(s);
         if (blas_id >= s->blas.size()) throw RcError(RC_ERR_INVALID_ARGUMENT, "blas_id out of range");
         Blas& b = s->blas[blas_id];
+        rc_wait_async_mutations(s);  // (an asynchronous geometry update on a caller's stream may still be writing the tree collapsed here)
         rc_timing_scene_begin(s, s->stream);
         rc_build_blas4(s, b);
         rc_timing_scene_end(s, s->stream);
@@ -1041,6 +1052,7 @@ int rc_scene_save(rc_scene* s, const char* path) {
         use_device(s);
         require_synced(s);  // compaction has run: no deleted handles, no unreferenced geometry
         rc_ensure_world_bound(s);  // (also waits for an asynchronous refit still in flight)
+        rc_ensure_blas_bounds(s);
         RC_HIP(hipStreamSynchronize(s->stream));
         FileCloser fc{fopen(path, "wb")};
         if (!fc.f) throw RcError(RC_ERR_INVALID_ARGUMENT, std::string("cannot open ") + path);
@@ -1249,6 +1261,48 @@ int rc_rebuild_tlas_device_async(rc_scene* s, void* stream) {
     });
 }
 
+// update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) with a backend-resident soup, on the caller's stream and in place
+// (rc_update_geometry_async, rc_build.hip).  State afterwards: as after rc_update_transforms_device.
+static void update_geometry_device(rc_scene* s, uint32_t handle, const float* d_verts, const uint32_t* d_meta, uint32_t n, const float* d_mesh_verts,
+                                   const float* d_mesh_normals, bool mesh, void* stream) {
+    const HandleRange r = live_range(s, handle);
+    if (r.count == 0) throw RcError(RC_ERR_INVALID_HANDLE, "Handle has no instances");
+    if (!s->has_static || s->dirty || s->mirror_edited)
+        throw RcError(RC_ERR_NOT_SYNCED, "the asynchronous geometry update rewrites the arrays where the last rc_sync put them: the scene has pending host-side mutations, call rc_sync first");
+    const uint32_t blas_idx = s->instances[r.first].blas_index - 1;  // :814-816 (blas_index never changes on the device: a stale mirror still holds it)
+    if (blas_idx >= s->blas.size() || blas_idx >= s->descs.size()) throw RcError(RC_ERR_INVALID_HANDLE, "Handle refers to no geometry");
+    Blas& b = s->blas[blas_idx];
+    if (mesh) {
+        if (!b.has_attrs || b.n_mesh_faces == 0) throw RcError(RC_ERR_INVALID_ARGUMENT, "the handle's geometry was not added as a mesh");
+        if (n != b.n_mesh_verts) throw RcError(RC_ERR_INVALID_ARGUMENT, "Vertex count (" + std::to_string(n) + ") != the mesh's (" + std::to_string(b.n_mesh_verts) + ")");
+        n = b.n_mesh_faces;
+    }
+    use_device(s);
+    rc_update_geometry_async(s, blas_idx, d_verts, d_meta, n, d_mesh_verts, d_mesh_normals, (hipStream_t)stream);
+    b.n_nodes4 = 0;  // the BLAS4 was collapsed from the old tree
+    s->vf_order_valid = false;
+    s->host_instances_stale = true;
+    s->device_dirty = true;
+    s->transforms_dirty = true;
+}
+
+int rc_update_geometry_device_async(rc_scene* s, uint32_t handle, const float* d_verts, const uint32_t* d_meta, uint32_t n, void* stream) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    return guarded([&] {
+        if (!d_verts) throw RcError(RC_ERR_INVALID_ARGUMENT, "d_verts is NULL");
+        if (n == 0) throw RcError(RC_ERR_INVALID_ARGUMENT, "n is 0: an empty soup cannot keep the primitive count");
+        update_geometry_device(s, handle, d_verts, d_meta, n, nullptr, nullptr, false, stream);
+    });
+}
+
+int rc_update_mesh_vertices_device_async(rc_scene* s, uint32_t handle, const float* d_verts, const float* d_normals, uint32_t nv, void* stream) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    return guarded([&] {
+        if (!d_verts) throw RcError(RC_ERR_INVALID_ARGUMENT, "d_verts is NULL");
+        update_geometry_device(s, handle, nullptr, nullptr, nv, d_verts, d_normals, true, stream);
+    });
+}
+
 int rc_set_option(rc_scene* s, const char* name, int64_t value) {
     if (!s || !name) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
     std::string k(name);
@@ -1277,6 +1331,7 @@ int rc_set_option(rc_scene* s, const char* name, int64_t value) {
             s->capture_slots.clear();
             s->last_capture = -1;
             if (s->captured_refit) { s->captured_refit = false; s->bound_stale = true; }  // (no replay can move the root box any more: one more read-back settles it)
+            if (s->captured_deform) { s->captured_deform = false; s->blas_bounds_stale = true; }
             if (s->captured_update) { s->captured_update = false; s->host_instances_stale = s->host_instances_stale || !s->mirror_edited; }
         }
     }

@@ -105,12 +105,14 @@ struct Blas {  // one geometry: build_blas output (src/instanced-bvh.jl:111-118)
     // mesh attributes (rc_add_mesh): per-vertex normals / uvs, the face indices and the source face of every sorted primitive
     DevBuf<float> m_normals, m_uvs;
     DevBuf<uint32_t> m_indices, src_face;
+    DevBuf<uint32_t> m_face_meta;  // metadata by source face, kept by rc_add_mesh* for rc_update_mesh_vertices_device_async (a loaded scene has none: recovered from the primitives on first use)
     bool has_attrs = false, has_uvs = false;
     uint32_t n_mesh_verts = 0, n_mesh_faces = 0;
     // BLAS4 (src/bvh4.jl:154-162), built on request by rc_blas4_build
     DevBuf<RcNode4> nodes4;
     uint32_t n_nodes4 = 0;
     uint32_t root_word4 = 1;  // root index, leaf bit set when the tree is a single leaf
+    bool root_on_device = false;  // updated in place on the device since root_min / root_max were last read back (rc_ensure_blas_bounds)
 };
 
 struct HandleRange {
@@ -250,6 +252,20 @@ struct rc_scene {
         bool onesweep = false;
         uint32_t n = 0;
     } rebuild;
+    // scratch of rc_update_geometry_async (a caller's stream): the whole BLAS build chain's, the staged result included.  One set per scene, grown
+    // by eager calls only and sized for the largest soup seen; calls on ONE stream at a time share it (stream order)
+    struct DeformScratch {
+        DevBuf<uint32_t> flags, pos, slot_face, keys_a, keys_b, vals_a, vals_b, enc, partials, arrive, remap;  // remap: the staged tree's top renumbering (single-BLAS scenes)
+        DevBuf<RcPrim> compact, prims;  // compacted faces in input order; Morton-sorted
+        DevBuf<RcNode> nodes;           // the new tree, committed only when the face count matches
+        DevBuf<uint4> ranges;
+        DevBuf<float> soup;             // mesh form: the expanded faces
+        DevBuf<unsigned char> tmp;      // scan / sort storage
+        std::map<uint32_t, size_t> scan_bytes, sort_bytes;  // per item count, queried by eager calls
+    } deform;
+    // blas_bounds_stale  set: rc_update_geometry_async (the root boxes in d_descs are newer than descs / Blas::root_min,max).  cleared: rc_ensure_blas_bounds
+    //                    (read-back), rebuilding rc_sync.  captured_deform: the call was captured -- re-read on every use, like captured_refit
+    bool blas_bounds_stale = false, captured_deform = false;
     DevBuf<uint32_t> inst_leaf;        // instance -> sorted position (1-based) of its TLAS leaf: topology only, built by rc_build_tlas for k_update_instances
     DevBuf<uint32_t> tlas_remap;       // same for the TLAS's internal nodes (top levels too large for the full LDS kernels), kept for refits
     uint32_t tlas_top_k = 0;
@@ -380,6 +396,9 @@ void rc_mat3x4_inverse(const float m[12], float out[12]);
 void rc_update_instances_async(rc_scene* s, uint32_t first, uint32_t m, const float* d_xforms, hipStream_t stream);  // transforms -> descriptors, records, cull spheres, leaf boxes
 void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t stream);  // refit_tlas! on `stream`, no read-back: leaves the world bound stale
 void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t stream);  // rebuild_bvh! on `stream` from the device descriptors, in place, no read-back
+// build_blas on `stream` from a device soup (or, with d_mesh_verts, the geometry's stored faces), committed in place when the valid-face count is unchanged
+void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_verts, const uint32_t* d_meta, uint32_t n, const float* d_mesh_verts, const float* d_mesh_normals, hipStream_t stream);
+void rc_ensure_blas_bounds(rc_scene* s);  // descs / Blas::root_min,max current after rc_update_geometry_async (waits; throws while its stream is being captured)
 void rc_wait_async_mutations(rc_scene* s);                      // host wait for what the two above enqueued (throws while their stream is being captured)
 void rc_ensure_world_bound(rc_scene* s, hipStream_t for_stream = nullptr);  // root_min / root_max current, or an error when `for_stream` is being captured
 
@@ -426,6 +445,7 @@ constexpr int kClaimShards = 16, kShardBase = 64, kShardStrideWords = 64;
 constexpr int kStatsWords = 24;  // u64 dev statistics behind the status word of slot 0 (u32 words 8 .. 55: below kShardBase)
 inline uint32_t* rc_counter_slot(rc_scene* s) { return s->counters.p + (size_t)s->cur_slot * kCounterSlotWords; }  // slot of the launch being prepared (launch_mu held)
 inline uint32_t* rc_status_word(rc_scene* s) { return s->counters.p + 4; }
+inline uint32_t* rc_geometry_status_word(rc_scene* s) { return s->counters.p + 5; }  // sticky like the word before it: an in-place geometry update met a changed face count
 inline unsigned long long* rc_stats_words(rc_scene* s) { return reinterpret_cast<unsigned long long*>(s->counters.p + 8); }
 // Serialises the enqueue of one launch on a scene and does its bookkeeping.  Construction takes launch_mu, picks the stack spill region
 // of `stream` and the launch's counter slot, and orders the launch behind the slot's previous user; start() records the slot's first

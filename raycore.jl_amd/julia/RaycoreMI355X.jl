@@ -478,6 +478,19 @@ refit_tlas_async!(t::MI355XTLAS; stream::Ptr{Cvoid} = C_NULL) =
 Raycore.rebuild_bvh!(t::MI355XTLAS, stream::Ptr{Cvoid}) =
     (check(ccall((:rc_rebuild_tlas_device_async, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), t.ptr, stream)); t)
 
+# update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) with a backend-resident soup: `d_verts` points at n x 9 Float32 in
+# device memory, read when the kernels run on `stream`; the BLAS is rebuilt there and committed in place when the number of non-degenerate
+# faces is unchanged (otherwise nothing changes and the next wait reports it).  Commit with refit_tlas_async! / rebuild_bvh! on the same
+# stream, or with sync!.  update_mesh_vertices! is the form for a geometry added as a mesh: new positions (nv x 3), optionally new normals.
+function Raycore.update!(t::MI355XTLAS, h::TLASHandle, d_verts::Ptr{Cfloat}, n::Integer, stream::Ptr{Cvoid}; d_meta::Ptr{UInt32} = Ptr{UInt32}(C_NULL))
+    check(ccall((:rc_update_geometry_device_async, LIB), Cint, (Ptr{Cvoid}, UInt32, Ptr{Cfloat}, Ptr{UInt32}, UInt32, Ptr{Cvoid}), t.ptr, h.id, d_verts, d_meta, n, stream))
+    return t
+end
+function update_mesh_vertices!(t::MI355XTLAS, h::TLASHandle, d_verts::Ptr{Cfloat}, nv::Integer, stream::Ptr{Cvoid}; d_normals::Ptr{Cfloat} = Ptr{Cfloat}(C_NULL))
+    check(ccall((:rc_update_mesh_vertices_device_async, LIB), Cint, (Ptr{Cvoid}, UInt32, Ptr{Cfloat}, Ptr{Cfloat}, UInt32, Ptr{Cvoid}), t.ptr, h.id, d_verts, d_normals, nv, stream))
+    return t
+end
+
 # collide_instances / collide_instances_any (src/collision.jl:189-262)
 function Raycore.collide_instances(t::MI355XTLAS)
     n = Ref{UInt64}(0)

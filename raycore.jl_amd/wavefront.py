@@ -49,9 +49,14 @@ class WavefrontPaths:
     rebuild=True (needs `dynamic`): the head of every frame calls rebuild_device_async instead of refit_device_async, so every frame
     traces the tree a fresh sync would build from the tensors' transforms.  A caller who wants a rebuild only every K frames keeps the
     default and calls accel.rebuild_device_async(stream) eagerly between replays of the captured refit frame: the rebuild works in place,
-    so the captured graph stays valid and refits the new topology from then on."""
+    so the captured graph stays valid and refits the new topology from then on.
 
-    def __init__(self, accel, width, height, samples, depth, camera, light, seed=0, bias=1e-3, compact=True, dynamic=None, rebuild=False):
+    deform: a list of (handle, soup tensor) pairs -- float32 (n, 9) or (n, 3, 3) on the accel's device.  Every frame then starts with
+    update_geometry_device_async for each pair, before the `dynamic` transform updates and the refit (or rebuild) that ends the head of
+    the frame; `deform` without `dynamic` still ends it with a refit.  A soup must keep its number of non-degenerate faces."""
+
+    def __init__(self, accel, width, height, samples, depth, camera, light, seed=0, bias=1e-3, compact=True, dynamic=None, rebuild=False,
+                 deform=None):
         import torch
         if depth < 1:
             raise ValueError("depth must be at least 1")
@@ -66,6 +71,7 @@ class WavefrontPaths:
         self.seed, self.bias, self.compact = int(seed), float(bias), bool(compact)
         self.dynamic = list(dynamic) if dynamic else []
         self.rebuild = bool(rebuild)
+        self.deform = list(deform) if deform else []
         dev = torch.device("cuda", accel.device)
         rec = lambda: torch.zeros(self.n * 32, dtype=torch.uint8, device=dev)  # noqa: E731
         self.rays = [rec() for _ in range(depth)]
@@ -83,7 +89,7 @@ class WavefrontPaths:
         self._graph_stream = None
 
     def buffers(self):
-        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic]
+        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic] + [t for _, t in self.deform]
 
     def run(self, stream=None):
         """Enqueue one frame on `stream` (a torch.cuda.Stream; None = the current stream).  No host synchronisation.  The first frame on
@@ -95,7 +101,9 @@ class WavefrontPaths:
                 buf.record_stream(s)
             self._streams.add(st)
         a, c, n = self.accel, self.camera, self.n
-        if self.dynamic:
+        for handle, soup in self.deform:
+            a.update_geometry_device_async(handle, soup, stream=st)
+        if self.dynamic or self.deform:
             for handle, xf in self.dynamic:
                 a.update_transforms_device(handle, xf, stream=st)
             if self.rebuild:
