@@ -593,18 +593,23 @@ __global__ __launch_bounds__(kTopBlock) void k_top_remap(const RcNode* nodes, ui
     if (t < total) remap[d_list[t] - 1] = v_list[t];
     if (t < n_top) remap[top[t] - 1] = t + 1u;
 }
+// Node i (0-based) into the traversal copy through the renumbering (remap == nullptr: none): an internal node moves to its new slot and
+// names its internal children by their new indices
 // (blas: the leaves -- nodes n_leaves .. 2 n_leaves - 1 -- hold triangles and take the leaf packing; a TLAS's leaves hold instance boxes)
-__global__ void k_pack_nodes_remap(const RcNode* src, RcNode* dst, uint32_t n_nodes, uint32_t n_leaves, const uint32_t* remap, bool blas) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_nodes) return;
-    RcNode nd = src[i];
+// (a device function: k_pack_nodes_remap runs it over a finished tree, k_deform_commit over the staged one it is committing)
+__device__ inline void pack_node_renumbered(RcNode nd, uint32_t i, uint32_t n_leaves, const uint32_t* remap, bool blas, RcNode* dst) {
     uint32_t at = i;
-    if (i + 1u < n_leaves) {
+    if (remap && i + 1u < n_leaves) {
         if (nd.child0 < n_leaves) nd.child0 = remap[nd.child0 - 1];
         if (nd.child1 < n_leaves) nd.child1 = remap[nd.child1 - 1];
         at = remap[i] - 1u;
     }
     dst[at] = (blas && i + 1u >= n_leaves) ? rc_pack_leaf(nd) : rc_pack_node(nd);
+}
+__global__ void k_pack_nodes_remap(const RcNode* src, RcNode* dst, uint32_t n_nodes, uint32_t n_leaves, const uint32_t* remap, bool blas) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes) return;
+    pack_node_renumbered(src[i], i, n_leaves, remap, blas, dst);
 }
 
 // Traversal copy of a node array in the packed order of rc_pack_node (interior nodes, TLAS leaves) / rc_pack_leaf (the triangles of a BLAS:
@@ -879,20 +884,29 @@ __global__ __launch_bounds__(kFusedInst) void k_rebuild_tlas_fused(const RcInsta
     if (t < n) reinterpret_cast<uint32_t*>(ranges + (n - 1u))[t] = reinterpret_cast<const uint32_t*>(l_meta + (n - 1u))[t];
 }
 
+// Non-owning view of the scratch ONE build chain runs on: a chain body below receives (stream, view) and nothing about who calls it.
+// Three sets exist, so that chains on different streams never share a word: the scene's loose members (the builds on the scene's own
+// stream), s->rebuild (rc_rebuild_tlas_async) and s->deform (rc_update_geometry_async), both on a caller's stream.
+struct ChainBufs {
+    uint32_t *keys_a, *keys_b, *vals_a, *vals_b;  // the sort's input pairs; the sorted keys and the permutation
+    uint32_t *partials, *enc;                     // scene bounds: one partial per block, their fold
+    uint32_t *zeroed, *arrive;   // run_refit zeroes from `zeroed` through its n - 1 arrival counters at `arrive` in one memset (words in front of the counters are the owner's)
+    uint4* ranges;               // topology records: topology_records(n)
+    float* aabbs;                // TLAS only: 6 floats per instance
+    DevBuf<unsigned char>* tmp;  // the sort's temporary storage
+    size_t sort_bytes;           // its size where it was reserved earlier (a chain that may not allocate); 0: query and reserve at the sort
+    bool onesweep;
+};
 // stable sortperm of the 30-bit keys (Base.sortperm / AK.sortperm, src/instanced-bvh.jl:1399, 1533-1540).  rocPRIM's default switches
 // from Onesweep to a merge sort at <= 1 Mi items (block sort + log2(n / 1024) partition/merge launch pairs: 146 us for 1 M keys); both
 // are stable, so the permutation is the same and the switch point is ours to choose (opt.onesweep_min).
-struct SortBufs {
-    uint32_t *keys_a, *keys_b, *vals_a, *vals_b;
-    DevBuf<unsigned char>* tmp;
-};
-// The size query is a host call that depends on n and the configuration alone.  bytes == nullptr: query, reserve, sort.  *bytes == 0: query
-// and reserve only, the size is returned (rc_build_tlas, on behalf of the rebuild that may not allocate).  Otherwise: sort with storage of
-// that size, reserved earlier -- no query, no allocation.
+// The size query is a host call that depends on n and the configuration alone.  bytes == nullptr (the chains): the view's size, or query,
+// reserve, sort where it brings none.  *bytes == 0: query and reserve only, the size is returned (rc_build_tlas, on behalf of the rebuild
+// that may not allocate).  Otherwise: sort with storage of that size, reserved earlier -- no query, no allocation.
 template <size_t MergeLimit>
-static void sort_pairs_cfg(const SortBufs& b, uint32_t n, hipStream_t st, size_t* bytes) {
+static void sort_pairs_cfg(const ChainBufs& b, uint32_t n, hipStream_t st, size_t* bytes) {
     using Cfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, MergeLimit>;
-    size_t tmp = bytes ? *bytes : 0;
+    size_t tmp = bytes ? *bytes : b.sort_bytes;
     if (!tmp) {
         RC_HIP(rocprim::radix_sort_pairs<Cfg>(nullptr, tmp, b.keys_a, b.keys_b, b.vals_a, b.vals_b, n, 0u, 30u, st));
         if (!tmp) tmp = 1;
@@ -901,12 +915,9 @@ static void sort_pairs_cfg(const SortBufs& b, uint32_t n, hipStream_t st, size_t
     }
     RC_HIP(rocprim::radix_sort_pairs<Cfg>(b.tmp->p, tmp, b.keys_a, b.keys_b, b.vals_a, b.vals_b, n, 0u, 30u, st));
 }
-static void sort_pairs_with(const SortBufs& b, uint32_t n, bool onesweep, hipStream_t st, size_t* bytes) {
-    if (onesweep) sort_pairs_cfg<4096>(b, n, st, bytes);
+void sort_pairs(hipStream_t st, const ChainBufs& b, uint32_t n, size_t* bytes = nullptr) {
+    if (b.onesweep) sort_pairs_cfg<4096>(b, n, st, bytes);
     else sort_pairs_cfg<(size_t)1 << 30>(b, n, st, bytes);
-}
-void sort_pairs(rc_scene* s, uint32_t n) {
-    sort_pairs_with(SortBufs{s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, &s->sort_tmp}, n, (int64_t)n >= s->opt.onesweep_min, s->stream, nullptr);
 }
 
 void reserve_build_scratch(rc_scene* s, uint32_t n) {
@@ -914,19 +925,65 @@ void reserve_build_scratch(rc_scene* s, uint32_t n) {
     s->flags.reserve(n);
     s->scene_enc.reserve(8);
 }
+inline size_t topology_records(uint32_t n) { return n > 1 ? (size_t)(n - 1) + (n + 3) / 4 : 1; }  // one record per internal node, then the leaves' parent words
+inline unsigned blas_bounds_blocks(uint32_t n) { return std::min(grid_for(n), 1024u); }
 
-// Karras topology + parents for n items with sorted keys in keys_b
-void emit_tree(rc_scene* s, RcNode* nodes, uint32_t n, DevBuf<uint4>& ranges) {
-    ranges.reserve(n > 1 ? (size_t)(n - 1) + (n + 3) / 4 : 1);  // one record per internal node, then the leaves' parent words
-    if (n > 1) hipLaunchKernelGGL(k_topology, dim3(grid_for(n - 1)), dim3(kBlock), 0, s->stream, nodes, s->keys_b.p, (int)n, ranges.p);
-    else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, s->stream, nodes, 1u);  // single leaf: empty node, the leaf kernel fills the payload
+// The scene's own scratch for a build of n items on the scene's stream, reserved here: a host call that may allocate
+ChainBufs scene_bufs(rc_scene* s, uint32_t n, unsigned partial_blocks, DevBuf<uint4>& ranges) {
+    reserve_build_scratch(s, n);
+    s->bounds_partials.reserve((size_t)partial_blocks * 6); ranges.reserve(topology_records(n));
+    return ChainBufs{s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, s->bounds_partials.p, s->scene_enc.p, s->flags.p, s->flags.p, ranges.p,
+                     s->aabb_tmp.p, &s->sort_tmp, 0, (int64_t)n >= s->opt.onesweep_min};
+}
+// The TLAS's scratch on a caller's stream.  Arrival counters of its own (s->tlas_flags), because s->flags is also the BLAS builds' (other stream)
+ChainBufs rebuild_bufs(rc_scene* s) {
+    auto& r = s->rebuild;
+    return ChainBufs{r.keys_a.p, r.keys_b.p, r.vals_a.p, r.vals_b.p, r.partials.p, r.enc.p, s->tlas_flags.p, s->tlas_flags.p, s->tlas_ranges.p,
+                     r.aabbs.p, &r.sort_tmp, r.sort_bytes, r.onesweep};
 }
 
-void run_refit(rc_scene* s, RcNode* nodes, const RcPrim* prims, uint32_t n, int tlas, const DevBuf<uint4>& ranges, hipStream_t st, uint32_t* flags = nullptr) {
+// Karras topology + parents for n items with sorted keys in b.keys_b
+void emit_tree(hipStream_t st, const ChainBufs& b, RcNode* nodes, uint32_t n) {
+    if (n > 1) hipLaunchKernelGGL(k_topology, dim3(grid_for(n - 1)), dim3(kBlock), 0, st, nodes, b.keys_b, (int)n, b.ranges);
+    else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, st, nodes, 1u);  // single leaf: empty node, the leaf kernel fills the payload
+}
+
+void run_refit(hipStream_t st, const ChainBufs& b, RcNode* nodes, const RcPrim* prims, uint32_t n, int tlas) {
+    const size_t words = (size_t)(b.arrive - b.zeroed) + (n - 1);
+    if (words) RC_HIP(hipMemsetAsync(b.zeroed, 0, sizeof(uint32_t) * words, st));
     if (n < 2) return;
-    if (!flags) flags = s->flags.p;
-    RC_HIP(hipMemsetAsync(flags, 0, sizeof(uint32_t) * (n - 1), st));
-    hipLaunchKernelGGL(k_refit, dim3((n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, nodes, prims, flags, ranges.p, n, tlas);
+    hipLaunchKernelGGL(k_refit, dim3((n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, nodes, prims, b.arrive, b.ranges, n, tlas);
+}
+
+// old -> new index of a tree's internal nodes when its top K go to the front in breadth-first order (k_top_remap); depends on the topology only
+void top_renumber(hipStream_t st, const RcNode* nodes, uint32_t n_leaves, uint32_t K, uint32_t* remap) {
+    hipLaunchKernelGGL(k_iota1, dim3(grid_for(n_leaves - 1)), dim3(kBlock), 0, st, remap, n_leaves - 1);
+    hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, st, nodes, n_leaves, K, remap);
+}
+
+// The degenerate filter over n faces: flags, their exclusive scan `pos` (storage `tmp`, sized by the caller), the valid ones compacted into `out`
+void ingest_chain(hipStream_t st, const float* verts, const uint32_t* meta, uint32_t n, uint32_t* flags, uint32_t* pos, void* tmp, size_t tmp_bytes,
+                  RcPrim* out, uint32_t* slot_face) {
+    hipLaunchKernelGGL(k_flag_valid_faces, dim3(grid_for(n)), dim3(kBlock), 0, st, verts, n, flags);
+    RC_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, flags, pos, (int)n, st));
+    hipLaunchKernelGGL(k_compact_faces, dim3(grid_for(n)), dim3(kBlock), 0, st, verts, meta, flags, pos, n, out, slot_face);
+}
+
+// build_blas (src/instanced-bvh.jl:1376-1443) over the n compacted primitives `in`, in two steps; between them a caller may gather more
+// than the primitives through the sorted permutation (b.vals_b).  First the Morton order: `prims` = `in` sorted ...
+void blas_sort_chain(hipStream_t st, const ChainBufs& b, const RcPrim* in, uint32_t n, RcPrim* prims) {
+    const unsigned nb = blas_bounds_blocks(n);
+    hipLaunchKernelGGL(k_blas_scene_bounds, dim3(nb), dim3(kBlock), 0, st, in, n, b.partials);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(384), 0, st, b.partials, nb, b.enc);
+    hipLaunchKernelGGL(k_blas_morton, dim3(grid_for(n)), dim3(kBlock), 0, st, in, n, b.enc, b.keys_a, b.vals_a);
+    sort_pairs(st, b, n);
+    hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(n)), dim3(kBlock), 0, st, in, b.vals_b, n, prims);
+}
+// ... then the tree over them: topology from the sorted keys, leaves, bottom-up boxes
+void blas_tree_chain(hipStream_t st, const ChainBufs& b, const RcPrim* prims, uint32_t n, RcNode* nodes) {
+    emit_tree(st, b, nodes, n);
+    hipLaunchKernelGGL(k_blas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, st, nodes, prims, n);
+    run_refit(st, b, nodes, prims, n, 0);
 }
 
 __host__ __device__ inline void host_root_aabb(const RcNode& root, bool tlas, float mn[3], float mx[3]) {
@@ -942,6 +999,53 @@ __host__ __device__ inline void host_root_aabb(const RcNode& root, bool tlas, fl
         a = min3v(min3v(v0, v1), v2); b = max3v(max3v(v0, v1), v2);
     }
     mn[0] = a.x; mn[1] = a.y; mn[2] = a.z; mx[0] = b.x; mx[1] = b.y; mx[2] = b.z;
+}
+
+// The box of the tree at d_root, behind everything enqueued on the scene's stream: the one host wait of a synchronous build or refit
+void read_root_aabb(rc_scene* s, const RcNode* d_root, bool tlas, float mn[3], float mx[3]) {
+    RcNode root;
+    RC_HIP(hipMemcpyAsync(&root, d_root, sizeof(RcNode), hipMemcpyDeviceToHost, s->stream));
+    RC_HIP(hipStreamSynchronize(s->stream));
+    RC_HIP(hipGetLastError());
+    host_root_aabb(root, tlas, mn, mx);
+}
+
+// What a TLAS derives per instance from the descriptors in s->d_instances: with `recs` the traversal records and entry-cull spheres, with
+// `leaves` the leaf nodes -- in the order of `sorted` (a build), or each leaf for the instance it already names (a refit: nullptr).
+void per_instance_pass(rc_scene* s, hipStream_t st, uint32_t n, bool recs, bool leaves, const uint32_t* sorted = nullptr) {
+    if (recs) hipLaunchKernelGGL(k_inst_recs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, s->d_blas_nprims.p, n, s->inst_recs.p,
+                                 (const uint32_t*)s->blas_cull_bits.p, s->inst_cull.p);
+    if (leaves) hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, st, s->tlas_nodes.p, sorted, s->d_instances.p, s->d_descs.p, n);
+}
+
+// The TLAS part of the traversal copy (behind the BLAS nodes), renumbered when the scene keeps the TLAS's top in LDS (tlas_top_k).
+void pack_tlas(rc_scene* s, hipStream_t st) {
+    const uint32_t n = (s->n_tlas_nodes + 1) / 2;
+    if (s->tlas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, s->tlas_remap.p, false);
+    else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, 0u);
+}
+
+// build_tlas_topology (src/instanced-bvh.jl:1485-1594) from the n descriptors in s->d_instances, into the scene's TLAS arrays: tree,
+// instance -> leaf table, top renumbering, traversal copy.  Every array it writes was reserved by rc_build_tlas.
+void tlas_chain(rc_scene* s, hipStream_t st, const ChainBufs& b, uint32_t n) {
+    hipLaunchKernelGGL(k_instance_aabbs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, n, b.aabbs, b.partials);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(384), 0, st, b.partials, grid_for(n), b.enc);
+    hipLaunchKernelGGL(k_tlas_morton, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, n, b.enc, b.keys_a, b.vals_a);
+    sort_pairs(st, b, n);
+    emit_tree(st, b, s->tlas_nodes.p, n);
+    // n == 1 (:1553-1570): the single leaf holds the scene AABB == the instance's world AABB (same min/max set)
+    per_instance_pass(s, st, n, false, true, b.vals_b);
+    run_refit(st, b, s->tlas_nodes.p, nullptr, n, 1);
+    hipLaunchKernelGGL(k_inst_leaf, dim3(grid_for(n)), dim3(kBlock), 0, st, b.vals_b, n, s->inst_leaf.p);  // instance -> leaf (rc_update_instances_async)
+    if (s->tlas_top_k) top_renumber(st, s->tlas_nodes.p, n, s->tlas_top_k, s->tlas_remap.p);  // topology only: computed here, reused by every refit
+    pack_tlas(s, st);
+}
+
+// refit_tlas! (src/instanced-bvh.jl:2197-2222) in place: per-instance data (unless it is in place already) -> bottom-up refit -> traversal copy
+void refit_chain(rc_scene* s, hipStream_t st, const ChainBufs& b, uint32_t n, bool per_instance) {
+    if (per_instance) per_instance_pass(s, st, n, true, true);
+    run_refit(st, b, s->tlas_nodes.p, nullptr, n, 1);
+    pack_tlas(s, st);
 }
 
 }  // namespace
@@ -968,12 +1072,10 @@ uint32_t rc_ingest_faces(rc_scene* s, const float* d_verts, const uint32_t* d_me
     reserve_build_scratch(s, n);
     s->prim_tmp.reserve(n);
     if (keep_face_map) s->slot_face.reserve(n);
-    hipLaunchKernelGGL(k_flag_valid_faces, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, d_verts, n, s->keys_a.p);
     size_t tmp = 0;
     RC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, s->keys_a.p, s->keys_b.p, (int)n, s->stream));
     s->sort_tmp.reserve(tmp ? tmp : 1);
-    RC_HIP(hipcub::DeviceScan::ExclusiveSum(s->sort_tmp.p, tmp, s->keys_a.p, s->keys_b.p, (int)n, s->stream));
-    hipLaunchKernelGGL(k_compact_faces, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, d_verts, d_meta, s->keys_a.p, s->keys_b.p, n, s->prim_tmp.p, keep_face_map ? s->slot_face.p : nullptr);
+    ingest_chain(s->stream, d_verts, d_meta, n, s->keys_a.p, s->keys_b.p, s->sort_tmp.p, tmp, s->prim_tmp.p, keep_face_map ? s->slot_face.p : nullptr);
     uint32_t last[2];
     RC_HIP(hipMemcpyAsync(&last[0], s->keys_b.p + (n - 1), 4, hipMemcpyDeviceToHost, s->stream));
     RC_HIP(hipMemcpyAsync(&last[1], s->keys_a.p + (n - 1), 4, hipMemcpyDeviceToHost, s->stream));
@@ -1058,44 +1160,22 @@ void rc_launch_reflection_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_
 
 // build_blas (src/instanced-bvh.jl:1376-1443) over the n compacted primitives waiting in s->prim_tmp
 void rc_build_blas(rc_scene* s, uint32_t n, Blas& out, bool keep_face_map) {
-    reserve_build_scratch(s, n);
     out.prims.reserve(n);
     out.nodes.reserve(2 * (size_t)n - 1);
+    if (keep_face_map) out.src_face.reserve(n);
     out.n_prims = n;
     out.n_nodes = 2 * n - 1;
+    const ChainBufs b = scene_bufs(s, n, blas_bounds_blocks(n), s->range_tmp);
     rc_timing_scene_begin(s, s->stream);
-    {
-        const unsigned nb = std::min(grid_for(n), 1024u);
-        s->bounds_partials.reserve((size_t)nb * 6);
-        hipLaunchKernelGGL(k_blas_scene_bounds, dim3(nb), dim3(kBlock), 0, s->stream, s->prim_tmp.p, n, s->bounds_partials.p);
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(384), 0, s->stream, s->bounds_partials.p, nb, s->scene_enc.p);
-    }
-    hipLaunchKernelGGL(k_blas_morton, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->prim_tmp.p, n, s->scene_enc.p, s->keys_a.p, s->vals_a.p);
-    sort_pairs(s, n);
-    hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->prim_tmp.p, s->vals_b.p, n, out.prims.p);
-    if (keep_face_map) {  // source face of every Morton-sorted primitive: the attributes stay per vertex and are looked up through it
-        out.src_face.reserve(n);
+    blas_sort_chain(s->stream, b, s->prim_tmp.p, n, out.prims.p);
+    if (keep_face_map)  // source face of every Morton-sorted primitive: the attributes stay per vertex and are looked up through it
         hipLaunchKernelGGL(k_gather_u32, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->slot_face.p, s->vals_b.p, n, out.src_face.p);
-    }
-    emit_tree(s, out.nodes.p, n, s->range_tmp);
-    hipLaunchKernelGGL(k_blas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, out.nodes.p, out.prims.p, n);
-    run_refit(s, out.nodes.p, out.prims.p, n, 0, s->range_tmp, s->stream);
+    blas_tree_chain(s->stream, b, out.prims.p, n, out.nodes.p);
     rc_timing_scene_end(s, s->stream);
-    RcNode root;
-    RC_HIP(hipMemcpyAsync(&root, out.nodes.p, sizeof(RcNode), hipMemcpyDeviceToHost, s->stream));
-    RC_HIP(hipStreamSynchronize(s->stream));
-    RC_HIP(hipGetLastError());
-    host_root_aabb(root, false, out.root_min, out.root_max);
+    read_root_aabb(s, out.nodes.p, false, out.root_min, out.root_max);
 }
 
 // rebuild_bvh! minus compaction (src/instanced-bvh.jl:968-992): build_tlas_topology (:1485-1594) +
-// The TLAS part of the traversal copy (behind the BLAS nodes), renumbered when the scene keeps the TLAS's top in LDS (tlas_top_k).
-static void pack_tlas(rc_scene* s, hipStream_t st) {
-    const uint32_t n = (s->n_tlas_nodes + 1) / 2;
-    if (s->tlas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, s->tlas_remap.p, false);
-    else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, 0u);
-}
-
 // build_flat_blas_arrays! (:470-517) + the traversal instance records.
 void rc_build_tlas(rc_scene* s) {
     const uint32_t n = (uint32_t)s->instances.size();
@@ -1155,8 +1235,7 @@ void rc_build_tlas(rc_scene* s) {
         s->blas_top_k = n_int < room ? n_int : room;
         s->blas_top_k32 = s->blas_top_k < blas_room32 ? s->blas_top_k : blas_room32;
         s->top_remap.reserve(n_int);
-        hipLaunchKernelGGL(k_iota1, dim3(grid_for(n_int)), dim3(kBlock), 0, s->stream, s->top_remap.p, n_int);
-        hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, s->stream, s->blas[0].nodes.p, n_leaves, s->blas_top_k, s->top_remap.p);
+        top_renumber(s->stream, s->blas[0].nodes.p, n_leaves, s->blas_top_k, s->top_remap.p);
     }
     for (uint32_t i = 0; i < nb; ++i) {
         if (s->blas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->blas[i].n_nodes)), dim3(kBlock), 0, s->stream, s->blas[i].nodes.p, s->flat_nodes.p + s->descs[i].nodes_offset, s->blas[i].n_nodes, s->blas[i].n_prims, s->top_remap.p, true);
@@ -1184,22 +1263,10 @@ void rc_build_tlas(rc_scene* s) {
         RC_HIP(hipStreamSynchronize(s->stream));
         return;
     }
-    reserve_build_scratch(s, n);
     s->d_instances.reserve(n); s->inst_recs.reserve(n); s->inst_cull.reserve(2 * (size_t)n); s->aabb_tmp.reserve(6 * (size_t)n);
-    s->tlas_nodes.reserve(2 * (size_t)n - 1);
+    s->tlas_nodes.reserve(2 * (size_t)n - 1); s->inst_leaf.reserve(n);
+    if (s->tlas_top_k) s->tlas_remap.reserve(n - 1);
     s->n_tlas_nodes = 2 * n - 1;
-    RC_HIP(hipMemcpyAsync(s->d_instances.p, s->instances.data(), sizeof(RcInstanceDesc) * n, hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(k_inst_recs, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->d_instances.p, s->d_descs.p, s->d_blas_nprims.p, n, s->inst_recs.p,
-                       (const uint32_t*)s->blas_cull_bits.p, s->inst_cull.p);
-    s->bounds_partials.reserve((size_t)grid_for(n) * 6);
-    hipLaunchKernelGGL(k_instance_aabbs, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->d_instances.p, s->d_descs.p, n, s->aabb_tmp.p, s->bounds_partials.p);
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(384), 0, s->stream, s->bounds_partials.p, grid_for(n), s->scene_enc.p);
-    hipLaunchKernelGGL(k_tlas_morton, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->d_instances.p, s->d_descs.p, n, s->scene_enc.p, s->keys_a.p, s->vals_a.p);
-    sort_pairs(s, n);
-    emit_tree(s, s->tlas_nodes.p, n, s->tlas_ranges);
-    // n == 1 (:1553-1570): the single leaf holds the scene AABB == the instance's world AABB (same min/max set)
-    hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->tlas_nodes.p, s->vals_b.p, s->d_instances.p, s->d_descs.p, n);
-    run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges, s->stream);
     s->tlas_flags.reserve(n);  // arrival counters of the asynchronous refit: its own, because s->flags is also the BLAS builds' (other stream)
     {   // scratch of rc_rebuild_tlas_async, TLAS-only for the same reason; the sort's storage is sized here, where a host call may allocate
         auto& r = s->rebuild;
@@ -1208,21 +1275,12 @@ void rc_build_tlas(rc_scene* s) {
         r.n = n;
         r.onesweep = (int64_t)n >= s->opt.onesweep_min;
         r.sort_bytes = 0;
-        sort_pairs_with(SortBufs{r.keys_a.p, r.keys_b.p, r.vals_a.p, r.vals_b.p, &r.sort_tmp}, n, r.onesweep, s->stream, &r.sort_bytes);
+        sort_pairs(s->stream, rebuild_bufs(s), n, &r.sort_bytes);
     }
-    s->inst_leaf.reserve(n);  // instance -> leaf (rc_update_instances_async): topology only, like the renumbering below
-    hipLaunchKernelGGL(k_inst_leaf, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, (const uint32_t*)s->vals_b.p, n, s->inst_leaf.p);
-    if (s->tlas_top_k) {  // the renumbering depends on the topology only: computed here, reused by every refit
-        s->tlas_remap.reserve(n - 1);
-        hipLaunchKernelGGL(k_iota1, dim3(grid_for(n - 1)), dim3(kBlock), 0, s->stream, s->tlas_remap.p, n - 1);
-        hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, s->stream, s->tlas_nodes.p, n, s->tlas_top_k, s->tlas_remap.p);
-    }
-    pack_tlas(s, s->stream);
-    RcNode root;
-    RC_HIP(hipMemcpyAsync(&root, s->tlas_nodes.p, sizeof(RcNode), hipMemcpyDeviceToHost, s->stream));
-    RC_HIP(hipStreamSynchronize(s->stream));
-    RC_HIP(hipGetLastError());
-    host_root_aabb(root, true, s->root_min, s->root_max);
+    RC_HIP(hipMemcpyAsync(s->d_instances.p, s->instances.data(), sizeof(RcInstanceDesc) * n, hipMemcpyHostToDevice, s->stream));
+    per_instance_pass(s, s->stream, n, true, false);
+    tlas_chain(s, s->stream, scene_bufs(s, n, grid_for(n), s->tlas_ranges), n);
+    read_root_aabb(s, s->tlas_nodes.p, true, s->root_min, s->root_max);
     s->bound_stale = false;
 }
 
@@ -1232,23 +1290,14 @@ void rc_build_tlas(rc_scene* s) {
 void rc_refit_tlas(rc_scene* s, bool from_device, bool recompute_inverse) {
     const uint32_t n = (uint32_t)s->instances.size();
     if (n == 0) return;
-    reserve_build_scratch(s, n);
     if (from_device) {
         if (recompute_inverse) hipLaunchKernelGGL(k_update_inverses, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->d_instances.p, n);
         s->host_instances_stale = true;
     } else {
         RC_HIP(hipMemcpyAsync(s->d_instances.p, s->instances.data(), sizeof(RcInstanceDesc) * n, hipMemcpyHostToDevice, s->stream));
     }
-    hipLaunchKernelGGL(k_inst_recs, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->d_instances.p, s->d_descs.p, s->d_blas_nprims.p, n, s->inst_recs.p,
-                       (const uint32_t*)s->blas_cull_bits.p, s->inst_cull.p);
-    hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->tlas_nodes.p, (const uint32_t*)nullptr, s->d_instances.p, s->d_descs.p, n);
-    run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges, s->stream);
-    pack_tlas(s, s->stream);
-    RcNode root;
-    RC_HIP(hipMemcpyAsync(&root, s->tlas_nodes.p, sizeof(RcNode), hipMemcpyDeviceToHost, s->stream));
-    RC_HIP(hipStreamSynchronize(s->stream));
-    RC_HIP(hipGetLastError());
-    host_root_aabb(root, true, s->root_min, s->root_max);
+    refit_chain(s, s->stream, scene_bufs(s, n, grid_for(n), s->tlas_ranges), n, true);
+    read_root_aabb(s, s->tlas_nodes.p, true, s->root_min, s->root_max);
     s->bound_stale = false;
 }
 
@@ -1281,13 +1330,7 @@ void rc_update_instances_async(rc_scene* s, uint32_t first, uint32_t m, const fl
 void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
     const uint32_t n = (uint32_t)s->instances.size();
     if (n == 0) return;
-    if (per_instance) {
-        hipLaunchKernelGGL(k_inst_recs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, s->d_blas_nprims.p, n, s->inst_recs.p,
-                           (const uint32_t*)s->blas_cull_bits.p, s->inst_cull.p);
-        hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, st, s->tlas_nodes.p, (const uint32_t*)nullptr, s->d_instances.p, s->d_descs.p, n);
-    }
-    run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges, st, s->tlas_flags.p);
-    pack_tlas(s, st);
+    refit_chain(s, st, rebuild_bufs(s), n, per_instance);
     RC_HIP(hipGetLastError());
     s->host_instances_stale = true;
     s->bound_stale = true;
@@ -1295,37 +1338,19 @@ void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
     note_async_mutation(s, st);
 }
 
-// rebuild_bvh! (src/instanced-bvh.jl:968-992, build_tlas_topology :1485-1594) on `st` from the descriptors the device holds: what
-// rc_build_tlas does from k_instance_aabbs on, in place -- same buffers, same addresses, so captured updates, refits and traces stay valid
-// -- with the scratch reserved at sync time and without the root read-back.  per_instance as for rc_refit_tlas_async.
+// rebuild_bvh! (src/instanced-bvh.jl:968-992, build_tlas_topology :1485-1594) on `st` from the descriptors the device holds, in place --
+// same buffers, same addresses, so captured updates, refits and traces stay valid -- with the scratch reserved at sync time and without
+// the root read-back.  per_instance as for rc_refit_tlas_async.
 void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
     const uint32_t n = (uint32_t)s->instances.size();
     if (n == 0) return;
-    auto& r = s->rebuild;
-    if (r.n != n) throw RcError(4, "rebuild scratch does not match the instance count");  // (reserved by every rebuilding rc_sync)
-    if (per_instance)
-        hipLaunchKernelGGL(k_inst_recs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, s->d_blas_nprims.p, n, s->inst_recs.p,
-                           (const uint32_t*)s->blas_cull_bits.p, s->inst_cull.p);
-    RcNode* packed = s->flat_nodes.p + s->n_flat_nodes;
+    if (s->rebuild.n != n) throw RcError(4, "rebuild scratch does not match the instance count");  // (reserved by every rebuilding rc_sync)
+    if (per_instance) per_instance_pass(s, st, n, true, false);
     if (s->opt.tlas_rebuild_fused && n >= 2 && n <= (uint32_t)kFusedInst && s->tlas_top_k == 0) {
         hipLaunchKernelGGL(k_rebuild_tlas_fused, dim3(1), dim3(kFusedInst), 0, st, (const RcInstanceDesc*)s->d_instances.p, (const RcBlasDesc*)s->d_descs.p, n,
-                           s->tlas_nodes.p, packed, s->tlas_ranges.p, s->inst_leaf.p);
+                           s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->tlas_ranges.p, s->inst_leaf.p);
     } else {
-        hipLaunchKernelGGL(k_instance_aabbs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, n, r.aabbs.p, r.partials.p);
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(384), 0, st, r.partials.p, grid_for(n), r.enc.p);
-        hipLaunchKernelGGL(k_tlas_morton, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, n, r.enc.p, r.keys_a.p, r.vals_a.p);
-        size_t bytes = r.sort_bytes;
-        sort_pairs_with(SortBufs{r.keys_a.p, r.keys_b.p, r.vals_a.p, r.vals_b.p, &r.sort_tmp}, n, r.onesweep, st, &bytes);
-        if (n > 1) hipLaunchKernelGGL(k_topology, dim3(grid_for(n - 1)), dim3(kBlock), 0, st, s->tlas_nodes.p, r.keys_b.p, (int)n, s->tlas_ranges.p);
-        else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, st, s->tlas_nodes.p, 1u);
-        hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, st, s->tlas_nodes.p, (const uint32_t*)r.vals_b.p, s->d_instances.p, s->d_descs.p, n);
-        run_refit(s, s->tlas_nodes.p, nullptr, n, 1, s->tlas_ranges, st, s->tlas_flags.p);
-        hipLaunchKernelGGL(k_inst_leaf, dim3(grid_for(n)), dim3(kBlock), 0, st, (const uint32_t*)r.vals_b.p, n, s->inst_leaf.p);
-        if (s->tlas_top_k) {
-            hipLaunchKernelGGL(k_iota1, dim3(grid_for(n - 1)), dim3(kBlock), 0, st, s->tlas_remap.p, n - 1);
-            hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, st, s->tlas_nodes.p, n, s->tlas_top_k, s->tlas_remap.p);
-        }
-        pack_tlas(s, st);
+        tlas_chain(s, st, rebuild_bufs(s), n);
     }
     RC_HIP(hipGetLastError());
     s->host_instances_stale = true;
@@ -1364,7 +1389,7 @@ void rc_ensure_world_bound(rc_scene* s, hipStream_t for_stream) {
 }
 
 // ---- update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) on the caller's stream: build_blas (:1376-1443) from a device soup,
-// committed IN PLACE.  The chain is rc_ingest_faces + rc_build_blas without their two read-backs, over scratch of its own (s->deform), into
+// committed IN PLACE.  The chain runs over scratch of its own (s->deform), without a read-back, into
 // a staged tree; the host cannot learn the valid-face count without waiting, so the chain runs with the BLAS's current count and the three
 // kernels below -- the only ones that touch anything a trace, an export or a later sync reads -- first compare it with the count the
 // filter found (deform_ok: the scan's last element + the last flag).  On a mismatch they write nothing but the sticky status word; the
@@ -1411,15 +1436,9 @@ __global__ __launch_bounds__(kBlock) void k_deform_commit(DeformCommit c) {
     float rmin[3], rmax[3];
     host_root_aabb(c.new_nodes[0], false, rmin, rmax);
     if (i < n_nodes) {
-        RcNode nd = c.new_nodes[i];
+        const RcNode nd = c.new_nodes[i];
         c.blas_nodes[i] = nd;
-        uint32_t at = i;
-        if (c.remap && i + 1u < c.n_prims) {  // k_pack_nodes_remap
-            if (nd.child0 < c.n_prims) nd.child0 = c.remap[nd.child0 - 1];
-            if (nd.child1 < c.n_prims) nd.child1 = c.remap[nd.child1 - 1];
-            at = c.remap[i] - 1u;
-        }
-        c.flat_nodes[at] = i + 1u >= c.n_prims ? rc_pack_leaf(nd) : rc_pack_node(nd);
+        pack_node_renumbered(nd, i, c.n_prims, c.remap, true, c.flat_nodes);
     }
     if (i < c.n_prims) {
         const RcPrim p = c.new_prims[i];
@@ -1479,8 +1498,7 @@ void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_ver
     auto& D = s->deform;
     const uint32_t np = b.n_prims, cap_n = std::max(n, np);
     const bool mesh = d_mesh_verts != nullptr, capturing = stream_capturing(st);
-    const bool onesweep = (int64_t)np >= s->opt.onesweep_min;
-    const unsigned nb = std::min(grid_for(np), 1024u);
+    const bool renumber = s->blas_top_k > 0 && s->blas.size() == 1;
     // ---- scratch: grown by eager calls only
     auto need = [&](auto& buf, size_t count) {
         if (count <= buf.cap) return;
@@ -1490,19 +1508,23 @@ void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_ver
     need(D.flags, cap_n); need(D.pos, cap_n); need(D.compact, cap_n);
     if (mesh) { need(D.slot_face, cap_n); need(D.soup, 9 * (size_t)n); }
     need(D.keys_a, np); need(D.keys_b, np); need(D.vals_a, np); need(D.vals_b, np);
-    need(D.enc, 8); need(D.partials, (size_t)nb * 6); need(D.arrive, np);
-    if (s->blas_top_k > 0 && s->blas.size() == 1) need(D.remap, np - 1);
-    need(D.prims, np); need(D.nodes, 2 * (size_t)np - 1); need(D.ranges, np > 1 ? (size_t)(np - 1) + (np + 3) / 4 : 1);
+    need(D.enc, 8); need(D.partials, (size_t)blas_bounds_blocks(np) * 6); need(D.arrive, np);
+    if (renumber) need(D.remap, np - 1);
+    need(D.prims, np); need(D.nodes, 2 * (size_t)np - 1); need(D.ranges, topology_records(np));
+    // word 0 of D.arrive: the cull radius k_deform_commit folds into, zeroed with the refit's arrival counters behind it
+    ChainBufs bufs{D.keys_a.p, D.keys_b.p, D.vals_a.p, D.vals_b.p, D.partials.p, D.enc.p, D.arrive.p, D.arrive.p + 1, D.ranges.p,
+                   nullptr, &D.tmp, 0, (int64_t)np >= s->opt.onesweep_min};
     if (!D.scan_bytes.count(n) || !D.sort_bytes.count(np)) {
         if (capturing) throw RcError(1, "the geometry update has not run eagerly with these counts yet: its scan / sort storage cannot be sized while the stream is being captured");
         size_t scan = 0, sort = 0;
         RC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan, D.flags.p, D.pos.p, (int)n, st));
-        sort_pairs_with(SortBufs{D.keys_a.p, D.keys_b.p, D.vals_a.p, D.vals_b.p, &D.tmp}, np, onesweep, st, &sort);  // (size query + reserve, nothing enqueued)
+        sort_pairs(st, bufs, np, &sort);  // (size query + reserve, nothing enqueued)
         D.scan_bytes[n] = scan ? scan : 1;
         D.sort_bytes[np] = sort;
     }
-    size_t scan_bytes = D.scan_bytes[n], sort_bytes = D.sort_bytes[np];
-    need(D.tmp, std::max(scan_bytes, sort_bytes));
+    const size_t scan_bytes = D.scan_bytes[n];
+    bufs.sort_bytes = D.sort_bytes[np];
+    need(D.tmp, std::max(scan_bytes, bufs.sort_bytes));
     if (mesh && b.m_face_meta.cap < b.n_mesh_faces) {
         // a scene loaded from a file carries no per-face metadata: recovered from the surviving primitives through the face map (faces the
         // filter had dropped get the default, their index)
@@ -1511,31 +1533,16 @@ void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_ver
         hipLaunchKernelGGL(k_iota1, dim3(grid_for(b.n_mesh_faces)), dim3(kBlock), 0, st, b.m_face_meta.p, b.n_mesh_faces);
         hipLaunchKernelGGL(k_face_meta_of, dim3(grid_for(np)), dim3(kBlock), 0, st, (const RcPrim*)b.prims.p, (const uint32_t*)b.src_face.p, np, b.m_face_meta.p);
     }
-    // ---- rc_ingest_faces
+    // ---- the filter over the n faces, then the build over np slots into the staged arrays
     if (mesh) {  // (the kernel's per-face metadata output is not needed -- the compaction reads m_face_meta itself -- and lands in D.pos, which the scan overwrites)
         hipLaunchKernelGGL(k_expand_mesh, dim3(grid_for(n)), dim3(kBlock), 0, st, d_mesh_verts, (const uint32_t*)b.m_indices.p, (const uint32_t*)nullptr, true, n, D.soup.p, D.pos.p);
         d_verts = D.soup.p;
         d_meta = b.m_face_meta.p;
     }
-    hipLaunchKernelGGL(k_flag_valid_faces, dim3(grid_for(n)), dim3(kBlock), 0, st, d_verts, n, D.flags.p);
-    RC_HIP(hipcub::DeviceScan::ExclusiveSum(D.tmp.p, scan_bytes, D.flags.p, D.pos.p, (int)n, st));
-    hipLaunchKernelGGL(k_compact_faces, dim3(grid_for(n)), dim3(kBlock), 0, st, d_verts, d_meta, (const uint32_t*)D.flags.p, (const uint32_t*)D.pos.p, n, D.compact.p, mesh ? D.slot_face.p : (uint32_t*)nullptr);
-    // ---- rc_build_blas over np slots, into the staged arrays
-    hipLaunchKernelGGL(k_blas_scene_bounds, dim3(nb), dim3(kBlock), 0, st, (const RcPrim*)D.compact.p, np, D.partials.p);
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(384), 0, st, (const uint32_t*)D.partials.p, nb, D.enc.p);
-    hipLaunchKernelGGL(k_blas_morton, dim3(grid_for(np)), dim3(kBlock), 0, st, (const RcPrim*)D.compact.p, np, (const uint32_t*)D.enc.p, D.keys_a.p, D.vals_a.p);
-    sort_pairs_with(SortBufs{D.keys_a.p, D.keys_b.p, D.vals_a.p, D.vals_b.p, &D.tmp}, np, onesweep, st, &sort_bytes);
-    hipLaunchKernelGGL(k_gather_prims, dim3(grid_for(np)), dim3(kBlock), 0, st, (const RcPrim*)D.compact.p, (const uint32_t*)D.vals_b.p, np, D.prims.p);
-    if (np > 1) hipLaunchKernelGGL(k_topology, dim3(grid_for(np - 1)), dim3(kBlock), 0, st, D.nodes.p, (const uint32_t*)D.keys_b.p, (int)np, D.ranges.p);
-    else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, st, D.nodes.p, 1u);
-    hipLaunchKernelGGL(k_blas_leaves, dim3(grid_for(np)), dim3(kBlock), 0, st, D.nodes.p, (const RcPrim*)D.prims.p, np);
-    RC_HIP(hipMemsetAsync(D.arrive.p, 0, sizeof(uint32_t) * np, st));  // word 0: the cull radius being folded; then the refit's arrival counters
-    if (np > 1) hipLaunchKernelGGL(k_refit, dim3((np + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, D.nodes.p, (const RcPrim*)D.prims.p, D.arrive.p + 1, (const uint4*)D.ranges.p, np, 0);
-    const bool renumber = s->blas_top_k > 0 && s->blas.size() == 1;
-    if (renumber) {  // the renumbering follows the new topology (rc_build_tlas): staged too, the commit packs through it
-        hipLaunchKernelGGL(k_iota1, dim3(grid_for(np - 1)), dim3(kBlock), 0, st, D.remap.p, np - 1);
-        hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, st, (const RcNode*)D.nodes.p, np, s->blas_top_k, D.remap.p);
-    }
+    ingest_chain(st, d_verts, d_meta, n, D.flags.p, D.pos.p, D.tmp.p, scan_bytes, D.compact.p, mesh ? D.slot_face.p : nullptr);
+    blas_sort_chain(st, bufs, D.compact.p, np, D.prims.p);
+    blas_tree_chain(st, bufs, D.prims.p, np, D.nodes.p);
+    if (renumber) top_renumber(st, D.nodes.p, np, s->blas_top_k, D.remap.p);  // the renumbering follows the new topology (rc_build_tlas): staged too, the commit packs through it
     // ---- commit, then the instances of this BLAS
     const RcBlasDesc& hd = s->descs[blas_idx];
     DeformCommit c;

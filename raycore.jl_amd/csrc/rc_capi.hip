@@ -139,6 +139,14 @@ void require_synced(rc_scene* s) {
     if (!s->has_static || s->dirty || s->transforms_dirty)
         throw RcError(RC_ERR_NOT_SYNCED, "scene has pending mutations: call rc_sync before tracing (Adapt.adapt does this per dispatch)");
 }
+// The asynchronous device-side mutations write the arrays where the last rc_sync put them: nothing the host holds may be pending.
+void require_device_resident(rc_scene* s, const char* message) {
+    if (!s->has_static || s->dirty || s->mirror_edited) throw RcError(RC_ERR_NOT_SYNCED, message);
+}
+// A device-side update was enqueued: the DEVICE descriptors are newer than the mirror and than the last refit (rc_internal.h)
+void note_device_update(rc_scene* s) { s->host_instances_stale = s->device_dirty = s->transforms_dirty = true; }
+// A device-side refit / rebuild was enqueued: it commits the updates so far
+void note_device_commit(rc_scene* s) { s->device_dirty = s->transforms_dirty = false; }
 // The host-buffer queries run on streams of the library's own, which the caller cannot order behind an asynchronous update / refit it
 // enqueued on a stream of its own: they wait for it here (one flag test when nothing is pending).
 void require_synced_host(rc_scene* s) {
@@ -583,8 +591,7 @@ int rc_sync(rc_scene* s, int* action) {
             // them (the per-instance passes run again: they reproduce what the update kernel wrote); the mirror is refreshed when someone reads it
             rc_wait_async_mutations(s);
             rc_refit_tlas(s, true, false);
-            s->device_dirty = false;
-            s->transforms_dirty = false;
+            note_device_commit(s);
             if (action) *action = 1;
             return;
         }
@@ -1222,43 +1229,31 @@ int rc_update_transforms_device(rc_scene* s, uint32_t handle, const float* d_xfo
         const HandleRange r = live_range(s, handle);
         if (m != r.count) throw RcError(RC_ERR_INVALID_ARGUMENT, "Transform count (" + std::to_string(m) + ") != instance count (" + std::to_string(r.count) + ")");
         if (!d_xforms) throw RcError(RC_ERR_INVALID_ARGUMENT, "d_xforms is NULL");
-        if (!s->has_static || s->dirty || s->mirror_edited)
-            throw RcError(RC_ERR_NOT_SYNCED, "rc_update_transforms_device writes the descriptors where the last rc_sync put them: the scene has pending host-side mutations, call rc_sync first");
+        require_device_resident(s, "rc_update_transforms_device writes the descriptors where the last rc_sync put them: the scene has pending host-side mutations, call rc_sync first");
         use_device(s);
         rc_update_instances_async(s, r.first, m, d_xforms, (hipStream_t)stream);
-        s->host_instances_stale = true;
-        s->device_dirty = true;
-        s->transforms_dirty = true;
+        note_device_update(s);
     });
 }
 
-// refit_tlas! (src/instanced-bvh.jl:2197-2222) on the caller's stream: no read-back, no host wait; the world bound is refreshed lazily.
-int rc_refit_device_async(rc_scene* s, void* stream) {
+// refit_tlas! (src/instanced-bvh.jl:2197-2222) / rebuild_bvh! (:968-992; build_tlas_topology, :1485-1594: the refit with the topology built
+// anew from the device-side transforms) on the caller's stream, in place: no read-back, no host wait; the world bound is refreshed lazily.
+static int commit_device_async(rc_scene* s, void* stream, const char* not_synced, void (*commit)(rc_scene*, bool, hipStream_t)) {
     if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
     return guarded([&] {
-        if (!s->has_static || s->dirty || s->mirror_edited)
-            throw RcError(RC_ERR_NOT_SYNCED, "scene has pending host-side mutations: call rc_sync (rc_refit_device_async commits device-side updates only)");
+        require_device_resident(s, not_synced);
         use_device(s);
         // device_dirty: every change since the last refit came through rc_update_transforms_device, whose kernel has already written the
         // per-instance data; otherwise the descriptors were rewritten through rc_instance_buffer_device and it is derived from them here
-        rc_refit_tlas_async(s, !s->device_dirty, (hipStream_t)stream);
-        s->device_dirty = false;
-        s->transforms_dirty = false;
+        commit(s, !s->device_dirty, (hipStream_t)stream);
+        note_device_commit(s);
     });
 }
-
-// rebuild_bvh! (src/instanced-bvh.jl:968-992; build_tlas_topology, :1485-1594) on the caller's stream: the refit above with the topology built
-// anew from the device-side transforms, in place.
+int rc_refit_device_async(rc_scene* s, void* stream) {
+    return commit_device_async(s, stream, "scene has pending host-side mutations: call rc_sync (rc_refit_device_async commits device-side updates only)", rc_refit_tlas_async);
+}
 int rc_rebuild_tlas_device_async(rc_scene* s, void* stream) {
-    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
-    return guarded([&] {
-        if (!s->has_static || s->dirty || s->mirror_edited)
-            throw RcError(RC_ERR_NOT_SYNCED, "scene has pending host-side mutations: call rc_sync (rc_rebuild_tlas_device_async rebuilds from device-side transforms only)");
-        use_device(s);
-        rc_rebuild_tlas_async(s, !s->device_dirty, (hipStream_t)stream);
-        s->device_dirty = false;
-        s->transforms_dirty = false;
-    });
+    return commit_device_async(s, stream, "scene has pending host-side mutations: call rc_sync (rc_rebuild_tlas_device_async rebuilds from device-side transforms only)", rc_rebuild_tlas_async);
 }
 
 // update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) with a backend-resident soup, on the caller's stream and in place
@@ -1267,8 +1262,7 @@ static void update_geometry_device(rc_scene* s, uint32_t handle, const float* d_
                                    const float* d_mesh_normals, bool mesh, void* stream) {
     const HandleRange r = live_range(s, handle);
     if (r.count == 0) throw RcError(RC_ERR_INVALID_HANDLE, "Handle has no instances");
-    if (!s->has_static || s->dirty || s->mirror_edited)
-        throw RcError(RC_ERR_NOT_SYNCED, "the asynchronous geometry update rewrites the arrays where the last rc_sync put them: the scene has pending host-side mutations, call rc_sync first");
+    require_device_resident(s, "the asynchronous geometry update rewrites the arrays where the last rc_sync put them: the scene has pending host-side mutations, call rc_sync first");
     const uint32_t blas_idx = s->instances[r.first].blas_index - 1;  // :814-816 (blas_index never changes on the device: a stale mirror still holds it)
     if (blas_idx >= s->blas.size() || blas_idx >= s->descs.size()) throw RcError(RC_ERR_INVALID_HANDLE, "Handle refers to no geometry");
     Blas& b = s->blas[blas_idx];
@@ -1281,9 +1275,7 @@ static void update_geometry_device(rc_scene* s, uint32_t handle, const float* d_
     rc_update_geometry_async(s, blas_idx, d_verts, d_meta, n, d_mesh_verts, d_mesh_normals, (hipStream_t)stream);
     b.n_nodes4 = 0;  // the BLAS4 was collapsed from the old tree
     s->vf_order_valid = false;
-    s->host_instances_stale = true;
-    s->device_dirty = true;
-    s->transforms_dirty = true;
+    note_device_update(s);
 }
 
 int rc_update_geometry_device_async(rc_scene* s, uint32_t handle, const float* d_verts, const uint32_t* d_meta, uint32_t n, void* stream) {

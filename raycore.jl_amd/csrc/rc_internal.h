@@ -281,7 +281,8 @@ struct rc_scene {
     std::vector<uint32_t> blas_nprims;
     float root_min[3] = {0, 0, 0}, root_max[3] = {0, 0, 0};
 
-    // scratch
+    // scratch of the builds on the scene's own stream.  rc_build.hip hands each of the three sets -- this one, `rebuild`, `deform` -- to the same
+    // chain bodies as a non-owning view (ChainBufs): the sets stay apart because their chains may run at the same time on different streams
     DevBuf<uint32_t> keys_a, keys_b, vals_a, vals_b, flags, scene_enc, bounds_partials;
     DevBuf<unsigned char> sort_tmp;
     DevBuf<float> aabb_tmp;
