@@ -595,28 +595,33 @@ __global__ __launch_bounds__(kTopBlock) void k_top_remap(const RcNode* nodes, ui
 }
 // Node i (0-based) into the traversal copy through the renumbering (remap == nullptr: none): an internal node moves to its new slot and
 // names its internal children by their new indices
-// (blas: the leaves -- nodes n_leaves .. 2 n_leaves - 1 -- hold triangles and take the leaf packing; a TLAS's leaves hold instance boxes)
+// (the leaves -- nodes n_leaves .. 2 n_leaves - 1 --: tlas_cull == nullptr, a BLAS: they hold triangles and take the leaf packing; else a
+// TLAS: its leaves take the entry data of their instance, rc_pack_tlas_leaf, from the entry-cull spheres at tlas_cull)
 // (a device function: k_pack_nodes_remap runs it over a finished tree, k_deform_commit over the staged one it is committing)
-__device__ inline void pack_node_renumbered(RcNode nd, uint32_t i, uint32_t n_leaves, const uint32_t* remap, bool blas, RcNode* dst) {
+__device__ inline RcNode pack_node_or_leaf(const RcNode& nd, bool leaf, const float4* tlas_cull) {
+    if (!leaf) return rc_pack_node(nd);
+    return tlas_cull ? rc_pack_tlas_leaf(nd, tlas_cull + 2 * (size_t)nd.child1) : rc_pack_leaf(nd);
+}
+__device__ inline void pack_node_renumbered(RcNode nd, uint32_t i, uint32_t n_leaves, const uint32_t* remap, const float4* tlas_cull, RcNode* dst) {
     uint32_t at = i;
     if (remap && i + 1u < n_leaves) {
         if (nd.child0 < n_leaves) nd.child0 = remap[nd.child0 - 1];
         if (nd.child1 < n_leaves) nd.child1 = remap[nd.child1 - 1];
         at = remap[i] - 1u;
     }
-    dst[at] = (blas && i + 1u >= n_leaves) ? rc_pack_leaf(nd) : rc_pack_node(nd);
+    dst[at] = pack_node_or_leaf(nd, i + 1u >= n_leaves, tlas_cull);
 }
-__global__ void k_pack_nodes_remap(const RcNode* src, RcNode* dst, uint32_t n_nodes, uint32_t n_leaves, const uint32_t* remap, bool blas) {
+__global__ void k_pack_nodes_remap(const RcNode* src, RcNode* dst, uint32_t n_nodes, uint32_t n_leaves, const uint32_t* remap, const float4* tlas_cull) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_nodes) return;
-    pack_node_renumbered(src[i], i, n_leaves, remap, blas, dst);
+    pack_node_renumbered(src[i], i, n_leaves, remap, tlas_cull, dst);
 }
 
-// Traversal copy of a node array in the packed order of rc_pack_node (interior nodes, TLAS leaves) / rc_pack_leaf (the triangles of a BLAS:
-// nodes n_leaves .. of a tree with n_leaves leaves; blas_leaves = 0 for a TLAS).
-__global__ void k_pack_nodes(const RcNode* src, RcNode* dst, uint32_t n, uint32_t blas_leaves) {
+// Traversal copy of a node array: interior nodes in the packed order of rc_pack_node, the leaves -- nodes n_leaves .. of a tree with n_leaves
+// leaves -- as rc_pack_leaf (the triangles of a BLAS: tlas_cull == nullptr) or rc_pack_tlas_leaf (a TLAS).
+__global__ void k_pack_nodes(const RcNode* src, RcNode* dst, uint32_t n, uint32_t n_leaves, const float4* tlas_cull) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (blas_leaves && i + 1u >= blas_leaves) ? rc_pack_leaf(src[i]) : rc_pack_node(src[i]);
+    if (i < n) dst[i] = pack_node_or_leaf(src[i], i + 1u >= n_leaves, tlas_cull);
 }
 
 // Per BLAS: the radius, about the centre of its root AABB, of the sphere that holds every LEAF AABB (for a triangle: the distance from the
@@ -812,7 +817,7 @@ __global__ void k_inst_leaf(const uint32_t* sorted, uint32_t n, uint32_t* leaf_o
 constexpr int kFusedInst = rc::kTlasLdsInst;
 __global__ __launch_bounds__(kFusedInst) void k_rebuild_tlas_fused(const RcInstanceDesc* __restrict__ inst, const RcBlasDesc* __restrict__ descs, uint32_t n,
                                                                    RcNode* __restrict__ nodes, RcNode* __restrict__ packed, uint4* __restrict__ ranges,
-                                                                   uint32_t* __restrict__ leaf_of) {
+                                                                   uint32_t* __restrict__ leaf_of, const float4* __restrict__ cull) {
     __shared__ RcNode l_nodes[2 * kFusedInst - 1];
     __shared__ uint4 l_meta[(kFusedInst - 1) + kFusedInst / 4];  // k_topology's compact records, then one parent word per leaf
     __shared__ float l_x[kFusedInst * 12];
@@ -868,7 +873,7 @@ __global__ __launch_bounds__(kFusedInst) void k_rebuild_tlas_fused(const RcInsta
     __syncthreads();
     for (uint32_t i = t; i < 2u * n - 1u; i += kFusedInst) {  // canonical node and traversal copy (k_pack_nodes), 16-byte stores
         const RcNode nd = l_nodes[i];
-        const RcNode pk = rc_pack_node(nd);
+        const RcNode pk = pack_node_or_leaf(nd, i + 1u >= n, cull);  // (the spheres are in place before the rebuild: k_inst_recs / k_update_instances)
         uint4* q = reinterpret_cast<uint4*>(&nodes[i]);
         uint4* r = reinterpret_cast<uint4*>(&packed[i]);
         q[0] = make_uint4(__float_as_uint(nd.f[0]), __float_as_uint(nd.f[1]), __float_as_uint(nd.f[2]), __float_as_uint(nd.f[3]));
@@ -1018,11 +1023,13 @@ void per_instance_pass(rc_scene* s, hipStream_t st, uint32_t n, bool recs, bool 
     if (leaves) hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, st, s->tlas_nodes.p, sorted, s->d_instances.p, s->d_descs.p, n);
 }
 
-// The TLAS part of the traversal copy (behind the BLAS nodes), renumbered when the scene keeps the TLAS's top in LDS (tlas_top_k).
+// The TLAS part of the traversal copy (behind the BLAS nodes), renumbered when the scene keeps the TLAS's top in LDS (tlas_top_k).  Its
+// leaves copy the entry-cull spheres: every chain that changes a sphere (k_inst_recs, k_update_instances, k_deform_instances) ends here
+// or in the fused rebuild's copy-out before a trace may run.
 void pack_tlas(rc_scene* s, hipStream_t st) {
     const uint32_t n = (s->n_tlas_nodes + 1) / 2;
-    if (s->tlas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, s->tlas_remap.p, false);
-    else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, 0u);
+    if (s->tlas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, s->tlas_remap.p, (const float4*)s->inst_cull.p);
+    else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, (const float4*)s->inst_cull.p);
 }
 
 // build_tlas_topology (src/instanced-bvh.jl:1485-1594) from the n descriptors in s->d_instances, into the scene's TLAS arrays: tree,
@@ -1238,8 +1245,8 @@ void rc_build_tlas(rc_scene* s) {
         top_renumber(s->stream, s->blas[0].nodes.p, n_leaves, s->blas_top_k, s->top_remap.p);
     }
     for (uint32_t i = 0; i < nb; ++i) {
-        if (s->blas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->blas[i].n_nodes)), dim3(kBlock), 0, s->stream, s->blas[i].nodes.p, s->flat_nodes.p + s->descs[i].nodes_offset, s->blas[i].n_nodes, s->blas[i].n_prims, s->top_remap.p, true);
-        else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->blas[i].n_nodes)), dim3(kBlock), 0, s->stream, s->blas[i].nodes.p, s->flat_nodes.p + s->descs[i].nodes_offset, s->blas[i].n_nodes, s->blas[i].n_prims);
+        if (s->blas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->blas[i].n_nodes)), dim3(kBlock), 0, s->stream, s->blas[i].nodes.p, s->flat_nodes.p + s->descs[i].nodes_offset, s->blas[i].n_nodes, s->blas[i].n_prims, s->top_remap.p, (const float4*)nullptr);
+        else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->blas[i].n_nodes)), dim3(kBlock), 0, s->stream, s->blas[i].nodes.p, s->flat_nodes.p + s->descs[i].nodes_offset, s->blas[i].n_nodes, s->blas[i].n_prims, (const float4*)nullptr);
         RC_HIP(hipMemcpyAsync(s->flat_prims.p + s->descs[i].primitives_offset, s->blas[i].prims.p, sizeof(RcPrim) * s->blas[i].n_prims, hipMemcpyDeviceToDevice, s->stream));
     }
     if (nb) RC_HIP(hipMemcpyAsync(s->d_descs.p, s->descs.data(), sizeof(RcBlasDesc) * nb, hipMemcpyHostToDevice, s->stream));
@@ -1348,7 +1355,7 @@ void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
     if (per_instance) per_instance_pass(s, st, n, true, false);
     if (s->opt.tlas_rebuild_fused && n >= 2 && n <= (uint32_t)kFusedInst && s->tlas_top_k == 0) {
         hipLaunchKernelGGL(k_rebuild_tlas_fused, dim3(1), dim3(kFusedInst), 0, st, (const RcInstanceDesc*)s->d_instances.p, (const RcBlasDesc*)s->d_descs.p, n,
-                           s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->tlas_ranges.p, s->inst_leaf.p);
+                           s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->tlas_ranges.p, s->inst_leaf.p, (const float4*)s->inst_cull.p);
     } else {
         tlas_chain(s, st, rebuild_bufs(s), n);
     }
@@ -1438,7 +1445,7 @@ __global__ __launch_bounds__(kBlock) void k_deform_commit(DeformCommit c) {
     if (i < n_nodes) {
         const RcNode nd = c.new_nodes[i];
         c.blas_nodes[i] = nd;
-        pack_node_renumbered(nd, i, c.n_prims, c.remap, true, c.flat_nodes);
+        pack_node_renumbered(nd, i, c.n_prims, c.remap, nullptr, c.flat_nodes);
     }
     if (i < c.n_prims) {
         const RcPrim p = c.new_prims[i];

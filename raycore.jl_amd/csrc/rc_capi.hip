@@ -1387,6 +1387,8 @@ int rc_get_option(rc_scene* s, const char* name, int64_t* value) {
         *value = !h ? 0 : (k == "debug_order_n" ? (int64_t)h->n_chunks : (k == "debug_ctl_ptr" ? (int64_t)(uintptr_t)(h->ctl.p + h->parity * rc_scene::ChunkHistory::kHeaderWords) : (k == "debug_cost_ptr" ? (int64_t)(uintptr_t)h->cost.p : (int64_t)(uintptr_t)h->order.p)));
     }
     else if (k == "debug_inst_cull_ptr") *value = (int64_t)(uintptr_t)s->inst_cull.p;  // dev: the entry-cull spheres, 2 x float4 per instance
+    else if (k == "debug_flat_nodes_ptr") *value = (int64_t)(uintptr_t)s->flat_nodes.p;  // dev: the traversal copy, 64-byte records; the TLAS's start at record ...
+    else if (k == "debug_flat_tlas_off") *value = (int64_t)s->n_flat_nodes;
     else if (k == "cost_thr") *value = s->opt.cost_thr;
     else if (k == "vf_first_touch") *value = s->opt.vf_first_touch;
     else if (k == "release_captures") {  // captured launches currently holding a region and a slot

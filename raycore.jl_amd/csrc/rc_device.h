@@ -56,6 +56,21 @@ __host__ __device__ inline RcNode rc_pack_leaf(const RcNode& n) {
     return p;
 }
 
+// Traversal copy of a TLAS LEAF.  No traversal reads a TLAS leaf's box from the copy (the parent's slab test has used it; the canonical
+// array keeps it for exports, refits and collision), so its dwords 0-11 carry what an instance ENTRY needs instead, at the offset at which a
+// ray inside an instance finds a triangle: the persistent kernels fetch both kinds of leaf with one set of loads (phased_trace).
+//   dword 0..3 = c_w.xyz, A  and  dword 4 = B  of the instance's entry-cull sphere (`cull` = its two float4 in rc_scene::inst_cull, k_inst_recs)
+//   dword 5    = the instance index (child1 again: one 16-byte load brings B and the index)        dword 6..11 = 0
+__host__ __device__ inline RcNode rc_pack_tlas_leaf(const RcNode& n, const float4* cull) {
+    RcNode p;
+    p.f[0] = cull[0].x; p.f[1] = cull[0].y; p.f[2] = cull[0].z; p.f[3] = cull[0].w;
+    p.f[4] = cull[1].x;
+    __builtin_memcpy(&p.f[5], &n.child1, sizeof(uint32_t));
+    for (int k = 6; k < 12; ++k) p.f[k] = 0.0f;
+    p.child0 = n.child0; p.child1 = n.child1; p.parent = n.parent; p.pad = 0;
+    return p;
+}
+
 // Traversal record of a BVHNode4 (src/bvh4.jl:40-69), 128 bytes; word layout documented in rc_bvh4.hip.
 struct __attribute__((aligned(128))) RcNode4 {
     uint32_t w[32];

@@ -24,7 +24,7 @@ struct SceneView {  // the StaticTLAS arrays a kernel reads (src/instanced-bvh.j
     uint32_t tlas_off;        // a copy of the TLAS nodes sits at blas_nodes[tlas_off ...] (single-base addressing)
     uint32_t n_nodes_total;   // BLAS + TLAS nodes in blas_nodes (sizes the buffer descriptor)
     uint32_t n_inst;          // instance records
-    const float4* inst_cull;  // per instance (c_w, A), (B, ...): the entry-cull sphere (rc_build.hip k_inst_recs); nullptr = never skip an entry
+    uint32_t entry_cull;      // test an instance's entry-cull sphere -- (c_w, A), B in dwords 0-4 of its TLAS leaf's record (rc_pack_tlas_leaf) -- before entering it; 0 = never skip an entry
     uint32_t* overflow;       // [kTotalStack][total_threads] spill area of the lane stacks (entries below the LDS depth unused)
     uint32_t total_threads;
     uint32_t* status;         // [0] = stack overflow flag
@@ -704,8 +704,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
     const __amdgpu_buffer_rsrc_t irs = make_rsrc(av.inst, av.n_inst * 64u);
     // entry cull (k_inst_recs, rc_build.hip): per ray 1 / (d . d) -- NaN when the ray is outside the regime the cull's bounds assume, which
     // fails every comparison below --, 1 / |d| and the ray's share of the margin
-    const bool cull_on = av.inst_cull != nullptr;
-    const __amdgpu_buffer_rsrc_t crs = make_rsrc(av.inst_cull, cull_on ? av.n_inst * 32u : 0u);
+    const bool cull_on = av.entry_cull != 0u;
     float c_idd = 0.f, c_idl = 0.f, c_ray = 0.f, c_dd = 0.f;
     unsigned long long pool_next = 0, pool_end = 0;
     bool exhausted = false;
@@ -812,68 +811,26 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
             RC_MARK("interior_end");
             if (n_int < thr_eff) break;  // too few interior lanes left: serve the waiting ones first
         }
-        // ---- leaf phase: fast_intersect_triangle (:1756-1797) on BLAS leaves, then pop
+        // ---- record phase: the lanes whose node is a leaf of their level.  A BLAS leaf's record holds a triangle (rc_pack_leaf), a TLAS
+        // leaf's the entry-cull sphere and the index of its instance (rc_pack_tlas_leaf) -- at the same offset expression in the same
+        // buffer (cur_off == tlas_off at top level), so ONE set of three loads and one wait serves fast_intersect_triangle (:1756-1797) and
+        // the entry cull.  Which lanes enter is known before the triangle lanes run: a lane that leaves its instance in this pass and pops
+        // a TLAS leaf enters in the next one.  With the cull off an entering lane needs the instance index alone and keeps the short fetch.
+        bool enter = false, was_skipped = false;
         {
-            const bool is_leaf = cur_inst >= 0 && node >= n_level && node < kSent;
+            const bool at_leaf = node >= n_level && node < kSent;
+            const bool is_leaf = cur_inst >= 0 && at_leaf;
+            const bool is_entry = cur_inst < 0 && at_leaf;
             if (STATS && __ballot(is_leaf)) { st_iter[2] += 1; st_lane[2] += is_leaf ? 1 : 0; }
+            if (STATS && __ballot(is_entry)) st_sub[1] += 1;
             RC_MARK("leaf_begin");
-            if (is_leaf) {
+            if (is_leaf || (is_entry && cull_on)) {
                 const uint32_t off = (cur_off + node) << 6;
                 const float4 qa = buf_f4(nrs1, off), qb = buf_f4(nrs1, off, 16), qc = buf_f4(nrs1, off, 32);
-                // rc_pack_leaf: qa = v0 (y, z | z, x), qb = e1 (z, x | y, z), qc = e2 (z, x | y, z).  The statements of :1766-1790 with each
-                // cross product's x and y as one packed multiply-multiply-subtract; every component is the same IEEE operation on the same
-                // operands as in the scalar form (no contraction), the dot products keep their (a.x b.x + a.y b.y) + a.z b.z order
-                const v2f A0 = {qa.x, qa.y}, A1 = {qa.z, qa.w}, B0 = {qb.x, qb.y}, B1 = {qb.z, qb.w}, C0 = {qc.x, qc.y}, C1 = {qc.z, qc.w};
-                const float e1x = B0.y, e1y = B1.x, e1z = B0.x, e2x = C0.y, e2y = C1.x, e2z = C0.x, dx = dzx.y, dy = dyz.x, dz = dyz.y;
-                const v2f s1xy = dyz * C0 - dzx * C1;          // s1 = d x e2
-                const float s1z = dx * e2y - dy * e2x;
-                const float det = (s1xy.x * e1x + s1xy.y * e1y) + s1z * e1z;
-                const float invd = 1.0f / det;
-                const v2f ddyz = oyz - A0, ddzx = ozx - A1;    // dd = o - v0
-                const float ddx = ddzx.y, ddy = ddyz.x, ddz = ddyz.y;
-                const float u = ((ddx * s1xy.x + ddy * s1xy.y) + ddz * s1z) * invd;
-                const v2f s2xy = ddyz * B0 - ddzx * B1;        // s2 = dd x e1
-                const float s2z = ddx * e1y - ddy * e1x;
-                const float v = ((dx * s2xy.x + dy * s2xy.y) + dz * s2z) * invd;
-                const float t = ((e2x * s2xy.x + e2y * s2xy.y) + e2z * s2z) * invd;
-                const bool hit = !(u < 0.0f || u > 1.0f) && !(v < 0.0f || (u + v) > 1.0f) && !(t < tmin || t > closest_t);
-                closest_prim = hit ? node - n_level + 1u : closest_prim;  // leaf of sorted primitive j sits at n-1+j
-                closest_inst = hit ? cur_inst : closest_inst;
-                closest_t = hit ? t : closest_t;
-                hit_u = hit ? u : hit_u;
-                hit_v = hit ? v : hit_v;
-                if (ANY && hit) node = kInv;  // :2106-2115
-                else node = st.pop(sp);
-            }
-            RC_MARK("leaf_end");
-        }
-        // ---- switch phase: return to the top level (:1996-2006) or enter an instance (:1961-1977)
-        bool was_skipped = false;
-        {
-            const bool is_exit = node == kSent;
-            const bool is_entry = cur_inst < 0 && node >= n_level && node < kSent;
-            if (STATS && __ballot(is_exit || is_entry)) { st_iter[3] += 1; st_lane[3] += (is_exit || is_entry) ? 1 : 0; }
-            if (STATS) { if (__ballot(is_exit)) st_sub[0] += 1; if (__ballot(is_entry)) st_sub[1] += 1; }
-            RC_MARK("switch_begin");
-            if (is_exit) {
-                node = st.pop(sp);
-                cur_inst = -1;
-                cur_off = tlas_off; n_level = n_instances;
-                // back to the world ray (:2003-2005).  Only inv and (-o) * inv are restored: the top level has no triangle tests, so the
-                // ray's o and d are not read again before the next instance entry overwrites them from wo / wd
-                inv = winv;
-                ox = mk3(-wo.x * inv.x, -wo.y * inv.y, -wo.z * inv.z);
-                RC_MARK("switch_end");
-            } else if (is_entry) {
-                RC_MARK("entry_begin");
-                float4 m0, m1, m2;
-                u4v m3;
-                if (TLAS_LDS) cur_inst = (int)lt[node - n_level];  // leaf of sorted instance j is node n - 1 + j; its child1 word
-                else cur_inst = (int)__builtin_amdgcn_raw_buffer_load_b32(nrs1, (cur_off + node) << 6, 52, 0);
-                bool skip = false;
-                if (cull_on) {  // does the ray's segment stay clear of the instance's entry-cull sphere?  (derivation: k_inst_recs, rc_build.hip)
-                    const float4 cs = buf_f4(crs, (uint32_t)cur_inst << 5);
-                    const float cB = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(crs, (uint32_t)cur_inst << 5, 16, 0));
+                if (is_entry) {  // does the ray's segment stay clear of the instance's entry-cull sphere?  (derivation: k_inst_recs, rc_build.hip)
+                    const float4 cs = qa;
+                    const float cB = qb.x;
+                    cur_inst = (int)__float_as_uint(qb.y);
                     const float Lx = cs.x - wo.x, Ly = cs.y - wo.y, Lz = cs.z - wo.z;
                     const float LL = __builtin_fmaf(Lz, Lz, __builtin_fmaf(Ly, Ly, Lx * Lx));
                     const float bq = __builtin_fmaf(Lz, wd.z, __builtin_fmaf(Ly, wd.y, Lx * wd.x));
@@ -886,13 +843,64 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
                     const float Ae = cs.w + c_ray;
                     const float tb = 2.0f * __builtin_fmaf(Ae, c_idl, __builtin_fabsf(tc));
                     const float R = __builtin_fmaf(__builtin_fmaf(5.0e-6f, c_dd * c_idl, cB), tb, Ae);  // (B + 5e-6 |d|) t_bound + A + A_ray
-                    skip = seg > R * R;                                           // (any NaN or Inf on the way: false, the instance is entered)
-                }
-                if (STATS) was_skipped = skip;
-                if (skip) {
-                    cur_inst = -1;
-                    node = st.pop(sp);
+                    const bool skip = seg > R * R;                                // (any NaN or Inf on the way: false, the instance is entered)
+                    if (STATS) was_skipped = skip;
+                    if (skip) {
+                        cur_inst = -1;
+                        node = st.pop(sp);
+                    } else enter = true;
                 } else {
+                    // rc_pack_leaf: qa = v0 (y, z | z, x), qb = e1 (z, x | y, z), qc = e2 (z, x | y, z).  The statements of :1766-1790 with each
+                    // cross product's x and y as one packed multiply-multiply-subtract; every component is the same IEEE operation on the same
+                    // operands as in the scalar form (no contraction), the dot products keep their (a.x b.x + a.y b.y) + a.z b.z order
+                    const v2f A0 = {qa.x, qa.y}, A1 = {qa.z, qa.w}, B0 = {qb.x, qb.y}, B1 = {qb.z, qb.w}, C0 = {qc.x, qc.y}, C1 = {qc.z, qc.w};
+                    const float e1x = B0.y, e1y = B1.x, e1z = B0.x, e2x = C0.y, e2y = C1.x, e2z = C0.x, dx = dzx.y, dy = dyz.x, dz = dyz.y;
+                    const v2f s1xy = dyz * C0 - dzx * C1;          // s1 = d x e2
+                    const float s1z = dx * e2y - dy * e2x;
+                    const float det = (s1xy.x * e1x + s1xy.y * e1y) + s1z * e1z;
+                    const float invd = 1.0f / det;
+                    const v2f ddyz = oyz - A0, ddzx = ozx - A1;    // dd = o - v0
+                    const float ddx = ddzx.y, ddy = ddyz.x, ddz = ddyz.y;
+                    const float u = ((ddx * s1xy.x + ddy * s1xy.y) + ddz * s1z) * invd;
+                    const v2f s2xy = ddyz * B0 - ddzx * B1;        // s2 = dd x e1
+                    const float s2z = ddx * e1y - ddy * e1x;
+                    const float v = ((dx * s2xy.x + dy * s2xy.y) + dz * s2z) * invd;
+                    const float t = ((e2x * s2xy.x + e2y * s2xy.y) + e2z * s2z) * invd;
+                    const bool hit = !(u < 0.0f || u > 1.0f) && !(v < 0.0f || (u + v) > 1.0f) && !(t < tmin || t > closest_t);
+                    closest_prim = hit ? node - n_level + 1u : closest_prim;  // leaf of sorted primitive j sits at n-1+j
+                    closest_inst = hit ? cur_inst : closest_inst;
+                    closest_t = hit ? t : closest_t;
+                    hit_u = hit ? u : hit_u;
+                    hit_v = hit ? v : hit_v;
+                    if (ANY && hit) node = kInv;  // :2106-2115
+                    else node = st.pop(sp);
+                }
+            } else if (is_entry) {  // cull off: the instance index alone
+                if (TLAS_LDS) cur_inst = (int)lt[node - n_level];  // leaf of sorted instance j is node n - 1 + j; its child1 word
+                else cur_inst = (int)__builtin_amdgcn_raw_buffer_load_b32(nrs1, (cur_off + node) << 6, 52, 0);
+                enter = true;
+            }
+            RC_MARK("leaf_end");
+        }
+        // ---- switch phase: return to the top level (:1996-2006) or enter an instance (:1961-1977)
+        {
+            const bool is_exit = node == kSent;  // (also a lane whose triangle test has just popped the sentinel)
+            if (STATS && __ballot(is_exit || enter || was_skipped)) { st_iter[3] += 1; st_lane[3] += (is_exit || enter || was_skipped) ? 1 : 0; }
+            if (STATS && __ballot(is_exit)) st_sub[0] += 1;
+            RC_MARK("switch_begin");
+            if (is_exit) {
+                node = st.pop(sp);
+                cur_inst = -1;
+                cur_off = tlas_off; n_level = n_instances;
+                // back to the world ray (:2003-2005).  Only inv and (-o) * inv are restored: the top level has no triangle tests, so the
+                // ray's o and d are not read again before the next instance entry overwrites them from wo / wd
+                inv = winv;
+                ox = mk3(-wo.x * inv.x, -wo.y * inv.y, -wo.z * inv.z);
+                RC_MARK("switch_end");
+            } else if (enter) {
+                RC_MARK("entry_begin");
+                float4 m0, m1, m2;
+                u4v m3;
                 if (INST_LDS) {
                     const float2* q = il + cur_inst;
                     const float2 p0 = q[0], p1 = q[kTlasLdsInst], p2 = q[2 * kTlasLdsInst], p3 = q[3 * kTlasLdsInst],
@@ -915,7 +923,6 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
                 oyz = v2f{o.y, o.z}; ozx = v2f{o.z, o.x}; dyz = v2f{d.y, d.z}; dzx = v2f{d.z, d.x};
                 inv = safe_inv3(d);
                 ox = mk3(-o.x * inv.x, -o.y * inv.y, -o.z * inv.z);
-                }
                 RC_MARK("entry_end");
             }
         }
