@@ -340,6 +340,30 @@ int rc_hit_points_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_
 int rc_shadow_rays_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float light[3],
                           float bias, rc_ray* d_shadow_rays, void* stream);
 
+/* Shadow visibility of all hits x all lights in ONE traversal launch: generate_shadow_rays! (docs/src/wavefront-renderer.jl:279-333,
+ * slot (idx-1)*NLights + light_idx) and test_shadow_rays! (:340-362) fused, producing the `visible` Bool that shade_primary_hits!
+ * reads (:395-416).  d_rays / d_hits: the closest-hit stage's n rays and hit records, slot i belongs to ray i as for
+ * rc_shadow_rays_device.  d_lights: a DEVICE array of n_lights x 3 f32 point-light positions, read when the KERNEL RUNS, not when the call
+ * is made (the convention of rc_update_transforms_device): a captured call follows lights that move between replays.
+ * d_visible: n x n_lights bytes; byte i * n_lights + l is the reference's shadow_result_queue[(idx-1)*NLights + light_idx].visible.
+ * Identity with the composed path, exact, no tolerance: d_visible[i * n_lights + l] == (d_hits[i].hit && !any_hit(shadow_ray(i, l)).hit),
+ * where shadow_ray(i, l) is bit for bit the ray rc_shadow_rays_device(..., light_l, bias, ...) writes for slot i (the same device
+ * function makes both) and any_hit is what rc_trace_any_device reports for it.  A slot whose primary ray missed gets 0 for every light
+ * and costs no traversal: its work item is the bounce stage's dead ray (t_max = -1, see rc_bounce_rays_device).
+ * One persistent any_hit launch over the n * n_lights (hit, light) items, item i * n_lights + l, so neighbouring lanes share a hit's
+ * records; the shadow rays are generated when a lane takes an item and are never stored: neither the L x n x 32 B of shadow rays nor the
+ * L x n x 32 B of any_hit records of the composed path exist.  The items are claimed in natural order (no batch recognition: the rays are
+ * generated); the entry cull follows rc_trace_any_device (off unless option "entry_cull" is 2).
+ * No allocation, copy, event or host synchronisation and no scene-owned scratch: re-entrant across streams like the other *_device
+ * queries, and captured on a capturing stream under the rules of the trace / driver launches (one capture slot; the stream must have run
+ * the call eagerly before).  A stack overflow is reported by rc_wait like any device launch's.  After an asynchronous refit / rebuild /
+ * geometry update on the same stream the call sees the new scene, like a trace.  n == 0 or n_lights == 0: succeeds, nothing is enqueued.
+ * Errors, before anything is enqueued: RC_ERR_INVALID_ARGUMENT (NULL scene; NULL d_rays, d_hits, d_lights or d_visible while there is
+ * work; n * n_lights >= 2^32), RC_ERR_NOT_SYNCED (never synced, or pending mutations / transform updates without their refit).
+ * Measured against the composed path (L x (rc_shadow_rays_device + rc_trace_any_device)) in docs/EXPERIMENTS.md, "Shadow visibility". */
+int rc_shadow_visibility_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float* d_lights,
+                                uint32_t n_lights, float bias, uint8_t* d_visible, void* stream);
+
 /* ---- BVH4 (src/bvh4.jl; exported by the reference as BVHNode4 / BLAS4 / build_blas4 / closest_hit4 / any_hit4).
  * BLAS-level only, as in the reference: rays are traced in the geometry's own space, no instances.
  * rc_bvh4_node = BVHNode4, 120 bytes (src/bvh4.jl:40-69): interior nodes hold 1-based BVH4 child indices, a leaf

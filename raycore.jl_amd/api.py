@@ -509,6 +509,14 @@ class TLAS:
         check(lib().rc_shadow_rays_device(self._h, ptr(d_rays), ptr(d_hits), int(n), ptr(lv), float(bias), ptr(d_shadow_rays),
                                           ptr(stream) if stream else None))
 
+    def shadow_visibility_device(self, d_rays, d_hits, n, d_lights, n_lights, d_visible, bias=0.01, stream=None):
+        """Shadow visibility of all hits x all lights in one traversal launch (rc_shadow_visibility_device; generate_shadow_rays! +
+        test_shadow_rays!, docs/src/wavefront-renderer.jl:279-362).  d_lights: device pointer to n_lights x 3 f32 positions, read when the
+        kernel runs; d_visible: device pointer to n * n_lights bytes, byte i * n_lights + l = hit i is lit by light l -- what
+        shadow_rays_device + trace_device(mode='any') per light give, without their buffers."""
+        check(lib().rc_shadow_visibility_device(self._h, ptr(d_rays), ptr(d_hits), int(n), ptr(d_lights), int(n_lights), float(bias),
+                                                ptr(d_visible), ptr(stream) if stream else None))
+
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib().rc_last_kernel_ms(self._h, C.byref(ms)))

@@ -1594,6 +1594,18 @@ int rc_shadow_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hit
     });
 }
 
+int rc_shadow_visibility_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float* d_lights, uint32_t n_lights, float bias,
+                                uint8_t* d_visible, void* stream) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (n && n_lights && (!d_rays || !d_hits || !d_lights || !d_visible)) return fail(RC_ERR_INVALID_ARGUMENT, "rc_shadow_visibility_device: NULL argument");
+    if (n_lights && n >= ((1ull << 32) + n_lights - 1) / n_lights) return fail(RC_ERR_INVALID_ARGUMENT, "rc_shadow_visibility_device: n * n_lights must be below 2^32");
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        rc_launch_shadow_visibility(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, d_lights, n_lights, bias, d_visible, (hipStream_t)stream);
+    });
+}
+
 int rc_bounce_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                           const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n_out, uint64_t seed, uint32_t bounce, float bias,
                           rc_ray* d_out, void* stream) {

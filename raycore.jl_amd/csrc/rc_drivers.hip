@@ -435,22 +435,78 @@ __global__ void k_hit_points(SceneView v, const RcRay* rays, const RcHit* hits, 
 // generate_shadow_rays! for one point light (:288-333): slot i of the output belongs to ray i; misses get the
 // reference's dummy ray (o = 0, d = (0,0,1), t_max = 0), hits a ray from hit_point + normal*bias toward the light with
 // t_max = distance, ready for rc_trace_any_device.
+// The shadow ray of one hit toward one light (:296-329): shared by the stage kernel and the fused visibility driver, so the two agree bit for bit.
+__device__ inline RcRay shadow_ray(const SceneView& v, const RcRay& r, const RcHit& h, const float3_ light, float bias) {
+    float3_ p, nn;
+    hit_frame(v, r, h, p, nn);
+    const float3_ o = add3(p, scale3(nn, bias));
+    const float3_ lv = sub3(light, o);
+    const float dist = __builtin_sqrtf(dot3(lv, lv));
+    return RcRay{o.x, o.y, o.z, 0.f, (lv.x / dist), (lv.y / dist), (lv.z / dist), dist};
+}
 __global__ void k_shadow_rays(SceneView v, const RcRay* rays, const RcHit* hits, uint64_t n, float lx, float ly, float lz, float bias, RcRay* out) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         RcRay s{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
         const RcHit h = hits[i];
-        if (h.hit) {
-            float3_ p, nn;
-            hit_frame(v, rays[i], h, p, nn);
-            const float3_ o = add3(p, scale3(nn, bias));
-            const float3_ lv = sub3(mk3(lx, ly, lz), o);
-            const float dist = __builtin_sqrtf(dot3(lv, lv));
-            s = RcRay{o.x, o.y, o.z, 0.f, (lv.x / dist), (lv.y / dist), (lv.z / dist), dist};
-        }
+        if (h.hit) s = shadow_ray(v, rays[i], h, mk3(lx, ly, lz), bias);
         float4* q = reinterpret_cast<float4*>(out + i);
         q[0] = make_float4(s.ox, s.oy, s.oz, s.tmin);
         q[1] = make_float4(s.dx, s.dy, s.dz, s.tmax);
     }
+}
+
+// generate_shadow_rays! + test_shadow_rays! for all hits x all lights (:279-362) fused on the persistent phased traversal core: work item
+// j = i * n_lights + l is hit i seen from light l (the reference's slot (idx-1)*NLights + light_idx), so neighbouring lanes share a hit's
+// records.  The shadow ray is made when a lane is refilled and never stored; a finished any_hit writes the one byte the shading reads.  An
+// item whose primary ray missed gets the bounce stage's dead ray (t_max = -1, misses everything) and the byte 0.
+struct ShadowSource {
+    const SceneView& v;
+    const RcRay* rays;
+    const RcHit* hits;
+    const float* lights;  // n_lights x 3, read here: a captured launch follows lights that move between replays
+    uint32_t n_lights;
+    float bias;
+    __device__ inline RcRay operator()(uint64_t j) const {
+        const uint32_t i = (uint32_t)j / n_lights, l = (uint32_t)j - i * n_lights;  // (n * n_lights < 2^32)
+        const RcHit h = hits[i];
+        if (!h.hit) return RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
+        const float* lp = lights + 3u * (size_t)l;
+        return shadow_ray(v, load_ray(rays, i), h, mk3(lp[0], lp[1], lp[2]), bias);
+    }
+    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
+};
+struct VisibilitySink {
+    const RcHit* hits;
+    uint32_t n_lights;
+    uint8_t* visible;
+    __device__ inline void operator()(uint64_t j, bool hit, float, float, float, uint32_t, int) const {
+        const uint32_t lit = hits[(uint32_t)j / n_lights].hit;  // a dead item's ray misses too: its byte is 0, not "visible"
+        visible[j] = (lit && !hit) ? 1u : 0u;
+    }
+};
+__global__ __launch_bounds__(kBlock, 6) void k_shadow_visibility(SceneView v, PersistArgs p, const RcRay* rays, const RcHit* hits, const float* lights, uint32_t n_lights,
+                                                                  float bias, uint8_t* visible) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    phased_trace<true, kLdsStack, false>(v, p, lds_stack, ShadowSource{v, rays, hits, lights, n_lights, bias}, VisibilitySink{hits, n_lights, visible});
+}
+__global__ __launch_bounds__(kMidBlock, 6) void k_shadow_visibility_lds(SceneView v, PersistArgs p, const RcRay* rays, const RcHit* hits, const float* lights,
+                                                                         uint32_t n_lights, float bias, uint8_t* visible) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const LdsTop top(smem + (size_t)kMidStack * kMidBlock * 4);
+    stage_lds_top<kMidBlock>(top, v, p.blas_k, p.lds_blas_base);
+    __syncthreads();
+    phased_trace<true, kMidStack, false, ShadowSource, VisibilitySink, kMidBlock, true, true>(v, p, reinterpret_cast<uint32_t*>(smem), ShadowSource{v, rays, hits, lights, n_lights, bias},
+                                                                                              VisibilitySink{hits, n_lights, visible}, top);
+}
+__global__ __launch_bounds__(kMidBlock, 6) void k_shadow_visibility_partial(SceneView v, PersistArgs p, const RcRay* rays, const RcHit* hits, const float* lights,
+                                                                             uint32_t n_lights, float bias, uint8_t* visible) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    LdsTop top;
+    top.tl = reinterpret_cast<float2*>(smem + (size_t)kMidStack * kMidBlock * 4);
+    stage_partial_top<kMidBlock>(top.tl, v, p.tlas_k, p.blas_k, p.lds_blas_base);
+    __syncthreads();
+    phased_trace<true, kMidStack, false, ShadowSource, VisibilitySink, kMidBlock, false, false, true>(v, p, reinterpret_cast<uint32_t*>(smem), ShadowSource{v, rays, hits, lights, n_lights, bias},
+                                                                                                      VisibilitySink{hits, n_lights, visible}, top);
 }
 
 // cosine_sample_hemisphere (src/math.jl:1-21, concentric disk) in the frame (bu, bv, n), combined as random_hemisphere_uniform does
@@ -841,6 +897,41 @@ void rc_launch_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits
     hipLaunchKernelGGL(k_shadow_rays, dim3(blocks), dim3(256), 0, stream, rc_scene_view_static(s), d_rays, d_hits, n, light[0], light[1], light[2], bias, d_out);
     RC_HIP(hipGetLastError());
     rc_note_stage_launch(s, stream);
+}
+
+// One persistent any_hit launch over the n * n_lights (hit, light) items (ShadowSource / VisibilitySink); natural claim order -- the rays are
+// generated, there is no batch to recognise.  n * n_lights < 2^32 (checked by the caller).
+void rc_launch_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, uint32_t n_lights, float bias,
+                                 uint8_t* d_visible, hipStream_t stream) {
+    const uint64_t total = n * n_lights;
+    if (total == 0) return;
+    check_buffer_range(s);
+    RcLaunchGuard launch(s, stream);
+    const bool partial = rc_partial_driver_ok(s);
+    const bool lds = partial || rc_lds_driver_ok(s);
+    const uint32_t bs = lds ? (uint32_t)kMidBlock : (uint32_t)kBlock;
+    const uint32_t blocks = lds ? rc_lds_driver_blocks(s, total) : rc_persistent_blocks(s, total);
+    SceneView v = rc_scene_view(s, blocks * bs);
+    if (s->opt.entry_cull < 2) v.entry_cull = 0u;  // any_hit: the rule of rc_launch_trace
+    PersistArgs p = rc_persist_args(s, total, blocks * bs);
+    launch.start();
+    if (partial) {
+        rc_partial_driver_args(s, p);
+        if (!s->lds_attr_set[17]) {
+            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shadow_visibility_partial), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartialLdsBytes));
+            s->lds_attr_set[17] = true;
+        }
+        hipLaunchKernelGGL(k_shadow_visibility_partial, dim3(blocks), dim3(kMidBlock), kPartialLdsBytes, stream, v, p, d_rays, d_hits, d_lights, n_lights, bias, d_visible);
+    } else if (lds) {
+        rc_lds_driver_args(s, p);
+        if (!s->lds_attr_set[16]) {
+            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shadow_visibility_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes));
+            s->lds_attr_set[16] = true;
+        }
+        hipLaunchKernelGGL(k_shadow_visibility_lds, dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, v, p, d_rays, d_hits, d_lights, n_lights, bias, d_visible);
+    } else
+    hipLaunchKernelGGL(k_shadow_visibility, dim3(blocks), dim3(kBlock), 0, stream, v, p, d_rays, d_hits, d_lights, n_lights, bias, d_visible);
+    launch.finish();
 }
 
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,

@@ -423,6 +423,12 @@ shadow_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitRe
                     bias::Float32 = 0.01f0, stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_shadow_rays_device, LIB), Cint, (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, Ptr{Float32}, Cfloat, Ptr{RTRay}, Ptr{Cvoid}),
                 a.owner.ptr, d_rays, d_hits, n, Float32[light...], bias, d_out, stream))
+"Shadow visibility of all hits x all lights in one traversal launch: byte `i * n_lights + l` (0-based) of `d_visible` = hit `i` is lit by light `l`; `d_lights` is a device array of n_lights x 3 Float32, read when the kernel runs."
+shadow_visibility_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n::Integer, d_lights::Ptr{Float32},
+                          n_lights::Integer, d_visible::Ptr{UInt8}; bias::Float32 = 0.01f0, stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_shadow_visibility_device, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, Ptr{Float32}, UInt32, Cfloat, Ptr{UInt8}, Ptr{Cvoid}),
+                a.owner.ptr, d_rays, d_hits, n, d_lights, n_lights, bias, d_visible, stream))
 "Diffuse (cosine-weighted) bounce rays: slot-aligned, or gathered through `d_src` / `d_src_count` (a device count; `wrap` = round robin)."
 bounce_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n_out::Integer, d_out::Ptr{RTRay};
                     seed::UInt64 = UInt64(0), bounce::Integer = 0, bias::Float32 = 1f-3, d_src::Ptr{UInt32} = Ptr{UInt32}(C_NULL),

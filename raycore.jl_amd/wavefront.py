@@ -53,21 +53,39 @@ class WavefrontPaths:
 
     deform: a list of (handle, soup tensor) pairs -- float32 (n, 9) or (n, 3, 3) on the accel's device.  Every frame then starts with
     update_geometry_device_async for each pair, before the `dynamic` transform updates and the refit (or rebuild) that ends the head of
-    the frame; `deform` without `dynamic` still ends it with a refit.  A soup must keep its number of non-degenerate faces."""
+    the frame; `deform` without `dynamic` still ends it with a refit.  A soup must keep its number of non-degenerate faces.
 
-    def __init__(self, accel, width, height, samples, depth, camera, light, seed=0, bias=1e-3, compact=True, dynamic=None, rebuild=False,
-                 deform=None):
-        import torch
+    lights + fused_shadows=True: several point lights tested in one launch per depth.  `lights` is a float32 (L, 3) tensor on the accel's
+    device (or an array, uploaded once into self.lights); each depth then runs one shadow_visibility_device into visible[b], a uint8 tensor
+    of n * L bytes (byte i * L + l: slot i of hits[b] is lit by light l), and shadow_rays[b] / shadow_hits[b] do not exist (empty lists).
+    The lights are read when the frame runs: in-place edits of the tensor show up in the next run() or replay().  `light` is not used then."""
+
+    def __init__(self, accel, width, height, samples, depth, camera, light=None, seed=0, bias=1e-3, compact=True, dynamic=None, rebuild=False,
+                 deform=None, lights=None, fused_shadows=False):
         if depth < 1:
             raise ValueError("depth must be at least 1")
         if rebuild and not dynamic:
             raise ValueError("rebuild=True needs dynamic: the rebuild follows the transform updates at the head of the frame")
+        self.fused_shadows = bool(fused_shadows)
+        if lights is not None and not self.fused_shadows:
+            raise ValueError("lights= needs fused_shadows=True: the composed stages trace one `light`")
+        if self.fused_shadows and lights is None:
+            raise ValueError("fused_shadows=True needs lights=: a float32 (L, 3) tensor or array of point-light positions")
+        if not self.fused_shadows and light is None:
+            raise ValueError("light is required (or lights= with fused_shadows=True)")
+        if self.fused_shadows:
+            shape = tuple(lights.shape) if hasattr(lights, "shape") else np.asarray(lights).shape
+            if len(shape) != 2 or shape[1] != 3 or shape[0] < 1:
+                raise ValueError("lights must have shape (L, 3) with L >= 1")
+            if int(width) * int(height) * int(samples) * shape[0] >= 2 ** 32:
+                raise ValueError("width * height * samples * L must be below 2^32")
+        import torch
         self.accel, self.width, self.height, self.samples, self.depth = accel, int(width), int(height), int(samples), int(depth)
         self.n = self.width * self.height * self.samples
         if self.n == 0 or self.n >= 2 ** 31:
             raise ValueError("width * height * samples must be in [1, 2^31)")
         self.camera = {k: (np.asarray(v, np.float32) if k in ("pos", "right", "up", "forward") else float(v)) for k, v in camera.items()}
-        self.light = np.ascontiguousarray(light, dtype=np.float32)
+        self.light = None if light is None else np.ascontiguousarray(light, dtype=np.float32)
         self.seed, self.bias, self.compact = int(seed), float(bias), bool(compact)
         self.dynamic = list(dynamic) if dynamic else []
         self.rebuild = bool(rebuild)
@@ -76,8 +94,18 @@ class WavefrontPaths:
         rec = lambda: torch.zeros(self.n * 32, dtype=torch.uint8, device=dev)  # noqa: E731
         self.rays = [rec() for _ in range(depth)]
         self.hits = [rec() for _ in range(depth)]
-        self.shadow_rays = [rec() for _ in range(depth)]
-        self.shadow_hits = [rec() for _ in range(depth)]
+        self.lights, self.n_lights, self.visible = None, 0, []
+        if self.fused_shadows:
+            if isinstance(lights, torch.Tensor):
+                if lights.dtype != torch.float32 or lights.device != dev or not lights.is_contiguous():
+                    raise ValueError("lights must be a contiguous float32 tensor on the accel's device")
+                self.lights = lights
+            else:
+                self.lights = torch.from_numpy(np.ascontiguousarray(lights, dtype=np.float32)).to(dev)
+            self.n_lights = int(self.lights.shape[0])
+            self.visible = [torch.zeros(self.n * self.n_lights, dtype=torch.uint8, device=dev) for _ in range(depth)]
+        self.shadow_rays = [] if self.fused_shadows else [rec() for _ in range(depth)]
+        self.shadow_hits = [] if self.fused_shadows else [rec() for _ in range(depth)]
         self.path_ids = [torch.arange(self.n, dtype=torch.int32, device=dev)] + [
             torch.full((self.n,), -1, dtype=torch.int32, device=dev) for _ in range(depth - 1)]
         self.indices = torch.zeros(self.n, dtype=torch.int32, device=dev)
@@ -89,7 +117,8 @@ class WavefrontPaths:
         self._graph_stream = None
 
     def buffers(self):
-        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic] + [t for _, t in self.deform]
+        fused = self.visible + [self.lights] if self.fused_shadows else []
+        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + fused + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic] + [t for _, t in self.deform]
 
     def run(self, stream=None):
         """Enqueue one frame on `stream` (a torch.cuda.Stream; None = the current stream).  No host synchronisation.  The first frame on
@@ -114,9 +143,13 @@ class WavefrontPaths:
                                      self.rays[0].data_ptr(), samples=self.samples, seed=self.seed, jitter=True, stream=st)
         a.trace_device(self.rays[0].data_ptr(), self.hits[0].data_ptr(), n, stream=st)
         for b in range(self.depth):
-            a.shadow_rays_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.light, self.shadow_rays[b].data_ptr(),
-                                 bias=self.bias, stream=st)
-            a.trace_device(self.shadow_rays[b].data_ptr(), self.shadow_hits[b].data_ptr(), n, mode="any", stream=st)
+            if self.fused_shadows:
+                a.shadow_visibility_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.lights.data_ptr(), self.n_lights,
+                                           self.visible[b].data_ptr(), bias=self.bias, stream=st)
+            else:
+                a.shadow_rays_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.light, self.shadow_rays[b].data_ptr(),
+                                     bias=self.bias, stream=st)
+                a.trace_device(self.shadow_rays[b].data_ptr(), self.shadow_hits[b].data_ptr(), n, mode="any", stream=st)
             if b + 1 >= self.depth:
                 break
             src = cnt = None
@@ -149,8 +182,8 @@ class WavefrontPaths:
 
     def traced_rays(self):
         """Ray slots one frame traces: per depth one closest-hit pass (primary or bounce) and one any-hit pass (shadow) over every slot,
-        dead ones included."""
-        return self.n * 2 * self.depth
+        dead ones included -- with fused_shadows one any-hit item per slot and light."""
+        return self.n * (1 + (self.n_lights if self.fused_shadows else 1)) * self.depth
 
 
 def c4_bounce_rays_device(accel, d_rays, d_hits, n_primary, n_rays, d_out, seed=0xC4, stream=None):
