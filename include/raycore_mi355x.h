@@ -346,10 +346,15 @@ int rc_shadow_rays_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d
  * rc_shadow_rays_device.  d_lights: a DEVICE array of n_lights x 3 f32 point-light positions, read when the KERNEL RUNS, not when the call
  * is made (the convention of rc_update_transforms_device): a captured call follows lights that move between replays.
  * d_visible: n x n_lights bytes; byte i * n_lights + l is the reference's shadow_result_queue[(idx-1)*NLights + light_idx].visible.
- * Identity with the composed path, exact, no tolerance: d_visible[i * n_lights + l] == (d_hits[i].hit && !any_hit(shadow_ray(i, l)).hit),
+ * Identity with the composed path, exact, no tolerance:
+ * d_visible[i * n_lights + l] == (d_hits[i].hit && shadow_ray(i, l).t_max > 0 && !any_hit(shadow_ray(i, l)).hit),
  * where shadow_ray(i, l) is bit for bit the ray rc_shadow_rays_device(..., light_l, bias, ...) writes for slot i (the same device
- * function makes both) and any_hit is what rc_trace_any_device reports for it.  A slot whose primary ray missed gets 0 for every light
- * and costs no traversal: its work item is the bounce stage's dead ray (t_max = -1, see rc_bounce_rays_device).
+ * function makes both) and any_hit is what rc_trace_any_device reports for it.  The middle term is the reference's gate
+ * (`ray.t_max > 0 ? !any_hit(...) : false`, :353-358): a shadow ray whose t_max is 0 (the light sits on the shadow origin) or NaN (a hit
+ * with NaN t, or a NaN normal out of a singular instance transform) is not visible, whatever an any_hit of it would report.  The composed
+ * path's caller holds the shadow rays and applies the gate there; here the ray is never stored, so the kernel does.  A slot whose primary
+ * ray missed gets 0 for every light; it and a gated item cost no traversal: their work item is the bounce stage's dead ray (t_max = -1,
+ * see rc_bounce_rays_device).
  * One persistent any_hit launch over the n * n_lights (hit, light) items, item i * n_lights + l, so neighbouring lanes share a hit's
  * records; the shadow rays are generated when a lane takes an item and are never stored: neither the L x n x 32 B of shadow rays nor the
  * L x n x 32 B of any_hit records of the composed path exist.  The items are claimed in natural order (no batch recognition: the rays are

@@ -513,7 +513,8 @@ class TLAS:
         """Shadow visibility of all hits x all lights in one traversal launch (rc_shadow_visibility_device; generate_shadow_rays! +
         test_shadow_rays!, docs/src/wavefront-renderer.jl:279-362).  d_lights: device pointer to n_lights x 3 f32 positions, read when the
         kernel runs; d_visible: device pointer to n * n_lights bytes, byte i * n_lights + l = hit i is lit by light l -- what
-        shadow_rays_device + trace_device(mode='any') per light give, without their buffers."""
+        shadow_rays_device + trace_device(mode='any') per light give, without their buffers, under the reference's gate: a shadow ray
+        whose t_max is not > 0 (0 or NaN) is not visible."""
         check(lib().rc_shadow_visibility_device(self._h, ptr(d_rays), ptr(d_hits), int(n), ptr(d_lights), int(n_lights), float(bias),
                                                 ptr(d_visible), ptr(stream) if stream else None))
 

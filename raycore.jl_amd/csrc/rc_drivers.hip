@@ -457,8 +457,10 @@ __global__ void k_shadow_rays(SceneView v, const RcRay* rays, const RcHit* hits,
 
 // generate_shadow_rays! + test_shadow_rays! for all hits x all lights (:279-362) fused on the persistent phased traversal core: work item
 // j = i * n_lights + l is hit i seen from light l (the reference's slot (idx-1)*NLights + light_idx), so neighbouring lanes share a hit's
-// records.  The shadow ray is made when a lane is refilled and never stored; a finished any_hit writes the one byte the shading reads.  An
-// item whose primary ray missed gets the bounce stage's dead ray (t_max = -1, misses everything) and the byte 0.
+// records.  The shadow ray is made when a lane is refilled and never stored; a finished any_hit writes the one byte the shading reads.
+// test_shadow_rays! (:353-358) is `ray.t_max > 0 ? !any_hit(...) : false`: an item whose primary ray missed, or whose shadow ray has a t_max
+// that is not > 0 (0: the light sits on the shadow origin; NaN: a NaN t or normal out of a singular instance), gets the bounce stage's dead
+// ray (t_max = -1, misses everything, costs no traversal) and the byte 0.  The ray is never stored, so only the kernel can apply that gate.
 struct ShadowSource {
     const SceneView& v;
     const RcRay* rays;
@@ -471,23 +473,23 @@ struct ShadowSource {
         const RcHit h = hits[i];
         if (!h.hit) return RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
         const float* lp = lights + 3u * (size_t)l;
-        return shadow_ray(v, load_ray(rays, i), h, mk3(lp[0], lp[1], lp[2]), bias);
+        const RcRay s = shadow_ray(v, load_ray(rays, i), h, mk3(lp[0], lp[1], lp[2]), bias);
+        return s.tmax > 0.0f ? s : RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
     }
     static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
 };
 struct VisibilitySink {
-    const RcHit* hits;
-    uint32_t n_lights;
     uint8_t* visible;
-    __device__ inline void operator()(uint64_t j, bool hit, float, float, float, uint32_t, int) const {
-        const uint32_t lit = hits[(uint32_t)j / n_lights].hit;  // a dead item's ray misses too: its byte is 0, not "visible"
-        visible[j] = (lit && !hit) ? 1u : 0u;
+    // A ray that missed comes back with the t_max it went in with (the core's closest_t starts there and only an accepted hit lowers it):
+    // > 0 for a live shadow ray, -1 for a dead item -- whose byte is 0, not "visible" -- and 0 from the empty-scene path.
+    __device__ inline void operator()(uint64_t j, bool hit, float t, float, float, uint32_t, int) const {
+        visible[j] = (!hit && t > 0.0f) ? 1u : 0u;
     }
 };
 __global__ __launch_bounds__(kBlock, 6) void k_shadow_visibility(SceneView v, PersistArgs p, const RcRay* rays, const RcHit* hits, const float* lights, uint32_t n_lights,
                                                                   float bias, uint8_t* visible) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    phased_trace<true, kLdsStack, false>(v, p, lds_stack, ShadowSource{v, rays, hits, lights, n_lights, bias}, VisibilitySink{hits, n_lights, visible});
+    phased_trace<true, kLdsStack, false>(v, p, lds_stack, ShadowSource{v, rays, hits, lights, n_lights, bias}, VisibilitySink{visible});
 }
 __global__ __launch_bounds__(kMidBlock, 6) void k_shadow_visibility_lds(SceneView v, PersistArgs p, const RcRay* rays, const RcHit* hits, const float* lights,
                                                                          uint32_t n_lights, float bias, uint8_t* visible) {
@@ -496,7 +498,7 @@ __global__ __launch_bounds__(kMidBlock, 6) void k_shadow_visibility_lds(SceneVie
     stage_lds_top<kMidBlock>(top, v, p.blas_k, p.lds_blas_base);
     __syncthreads();
     phased_trace<true, kMidStack, false, ShadowSource, VisibilitySink, kMidBlock, true, true>(v, p, reinterpret_cast<uint32_t*>(smem), ShadowSource{v, rays, hits, lights, n_lights, bias},
-                                                                                              VisibilitySink{hits, n_lights, visible}, top);
+                                                                                              VisibilitySink{visible}, top);
 }
 __global__ __launch_bounds__(kMidBlock, 6) void k_shadow_visibility_partial(SceneView v, PersistArgs p, const RcRay* rays, const RcHit* hits, const float* lights,
                                                                              uint32_t n_lights, float bias, uint8_t* visible) {
@@ -506,7 +508,7 @@ __global__ __launch_bounds__(kMidBlock, 6) void k_shadow_visibility_partial(Scen
     stage_partial_top<kMidBlock>(top.tl, v, p.tlas_k, p.blas_k, p.lds_blas_base);
     __syncthreads();
     phased_trace<true, kMidStack, false, ShadowSource, VisibilitySink, kMidBlock, false, false, true>(v, p, reinterpret_cast<uint32_t*>(smem), ShadowSource{v, rays, hits, lights, n_lights, bias},
-                                                                                                      VisibilitySink{hits, n_lights, visible}, top);
+                                                                                                      VisibilitySink{visible}, top);
 }
 
 // cosine_sample_hemisphere (src/math.jl:1-21, concentric disk) in the frame (bu, bv, n), combined as random_hemisphere_uniform does

@@ -40,13 +40,16 @@ def lights_tensor(lights):
 
 
 def oracle_visibility(o, rays, lights):
-    """(primary hits, visible[n, L]) from the oracle alone: trace, then per light shadow_rays and any_hit."""
+    """(primary hits, visible[n, L]) from the oracle alone: trace, then per light shadow_rays, the reference's t_max > 0 gate and any_hit.
+    On these clean worlds every hit's shadow ray passes the gate (tests/test_gpu_stage_fuzz.py has the scenes where it does not)."""
     want = o.trace(rays, nthreads=16)
     lit = want["hit"] == 1
     vis = np.zeros((len(rays), len(lights)), np.uint8)
     for l, light in enumerate(lights):
-        shadow = o.trace(o.shadow_rays(rays, want, light, BIAS), mode="any", nthreads=16)
-        vis[:, l] = lit & (shadow["hit"] == 0)
+        shadow_rays = o.shadow_rays(rays, want, light, BIAS)
+        assert np.all(shadow_rays["tmax"][lit] > 0), f"light {l}: a hit slot's shadow ray has a t_max that is not > 0"
+        shadow = o.trace(shadow_rays, mode="any", nthreads=16)
+        vis[:, l] = lit & (shadow_rays["tmax"] > 0) & (shadow["hit"] == 0)
     return want, vis
 
 
