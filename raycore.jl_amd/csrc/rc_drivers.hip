@@ -136,29 +136,41 @@ __global__ void k_illumination_fold(const uint32_t* scratch, uint32_t n8, uint32
         seen = prev;
     }
 }
-__global__ __launch_bounds__(kBlock, 6) void k_illumination(SceneView v, PersistArgs p, GridParams g, uint64_t ray_begin, uint32_t* scratch, uint32_t n8) {
+// A driver job is the kernel argument of the three shells below: a trivially copyable struct of the job's own parameters that makes the
+// Source and the Sink next to the kernel's SceneView.
+struct IlluminationJob {
+    GridParams g;
+    uint64_t ray_begin;
+    uint32_t* scratch;
+    uint32_t n8;
+    __device__ inline GridSource source(const SceneView&) const { return GridSource{g, ray_begin}; }
+    __device__ inline HistogramSink sink(const SceneView& v) const { return HistogramSink{v.inst, v.prims, v.n_prims, scratch, n8}; }
+};
+// The three shapes every driver runs in (DriverLaunch picks one): they differ in what sits in LDS when phased_trace starts.
+template <bool ANY, class Job>
+__global__ __launch_bounds__(kBlock, 6) void k_driver(SceneView v, PersistArgs p, Job j) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    phased_trace<false, kLdsStack, false>(v, p, lds_stack, GridSource{g, ray_begin}, HistogramSink{v.inst, v.prims, v.n_prims, scratch, n8});
+    phased_trace<ANY, kLdsStack, false>(v, p, lds_stack, j.source(v), j.sink(v));
 }
 // Small top level (<= kTlasLdsNodes nodes): the shape of trace kernel 5 -- two 768-thread workgroups per CU, TLAS (and a single BLAS's
 // top nodes) in LDS planes.
-__global__ __launch_bounds__(kMidBlock, 6) void k_illumination_lds(SceneView v, PersistArgs p, GridParams g, uint64_t ray_begin, uint32_t* scratch, uint32_t n8) {
+template <bool ANY, class Job>
+__global__ __launch_bounds__(kMidBlock, 6) void k_driver_lds(SceneView v, PersistArgs p, Job j) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const LdsTop top(smem + (size_t)kMidStack * kMidBlock * 4);
     stage_lds_top<kMidBlock>(top, v, p.blas_k, p.lds_blas_base);
     __syncthreads();
-    phased_trace<false, kMidStack, false, GridSource, HistogramSink, kMidBlock, true, true>(v, p, reinterpret_cast<uint32_t*>(smem), GridSource{g, ray_begin},
-                                                                                            HistogramSink{v.inst, v.prims, v.n_prims, scratch, n8}, top);
+    phased_trace<ANY, kMidStack, false, decltype(j.source(v)), decltype(j.sink(v)), kMidBlock, true, true>(v, p, reinterpret_cast<uint32_t*>(smem), j.source(v), j.sink(v), top);
 }
 // Larger top levels (the shape of trace kernel 6): only the breadth-first tops of the TLAS and of a single BLAS are staged.
-__global__ __launch_bounds__(kMidBlock, 6) void k_illumination_partial(SceneView v, PersistArgs p, GridParams g, uint64_t ray_begin, uint32_t* scratch, uint32_t n8) {
+template <bool ANY, class Job>
+__global__ __launch_bounds__(kMidBlock, 6) void k_driver_partial(SceneView v, PersistArgs p, Job j) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     LdsTop top;
     top.tl = reinterpret_cast<float2*>(smem + (size_t)kMidStack * kMidBlock * 4);
     stage_partial_top<kMidBlock>(top.tl, v, p.tlas_k, p.blas_k, p.lds_blas_base);
     __syncthreads();
-    phased_trace<false, kMidStack, false, GridSource, HistogramSink, kMidBlock, false, false, true>(v, p, reinterpret_cast<uint32_t*>(smem), GridSource{g, ray_begin},
-                                                                                                     HistogramSink{v.inst, v.prims, v.n_prims, scratch, n8}, top);
+    phased_trace<ANY, kMidStack, false, decltype(j.source(v)), decltype(j.sink(v)), kMidBlock, false, false, true>(v, p, reinterpret_cast<uint32_t*>(smem), j.source(v), j.sink(v), top);
 }
 
 // ---- Philox4x32-10 (Salmon et al., SC'11) ---------------------------------------------------------------
@@ -339,63 +351,25 @@ __global__ void k_vf_totals_fold(const unsigned long long* scratch, uint32_t n8,
     for (uint32_t c = 0; c < kTotalsCopies; ++c) sum += scratch[(size_t)c * 8u * n8 + (j & 7u) * n8 + (j >> 3)];
     if (sum) atomicAdd(received + j, sum);  // (ACCUMULATES; atomic, so that shards traced concurrently on several streams may share one vector -- ADVICE r4)
 }
-__global__ __launch_bounds__(kBlock, 6) void k_vf_totals(SceneView v, PersistArgs p, uint32_t k0, uint32_t k1, uint32_t src_begin, uint32_t ray_begin,
-                                                          uint32_t n_ray, unsigned long long* received, uint32_t n8, unsigned long long* emitted) {
-    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    phased_trace<false, kLdsStack, false>(v, p, lds_stack, ViewFactorSource{v.prims, nullptr, k0, k1, src_begin, ray_begin, n_ray},
-                                          ViewFactorTotalsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, received, n8, emitted});
-}
-__global__ __launch_bounds__(kMidBlock, 6) void k_vf_totals_lds(SceneView v, PersistArgs p, uint32_t k0, uint32_t k1, uint32_t src_begin, uint32_t ray_begin,
-                                                                 uint32_t n_ray, unsigned long long* received, uint32_t n8, unsigned long long* emitted) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LdsTop top(smem + (size_t)kMidStack * kMidBlock * 4);
-    stage_lds_top<kMidBlock>(top, v, p.blas_k, p.lds_blas_base);
-    __syncthreads();
-    phased_trace<false, kMidStack, false, ViewFactorSource, ViewFactorTotalsSink, kMidBlock, true, true>(
-        v, p, reinterpret_cast<uint32_t*>(smem), ViewFactorSource{v.prims, nullptr, k0, k1, src_begin, ray_begin, n_ray},
-        ViewFactorTotalsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, received, n8, emitted}, top);
-}
-__global__ __launch_bounds__(kMidBlock, 6) void k_vf_totals_partial(SceneView v, PersistArgs p, uint32_t k0, uint32_t k1, uint32_t src_begin, uint32_t ray_begin,
-                                                                     uint32_t n_ray, unsigned long long* received, uint32_t n8, unsigned long long* emitted) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    LdsTop top;
-    top.tl = reinterpret_cast<float2*>(smem + (size_t)kMidStack * kMidBlock * 4);
-    stage_partial_top<kMidBlock>(top.tl, v, p.tlas_k, p.blas_k, p.lds_blas_base);
-    __syncthreads();
-    phased_trace<false, kMidStack, false, ViewFactorSource, ViewFactorTotalsSink, kMidBlock, false, false, true>(
-        v, p, reinterpret_cast<uint32_t*>(smem), ViewFactorSource{v.prims, nullptr, k0, k1, src_begin, ray_begin, n_ray},
-        ViewFactorTotalsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, received, n8, emitted}, top);
-}
-__global__ __launch_bounds__(kBlock, 6) void k_view_factors(SceneView v, PersistArgs p, uint32_t k0, uint32_t k1, uint32_t src_begin,
-                                                             uint32_t ray_begin, uint32_t n_ray, uint32_t* matrix, uint64_t row_stride,
-                                                             uint64_t col_stride, uint32_t row_offset, uint32_t flags, const uint32_t* order) {
-    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    phased_trace<false, kLdsStack, false>(v, p, lds_stack, ViewFactorSource{v.prims, order, k0, k1, src_begin, ray_begin, n_ray},
-                                          ViewFactorSink{v.inst, v.prims, order, v.n_prims, src_begin, n_ray, matrix, row_stride, col_stride, row_offset, flags});
-}
-__global__ __launch_bounds__(kMidBlock, 6) void k_view_factors_lds(SceneView v, PersistArgs p, uint32_t k0, uint32_t k1, uint32_t src_begin,
-                                                                    uint32_t ray_begin, uint32_t n_ray, uint32_t* matrix, uint64_t row_stride,
-                                                                    uint64_t col_stride, uint32_t row_offset, uint32_t flags, const uint32_t* order) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LdsTop top(smem + (size_t)kMidStack * kMidBlock * 4);
-    stage_lds_top<kMidBlock>(top, v, p.blas_k, p.lds_blas_base);
-    __syncthreads();
-    phased_trace<false, kMidStack, false, ViewFactorSource, ViewFactorSink, kMidBlock, true, true>(
-        v, p, reinterpret_cast<uint32_t*>(smem), ViewFactorSource{v.prims, order, k0, k1, src_begin, ray_begin, n_ray},
-        ViewFactorSink{v.inst, v.prims, order, v.n_prims, src_begin, n_ray, matrix, row_stride, col_stride, row_offset, flags}, top);
-}
-__global__ __launch_bounds__(kMidBlock, 6) void k_view_factors_partial(SceneView v, PersistArgs p, uint32_t k0, uint32_t k1, uint32_t src_begin,
-                                                                        uint32_t ray_begin, uint32_t n_ray, uint32_t* matrix, uint64_t row_stride,
-                                                                        uint64_t col_stride, uint32_t row_offset, uint32_t flags, const uint32_t* order) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    LdsTop top;
-    top.tl = reinterpret_cast<float2*>(smem + (size_t)kMidStack * kMidBlock * 4);
-    stage_partial_top<kMidBlock>(top.tl, v, p.tlas_k, p.blas_k, p.lds_blas_base);
-    __syncthreads();
-    phased_trace<false, kMidStack, false, ViewFactorSource, ViewFactorSink, kMidBlock, false, false, true>(
-        v, p, reinterpret_cast<uint32_t*>(smem), ViewFactorSource{v.prims, order, k0, k1, src_begin, ray_begin, n_ray},
-        ViewFactorSink{v.inst, v.prims, order, v.n_prims, src_begin, n_ray, matrix, row_stride, col_stride, row_offset, flags}, top);
-}
+struct ViewFactorTotalsJob {
+    uint32_t k0, k1, src_begin, ray_begin, n_ray;
+    unsigned long long* received;
+    uint32_t n8;
+    unsigned long long* emitted;
+    __device__ inline ViewFactorSource source(const SceneView& v) const { return ViewFactorSource{v.prims, nullptr, k0, k1, src_begin, ray_begin, n_ray}; }
+    __device__ inline ViewFactorTotalsSink sink(const SceneView& v) const { return ViewFactorTotalsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, received, n8, emitted}; }
+};
+struct ViewFactorJob {
+    uint32_t k0, k1, src_begin, ray_begin, n_ray;
+    uint32_t* matrix;
+    uint64_t row_stride, col_stride;
+    uint32_t row_offset, flags;
+    const uint32_t* order;
+    __device__ inline ViewFactorSource source(const SceneView& v) const { return ViewFactorSource{v.prims, order, k0, k1, src_begin, ray_begin, n_ray}; }
+    __device__ inline ViewFactorSink sink(const SceneView& v) const {
+        return ViewFactorSink{v.inst, v.prims, order, v.n_prims, src_begin, n_ray, matrix, row_stride, col_stride, row_offset, flags};
+    }
+};
 
 __global__ void k_meta_keys(const RcPrim* prims, uint32_t n, uint32_t* keys, uint32_t* vals) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -486,30 +460,17 @@ struct VisibilitySink {
         visible[j] = (!hit && t > 0.0f) ? 1u : 0u;
     }
 };
-__global__ __launch_bounds__(kBlock, 6) void k_shadow_visibility(SceneView v, PersistArgs p, const RcRay* rays, const RcHit* hits, const float* lights, uint32_t n_lights,
-                                                                  float bias, uint8_t* visible) {
-    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    phased_trace<true, kLdsStack, false>(v, p, lds_stack, ShadowSource{v, rays, hits, lights, n_lights, bias}, VisibilitySink{visible});
-}
-__global__ __launch_bounds__(kMidBlock, 6) void k_shadow_visibility_lds(SceneView v, PersistArgs p, const RcRay* rays, const RcHit* hits, const float* lights,
-                                                                         uint32_t n_lights, float bias, uint8_t* visible) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LdsTop top(smem + (size_t)kMidStack * kMidBlock * 4);
-    stage_lds_top<kMidBlock>(top, v, p.blas_k, p.lds_blas_base);
-    __syncthreads();
-    phased_trace<true, kMidStack, false, ShadowSource, VisibilitySink, kMidBlock, true, true>(v, p, reinterpret_cast<uint32_t*>(smem), ShadowSource{v, rays, hits, lights, n_lights, bias},
-                                                                                              VisibilitySink{visible}, top);
-}
-__global__ __launch_bounds__(kMidBlock, 6) void k_shadow_visibility_partial(SceneView v, PersistArgs p, const RcRay* rays, const RcHit* hits, const float* lights,
-                                                                             uint32_t n_lights, float bias, uint8_t* visible) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    LdsTop top;
-    top.tl = reinterpret_cast<float2*>(smem + (size_t)kMidStack * kMidBlock * 4);
-    stage_partial_top<kMidBlock>(top.tl, v, p.tlas_k, p.blas_k, p.lds_blas_base);
-    __syncthreads();
-    phased_trace<true, kMidStack, false, ShadowSource, VisibilitySink, kMidBlock, false, false, true>(v, p, reinterpret_cast<uint32_t*>(smem), ShadowSource{v, rays, hits, lights, n_lights, bias},
-                                                                                                      VisibilitySink{visible}, top);
-}
+// The job's kernel argument (k_driver*): today's parameters in their order, and the Source / Sink they become next to the kernel's SceneView.
+struct ShadowJob {
+    const RcRay* rays;
+    const RcHit* hits;
+    const float* lights;
+    uint32_t n_lights;
+    float bias;
+    uint8_t* visible;
+    __device__ inline ShadowSource source(const SceneView& v) const { return ShadowSource{v, rays, hits, lights, n_lights, bias}; }  // (v: the kernel's own by-value parameter)
+    __device__ inline VisibilitySink sink(const SceneView&) const { return VisibilitySink{visible}; }
+};
 
 // cosine_sample_hemisphere (src/math.jl:1-21, concentric disk) in the frame (bu, bv, n), combined as random_hemisphere_uniform does
 // (u*x + v*y + n*z, not renormalised).  pi is Float32(pi); cos / sin of theta in [-pi/4, 3pi/4] through sincos_f64, rounded once.
@@ -667,7 +628,71 @@ static void check_buffer_range(rc_scene* s) {
         throw RcError(1, "driver kernels address nodes with 32-bit buffer offsets: scenes above 64 M nodes are not supported yet");
 }
 
-static unsigned long long* rc_totals_scratch(rc_scene* s, hipStream_t stream, bool capturing, size_t words);  // (below) per-stream scratch counters of the drivers
+// Scratch counters of a totals launch (launch_mu held): launches on one stream are ordered and share an area; another stream gets its own (up to
+// 16: then an idle stream's area is taken over, else the oldest stream is waited for); a CAPTURED launch owns its area like its spill region.
+static unsigned long long* rc_totals_scratch(rc_scene* s, hipStream_t stream, bool capturing, size_t words) {
+    if (words == 0) words = 1;
+    if (capturing) {  // (inside an RcLaunchGuard that took a capture slot)
+        auto& owned = s->capture_slots[s->cur_capture].scratch;
+        owned.emplace_back(new DevBuf<unsigned long long>());
+        owned.back()->reserve(words);
+        return owned.back()->p;
+    }
+    size_t idx = 0;
+    for (; idx < s->totals_scratch.size(); ++idx) if (s->totals_scratch[idx].stream == stream) break;
+    if (idx == s->totals_scratch.size()) {
+        if (s->totals_scratch.size() < 16) {
+            s->totals_scratch.emplace_back();
+            s->totals_scratch.back().buf.reset(new DevBuf<unsigned long long>());
+        } else {  // take over the area whose last launch is done (the entry's own event: never the caller's stream handle), else wait for the oldest's
+            size_t victim = s->totals_scratch.size();
+            for (size_t i = 0; i < s->totals_scratch.size() && victim == s->totals_scratch.size(); ++i)
+                if (s->totals_scratch[i].last.idle()) victim = i;
+            if (victim == s->totals_scratch.size()) { victim = 0; s->totals_scratch[0].last.wait(); }
+            std::rotate(s->totals_scratch.begin() + victim, s->totals_scratch.begin() + victim + 1, s->totals_scratch.end());
+        }
+        idx = s->totals_scratch.size() - 1;
+        s->totals_scratch[idx].stream = stream;
+    }
+    s->totals_scratch[idx].buf->reserve(words);
+    s->cur_scratch = (int)idx;
+    return s->totals_scratch[idx].buf->p;
+}
+
+namespace {
+// What every driver launch on the persistent phased core shares.  Construction takes the launch guard, picks the shape the scene gets (plain
+// 256 threads, top level in LDS, partial tops in LDS) and its grid, and fills the view and the persistent arguments; run() adds the shape's
+// own arguments and launches that shape's shell for the job.  The caller keeps what is its own around guard.start() / run() / guard.finish().
+struct DriverLaunch {
+    RcLaunchGuard guard;
+    rc_scene* s;
+    hipStream_t stream;
+    bool partial, lds;
+    uint32_t blocks;
+    SceneView v;
+    PersistArgs p;
+    DriverLaunch(rc_scene* scene, hipStream_t st, uint64_t n_items)
+        : guard(scene, st), s(scene), stream(st), partial(rc_partial_driver_ok(scene)), lds(partial || rc_lds_driver_ok(scene)),
+          blocks(lds ? rc_lds_driver_blocks(scene, n_items) : rc_persistent_blocks(scene, n_items)) {
+        const uint32_t threads = blocks * (lds ? (uint32_t)kMidBlock : (uint32_t)kBlock);
+        v = rc_scene_view(s, threads);
+        p = rc_persist_args(s, n_items, threads);
+    }
+    template <bool ANY, class Job>
+    void run(const Job& job) {
+        if (partial) {
+            rc_partial_driver_args(s, p);
+            rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&k_driver_partial<ANY, Job>), kPartialLdsBytes);
+            hipLaunchKernelGGL((k_driver_partial<ANY, Job>), dim3(blocks), dim3(kMidBlock), kPartialLdsBytes, stream, v, p, job);
+        } else if (lds) {
+            rc_lds_driver_args(s, p);
+            rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&k_driver_lds<ANY, Job>), kMidLdsBytes);
+            hipLaunchKernelGGL((k_driver_lds<ANY, Job>), dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, v, p, job);
+        } else
+            hipLaunchKernelGGL((k_driver<ANY, Job>), dim3(blocks), dim3(kBlock), 0, stream, v, p, job);
+    }
+};
+}  // namespace
 
 void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, uint64_t ray_begin, uint64_t ray_end,
                             float* d_counts, hipStream_t stream) {
@@ -675,43 +700,22 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
     check_buffer_range(s);
     rc_ensure_world_bound(s, stream);
     GridParams g = grid_params(s, viewdir, grid);
-    const bool partial = rc_partial_driver_ok(s);
-    const bool lds = partial || rc_lds_driver_ok(s);
-    const uint32_t bs = lds ? (uint32_t)kMidBlock : (uint32_t)kBlock;
-    uint32_t blocks = lds ? rc_lds_driver_blocks(s, ray_end - ray_begin) : rc_persistent_blocks(s, ray_end - ray_begin);
-    RcLaunchGuard launch(s, stream);
-    SceneView v = rc_scene_view(s, blocks * bs);
-    PersistArgs p = rc_persist_args(s, ray_end - ray_begin, blocks * bs);
+    DriverLaunch launch(s, stream, ray_end - ray_begin);
     const uint32_t np = s->n_flat_prims, n8 = (np + 7u) / 8u;
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(rc_totals_scratch(s, stream, launch.capturing, ((size_t)kHistCopies * 8u * n8 + 1u) / 2u));  // private copies of the histogram (HistogramSink)
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(rc_totals_scratch(s, stream, launch.guard.capturing, ((size_t)kHistCopies * 8u * n8 + 1u) / 2u));  // private copies of the histogram (HistogramSink)
     RC_HIP(hipMemsetAsync(scratch, 0, sizeof(uint32_t) * kHistCopies * 8u * n8, stream));
-    launch.start();
+    launch.guard.start();
     // a repeated get_illumination (same grid: item i is the same cell every time) claims the chunks that held long rays last time first
-    if (!launch.capturing && ray_begin == 0) {
+    if (!launch.guard.capturing && ray_begin == 0) {
         // (the rays are generated: the batch is described by its view direction and grid size -- another direction is another batch)
         const float diag = sqrtf((s->root_max[0] - s->root_min[0]) * (s->root_max[0] - s->root_min[0]) + (s->root_max[1] - s->root_min[1]) * (s->root_max[1] - s->root_min[1]) +
                                  (s->root_max[2] - s->root_min[2]) * (s->root_max[2] - s->root_min[2]));
         const float stand_in[8] = {(float)grid * diag, 0.f, 0.f, 0.f, g.dir[0], g.dir[1], g.dir[2], 0.f};
-        rc_cost_order_setup(s, ray_end, 2, stream, p.claim, nullptr, stand_in);
+        rc_cost_order_setup(s, ray_end, 2, stream, launch.p.claim, nullptr, stand_in);
     }
-    if (partial) {
-        rc_partial_driver_args(s, p);
-        if (!s->lds_attr_set[8]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_illumination_partial), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartialLdsBytes));
-            s->lds_attr_set[8] = true;
-        }
-        hipLaunchKernelGGL(k_illumination_partial, dim3(blocks), dim3(kMidBlock), kPartialLdsBytes, stream, v, p, g, ray_begin, scratch, n8);
-    } else if (lds) {
-        rc_lds_driver_args(s, p);
-        if (!s->lds_attr_set[4]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_illumination_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes));
-            s->lds_attr_set[4] = true;
-        }
-        hipLaunchKernelGGL(k_illumination_lds, dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, v, p, g, ray_begin, scratch, n8);
-    } else
-    hipLaunchKernelGGL(k_illumination, dim3(blocks), dim3(kBlock), 0, stream, v, p, g, ray_begin, scratch, n8);
+    launch.run<false>(IlluminationJob{g, ray_begin, scratch, n8});
     if (np) hipLaunchKernelGGL(k_illumination_fold, dim3((np + 255) / 256), dim3(256), 0, stream, scratch, n8, np, d_counts);
-    launch.finish();
+    launch.guard.finish();
 }
 
 // RC_VF_SOURCES_BY_METADATA: the flat primitives' indices sorted by (metadata, index) -- and the sorted metadata themselves on the host --
@@ -749,65 +753,10 @@ void rc_launch_view_factors(rc_scene* s, uint32_t rays_per_triangle, uint64_t se
     uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
     if (flags & 2u) rc_ensure_vf_order(s);  // RC_VF_SOURCES_BY_METADATA
     const uint32_t* order = (flags & 2u) ? s->vf_order.p : nullptr;
-    RcLaunchGuard launch(s, stream);
-    const bool partial = rc_partial_driver_ok(s);
-    const bool lds = partial || rc_lds_driver_ok(s);
-    const uint32_t bs = lds ? (uint32_t)kMidBlock : (uint32_t)kBlock;
-    uint32_t blocks = lds ? rc_lds_driver_blocks(s, total) : rc_persistent_blocks(s, total);
-    SceneView v = rc_scene_view(s, blocks * bs);
-    PersistArgs p = rc_persist_args(s, total, blocks * bs);
-    launch.start();
-    if (partial) {
-        rc_partial_driver_args(s, p);
-        if (!s->lds_attr_set[9]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_view_factors_partial), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartialLdsBytes));
-            s->lds_attr_set[9] = true;
-        }
-        hipLaunchKernelGGL(k_view_factors_partial, dim3(blocks), dim3(kMidBlock), kPartialLdsBytes, stream, v, p, (uint32_t)seed, (uint32_t)(seed >> 32), src_begin,
-                           ray_begin, ray_end - ray_begin, d_matrix, row_stride, col_stride, row_offset, flags, order);
-    } else if (lds) {
-        rc_lds_driver_args(s, p);
-        if (!s->lds_attr_set[5]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_view_factors_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes));
-            s->lds_attr_set[5] = true;
-        }
-        hipLaunchKernelGGL(k_view_factors_lds, dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, v, p, (uint32_t)seed, (uint32_t)(seed >> 32), src_begin,
-                           ray_begin, ray_end - ray_begin, d_matrix, row_stride, col_stride, row_offset, flags, order);
-    } else
-    hipLaunchKernelGGL(k_view_factors, dim3(blocks), dim3(kBlock), 0, stream, v, p, (uint32_t)seed, (uint32_t)(seed >> 32), src_begin,
-                       ray_begin, ray_end - ray_begin, d_matrix, row_stride, col_stride, row_offset, flags, order);
-    launch.finish();
-}
-
-// Scratch counters of a totals launch (launch_mu held): launches on one stream are ordered and share an area; another stream gets its own (up to
-// 16: then an idle stream's area is taken over, else the oldest stream is waited for); a CAPTURED launch owns its area like its spill region.
-static unsigned long long* rc_totals_scratch(rc_scene* s, hipStream_t stream, bool capturing, size_t words) {
-    if (words == 0) words = 1;
-    if (capturing) {  // (inside an RcLaunchGuard that took a capture slot)
-        auto& owned = s->capture_slots[s->cur_capture].scratch;
-        owned.emplace_back(new DevBuf<unsigned long long>());
-        owned.back()->reserve(words);
-        return owned.back()->p;
-    }
-    size_t idx = 0;
-    for (; idx < s->totals_scratch.size(); ++idx) if (s->totals_scratch[idx].stream == stream) break;
-    if (idx == s->totals_scratch.size()) {
-        if (s->totals_scratch.size() < 16) {
-            s->totals_scratch.emplace_back();
-            s->totals_scratch.back().buf.reset(new DevBuf<unsigned long long>());
-        } else {  // take over the area whose last launch is done (the entry's own event: never the caller's stream handle), else wait for the oldest's
-            size_t victim = s->totals_scratch.size();
-            for (size_t i = 0; i < s->totals_scratch.size() && victim == s->totals_scratch.size(); ++i)
-                if (s->totals_scratch[i].last.idle()) victim = i;
-            if (victim == s->totals_scratch.size()) { victim = 0; s->totals_scratch[0].last.wait(); }
-            std::rotate(s->totals_scratch.begin() + victim, s->totals_scratch.begin() + victim + 1, s->totals_scratch.end());
-        }
-        idx = s->totals_scratch.size() - 1;
-        s->totals_scratch[idx].stream = stream;
-    }
-    s->totals_scratch[idx].buf->reserve(words);
-    s->cur_scratch = (int)idx;
-    return s->totals_scratch[idx].buf->p;
+    DriverLaunch launch(s, stream, total);
+    launch.guard.start();
+    launch.run<false>(ViewFactorJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, d_matrix, row_stride, col_stride, row_offset, flags, order});
+    launch.guard.finish();
 }
 
 // Totals of rays [ray_begin, ray_end) of the sources with flat indices [src_begin, src_end), ACCUMULATED into d_received / d_emitted
@@ -819,39 +768,17 @@ void rc_launch_vf_totals(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
     if (src_begin >= src_end || ray_begin >= ray_end || (!d_received && !d_emitted)) return;
     check_buffer_range(s);
     const uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
-    RcLaunchGuard launch(s, stream);
-    const bool partial = rc_partial_driver_ok(s);
-    const bool lds = partial || rc_lds_driver_ok(s);
-    const uint32_t bs = lds ? (uint32_t)kMidBlock : (uint32_t)kBlock;
-    const uint32_t blocks = lds ? rc_lds_driver_blocks(s, total) : rc_persistent_blocks(s, total);
-    SceneView v = rc_scene_view(s, blocks * bs);
-    PersistArgs p = rc_persist_args(s, total, blocks * bs);
+    DriverLaunch launch(s, stream, total);
     const uint32_t np = s->n_flat_prims, n8 = (np + 7u) / 8u;
     unsigned long long* scratch = nullptr;
     if (d_received) {  // the private copies of the hot vector (see ViewFactorTotalsSink): one scratch area per stream, launches on one stream are ordered
-        scratch = rc_totals_scratch(s, stream, launch.capturing, (size_t)kTotalsCopies * 8u * n8);
+        scratch = rc_totals_scratch(s, stream, launch.guard.capturing, (size_t)kTotalsCopies * 8u * n8);
         RC_HIP(hipMemsetAsync(scratch, 0, sizeof(unsigned long long) * kTotalsCopies * 8u * n8, stream));
     }
-    launch.start();
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), n_ray = ray_end - ray_begin;
-    if (partial) {
-        rc_partial_driver_args(s, p);
-        if (!s->lds_attr_set[11]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vf_totals_partial), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartialLdsBytes));
-            s->lds_attr_set[11] = true;
-        }
-        hipLaunchKernelGGL(k_vf_totals_partial, dim3(blocks), dim3(kMidBlock), kPartialLdsBytes, stream, v, p, k0, k1, src_begin, ray_begin, n_ray, scratch, n8, d_emitted);
-    } else if (lds) {
-        rc_lds_driver_args(s, p);
-        if (!s->lds_attr_set[10]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vf_totals_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes));
-            s->lds_attr_set[10] = true;
-        }
-        hipLaunchKernelGGL(k_vf_totals_lds, dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, v, p, k0, k1, src_begin, ray_begin, n_ray, scratch, n8, d_emitted);
-    } else
-    hipLaunchKernelGGL(k_vf_totals, dim3(blocks), dim3(kBlock), 0, stream, v, p, k0, k1, src_begin, ray_begin, n_ray, scratch, n8, d_emitted);
+    launch.guard.start();
+    launch.run<false>(ViewFactorTotalsJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, scratch, n8, d_emitted});
     if (d_received) hipLaunchKernelGGL(k_vf_totals_fold, dim3((np + 255) / 256), dim3(256), 0, stream, scratch, n8, np, d_received);
-    launch.finish();
+    launch.guard.finish();
 }
 
 // Kernels outside RcLaunchGuard that read scene memory on a caller's stream (the wavefront stages): remember the stream's latest such
@@ -908,32 +835,11 @@ void rc_launch_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* 
     const uint64_t total = n * n_lights;
     if (total == 0) return;
     check_buffer_range(s);
-    RcLaunchGuard launch(s, stream);
-    const bool partial = rc_partial_driver_ok(s);
-    const bool lds = partial || rc_lds_driver_ok(s);
-    const uint32_t bs = lds ? (uint32_t)kMidBlock : (uint32_t)kBlock;
-    const uint32_t blocks = lds ? rc_lds_driver_blocks(s, total) : rc_persistent_blocks(s, total);
-    SceneView v = rc_scene_view(s, blocks * bs);
-    if (s->opt.entry_cull < 2) v.entry_cull = 0u;  // any_hit: the rule of rc_launch_trace
-    PersistArgs p = rc_persist_args(s, total, blocks * bs);
-    launch.start();
-    if (partial) {
-        rc_partial_driver_args(s, p);
-        if (!s->lds_attr_set[17]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shadow_visibility_partial), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartialLdsBytes));
-            s->lds_attr_set[17] = true;
-        }
-        hipLaunchKernelGGL(k_shadow_visibility_partial, dim3(blocks), dim3(kMidBlock), kPartialLdsBytes, stream, v, p, d_rays, d_hits, d_lights, n_lights, bias, d_visible);
-    } else if (lds) {
-        rc_lds_driver_args(s, p);
-        if (!s->lds_attr_set[16]) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shadow_visibility_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes));
-            s->lds_attr_set[16] = true;
-        }
-        hipLaunchKernelGGL(k_shadow_visibility_lds, dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, v, p, d_rays, d_hits, d_lights, n_lights, bias, d_visible);
-    } else
-    hipLaunchKernelGGL(k_shadow_visibility, dim3(blocks), dim3(kBlock), 0, stream, v, p, d_rays, d_hits, d_lights, n_lights, bias, d_visible);
-    launch.finish();
+    DriverLaunch launch(s, stream, total);
+    if (s->opt.entry_cull < 2) launch.v.entry_cull = 0u;  // any_hit: the rule of rc_launch_trace
+    launch.guard.start();
+    launch.run<true>(ShadowJob{d_rays, d_hits, d_lights, n_lights, bias, d_visible});
+    launch.guard.finish();
 }
 
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,

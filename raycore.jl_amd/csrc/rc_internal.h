@@ -321,6 +321,7 @@ struct rc_scene {
         uint64_t seq = 0;
     };
     std::vector<LaunchSlot> slots;    // kCounterSlots + 1: the last entry is the scene's own pair (ev0 / ev1)
+    std::set<const void*> dynamic_lds_set;  // kernels whose hipFuncAttributeMaxDynamicSharedMemorySize is set on this scene's device (rc_ensure_dynamic_lds)
     uint64_t timing_seq = 0;
     TimingRef last_timing;            // most recent timed operation on the scene by any thread
     // cost-ordered claiming: what the last launch of a shape learned about its chunks (rc_cost_order_setup, rc_traverse.hip)
@@ -377,8 +378,6 @@ struct rc_scene {
     DevBuf<unsigned char> compact_tmp;
     DevBuf<uint32_t> collide_counts;  // collide_instances' per-leaf counts / prefix sums (the reference's `cache`)
     DevBuf<uint2> contact_stage;
-
-    bool lds_attr_set[18] = {};  // hipFuncAttributeMaxDynamicSharedMemorySize done for kernels 4 / 5 (closest, any), illumination, view factors, [6, 7] kernel 6, [8, 9] the partial-LDS drivers, [10, 11] view-factor totals, [12, 13] kernel 5 and [14, 15] kernel 6 with 16-bit stacks, [16, 17] shadow visibility
 
     TraceOptions opt;
 };
@@ -465,6 +464,7 @@ struct RcLaunchGuard {
     void bind();   // the launch's ONE kernel carries the slot's events (hipExtLaunchKernelGGL) instead of event records around it
     void finish();
 };
+void rc_ensure_dynamic_lds(rc_scene* s, const void* fn, size_t bytes);  // before launching `fn` with `bytes` of dynamic LDS (launch_mu held): raises the function's limit once per scene
 void rc_claim_fill(rc_scene* s, uint64_t n_items, uint32_t total_waves, rc::RcClaim& out);  // the RcClaim of the launch being prepared
 // timing of operations that are not launches through RcLaunchGuard (builds, refits: mutations, externally serialised)
 void rc_timing_scene_begin(rc_scene* s, hipStream_t stream);

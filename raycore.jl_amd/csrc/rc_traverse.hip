@@ -609,6 +609,12 @@ rc::PersistArgs rc_persist_args(rc_scene* s, uint64_t n_items, uint32_t total_th
     return p;
 }
 
+void rc_ensure_dynamic_lds(rc_scene* s, const void* fn, size_t bytes) {
+    if (s->dynamic_lds_set.count(fn)) return;
+    RC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    s->dynamic_lds_set.insert(fn);
+}
+
 // The drivers' LDS variants (768-thread workgroups, node planes) apply under the same conditions as trace kernel 5.
 bool rc_lds_driver_ok(rc_scene* s) {
     return s->opt.kernel != 3 && s->n_tlas_nodes > 0 && s->n_tlas_nodes <= (uint32_t)kTlasLdsNodes && (uint64_t)(s->n_flat_nodes + s->n_tlas_nodes) * 64u < (1ull << 32);
@@ -647,51 +653,26 @@ static void launch_variant(rc_scene* s, int64_t kernel, const TraceArgs& a, uint
     s->bound_used = e0 != nullptr;
 #define RC_LAUNCH_P(L, W) hipExtLaunchKernelGGL((k_trace_persistent<ANY, L, W, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a)
 #define RC_LAUNCH_S(L, W) hipExtLaunchKernelGGL((k_trace_simple<ANY, L, W>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a)
+// a kernel with dynamic LDS: the function's limit is raised first, once per scene = per device (the attribute belongs to the function on one device)
+#define RC_LAUNCH_LDS(K, BLOCK, BYTES) do { rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&K), BYTES); hipExtLaunchKernelGGL(K, dim3(blocks), dim3(BLOCK), BYTES, stream, e0, e1, 0u, a); } while (0)
     if (kernel == 4) {
-        bool& attr_set = s->lds_attr_set[ANY ? 1 : 0];  // per scene = per device: the attribute belongs to the function on one device
-        if (!attr_set) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_phased_lds<ANY, kBigBlock, kLdsStack, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBigLdsBytes));
-            attr_set = true;
-        }
-        hipExtLaunchKernelGGL((k_trace_phased_lds<ANY, kBigBlock, kLdsStack, 4>), dim3(blocks), dim3(kBigBlock), kBigLdsBytes, stream, e0, e1, 0u, a);
+        RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kBigBlock, kLdsStack, 4>), kBigBlock, kBigLdsBytes);
     } else if (kernel == 5) {
-        bool& attr_set = s->lds_attr_set[2 + (ANY ? 1 : 0)];
-        if (!attr_set) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes));
-            attr_set = true;
-        }
-        if (stats && rc_stack16(s)) {  // dev: the same kernel with per-phase pass / lane counters (option "stats"; tools/isa_mix.py weights the phases' static opcode histograms with them)
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes16));
-            hipExtLaunchKernelGGL((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, true, true>), dim3(blocks), dim3(kMidBlock), kMidLdsBytes16, stream, e0, e1, 0u, a);
-        } else if (stats) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes));
-            hipExtLaunchKernelGGL((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, true>), dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, e0, e1, 0u, a);
-        } else if (a.timeline) {  // dev: the same kernel with per-wave event times written to the caller's buffer (option "timeline_ptr")
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes));
-            hipExtLaunchKernelGGL((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, true>), dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, e0, e1, 0u, a);
-        } else if (rc_stack16(s)) {
-            bool& set16 = s->lds_attr_set[12 + (ANY ? 1 : 0)];
-            if (!set16) {
-                RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMidLdsBytes16));
-                set16 = true;
-            }
-            hipExtLaunchKernelGGL((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, false, true>), dim3(blocks), dim3(kMidBlock), kMidLdsBytes16, stream, e0, e1, 0u, a);
-        } else
-        hipExtLaunchKernelGGL((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6>), dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, e0, e1, 0u, a);
+        rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6>), kMidLdsBytes);  // (as before: whichever variant runs)
+        if (stats && rc_stack16(s))  // dev: the same kernel with per-phase pass / lane counters (option "stats"; tools/isa_mix.py weights the phases' static opcode histograms with them)
+            RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, true, true>), kMidBlock, kMidLdsBytes16);
+        else if (stats)
+            RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, true>), kMidBlock, kMidLdsBytes);
+        else if (a.timeline)  // dev: the same kernel with per-wave event times written to the caller's buffer (option "timeline_ptr")
+            RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, true>), kMidBlock, kMidLdsBytes);
+        else if (rc_stack16(s))
+            RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, false, true>), kMidBlock, kMidLdsBytes16);
+        else
+            hipExtLaunchKernelGGL((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6>), dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, e0, e1, 0u, a);
     } else if (kernel == 6 && rc_stack16(s)) {
-        bool& attr_set = s->lds_attr_set[14 + (ANY ? 1 : 0)];
-        if (!attr_set) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_phased_partial<ANY, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartialLdsBytes16));
-            attr_set = true;
-        }
-        hipExtLaunchKernelGGL((k_trace_phased_partial<ANY, true>), dim3(blocks), dim3(kMidBlock), kPartialLdsBytes16, stream, e0, e1, 0u, a);
+        RC_LAUNCH_LDS((k_trace_phased_partial<ANY, true>), kMidBlock, kPartialLdsBytes16);
     } else if (kernel == 6) {
-        bool& attr_set = s->lds_attr_set[6 + (ANY ? 1 : 0)];
-        if (!attr_set) {
-            RC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trace_phased_partial<ANY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPartialLdsBytes));
-            attr_set = true;
-        }
-        hipExtLaunchKernelGGL((k_trace_phased_partial<ANY>), dim3(blocks), dim3(kMidBlock), kPartialLdsBytes, stream, e0, e1, 0u, a);
+        RC_LAUNCH_LDS((k_trace_phased_partial<ANY>), kMidBlock, kPartialLdsBytes);
     } else if (kernel == 3) {
         if (stats) hipExtLaunchKernelGGL((k_trace_phased<ANY, 24, 6, true>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
         else if (lds == 16) hipExtLaunchKernelGGL((k_trace_phased<ANY, 16, 8, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
@@ -712,6 +693,7 @@ static void launch_variant(rc_scene* s, int64_t kernel, const TraceArgs& a, uint
     }
 #undef RC_LAUNCH_P
 #undef RC_LAUNCH_S
+#undef RC_LAUNCH_LDS
 }
 
 uint32_t rc_blocks_per_cu(rc_scene* s) {

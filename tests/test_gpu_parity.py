@@ -611,12 +611,60 @@ def test_drivers_on_a_large_top_level(rc, oracle):
     assert t.get_option("tlas_top_k") > 0 and t.get_option("blas_top_k") > 0
     want_i = o.get_illumination((0.2, -0.1, -1.0), 300, nthreads=8)
     want_v = o.view_factors(64, seed=99, nthreads=8)
+    want_recv, want_emit = want_v.sum(axis=0, dtype=np.uint64), want_v.sum(axis=1, dtype=np.uint64)
     for kernel in (-1, 3):
         t.set_option("kernel", kernel)
         assert np.array_equal(rc.get_illumination(t, (0.2, -0.1, -1.0), 300), want_i), kernel
         assert np.array_equal(rc.view_factors(t, rays_per_triangle=64, seed=99), want_v), kernel
+        recv, emit = rc.view_factor_totals(t, 64, seed=99)  # the totals driver's partial shape runs nowhere else
+        assert recv.dtype == np.uint64 and emit.dtype == np.uint64, kernel
+        assert np.array_equal(recv, want_recv) and np.array_equal(emit, want_emit), kernel
+    assert t.get_option("claim_drift") == 0
     assert want_i.sum() > 1000 and want_v.sum() > 100
     t.free()
+
+
+def test_drivers_on_two_scenes_second_scene_first(rc, oracle):
+    """Two scenes on one device, each of the four persistent drivers (illumination, view-factor matrix, totals, fused shadow visibility) on
+    both, the scene built second launching first: what a scene remembers about a kernel's dynamic-LDS limit is its own and does not
+    lean on another scene having launched that kernel.  Both top levels fit in LDS (the shape with the largest dynamic LDS)."""
+    import torch
+    sc = rc.scenes
+    cfgs = [sc.config_c3(lon=8, bands=5, lattice=(3, 3, 2)), sc.config_c3(lon=6, bands=4, lattice=(2, 3, 2), seed=7)]
+    lights = np.array([[10, 10, 10], [-4, 6, 3]], np.float32)
+    worlds = []
+    for cfg in cfgs:
+        o = build_oracle(oracle, cfg)
+        rays = sc.c3_primary_rays(cfg, 192, 128)
+        hits = o.trace(rays, nthreads=8)
+        lit = hits["hit"] == 1
+        vis = np.zeros((len(rays), len(lights)), np.uint8)
+        for l, light in enumerate(lights):
+            sr = o.shadow_rays(rays, hits, light, 1e-3)
+            vis[:, l] = lit & (sr["tmax"] > 0) & (o.trace(sr, mode="any", nthreads=8)["hit"] == 0)
+        assert 100 < lit.sum() < len(rays) and 0 < vis[lit].sum() < vis[lit].size
+        worlds.append((cfg, o, rays, hits, vis))
+    scenes = [build_product(rc, cfg) for cfg, *_ in worlds]
+    viewdir = (0.2, -0.1, 1.0)
+    d_lights = torch.from_numpy(lights).cuda()
+    for i in (1, 0):
+        t, (cfg, o, rays, hits, vis) = scenes[i], worlds[i]
+        want_v = o.view_factors(64, seed=5, nthreads=8)
+        assert np.array_equal(rc.get_illumination(t, viewdir, 128), o.get_illumination(viewdir, 128, nthreads=8)), i
+        assert np.array_equal(rc.view_factors(t, rays_per_triangle=64, seed=5), want_v) and want_v.sum() > 100, i
+        recv, emit = rc.view_factor_totals(t, 64, seed=5)
+        assert np.array_equal(recv, want_v.sum(axis=0, dtype=np.uint64)) and np.array_equal(emit, want_v.sum(axis=1, dtype=np.uint64)), i
+        d_rays = torch.from_numpy(rays.view(np.uint8).reshape(-1).copy()).cuda()
+        d_hits = torch.from_numpy(hits.view(np.uint8).reshape(-1).copy()).cuda()
+        out = torch.full((vis.size + 64,), 0xAB, dtype=torch.uint8, device="cuda")
+        t.shadow_visibility_device(d_rays.data_ptr(), d_hits.data_ptr(), len(rays), d_lights.data_ptr(), len(lights), out.data_ptr(), bias=1e-3)
+        torch.cuda.synchronize()
+        t.wait_for_gpu()
+        got = out.cpu().numpy()
+        assert np.array_equal(got[:vis.size], vis.reshape(-1)) and np.all(got[vis.size:] == 0xAB), i
+    for t in scenes:
+        assert t.get_option("claim_drift") == 0
+        t.free()
 
 
 def test_illumination_hot_counters(rc, oracle):
