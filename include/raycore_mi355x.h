@@ -369,6 +369,56 @@ int rc_shadow_rays_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d
 int rc_shadow_visibility_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float* d_lights,
                                 uint32_t n_lights, float bias, uint8_t* d_visible, void* stream);
 
+/* Soft shadows: every light a small AREA light, `samples` shadow rays per (hit, light), the visible ones counted.  This is
+ * compute_light(...; shadow_samples) of the reference's tutorial (docs/src/raytracing-core.jl:58-99; raytracing_tutorial_content.md,
+ * "Part 6: Soft Shadows"), run for every light as compute_multi_light does (:119-129): the caller divides a count by `samples` to get the
+ * reference's shadow_factor (:94).
+ * d_rays / d_hits: the closest-hit stage's n rays and hit records.  d_lights: n_lights x 3 f32 positions, d_radii: n_lights f32 radii
+ * (the tutorial's light_radius, :69); both DEVICE arrays read when the KERNEL RUNS, so a captured call follows lights that move or
+ * resize between replays.  d_path_in (may be NULL) / path_base: the path of slot i is path_base + (d_path_in ? d_path_in[i] : i), exactly
+ * as in rc_bounce_rays_device: a compacted, chunked or sharded queue draws the same samples for the same path.
+ * The sampled target of (i, l, s) restates :61-81, every expression evaluated left to right in f32 with no contraction:
+ *   p = the hit point of slot i (rc_hit_points_device's);  lv = light_l - p;  light_dir = lv / sqrt(dot(lv, lv))
+ *   samples == 1: target = light_l; no random number is drawn (:74-81)
+ *   samples  > 1: off_k = (r_k * 2 - 1) * radius_l (k = 0, 1, 2);  off = off - light_dir * dot(off, light_dir);  target = light_l + off
+ * with dot(a, b) = (a1 b1 + a2 b2) + a3 b3.  The unseeded rand(Vec3f) (:76) is replaced by Philox4x32-10, counter layout
+ *   (lo32 path, hi32 path, s | depth << 16, 0x53460000 | l), key = (lo32 seed, hi32 seed);
+ * r0, r1, r2 = its first three words as 24-bit floats in [0, 1): (word >> 8) * 2^-24, the conversion of rc_bounce_rays_device.
+ * ray(i, l, s) is then rc_shadow_rays_device's ray toward the target: origin = hit point + normal * bias, direction = normalize(target -
+ * origin), t_max = the distance to the target.  That is the wavefront renderer's convention (docs/src/wavefront-renderer.jl:288-333), which
+ * this library already ships -- NOT the tutorial's t_max = Inf followed by `hit_dist >= shadow_dist` (:87-90): any_hit returns the first hit
+ * FOUND, not the nearest, so with an unbounded ray a first-found hit beyond the light would decide visibility.
+ *
+ * rc_soft_shadow_rays_device, the composed stage: writes n * n_lights * samples rays, ray(i, l, s) at slot (i * n_lights + l) * samples + s;
+ * a slot whose primary ray missed gets rc_shadow_rays_device's dummy ray (d = (0,0,1), t_max = 0).  The output feeds rc_trace_any_device
+ * unchanged.
+ * rc_soft_shadow_visibility_device, the fused driver: one persistent any_hit launch over all (hit, light, sample) items, the rays generated
+ * when a lane takes an item and never stored.  d_count: n x n_lights u32.  Identity with the composed path, exact, no tolerance:
+ *   d_count[i * n_lights + l] += sum over s of (d_hits[i].hit && ray(i, l, s).t_max > 0 && !any_hit(ray(i, l, s)).hit),
+ * where ray(i, l, s) is bit for bit what rc_soft_shadow_rays_device writes (the same device function makes both) and any_hit is what
+ * rc_trace_any_device reports for it.  The middle term is the gate of rc_shadow_visibility_device: a t_max of 0 or NaN (a NaN t or
+ * normal; with samples > 1 also a light that sits exactly on the hit point, whose light_dir and target are NaN) is not visible; it and a
+ * missed primary ray cost no traversal.  With samples == 1 no light_dir is computed: a light on the hit point then gives the hard
+ * shadow's ray of length |normal * bias| > 0, which is traced -- for that degenerate light a pair's result differs between S = 1 and S > 1.
+ * samples == 1: target == light, so the increment equals rc_shadow_visibility_device's byte for the same arguments.
+ * The call ACCUMULATES into d_count (the convention of rc_get_illumination_device and rc_view_factors_device): the caller zeroes it, and
+ * progressive accumulation over calls with different `seed` or `depth` is legal.  Each visible sample is one relaxed device-scope u32
+ * atomic add; integer adds are exact in any order, so the counts are reproducible.  Items are claimed in natural order; the entry cull
+ * follows rc_trace_any_device (off unless option "entry_cull" is 2).
+ * No allocation, copy, event, memset, host synchronisation or scene-owned scratch: re-entrant across streams, and captured on a capturing
+ * stream under the rules of the other driver launches (one capture slot; the stream must have run the call eagerly before).  A stack
+ * overflow is reported by rc_wait.  n == 0, n_lights == 0 or samples == 0: succeeds, nothing is enqueued.
+ * Errors, all before anything is enqueued: RC_ERR_INVALID_ARGUMENT (NULL scene, checked first and with or without a device; NULL d_rays,
+ * d_hits, d_lights, d_radii or output while there is work; n * n_lights * samples >= 2^32; samples >= 65536, depth >= 65536 or
+ * n_lights >= 65536), RC_ERR_NOT_SYNCED (the rules of rc_shadow_visibility_device).
+ * Measured against the composed path in docs/EXPERIMENTS.md, "Soft shadows". */
+int rc_soft_shadow_rays_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float* d_lights,
+                               const float* d_radii, uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth,
+                               const uint32_t* d_path_in, uint64_t path_base, float bias, rc_ray* d_shadow_rays, void* stream);
+int rc_soft_shadow_visibility_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float* d_lights,
+                                     const float* d_radii, uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth,
+                                     const uint32_t* d_path_in, uint64_t path_base, float bias, uint32_t* d_count, void* stream);
+
 /* ---- BVH4 (src/bvh4.jl; exported by the reference as BVHNode4 / BLAS4 / build_blas4 / closest_hit4 / any_hit4).
  * BLAS-level only, as in the reference: rays are traced in the geometry's own space, no instances.
  * rc_bvh4_node = BVHNode4, 120 bytes (src/bvh4.jl:40-69): interior nodes hold 1-based BVH4 child indices, a leaf

@@ -92,6 +92,8 @@ SYMBOLS = [
     ("rc_hit_points_device", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     ("rc_shadow_rays_device", _int, [_vp, _vp, _vp, _u64, _vp, C.c_float, _vp, _vp]),
     ("rc_shadow_visibility_device", _int, [_vp, _vp, _vp, _u64, _vp, _u32, C.c_float, _vp, _vp]),
+    ("rc_soft_shadow_rays_device", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _u32, _u64, _u32, _vp, _u64, C.c_float, _vp, _vp]),
+    ("rc_soft_shadow_visibility_device", _int, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _u32, _u64, _u32, _vp, _u64, C.c_float, _vp, _vp]),
     ("rc_blas4_build", _int, [_vp, _u32, _pu32]),
     ("rc_export_blas4_nodes", _int, [_vp, _u32, _vp, _u32, _pu32]),
     ("rc_trace_closest4", _int, [_vp, _u32, _vp, _vp, _u64]),

@@ -518,6 +518,25 @@ class TLAS:
         check(lib().rc_shadow_visibility_device(self._h, ptr(d_rays), ptr(d_hits), int(n), ptr(d_lights), int(n_lights), float(bias),
                                                 ptr(d_visible), ptr(stream) if stream else None))
 
+    def soft_shadow_rays_device(self, d_rays, d_hits, n, d_lights, d_radii, n_lights, samples, d_shadow_rays, seed=0, depth=0, bias=0.01,
+                                d_path_in=None, path_base=0, stream=None):
+        """The soft-shadow rays of all hits x all lights x `samples` (rc_soft_shadow_rays_device; compute_light's sampled area light,
+        docs/src/raytracing-core.jl:58-99): n * n_lights * samples RTRay slots, ray (i, l, s) at (i * n_lights + l) * samples + s, ready
+        for trace_device(mode='any').  d_lights / d_radii: device pointers to n_lights x 3 and n_lights f32, read when the kernel runs."""
+        check(lib().rc_soft_shadow_rays_device(self._h, ptr(d_rays), ptr(d_hits), int(n), ptr(d_lights), ptr(d_radii), int(n_lights), int(samples),
+                                               int(seed), int(depth), ptr(d_path_in) if d_path_in else None, int(path_base), float(bias),
+                                               ptr(d_shadow_rays), ptr(stream) if stream else None))
+
+    def soft_shadow_visibility_device(self, d_rays, d_hits, n, d_lights, d_radii, n_lights, samples, d_count, seed=0, depth=0, bias=0.01,
+                                      d_path_in=None, path_base=0, stream=None):
+        """Soft shadows in one traversal launch (rc_soft_shadow_visibility_device): d_count (device pointer, n * n_lights u32) is
+        ACCUMULATED -- count[i * n_lights + l] += the samples of light l that hit i sees, exactly what soft_shadow_rays_device +
+        trace_device(mode='any') + the t_max > 0 gate give, without their buffers.  The caller zeroes d_count and divides by `samples`
+        (the reference's shadow_factor).  samples == 1 is shadow_visibility_device's byte."""
+        check(lib().rc_soft_shadow_visibility_device(self._h, ptr(d_rays), ptr(d_hits), int(n), ptr(d_lights), ptr(d_radii), int(n_lights),
+                                                     int(samples), int(seed), int(depth), ptr(d_path_in) if d_path_in else None, int(path_base),
+                                                     float(bias), ptr(d_count), ptr(stream) if stream else None))
+
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib().rc_last_kernel_ms(self._h, C.byref(ms)))

@@ -1606,6 +1606,40 @@ int rc_shadow_visibility_device(rc_scene* s, const rc_ray* d_rays, const rc_hit*
     });
 }
 
+// What the two soft-shadow calls check before anything is enqueued (0: go on)
+static int soft_shadow_args(const char* name, rc_scene* s, const void* d_rays, const void* d_hits, uint64_t n, const void* d_lights, const void* d_radii,
+                            uint32_t n_lights, uint32_t samples, uint32_t depth, const void* d_out) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (n_lights >= 65536u || samples >= 65536u || depth >= 65536u)
+        return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": n_lights, samples and depth must be below 65536");
+    const uint64_t per_hit = (uint64_t)n_lights * samples;
+    if (per_hit && n >= ((1ull << 32) + per_hit - 1) / per_hit) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": n * n_lights * samples must be below 2^32");
+    if (n && per_hit && (!d_rays || !d_hits || !d_lights || !d_radii || !d_out)) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": NULL argument");
+    return 0;
+}
+int rc_soft_shadow_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
+                               uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
+                               float bias, rc_ray* d_shadow_rays, void* stream) {
+    if (int e = soft_shadow_args("rc_soft_shadow_rays_device", s, d_rays, d_hits, n, d_lights, d_radii, n_lights, samples, depth, d_shadow_rays)) return e;
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        rc_launch_soft_shadow_rays(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, d_lights, d_radii, n_lights, samples,
+                                   seed, depth, d_path_in, path_base, bias, reinterpret_cast<RcRay*>(d_shadow_rays), (hipStream_t)stream);
+    });
+}
+int rc_soft_shadow_visibility_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
+                                     uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
+                                     float bias, uint32_t* d_count, void* stream) {
+    if (int e = soft_shadow_args("rc_soft_shadow_visibility_device", s, d_rays, d_hits, n, d_lights, d_radii, n_lights, samples, depth, d_count)) return e;
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        rc_launch_soft_shadow_visibility(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, d_lights, d_radii, n_lights,
+                                         samples, seed, depth, d_path_in, path_base, bias, d_count, (hipStream_t)stream);
+    });
+}
+
 int rc_bounce_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                           const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n_out, uint64_t seed, uint32_t bounce, float bias,
                           rc_ray* d_out, void* stream) {

@@ -410,13 +410,16 @@ __global__ void k_hit_points(SceneView v, const RcRay* rays, const RcHit* hits, 
 // reference's dummy ray (o = 0, d = (0,0,1), t_max = 0), hits a ray from hit_point + normal*bias toward the light with
 // t_max = distance, ready for rc_trace_any_device.
 // The shadow ray of one hit toward one light (:296-329): shared by the stage kernel and the fused visibility driver, so the two agree bit for bit.
-__device__ inline RcRay shadow_ray(const SceneView& v, const RcRay& r, const RcHit& h, const float3_ light, float bias) {
-    float3_ p, nn;
-    hit_frame(v, r, h, p, nn);
+__device__ inline RcRay shadow_ray_from(const float3_ p, const float3_ nn, const float3_ light, float bias) {  // (p, nn): the hit's frame
     const float3_ o = add3(p, scale3(nn, bias));
     const float3_ lv = sub3(light, o);
     const float dist = __builtin_sqrtf(dot3(lv, lv));
     return RcRay{o.x, o.y, o.z, 0.f, (lv.x / dist), (lv.y / dist), (lv.z / dist), dist};
+}
+__device__ inline RcRay shadow_ray(const SceneView& v, const RcRay& r, const RcHit& h, const float3_ light, float bias) {
+    float3_ p, nn;
+    hit_frame(v, r, h, p, nn);
+    return shadow_ray_from(p, nn, light, bias);
 }
 __global__ void k_shadow_rays(SceneView v, const RcRay* rays, const RcHit* hits, uint64_t n, float lx, float ly, float lz, float bias, RcRay* out) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -470,6 +473,95 @@ struct ShadowJob {
     uint8_t* visible;
     __device__ inline ShadowSource source(const SceneView& v) const { return ShadowSource{v, rays, hits, lights, n_lights, bias}; }  // (v: the kernel's own by-value parameter)
     __device__ inline VisibilitySink sink(const SceneView&) const { return VisibilitySink{visible}; }
+};
+
+// ---- soft shadows: every light a small area light, `samples` shadow rays per (hit, light) -------------------------------------------
+// compute_light(...; shadow_samples) of the reference's tutorial (docs/src/raytracing-core.jl:58-99; compute_multi_light :119-129 runs it for
+// every light): shadow_factor = visible samples / shadow_samples.  The sampled target (:61-81), with the unseeded rand(Vec3f) replaced by
+// Philox4x32-10(counter = (lo32 path, hi32 path, s | depth << 16, 0x53460000 | l), key = seed) -- three 24-bit uniforms, the bounce stage's
+// conversion:
+//   p = hit point; lv = light - p; light_dir = lv / sqrt(dot3(lv, lv))
+//   samples == 1: target = light, no random number is drawn (:74-81)
+//   samples  > 1: off_k = (r_k * 2 - 1) * radius;  off = off - light_dir * dot3(off, light_dir);  target = light + off
+// every expression left to right, no contraction.  The ray toward the target is shadow_ray_from()'s, the body of shadow_ray(): origin = the biased hit point, t_max = the
+// distance to the target (the wavefront renderer's convention, not the tutorial's t_max = Inf followed by hit_dist >= shadow_dist: a
+// first-found any_hit beyond the light would otherwise decide visibility).
+struct SoftShadowParams {
+    const RcRay* rays;
+    const RcHit* hits;
+    const float* lights;       // n_lights x 3, read when the kernel runs
+    const float* radii;        // n_lights, likewise
+    const uint32_t* path_in;   // path of slot i (nullptr: i), as in k_bounce_rays
+    uint64_t path_base;
+    uint32_t n_lights, samples, k0, k1, depth;
+    float bias;
+};
+// The shadow ray of sample s of light l seen from slot i, whose primary ray hit (h = hits[i]): shared by the stage kernel and the fused
+// driver's source, so the two agree bit for bit.
+__device__ inline RcRay soft_shadow_ray(const SceneView& v, const SoftShadowParams& q, uint32_t i, uint32_t l, uint32_t s, const RcRay& r, const RcHit& h) {
+    const float* lp = q.lights + 3u * (size_t)l;
+    const float3_ light = mk3(lp[0], lp[1], lp[2]);
+    float3_ target = light;
+    float3_ p, nn;
+    hit_frame(v, r, h, p, nn);  // once: the target's light_dir and the ray's origin come from the same frame
+    if (q.samples > 1u) {
+        const float3_ lv = sub3(light, p);
+        const float ld = __builtin_sqrtf(dot3(lv, lv));
+        const float3_ light_dir = mk3((lv.x / ld), (lv.y / ld), (lv.z / ld));
+        const uint64_t path = q.path_base + (q.path_in ? (uint64_t)q.path_in[i] : (uint64_t)i);
+        uint32_t rnd[4];
+        philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), s | (q.depth << 16), 0x53460000u | l, q.k0, q.k1, rnd);
+        const float radius = q.radii[l];
+        float3_ off = mk3((u32_to_unit(rnd[0]) * 2.0f - 1.0f) * radius, (u32_to_unit(rnd[1]) * 2.0f - 1.0f) * radius, (u32_to_unit(rnd[2]) * 2.0f - 1.0f) * radius);
+        off = sub3(off, scale3(light_dir, dot3(off, light_dir)));
+        target = add3(light, off);
+    }
+    return shadow_ray_from(p, nn, target, q.bias);
+}
+// The composed stage: n * n_lights * samples rays, slot (i * n_lights + l) * samples + s; a slot whose primary ray missed gets k_shadow_rays'
+// dummy ray.  The output feeds rc_trace_any_device unchanged.
+__global__ void k_soft_shadow_rays(SceneView v, SoftShadowParams q, uint64_t total, RcRay* out) {
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t il = (uint32_t)j / q.samples, s = (uint32_t)j - il * q.samples;  // (total < 2^32)
+        const uint32_t i = il / q.n_lights, l = il - i * q.n_lights;
+        RcRay sr{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+        const RcHit h = q.hits[i];
+        if (h.hit) sr = soft_shadow_ray(v, q, i, l, s, q.rays[i], h);
+        float4* o4 = reinterpret_cast<float4*>(out + j);
+        o4[0] = make_float4(sr.ox, sr.oy, sr.oz, sr.tmin);
+        o4[1] = make_float4(sr.dx, sr.dy, sr.dz, sr.tmax);
+    }
+}
+// The fused driver: work item j = (i * n_lights + l) * samples + s, so the samples of a (hit, light) pair and the lights of a hit sit in
+// neighbouring lanes and share the hit's records.  ShadowSource's gate: a missed primary ray or a t_max that is not > 0 gives the dead ray.
+struct SoftShadowSource {
+    const SceneView& v;
+    SoftShadowParams q;
+    __device__ inline RcRay operator()(uint64_t j) const {
+        const uint32_t il = (uint32_t)j / q.samples, s = (uint32_t)j - il * q.samples;  // (n * n_lights * samples < 2^32)
+        const uint32_t i = il / q.n_lights, l = il - i * q.n_lights;
+        const RcHit h = q.hits[i];
+        if (!h.hit) return RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
+        const RcRay sr = soft_shadow_ray(v, q, i, l, s, load_ray(q.rays, i), h);
+        return sr.tmax > 0.0f ? sr : RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
+    }
+    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
+};
+// count[i * n_lights + l] += 1 for a visible sample (VisibilitySink's rule: a miss that comes back with a t_max > 0).  One relaxed
+// agent-scope u32 add per visible sample: integer adds are exact in any order, so the counts are reproducible; shadowed, gated and
+// missed items add nothing.
+struct VisibilityCountSink {
+    uint32_t* count;
+    uint32_t samples;
+    __device__ inline void operator()(uint64_t j, bool hit, float t, float, float, uint32_t, int) const {
+        if (!hit && t > 0.0f) __hip_atomic_fetch_add(count + (uint32_t)j / samples, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+struct SoftShadowJob {
+    SoftShadowParams q;
+    uint32_t* count;
+    __device__ inline SoftShadowSource source(const SceneView& v) const { return SoftShadowSource{v, q}; }  // (v: the kernel's own by-value parameter)
+    __device__ inline VisibilityCountSink sink(const SceneView&) const { return VisibilityCountSink{count, q.samples}; }
 };
 
 // cosine_sample_hemisphere (src/math.jl:1-21, concentric disk) in the frame (bu, bv, n), combined as random_hemisphere_uniform does
@@ -839,6 +931,36 @@ void rc_launch_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* 
     if (s->opt.entry_cull < 2) launch.v.entry_cull = 0u;  // any_hit: the rule of rc_launch_trace
     launch.guard.start();
     launch.run<true>(ShadowJob{d_rays, d_hits, d_lights, n_lights, bias, d_visible});
+    launch.guard.finish();
+}
+
+// The soft-shadow pair (SoftShadowParams): the composed stage writes the n * n_lights * samples rays; the driver is one persistent any_hit
+// launch over the same items in natural claim order that ACCUMULATES the visible samples into d_count.  total < 2^32 (checked by the caller).
+static SoftShadowParams soft_shadow_params(const RcRay* d_rays, const RcHit* d_hits, const float* d_lights, const float* d_radii, uint32_t n_lights,
+                                           uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias) {
+    return SoftShadowParams{d_rays, d_hits, d_lights, d_radii, d_path_in, path_base, n_lights, samples, (uint32_t)seed, (uint32_t)(seed >> 32), depth, bias};
+}
+void rc_launch_soft_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
+                                uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
+                                float bias, RcRay* d_out, hipStream_t stream) {
+    const uint64_t total = n * n_lights * samples;
+    if (total == 0) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, (uint64_t)s->n_cus * 8);
+    hipLaunchKernelGGL(k_soft_shadow_rays, dim3(blocks), dim3(256), 0, stream, rc_scene_view_static(s),
+                       soft_shadow_params(d_rays, d_hits, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias), total, d_out);
+    RC_HIP(hipGetLastError());
+    rc_note_stage_launch(s, stream);
+}
+void rc_launch_soft_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
+                                      uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in,
+                                      uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream) {
+    const uint64_t total = n * n_lights * samples;
+    if (total == 0) return;
+    check_buffer_range(s);
+    DriverLaunch launch(s, stream, total);
+    if (s->opt.entry_cull < 2) launch.v.entry_cull = 0u;  // any_hit: the rule of rc_launch_trace
+    launch.guard.start();
+    launch.run<true>(SoftShadowJob{soft_shadow_params(d_rays, d_hits, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias), d_count});
     launch.guard.finish();
 }
 

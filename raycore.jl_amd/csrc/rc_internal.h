@@ -499,6 +499,15 @@ void rc_launch_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits
 // visible[i * n_lights + l] = hit i is lit by light l: shadow-ray generation and any_hit for all hits x all lights in one traversal launch; n * n_lights < 2^32
 void rc_launch_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, uint32_t n_lights, float bias,
                                  uint8_t* d_visible, hipStream_t stream);
+// Soft shadows: `samples` rays per (hit, light) toward Philox-sampled points of an area light.  The composed stage writes ray
+// (i * n_lights + l) * samples + s; the driver ACCUMULATES the visible samples into count[i * n_lights + l] in one traversal launch.
+// n * n_lights * samples < 2^32; n_lights, samples, depth < 2^16
+void rc_launch_soft_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
+                                uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
+                                float bias, RcRay* d_out, hipStream_t stream);
+void rc_launch_soft_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
+                                      uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in,
+                                      uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream);
 // Diffuse (cosine-weighted) bounce rays, slot-aligned or gathered through d_src / *d_src_count (read on the device); n < 2^32, bounce < 2^16
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                            const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n, uint64_t seed, uint32_t bounce, float bias,

@@ -429,6 +429,24 @@ shadow_visibility_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{R
     check(ccall((:rc_shadow_visibility_device, LIB), Cint,
                 (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, Ptr{Float32}, UInt32, Cfloat, Ptr{UInt8}, Ptr{Cvoid}),
                 a.owner.ptr, d_rays, d_hits, n, d_lights, n_lights, bias, d_visible, stream))
+"Soft-shadow rays of all hits x all lights x `samples` (compute_light's sampled area light, docs/src/raytracing-core.jl:58-99): ray `(i, l, s)` (0-based) at slot `(i * n_lights + l) * samples + s` of `d_out`; `d_lights` (n_lights x 3) and `d_radii` (n_lights) are device arrays of Float32, read when the kernel runs."
+soft_shadow_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n::Integer, d_lights::Ptr{Float32},
+                         d_radii::Ptr{Float32}, n_lights::Integer, samples::Integer, d_out::Ptr{RTRay}; seed::UInt64 = UInt64(0),
+                         depth::Integer = 0, bias::Float32 = 0.01f0, d_path_in::Ptr{UInt32} = Ptr{UInt32}(C_NULL), path_base::Integer = 0,
+                         stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_soft_shadow_rays_device, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, Ptr{Float32}, Ptr{Float32}, UInt32, UInt32, UInt64, UInt32, Ptr{UInt32}, UInt64,
+                 Cfloat, Ptr{RTRay}, Ptr{Cvoid}),
+                a.owner.ptr, d_rays, d_hits, n, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias, d_out, stream))
+"Soft shadows in one traversal launch: `d_count[i * n_lights + l]` (0-based, n x n_lights UInt32, ACCUMULATED: zero it first) += the samples of light `l` that hit `i` sees; divide by `samples` for the reference's `shadow_factor`."
+soft_shadow_visibility_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n::Integer, d_lights::Ptr{Float32},
+                               d_radii::Ptr{Float32}, n_lights::Integer, samples::Integer, d_count::Ptr{UInt32}; seed::UInt64 = UInt64(0),
+                               depth::Integer = 0, bias::Float32 = 0.01f0, d_path_in::Ptr{UInt32} = Ptr{UInt32}(C_NULL),
+                               path_base::Integer = 0, stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_soft_shadow_visibility_device, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, Ptr{Float32}, Ptr{Float32}, UInt32, UInt32, UInt64, UInt32, Ptr{UInt32}, UInt64,
+                 Cfloat, Ptr{UInt32}, Ptr{Cvoid}),
+                a.owner.ptr, d_rays, d_hits, n, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias, d_count, stream))
 "Diffuse (cosine-weighted) bounce rays: slot-aligned, or gathered through `d_src` / `d_src_count` (a device count; `wrap` = round robin)."
 bounce_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n_out::Integer, d_out::Ptr{RTRay};
                     seed::UInt64 = UInt64(0), bounce::Integer = 0, bias::Float32 = 1f-3, d_src::Ptr{UInt32} = Ptr{UInt32}(C_NULL),

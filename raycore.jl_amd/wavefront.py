@@ -58,10 +58,17 @@ class WavefrontPaths:
     lights + fused_shadows=True: several point lights tested in one launch per depth.  `lights` is a float32 (L, 3) tensor on the accel's
     device (or an array, uploaded once into self.lights); each depth then runs one shadow_visibility_device into visible[b], a uint8 tensor
     of n * L bytes (byte i * L + l: slot i of hits[b] is lit by light l), and shadow_rays[b] / shadow_hits[b] do not exist (empty lists).
-    The lights are read when the frame runs: in-place edits of the tensor show up in the next run() or replay().  `light` is not used then."""
+    The lights are read when the frame runs: in-place edits of the tensor show up in the next run() or replay().  `light` is not used then.
+
+    shadow_samples > 1 (needs fused_shadows=True and light_radii): soft shadows.  `light_radii` is a float32 (L,) tensor on the accel's
+    device (or an array, uploaded once into self.light_radii), read when the frame runs like `lights`.  Each depth b then zeroes
+    shadow_counts[b] (an int32 tensor holding n * L u32 counts) on the frame's stream and runs one soft_shadow_visibility_device with
+    depth=b, d_path_in=path_ids[b] and the frame's seed: count i * L + l is the number of the shadow_samples samples of light l that slot i
+    of hits[b] sees, a path's samples do not depend on compaction, and visible[b] is not produced (an empty list).  light_radii with
+    shadow_samples == 1 is refused: one sample is the hard shadow and would ignore the radii."""
 
     def __init__(self, accel, width, height, samples, depth, camera, light=None, seed=0, bias=1e-3, compact=True, dynamic=None, rebuild=False,
-                 deform=None, lights=None, fused_shadows=False):
+                 deform=None, lights=None, fused_shadows=False, shadow_samples=1, light_radii=None):
         if depth < 1:
             raise ValueError("depth must be at least 1")
         if rebuild and not dynamic:
@@ -79,6 +86,23 @@ class WavefrontPaths:
                 raise ValueError("lights must have shape (L, 3) with L >= 1")
             if int(width) * int(height) * int(samples) * shape[0] >= 2 ** 32:
                 raise ValueError("width * height * samples * L must be below 2^32")
+        self.shadow_samples = int(shadow_samples)
+        if not 1 <= self.shadow_samples < 65536:
+            raise ValueError("shadow_samples must be in [1, 65536)")
+        if self.shadow_samples == 1 and light_radii is not None:
+            raise ValueError("light_radii needs shadow_samples > 1: one sample per light is the hard shadow, which has no radius")
+        if self.shadow_samples > 1:
+            if not self.fused_shadows:
+                raise ValueError("shadow_samples > 1 needs fused_shadows=True: soft shadows are one launch over hits x lights x samples")
+            if light_radii is None:
+                raise ValueError("shadow_samples > 1 needs light_radii=: a float32 (L,) tensor or array of area-light radii")
+            if shape[0] >= 65536:
+                raise ValueError("shadow_samples > 1 takes fewer than 65536 lights")
+            rshape = tuple(light_radii.shape) if hasattr(light_radii, "shape") else np.asarray(light_radii).shape
+            if rshape != (shape[0],):
+                raise ValueError("light_radii must have shape (L,), one radius per light")
+            if int(width) * int(height) * int(samples) * shape[0] * self.shadow_samples >= 2 ** 32:
+                raise ValueError("width * height * samples * L * shadow_samples must be below 2^32")
         import torch
         self.accel, self.width, self.height, self.samples, self.depth = accel, int(width), int(height), int(samples), int(depth)
         self.n = self.width * self.height * self.samples
@@ -103,7 +127,17 @@ class WavefrontPaths:
             else:
                 self.lights = torch.from_numpy(np.ascontiguousarray(lights, dtype=np.float32)).to(dev)
             self.n_lights = int(self.lights.shape[0])
-            self.visible = [torch.zeros(self.n * self.n_lights, dtype=torch.uint8, device=dev) for _ in range(depth)]
+            if self.shadow_samples == 1:
+                self.visible = [torch.zeros(self.n * self.n_lights, dtype=torch.uint8, device=dev) for _ in range(depth)]
+        self.light_radii, self.shadow_counts = None, []
+        if self.shadow_samples > 1:
+            if isinstance(light_radii, torch.Tensor):
+                if light_radii.dtype != torch.float32 or light_radii.device != dev or not light_radii.is_contiguous():
+                    raise ValueError("light_radii must be a contiguous float32 tensor on the accel's device")
+                self.light_radii = light_radii
+            else:
+                self.light_radii = torch.from_numpy(np.ascontiguousarray(light_radii, dtype=np.float32)).to(dev)
+            self.shadow_counts = [torch.zeros(self.n * self.n_lights, dtype=torch.int32, device=dev) for _ in range(depth)]
         self.shadow_rays = [] if self.fused_shadows else [rec() for _ in range(depth)]
         self.shadow_hits = [] if self.fused_shadows else [rec() for _ in range(depth)]
         self.path_ids = [torch.arange(self.n, dtype=torch.int32, device=dev)] + [
@@ -118,11 +152,14 @@ class WavefrontPaths:
 
     def buffers(self):
         fused = self.visible + [self.lights] if self.fused_shadows else []
+        if self.shadow_samples > 1:
+            fused = fused + self.shadow_counts + [self.light_radii]
         return self.rays + self.hits + self.shadow_rays + self.shadow_hits + fused + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic] + [t for _, t in self.deform]
 
     def run(self, stream=None):
         """Enqueue one frame on `stream` (a torch.cuda.Stream; None = the current stream).  No host synchronisation.  The first frame on
         a stream must run eagerly, before any capture on it."""
+        import torch
         s = _stream(stream)
         st = s.cuda_stream
         if st not in self._streams:  # the caching allocator must not hand the buffers out again while this stream may still use them
@@ -143,7 +180,13 @@ class WavefrontPaths:
                                      self.rays[0].data_ptr(), samples=self.samples, seed=self.seed, jitter=True, stream=st)
         a.trace_device(self.rays[0].data_ptr(), self.hits[0].data_ptr(), n, stream=st)
         for b in range(self.depth):
-            if self.fused_shadows:
+            if self.shadow_samples > 1:
+                with torch.cuda.stream(s):  # the call accumulates: zero on the frame's stream, whichever stream is current
+                    self.shadow_counts[b].zero_()
+                a.soft_shadow_visibility_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.lights.data_ptr(), self.light_radii.data_ptr(),
+                                                self.n_lights, self.shadow_samples, self.shadow_counts[b].data_ptr(), seed=self.seed, depth=b,
+                                                bias=self.bias, d_path_in=self.path_ids[b].data_ptr(), stream=st)
+            elif self.fused_shadows:
                 a.shadow_visibility_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.lights.data_ptr(), self.n_lights,
                                            self.visible[b].data_ptr(), bias=self.bias, stream=st)
             else:
@@ -182,8 +225,8 @@ class WavefrontPaths:
 
     def traced_rays(self):
         """Ray slots one frame traces: per depth one closest-hit pass (primary or bounce) and one any-hit pass (shadow) over every slot,
-        dead ones included -- with fused_shadows one any-hit item per slot and light."""
-        return self.n * (1 + (self.n_lights if self.fused_shadows else 1)) * self.depth
+        dead ones included -- with fused_shadows one any-hit item per slot and light, with shadow_samples > 1 per slot, light and sample."""
+        return self.n * (1 + (self.n_lights * self.shadow_samples if self.fused_shadows else 1)) * self.depth
 
 
 def c4_bounce_rays_device(accel, d_rays, d_hits, n_primary, n_rays, d_out, seed=0xC4, stream=None):
