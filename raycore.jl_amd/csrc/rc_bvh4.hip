@@ -462,10 +462,10 @@ void rc_launch_trace4(rc_scene* s, const Blas& b, const RcRay* d_rays, RcHit* d_
     a.nodes = b.nodes4.p; a.n_nodes = b.n_nodes4; a.root_word = b.root_word4; a.n_prims = b.n_prims;
     a.rays = d_rays; a.hits = d_hits; a.n_rays = n;
     if (n >= (1ull << 38)) throw RcError(1, "ray batches of 2^38 rays or more are not supported by the BVH4 kernels");
-    rc_claim_fill(s, n, total_threads / 64u, a.claim);
+    rc_claim_fill(launch, n, total_threads / 64u, a.claim);
     a.refill = (int)s->opt.refill;
     a.int_thr = (int)s->opt.sched_thr;
-    a.overflow = rc_launch_overflow(s, total_threads); a.total_threads = total_threads;  // (a captured launch: its own region, allocated here -- ADVICE r5)
+    a.overflow = rc_launch_overflow(launch, total_threads); a.total_threads = total_threads;  // (a captured launch: its own region, allocated here -- ADVICE r5)
     a.status = rc_status_word(s);
     launch.start();
     if (any_hit) hipLaunchKernelGGL((k_trace4<true, 24>), dim3(blocks), dim3(kBlock), 0, stream, a);

@@ -295,6 +295,8 @@ int rc_scene_create(int device, rc_scene** out) {
         RC_HIP(hipMemsetAsync(s->counters.p, 0, sizeof(uint32_t) * (size_t)kCounterSlots * kCounterSlotWords, s->stream));
         RC_HIP(hipStreamSynchronize(s->stream));
         s->slots.assign(kCounterSlots + 1, rc_scene::LaunchSlot());
+        // the per-stream pools never grow past these: reserved here so that no entry moves while an RcLaunchGuard points at its `last` event
+        s->overflow_regions.reserve(rc_scene::kMaxOverflowRegions); s->totals_scratch.reserve(rc_scene::kMaxTotalsScratch); s->histories.reserve(rc_scene::kMaxHistories);
         if (const char* e = getenv("RC_ENTRY_CULL")) s->opt.entry_cull = e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);  // test campaigns: the default of option "entry_cull" for every scene of the process
         if (const char* e = getenv("RC_STACK16")) s->opt.stack16 = e[0] == '0' ? 0 : 1;  // ... and of option "stack16"
     });

@@ -720,35 +720,22 @@ static void check_buffer_range(rc_scene* s) {
         throw RcError(1, "driver kernels address nodes with 32-bit buffer offsets: scenes above 64 M nodes are not supported yet");
 }
 
-// Scratch counters of a totals launch (launch_mu held): launches on one stream are ordered and share an area; another stream gets its own (up to
-// 16: then an idle stream's area is taken over, else the oldest stream is waited for); a CAPTURED launch owns its area like its spill region.
-static unsigned long long* rc_totals_scratch(rc_scene* s, hipStream_t stream, bool capturing, size_t words) {
+// Scratch counters of the launch's totals kernel: launches on one stream are ordered and share an area; another stream gets its own (up to
+// kMaxTotalsScratch: rc_stream_slot); a CAPTURED launch owns its area like its spill region.
+static unsigned long long* rc_totals_scratch(RcLaunchGuard& g, size_t words) {
     if (words == 0) words = 1;
-    if (capturing) {  // (inside an RcLaunchGuard that took a capture slot)
-        auto& owned = s->capture_slots[s->cur_capture].scratch;
+    if (g.capture >= 0) {
+        auto& owned = g.s->capture_slots[g.capture].scratch;
         owned.emplace_back(new DevBuf<unsigned long long>());
         owned.back()->reserve(words);
         return owned.back()->p;
     }
-    size_t idx = 0;
-    for (; idx < s->totals_scratch.size(); ++idx) if (s->totals_scratch[idx].stream == stream) break;
-    if (idx == s->totals_scratch.size()) {
-        if (s->totals_scratch.size() < 16) {
-            s->totals_scratch.emplace_back();
-            s->totals_scratch.back().buf.reset(new DevBuf<unsigned long long>());
-        } else {  // take over the area whose last launch is done (the entry's own event: never the caller's stream handle), else wait for the oldest's
-            size_t victim = s->totals_scratch.size();
-            for (size_t i = 0; i < s->totals_scratch.size() && victim == s->totals_scratch.size(); ++i)
-                if (s->totals_scratch[i].last.idle()) victim = i;
-            if (victim == s->totals_scratch.size()) { victim = 0; s->totals_scratch[0].last.wait(); }
-            std::rotate(s->totals_scratch.begin() + victim, s->totals_scratch.begin() + victim + 1, s->totals_scratch.end());
-        }
-        idx = s->totals_scratch.size() - 1;
-        s->totals_scratch[idx].stream = stream;
-    }
-    s->totals_scratch[idx].buf->reserve(words);
-    s->cur_scratch = (int)idx;
-    return s->totals_scratch[idx].buf->p;
+    bool fresh = false;
+    rc_scene::TotalsScratch& area = rc_stream_slot<rc_scene::kMaxTotalsScratch>(g.s->totals_scratch, g.stream, &fresh);
+    if (fresh) area.buf.reset(new DevBuf<unsigned long long>());
+    area.buf->reserve(words);
+    g.uses(area.last);
+    return area.buf->p;
 }
 
 namespace {
@@ -767,8 +754,8 @@ struct DriverLaunch {
         : guard(scene, st), s(scene), stream(st), partial(rc_partial_driver_ok(scene)), lds(partial || rc_lds_driver_ok(scene)),
           blocks(lds ? rc_lds_driver_blocks(scene, n_items) : rc_persistent_blocks(scene, n_items)) {
         const uint32_t threads = blocks * (lds ? (uint32_t)kMidBlock : (uint32_t)kBlock);
-        v = rc_scene_view(s, threads);
-        p = rc_persist_args(s, n_items, threads);
+        v = rc_scene_view(guard, threads);
+        p = rc_persist_args(guard, n_items, threads);
     }
     template <bool ANY, class Job>
     void run(const Job& job) {
@@ -794,7 +781,7 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
     GridParams g = grid_params(s, viewdir, grid);
     DriverLaunch launch(s, stream, ray_end - ray_begin);
     const uint32_t np = s->n_flat_prims, n8 = (np + 7u) / 8u;
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(rc_totals_scratch(s, stream, launch.guard.capturing, ((size_t)kHistCopies * 8u * n8 + 1u) / 2u));  // private copies of the histogram (HistogramSink)
+    uint32_t* scratch = reinterpret_cast<uint32_t*>(rc_totals_scratch(launch.guard, ((size_t)kHistCopies * 8u * n8 + 1u) / 2u));  // private copies of the histogram (HistogramSink)
     RC_HIP(hipMemsetAsync(scratch, 0, sizeof(uint32_t) * kHistCopies * 8u * n8, stream));
     launch.guard.start();
     // a repeated get_illumination (same grid: item i is the same cell every time) claims the chunks that held long rays last time first
@@ -803,7 +790,7 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
         const float diag = sqrtf((s->root_max[0] - s->root_min[0]) * (s->root_max[0] - s->root_min[0]) + (s->root_max[1] - s->root_min[1]) * (s->root_max[1] - s->root_min[1]) +
                                  (s->root_max[2] - s->root_min[2]) * (s->root_max[2] - s->root_min[2]));
         const float stand_in[8] = {(float)grid * diag, 0.f, 0.f, 0.f, g.dir[0], g.dir[1], g.dir[2], 0.f};
-        rc_cost_order_setup(s, ray_end, 2, stream, launch.p.claim, nullptr, stand_in);
+        rc_cost_order_setup(launch.guard, ray_end, 2, launch.p.claim, nullptr, stand_in);
     }
     launch.run<false>(IlluminationJob{g, ray_begin, scratch, n8});
     if (np) hipLaunchKernelGGL(k_illumination_fold, dim3((np + 255) / 256), dim3(256), 0, stream, scratch, n8, np, d_counts);
@@ -864,7 +851,7 @@ void rc_launch_vf_totals(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
     const uint32_t np = s->n_flat_prims, n8 = (np + 7u) / 8u;
     unsigned long long* scratch = nullptr;
     if (d_received) {  // the private copies of the hot vector (see ViewFactorTotalsSink): one scratch area per stream, launches on one stream are ordered
-        scratch = rc_totals_scratch(s, stream, launch.guard.capturing, (size_t)kTotalsCopies * 8u * n8);
+        scratch = rc_totals_scratch(launch.guard, (size_t)kTotalsCopies * 8u * n8);
         RC_HIP(hipMemsetAsync(scratch, 0, sizeof(unsigned long long) * kTotalsCopies * 8u * n8, stream));
     }
     launch.guard.start();

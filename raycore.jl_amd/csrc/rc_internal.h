@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "rc_device.h"
+#include "rc_stream_slots.h"
 
 struct RcError : std::runtime_error {
     int code;
@@ -289,12 +290,15 @@ struct rc_scene {
     DevBuf<uint4> range_tmp;    // compact topology of the BLAS being built (k_topology -> k_refit): per internal node its sorted-leaf range, child0, parent; then one parent word per leaf
     DevBuf<uint4> tlas_ranges;  // same for the TLAS; kept, because refit_tlas! reuses the topology
     DevBuf<RcPrim> prim_tmp;
-    // ---- launch bookkeeping: everything below is touched only with launch_mu held (RcLaunchGuard, rc_traverse.hip) ----
+    // ---- launch bookkeeping: the scene's POOLS, touched only with launch_mu held.  What belongs to the one launch being prepared -- its
+    // counter slot, capture slot, spill region, bound events -- lives in that launch's RcLaunchGuard (below), which holds the lock ----
     // The ENQUEUE of launches on one scene is serialised (microseconds); the kernels themselves overlap freely on their streams.
+    // overflow_regions, totals_scratch and histories are reserved to their fixed maxima at rc_scene_create and never reallocate: a guard
+    // keeps pointers to the `last` events of the entries its launch uses.
     std::mutex launch_mu;
     // global spill areas of the traversal stacks: one per stream that has launched on this scene (launches on one stream are
     // ordered and share theirs; launches on different streams may overlap and must not), at most kMaxOverflowRegions (a ninth stream
-    // takes over the region of an idle stream, or waits for the oldest).  Launches CAPTURED into a hipGraph never use these: each owns a
+    // takes over the region of an idle stream, or waits for the oldest: rc_stream_slot).  Launches CAPTURED into a hipGraph never use these: each owns a
     // region of its own (capture_regions).
     static constexpr int kMaxOverflowRegions = 8;  // each is allocated on first use by a new stream
     struct OverflowRegion { hipStream_t stream = nullptr; DevBuf<uint32_t> buf; RcEvent last; };  // last: behind the latest launch that used the region
@@ -304,16 +308,9 @@ struct rc_scene {
     // "release_capture" = the token option "last_capture_token" returned after the capture), once the caller's graph is gone.
     struct CaptureSlot { bool in_use = false; DevBuf<uint32_t> region; std::vector<std::unique_ptr<DevBuf<unsigned long long>>> scratch; };
     std::vector<CaptureSlot> capture_slots;  // kCounterSlots - kEagerSlots entries
-    int cur_capture = -1;              // the capture slot of the launch being prepared (-1: an eager launch)
-    int last_capture = -1;
-    int cur_region = -1, cur_history = -1, cur_scratch = -1;  // what the launch being prepared uses: RcLaunchGuard::finish records their events
-    uint32_t* cur_overflow = nullptr;  // the region of the launch being prepared (a captured launch's is allocated by rc_launch_overflow, which knows the grid)
-    bool guard_live = false;           // an RcLaunchGuard exists (set / cleared by it under launch_mu): the cur_* fields are meaningful
+    int last_capture = -1;             // the capture slot of the scene's most recent captured launch (option "last_capture_token")
     DevBuf<uint32_t> counters;        // kCounterSlots slots of claim counters (self-resetting, rc_claim_chunk), the sticky status word, dev statistics; zeroed at rc_scene_create
     uint64_t launch_seq = 0;          // eager launches so far; slot = launch_seq % kEagerSlots
-    int cur_slot = 0;                 // slot of the launch being prepared
-    hipEvent_t bound_t0 = nullptr, bound_t1 = nullptr;  // RcLaunchGuard::bind: the events the launch's kernel is to carry
-    bool bound_used = false;
     struct LaunchSlot {               // per counter slot: the events of its latest launch
         hipEvent_t t0 = nullptr, t1 = nullptr;  // timing pair; t1 also orders the slot's next user when that one runs on another stream
         hipStream_t stream = nullptr;
@@ -361,6 +358,7 @@ struct rc_scene {
     std::mutex host_call_mu;          // the other host-buffer entry points (illumination, view factors, collisions, exports) run one at a time
 
     DevBuf<float> f32_stage;
+    static constexpr int kMaxTotalsScratch = 16;
     struct TotalsScratch { hipStream_t stream = nullptr; std::unique_ptr<DevBuf<unsigned long long>> buf; RcEvent last; };
     std::vector<TotalsScratch> totals_scratch;  // view-factor totals / illumination: private copies of the accumulators, one area per stream (rc_drivers.hip; launch_mu); a captured launch's live in its CaptureSlot
     DevBuf<unsigned long long> u64_stage;  // view-factor totals: received[N] then emitted[N] (rc_multi.hip)
@@ -443,7 +441,6 @@ constexpr int kCounterSlots = 64, kEagerSlots = 48, kCounterSlotWords = 2048, kC
 constexpr int kSceneTimingSlot = kCounterSlots;
 constexpr int kClaimShards = 16, kShardBase = 64, kShardStrideWords = 64;
 constexpr int kStatsWords = 24;  // u64 dev statistics behind the status word of slot 0 (u32 words 8 .. 55: below kShardBase)
-inline uint32_t* rc_counter_slot(rc_scene* s) { return s->counters.p + (size_t)s->cur_slot * kCounterSlotWords; }  // slot of the launch being prepared (launch_mu held)
 inline uint32_t* rc_status_word(rc_scene* s) { return s->counters.p + 4; }
 inline uint32_t* rc_geometry_status_word(rc_scene* s) { return s->counters.p + 5; }  // sticky like the word before it: an in-place geometry update met a changed face count
 inline unsigned long long* rc_stats_words(rc_scene* s) { return reinterpret_cast<unsigned long long*>(s->counters.p + 8); }
@@ -451,21 +448,31 @@ inline unsigned long long* rc_stats_words(rc_scene* s) { return reinterpret_cast
 // of `stream` and the launch's counter slot, and orders the launch behind the slot's previous user; start() records the slot's first
 // timing event, finish() the second (both skipped while `stream` is being captured) and makes the launch the calling thread's -- and the
 // scene's -- latest timed operation.  Everything between construction and destruction runs with the lock held.
+// The state of the launch being prepared is the guard's own: whatever needs a launch's counter slot, spill region or capture slot takes the
+// guard, so it cannot run without one or see another launch's (the wavefront stages, which run unguarded, get rc_scene_view_static).
 struct RcLaunchGuard {
     rc_scene* s;
     hipStream_t stream;
     std::unique_lock<std::mutex> lock;
     bool capturing = false;
+    int slot = 0;                  // the launch's slot of claim counters and timing events
+    int capture = -1;              // its capture slot (-1: an eager launch)
+    uint32_t* overflow = nullptr;  // its stack spill region (a captured launch's is allocated by rc_launch_overflow, which knows the grid)
+    hipEvent_t carry_t0 = nullptr, carry_t1 = nullptr;  // bind(): the events the launch's kernel is to carry
+    bool carried = false;
+    RcEvent* busy[3];              // `last` of the per-stream resources the launch uses (a spill region, a history entry, a totals area: at most one of each): finish() marks them
+    int n_busy = 0;
     RcLaunchGuard(rc_scene* scene, hipStream_t stream);
-    ~RcLaunchGuard();
     RcLaunchGuard(const RcLaunchGuard&) = delete;
     RcLaunchGuard& operator=(const RcLaunchGuard&) = delete;
+    void uses(RcEvent& last) { busy[n_busy++] = &last; }  // whoever hands the launch a per-stream resource
+    uint32_t* counter_slot() const { return s->counters.p + (size_t)slot * kCounterSlotWords; }
     void start();
     void bind();   // the launch's ONE kernel carries the slot's events (hipExtLaunchKernelGGL) instead of event records around it
     void finish();
 };
 void rc_ensure_dynamic_lds(rc_scene* s, const void* fn, size_t bytes);  // before launching `fn` with `bytes` of dynamic LDS (launch_mu held): raises the function's limit once per scene
-void rc_claim_fill(rc_scene* s, uint64_t n_items, uint32_t total_waves, rc::RcClaim& out);  // the RcClaim of the launch being prepared
+void rc_claim_fill(RcLaunchGuard& g, uint64_t n_items, uint32_t total_waves, rc::RcClaim& out);  // the launch's RcClaim
 // timing of operations that are not launches through RcLaunchGuard (builds, refits: mutations, externally serialised)
 void rc_timing_scene_begin(rc_scene* s, hipStream_t stream);
 void rc_timing_scene_end(rc_scene* s, hipStream_t stream);

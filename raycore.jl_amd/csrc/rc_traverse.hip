@@ -382,16 +382,13 @@ RcLaunchGuard::RcLaunchGuard(rc_scene* scene, hipStream_t st) : s(scene), stream
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
     capturing = cap == hipStreamCaptureStatusActive;
-    const size_t region_words = (size_t)kTotalStack * (size_t)s->n_cus * 8 * kBlock;  // the largest grid any option can ask for: rc_set_option clamps blocks_per_cu to 8 blocks of 256 threads per CU
-    s->cur_capture = -1; s->cur_region = -1; s->cur_history = -1; s->cur_scratch = -1; s->cur_overflow = nullptr;
-    s->guard_live = true;
     if (capturing) {
         // A captured launch bakes its addresses into the graph and may be replayed at any time, beside eager launches and beside other
         // graphs: it gets a lane-stack spill region AND a slot of claim counters that no other launch, eager or captured, will ever use
         // (graphs captured on one stream used to share that stream's region, so two of them replayed side by side on a tree
         // deeper than the LDS stack overwrote each other's entries).  Both come from a pool of kCounterSlots - kEagerSlots capture slots per
         // scene, handed back by option "release_capture" (one) / "release_captures" (all) once the caller's graphs are gone.  The region
-        // is sized for the launch's own grid and allocated where that is known (rc_scene_view) -- inside the capture: the entry points run
+        // is sized for the launch's own grid and allocated where that is known (rc_launch_overflow) -- inside the capture: the entry points run
         // with the thread's capture-interaction mode relaxed, in which hipMalloc is legal.
         if (s->capture_slots.empty()) s->capture_slots.resize(kCounterSlots - kEagerSlots);
         int free_slot = -1;
@@ -401,47 +398,22 @@ RcLaunchGuard::RcLaunchGuard(rc_scene* scene, hipStream_t st) : s(scene), stream
                              "destroy a graph and hand its launches back (option \"release_capture\" with the token \"last_capture_token\" gave, or \"release_captures\" for all), "
                              "or capture several launches' worth of rays in one launch");
         s->capture_slots[free_slot].in_use = true;
-        s->cur_capture = s->last_capture = free_slot;
-        s->cur_overflow = nullptr;  // (rc_scene_view)
-        s->cur_slot = kEagerSlots + free_slot;
+        capture = s->last_capture = free_slot;
+        slot = kEagerSlots + free_slot;
     } else {
-        // the lane-stack spill area of the launch's stream (eager launches on one stream are ordered and share it)
-        size_t idx = 0;
-        for (; idx < s->overflow_regions.size(); ++idx)
-            if (s->overflow_regions[idx].stream == stream) break;
-        if (idx == s->overflow_regions.size() || s->overflow_regions[idx].buf.cap < region_words) {
-            if (idx == s->overflow_regions.size()) {
-                if (idx == (size_t)rc_scene::kMaxOverflowRegions) {  // one stream too many: take over the region whose last launch is done (oldest first), else wait for the oldest region's
-                    size_t victim = idx;
-                    for (size_t v = 0; v < idx; ++v)
-                        if (s->overflow_regions[v].last.idle()) { victim = v; break; }
-                    if (victim == idx) { victim = 0; s->overflow_regions[victim].last.wait(); }
-                    std::rotate(s->overflow_regions.begin() + victim, s->overflow_regions.begin() + victim + 1, s->overflow_regions.end());
-                    idx -= 1;
-                    s->overflow_regions[idx].stream = stream;
-                } else {
-                    s->overflow_regions.emplace_back();
-                    s->overflow_regions.back().stream = stream;
-                }
-            }
-            s->overflow_regions[idx].buf.reserve(region_words);
-        }
-        s->cur_region = (int)idx;
-        s->cur_overflow = s->overflow_regions[idx].buf.p;
+        // the lane-stack spill area of the launch's stream (eager launches on one stream are ordered and share it), sized for the largest
+        // grid any option can ask for: rc_set_option clamps blocks_per_cu to 8 blocks of 256 threads per CU
+        rc_scene::OverflowRegion& region = rc_stream_slot<rc_scene::kMaxOverflowRegions>(s->overflow_regions, stream);
+        region.buf.reserve((size_t)kTotalStack * (size_t)s->n_cus * 8 * kBlock);
+        uses(region.last);
+        overflow = region.buf.p;
         // the launch's slot of chunk counters; a launch that reuses an eager slot from another stream waits for the slot's previous user
         s->launch_seq += 1;
-        s->cur_slot = (int)(s->launch_seq % (uint64_t)kEagerSlots);
-        rc_scene::LaunchSlot& slot = s->slots[s->cur_slot];
-        if (slot.recorded && slot.stream != stream) RC_HIP(hipStreamWaitEvent(stream, slot.t1, 0));
+        slot = (int)(s->launch_seq % (uint64_t)kEagerSlots);
+        rc_scene::LaunchSlot& ls = s->slots[slot];
+        if (ls.recorded && ls.stream != stream) RC_HIP(hipStreamWaitEvent(stream, ls.t1, 0));
     }
     if (s->opt.stats) RC_HIP(hipMemsetAsync(rc_stats_words(s), 0, kStatsWords * sizeof(unsigned long long), stream));
-}
-
-// The launch state is the guard's: once it is gone no capture slot, region or spill pointer is current (a stale cur_capture
-// used to let a later unguarded call allocate into -- or index past -- the capture slots).  Runs with launch_mu still held.
-RcLaunchGuard::~RcLaunchGuard() {
-    s->cur_capture = -1; s->cur_region = -1; s->cur_history = -1; s->cur_scratch = -1; s->cur_overflow = nullptr;
-    s->guard_live = false;
 }
 
 static int rc_event_mode() {  // dev (tools/archive/event_probe.py): RC_EVENT_MODE = 0 product, 1 hipEventDisableSystemFence on t1 too, 2 no t0 event, 3 no events at all (single-stream runs only), 4 system fence on t0 as well (rounds 3-4)
@@ -450,44 +422,39 @@ static int rc_event_mode() {  // dev (tools/archive/event_probe.py): RC_EVENT_MO
 }
 void RcLaunchGuard::start() {
     if (capturing) return;
-    rc_scene::LaunchSlot& slot = s->slots[s->cur_slot];
-    if (!slot.t0) {
+    rc_scene::LaunchSlot& ls = s->slots[slot];
+    if (!ls.t0) {
         // t0 only marks a time in front of the kernel: nothing is published by it, so it skips the system-scope fence (0.5 % of a back-to-back
         // launch sequence, profiles/r05_launch_fixed_costs.txt); t1 keeps the default -- the host reads pinned words behind it
-        RC_HIP(hipEventCreateWithFlags(&slot.t0, rc_event_mode() == 4 ? hipEventDefault : hipEventDisableSystemFence));
-        RC_HIP(hipEventCreateWithFlags(&slot.t1, rc_event_mode() == 1 ? hipEventDisableSystemFence : hipEventDefault));
+        RC_HIP(hipEventCreateWithFlags(&ls.t0, rc_event_mode() == 4 ? hipEventDefault : hipEventDisableSystemFence));
+        RC_HIP(hipEventCreateWithFlags(&ls.t1, rc_event_mode() == 1 ? hipEventDisableSystemFence : hipEventDefault));
     }
-    if (rc_event_mode() < 2) RC_HIP(hipEventRecord(slot.t0, stream));
+    if (rc_event_mode() < 2) RC_HIP(hipEventRecord(ls.t0, stream));
 }
 
 void RcLaunchGuard::bind() {  // instead of start(): the launch's kernel carries the events itself (launch_variant)
     if (capturing) return;
     if (rc_event_mode() >= 2) { start(); return; }  // (dev modes measure the event packets)
-    rc_scene::LaunchSlot& slot = s->slots[s->cur_slot];
-    if (!slot.t0) {
-        RC_HIP(hipEventCreateWithFlags(&slot.t0, hipEventDisableSystemFence));
-        RC_HIP(hipEventCreateWithFlags(&slot.t1, hipEventDefault));
+    rc_scene::LaunchSlot& ls = s->slots[slot];
+    if (!ls.t0) {
+        RC_HIP(hipEventCreateWithFlags(&ls.t0, hipEventDisableSystemFence));
+        RC_HIP(hipEventCreateWithFlags(&ls.t1, hipEventDefault));
     }
-    s->bound_t0 = slot.t0; s->bound_t1 = slot.t1; s->bound_used = false;
+    carry_t0 = ls.t0; carry_t1 = ls.t1;
 }
 
 void RcLaunchGuard::finish() {
     RC_HIP(hipGetLastError());
-    const bool bound = s->bound_used;
-    s->bound_t0 = s->bound_t1 = nullptr; s->bound_used = false;
     if (capturing) return;  // a captured launch has no events of its own: the graph orders it, and its duration is the replay's business
-    rc_scene::LaunchSlot& slot = s->slots[s->cur_slot];
-    if (rc_event_mode() < 3 && !bound) RC_HIP(hipEventRecord(slot.t1, stream));
+    rc_scene::LaunchSlot& ls = s->slots[slot];
+    if (rc_event_mode() < 3 && !carried) RC_HIP(hipEventRecord(ls.t1, stream));
     // the per-stream resources this launch used are busy until here (asked by the next stream that wants to take one over)
     const bool closed = rc_event_mode() < 3;  // (they follow the launch's closing event instead of recording their own)
-    auto mark = [&](RcEvent& last) { if (closed) last.follow(slot.t1); else last.record(stream); };
-    if (s->cur_region >= 0) mark(s->overflow_regions[s->cur_region].last);
-    if (s->cur_history >= 0) mark(s->histories[s->cur_history].last);
-    if (s->cur_scratch >= 0) mark(s->totals_scratch[s->cur_scratch].last);
-    slot.stream = stream;
-    slot.recorded = true;
-    slot.seq = ++s->timing_seq;
-    note_timing(s, TimingRef{s->cur_slot, slot.seq, 0.f});
+    for (int i = 0; i < n_busy; ++i) { if (closed) busy[i]->follow(ls.t1); else busy[i]->record(stream); }
+    ls.stream = stream;
+    ls.recorded = true;
+    ls.seq = ++s->timing_seq;
+    note_timing(s, TimingRef{slot, ls.seq, 0.f});
 }
 
 void rc_timing_scene_begin(rc_scene* s, hipStream_t stream) { RC_HIP(hipEventRecord(s->ev0, stream)); }
@@ -523,8 +490,9 @@ float rc_timing_read(rc_scene* s) {
     return ms;
 }
 
-void rc_claim_fill(rc_scene* s, uint64_t n_items, uint32_t total_waves, rc::RcClaim& out) {
-    out.counters = rc_counter_slot(s) + kShardBase;
+void rc_claim_fill(RcLaunchGuard& g, uint64_t n_items, uint32_t total_waves, rc::RcClaim& out) {
+    rc_scene* s = g.s;
+    out.counters = g.counter_slot() + kShardBase;
     uint32_t shards = (uint32_t)s->opt.claim_shards, shift = 0;
     while (shards > 1 && shards > total_waves) shards >>= 1;  // every shard needs a wave: chunks dealt to a shard nobody drains would never be traced
     while ((2u << shift) <= shards) ++shift;
@@ -569,14 +537,12 @@ rc::SceneView rc_scene_view_static(rc_scene* s) {
     return v;
 }
 
-// The stack spill region of the launch being prepared (inside an RcLaunchGuard, launch_mu held).  An eager launch has its stream's
-// region already; a captured launch gets its own here, sized for its own grid of `total_threads` threads (every capture used
-// to pin the largest grid's 268 MB) -- allocated inside the capture: the entry points run with the thread's capture-interaction mode
-// relaxed, in which hipMalloc is legal.  Never returns null.
-uint32_t* rc_launch_overflow(rc_scene* s, uint32_t total_threads) {
-    if (!s->guard_live) throw RcError(1, "internal: rc_launch_overflow outside RcLaunchGuard");
-    if (s->cur_capture >= 0 && !s->cur_overflow) {
-        rc_scene::CaptureSlot& cs = s->capture_slots[s->cur_capture];
+// The launch's stack spill region.  An eager launch has its stream's region already; a captured launch gets its own here, sized for its
+// own grid of `total_threads` threads (every capture used to pin the largest grid's 268 MB) -- allocated inside the capture: the
+// entry points run with the thread's capture-interaction mode relaxed, in which hipMalloc is legal.  Never returns null.
+uint32_t* rc_launch_overflow(RcLaunchGuard& g, uint32_t total_threads) {
+    if (!g.overflow) {
+        rc_scene::CaptureSlot& cs = g.s->capture_slots[g.capture];
         try {
             cs.region.reserve((size_t)kTotalStack * std::max<uint32_t>(total_threads, 64u));
         } catch (const RcError&) {
@@ -585,27 +551,26 @@ uint32_t* rc_launch_overflow(rc_scene* s, uint32_t total_threads) {
             throw RcError(1, "could not allocate the stack spill region of a captured launch inside the capture (capture mode does not allow hipMalloc here): "
                              "capture with hipStreamCaptureModeRelaxed / ThreadLocal, or run the launch eagerly");
         }
-        s->cur_overflow = cs.region.p;
+        g.overflow = cs.region.p;
     }
-    if (!s->cur_overflow) throw RcError(1, "internal: the launch has no stack spill region");
-    return s->cur_overflow;
+    return g.overflow;
 }
 
-// The view of a traversal launch with `total_threads` threads (inside an RcLaunchGuard).
-rc::SceneView rc_scene_view(rc_scene* s, uint32_t total_threads) {
-    rc::SceneView v = rc_scene_view_static(s);
-    v.overflow = rc_launch_overflow(s, total_threads); v.total_threads = total_threads;
+// The view of the launch's traversal kernel with `total_threads` threads.
+rc::SceneView rc_scene_view(RcLaunchGuard& g, uint32_t total_threads) {
+    rc::SceneView v = rc_scene_view_static(g.s);
+    v.overflow = rc_launch_overflow(g, total_threads); v.total_threads = total_threads;
     return v;
 }
 
-// Arguments of a persistent launch with `total_threads` threads (inside an RcLaunchGuard).
-rc::PersistArgs rc_persist_args(rc_scene* s, uint64_t n_items, uint32_t total_threads) {
+// Arguments of the launch's persistent kernel with `total_threads` threads.
+rc::PersistArgs rc_persist_args(RcLaunchGuard& g, uint64_t n_items, uint32_t total_threads) {
     rc::PersistArgs p;
     p.n_items = n_items;
-    rc_claim_fill(s, n_items, total_threads / 64u, p.claim);
-    p.refill = (int)s->opt.refill;
-    p.int_thr = (int)s->opt.sched_thr;
-    p.stats = rc_stats_words(s);
+    rc_claim_fill(g, n_items, total_threads / 64u, p.claim);
+    p.refill = (int)g.s->opt.refill;
+    p.int_thr = (int)g.s->opt.sched_thr;
+    p.stats = rc_stats_words(g.s);
     return p;
 }
 
@@ -644,13 +609,15 @@ uint32_t rc_persistent_blocks(rc_scene* s, uint64_t n_items) {
 static bool rc_stack16(rc_scene* s) { return s->small_trees && s->opt.stack16 && !s->opt.timeline_ptr; }
 
 template <bool ANY>
-static void launch_variant(rc_scene* s, int64_t kernel, const TraceArgs& a, uint32_t blocks, hipStream_t stream) {
+static void launch_variant(RcLaunchGuard& g, int64_t kernel, const TraceArgs& a, uint32_t blocks) {
+    rc_scene* s = g.s;
+    const hipStream_t stream = g.stream;
     const int64_t lds = s->opt.lds_stack;
     const bool stats = s->opt.stats != 0;
     // The launch's timing / ordering events ride on the kernel's own dispatch (hipExtLaunchKernelGGL binds them to its start and end): no
     // event packets of their own around the kernel -- they cost ~3 us each between two back-to-back launches.  (Null outside RcLaunchGuard::bind.)
-    hipEvent_t e0 = s->bound_t0, e1 = s->bound_t1;
-    s->bound_used = e0 != nullptr;
+    hipEvent_t e0 = g.carry_t0, e1 = g.carry_t1;
+    g.carried = e0 != nullptr;
 #define RC_LAUNCH_P(L, W) hipExtLaunchKernelGGL((k_trace_persistent<ANY, L, W, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a)
 #define RC_LAUNCH_S(L, W) hipExtLaunchKernelGGL((k_trace_simple<ANY, L, W>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a)
 // a kernel with dynamic LDS: the function's limit is raised first, once per scene = per device (the attribute belongs to the function on one device)
@@ -855,7 +822,9 @@ __global__ __launch_bounds__(kOrderThreads) void k_order_scatter(uint32_t* cost_
 
 // The history entry of a launch shape (chunk count, mode, chunk geometry, stream): launches on one stream are ordered, so its buffers have
 // one user at a time; another stream gets its own entry.  Returns false when cost ordering does not apply to this launch.
-bool rc_cost_order_setup(rc_scene* s, uint64_t n, int any_hit, hipStream_t stream, rc::RcClaim& c, const RcRay* d_rays, const float* host_sample) {
+bool rc_cost_order_setup(RcLaunchGuard& g, uint64_t n, int any_hit, rc::RcClaim& c, const RcRay* d_rays, const float* host_sample) {
+    rc_scene* s = g.s;
+    const hipStream_t stream = g.stream;
     const uint64_t n_base64 = (n + c.pool - 1) / c.pool;  // chunks (the claim order permutes whole chunks; parts follow their chunk)
     // only where the order can matter: at least a claim per wave; the cost path maps rays to chunks with a shift (pool a power of two)
     if (s->n_tlas_nodes == 0) return false;  // (an empty scene's launches return before they look at the history: the header's two copies must flip with the host's parity)
@@ -908,7 +877,7 @@ bool rc_cost_order_setup(rc_scene* s, uint64_t n, int any_hit, hipStream_t strea
         h->parity = 0;
     }
     h->last_use = ++s->history_clock;
-    s->cur_history = (int)(h - s->histories.data());
+    g.uses(h->last);
     // (A shape whose batches never repeat leaves the mechanism for a while: counted and decided on the device, order_select / order_commit.)
     h->fresh_streak.ensure();
     h->gen += 1;
@@ -982,10 +951,10 @@ void rc_launch_trace(rc_scene* s, const RcRay* d_rays, RcHit* d_hits, uint64_t n
         total_threads = blocks * kMidBlock;
     }
     TraceArgs a;
-    a.v = rc_scene_view(s, total_threads);
+    a.v = rc_scene_view(launch, total_threads);
     if (any_hit && s->opt.entry_cull < 2) a.v.entry_cull = 0u;  // any_hit rays stop at their first hit and enter few instances that a cull would spare: the test costs what it saves (shadow rays -2 %); 2 = cull there too
     a.rays = d_rays; a.hits = d_hits; a.n_rays = n;
-    rc_claim_fill(s, n, total_threads / 64u, a.claim);
+    rc_claim_fill(launch, n, total_threads / 64u, a.claim);
     a.refill = (int)s->opt.refill;
     a.sched_thr = kernel == 2 ? 32 : (int)s->opt.sched_thr;  // kernel 2's vote threshold is its own (lanes that must wait for a batch), tuned at 32
     a.stats = rc_stats_words(s);
@@ -996,7 +965,7 @@ void rc_launch_trace(rc_scene* s, const RcRay* d_rays, RcHit* d_hits, uint64_t n
         a.tlas_k = wide ? s->tlas_top_k : s->tlas_top_k32; a.blas_k = s->opt.blas_top ? (wide ? s->blas_top_k : s->blas_top_k32) : 0; a.lds_blas_base = a.tlas_k;
     }
     launch.bind();
-    if (learn_order && (kernel == 3 || kernel == 5 || kernel == 6) && !launch.capturing) rc_cost_order_setup(s, n, any_hit, stream, a.claim, d_rays);  // (the rebuild pair, when there is one, runs in front of the timed kernel)
-    if (any_hit) launch_variant<true>(s, kernel, a, blocks, stream); else launch_variant<false>(s, kernel, a, blocks, stream);
+    if (learn_order && (kernel == 3 || kernel == 5 || kernel == 6) && !launch.capturing) rc_cost_order_setup(launch, n, any_hit, a.claim, d_rays);  // (the rebuild pair, when there is one, runs in front of the timed kernel)
+    if (any_hit) launch_variant<true>(launch, kernel, a, blocks); else launch_variant<false>(launch, kernel, a, blocks);
     launch.finish();
 }

@@ -1046,15 +1046,15 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
 
 }  // namespace rc
 
-rc::SceneView rc_scene_view(rc_scene* s, uint32_t total_threads);  // rc_traverse.hip: a traversal launch's view, inside an RcLaunchGuard
+rc::SceneView rc_scene_view(RcLaunchGuard& g, uint32_t total_threads);  // rc_traverse.hip: the launch's view
 rc::SceneView rc_scene_view_static(rc_scene* s);                    // the arrays only: no spill region, no side effects (stage kernels)
-uint32_t* rc_launch_overflow(rc_scene* s, uint32_t total_threads);  // the spill region of the launch being prepared (never null)
-rc::PersistArgs rc_persist_args(rc_scene* s, uint64_t n_items, uint32_t total_threads);
-// cost-ordered claiming for a launch inside an RcLaunchGuard: `kind` separates the histories of launches that map items to rays differently
+uint32_t* rc_launch_overflow(RcLaunchGuard& g, uint32_t total_threads);  // the launch's spill region (never null)
+rc::PersistArgs rc_persist_args(RcLaunchGuard& g, uint64_t n_items, uint32_t total_threads);
+// cost-ordered claiming for the launch: `kind` separates the histories of launches that map items to rays differently
 // (0 closest_hit, 1 any_hit, 2 the get_illumination grid)
 // d_rays: the launch's ray array (the batch is recognised by sample rays read on the device), or nullptr with host_sample[8] = a description of
 // generated rays (o.xyz, t_min, d.xyz, t_max of a stand-in ray: two launches whose stand-ins are close are the same batch)
-bool rc_cost_order_setup(rc_scene* s, uint64_t n_items, int kind, hipStream_t stream, rc::RcClaim& claim, const RcRay* d_rays, const float* host_sample = nullptr);
+bool rc_cost_order_setup(RcLaunchGuard& g, uint64_t n_items, int kind, rc::RcClaim& claim, const RcRay* d_rays, const float* host_sample = nullptr);
 bool rc_lds_driver_ok(rc_scene* s);
 bool rc_partial_driver_ok(rc_scene* s);
 void rc_partial_driver_args(rc_scene* s, rc::PersistArgs& p);
