@@ -204,9 +204,13 @@ int rc_trace_closest_device_batches(rc_scene* scene, const rc_ray* const* d_rays
 int rc_trace_any_device_batches(rc_scene* scene, const rc_ray* const* d_rays, rc_hit* const* d_hits, const uint64_t* n, int n_batches, void* stream);
 
 /* Kernel selection for the trace entry points (tuning / A-B measurement).  The default is the tuned
- * kernel; every variant returns identical results.  Names: "kernel" (-1 auto, 0..6),
- * "blocks_per_cu", "lds_stack", "refill", "sched_thr", "pool", "claim_shards" (scheduling knobs of the
- * persistent kernels), "taper" (guided claim sizes: towards the end of the claim order a 128-ray chunk is dealt in halves, quarters,
+ * kernel; every variant returns identical results.  Names: "kernel" (clamped to -1..6: -1 auto, 0 one ray per lane,
+ * 1 persistent waves, 3 phased, 5 phased with the top level in LDS -- scenes of at most 256 instances, else 3 runs --, 6 phased with the
+ * tops of the TLAS and of a single BLAS in LDS; 2 and 4 are retired ids kept as aliases: setting 2 stores 3, setting 4 stores 5, and
+ * rc_get_option returns what was stored),
+ * "blocks_per_cu", "refill", "sched_thr", "pool", "claim_shards" (scheduling knobs of the
+ * persistent kernels), "lds_stack" (retired: still accepted, without effect; reads back 24, the LDS depth of every 256-thread kernel),
+ * "taper" (guided claim sizes: towards the end of the claim order a 128-ray chunk is dealt in halves, quarters,
  * eighths; in eighths of (part size x waves) still to hand out per piece, default 12, 0 = whole chunks only), "cost_order" (1 = the
  * chunks that held long-lived rays in earlier launches of the same BATCH are claimed first: the batch is recognised on the device by sample
  * rays among up to four remembered per launch shape -- chunk count, mode, stream --, records its chunk costs in its launches 2-4 (never the first: a batch that does not come back pays nothing) and

@@ -1300,9 +1300,9 @@ int rc_update_mesh_vertices_device_async(rc_scene* s, uint32_t handle, const flo
 int rc_set_option(rc_scene* s, const char* name, int64_t value) {
     if (!s || !name) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
     std::string k(name);
-    if (k == "kernel") s->opt.kernel = value < -1 ? -1 : (value > 6 ? 6 : value);
-    else if (k == "blocks_per_cu") s->opt.blocks_per_cu = value < 0 ? 0 : (value > 8 ? 8 : value);  // 0 = derive from the stack depth; the stack spill area is sized for 8 blocks of 256 threads per CU
-    else if (k == "lds_stack") s->opt.lds_stack = value;
+    if (k == "kernel") s->opt.kernel = value < -1 ? -1 : (value > 6 ? 6 : (value == 2 ? 3 : (value == 4 ? 5 : value)));  // 2 and 4 are retired: aliases of their successors
+    else if (k == "blocks_per_cu") s->opt.blocks_per_cu = value < 0 ? 0 : (value > 8 ? 8 : value);  // 0 = the shape's own count; the stack spill area is sized for 8 blocks of 256 threads per CU
+    else if (k == "lds_stack") {}  // retired: every kernel keeps 24 entries per lane in LDS (the 768-thread shapes 16)
     else if (k == "refill") s->opt.refill = value < 1 ? 1 : (value > 64 ? 64 : value);
     else if (k == "stack16") s->opt.stack16 = value != 0;
     else if (k == "stats") s->opt.stats = value;
@@ -1354,7 +1354,7 @@ int rc_get_option(rc_scene* s, const char* name, int64_t* value) {
     if (k == "kernel") *value = s->opt.kernel;
     else if (k == "blocks_per_cu") *value = s->opt.blocks_per_cu;
     else if (k == "n_cus") *value = s->n_cus;
-    else if (k == "lds_stack") *value = s->opt.lds_stack;
+    else if (k == "lds_stack") *value = 24;
     else if (k == "refill") *value = s->opt.refill;
     else if (k == "pool") *value = s->opt.pool;
     else if (k == "claim_shards") *value = s->opt.claim_shards;

@@ -150,27 +150,22 @@ struct IlluminationJob {
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kBlock, 6) void k_driver(SceneView v, PersistArgs p, Job j) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    phased_trace<ANY, kLdsStack, false>(v, p, lds_stack, j.source(v), j.sink(v));
+    phased_trace<ANY, PlainShape<>>(v, p, lds_stack, j.source(v), j.sink(v));
 }
 // Small top level (<= kTlasLdsNodes nodes): the shape of trace kernel 5 -- two 768-thread workgroups per CU, TLAS (and a single BLAS's
 // top nodes) in LDS planes.
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kMidBlock, 6) void k_driver_lds(SceneView v, PersistArgs p, Job j) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LdsTop top(smem + (size_t)kMidStack * kMidBlock * 4);
-    stage_lds_top<kMidBlock>(top, v, p.blas_k, p.lds_blas_base);
-    __syncthreads();
-    phased_trace<ANY, kMidStack, false, decltype(j.source(v)), decltype(j.sink(v)), kMidBlock, true, true>(v, p, reinterpret_cast<uint32_t*>(smem), j.source(v), j.sink(v), top);
+    const LdsTop top = LdsShape<>::prologue(smem, v, p.blas_k, p.lds_blas_base, p.tlas_k);
+    phased_trace<ANY, LdsShape<>>(v, p, LdsShape<>::stacks(smem), j.source(v), j.sink(v), top);
 }
 // Larger top levels (the shape of trace kernel 6): only the breadth-first tops of the TLAS and of a single BLAS are staged.
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kMidBlock, 6) void k_driver_partial(SceneView v, PersistArgs p, Job j) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    LdsTop top;
-    top.tl = reinterpret_cast<float2*>(smem + (size_t)kMidStack * kMidBlock * 4);
-    stage_partial_top<kMidBlock>(top.tl, v, p.tlas_k, p.blas_k, p.lds_blas_base);
-    __syncthreads();
-    phased_trace<ANY, kMidStack, false, decltype(j.source(v)), decltype(j.sink(v)), kMidBlock, false, false, true>(v, p, reinterpret_cast<uint32_t*>(smem), j.source(v), j.sink(v), top);
+    const LdsTop top = PartialShape<>::prologue(smem, v, p.blas_k, p.lds_blas_base, p.tlas_k);
+    phased_trace<ANY, PartialShape<>>(v, p, PartialShape<>::stacks(smem), j.source(v), j.sink(v), top);
 }
 
 // ---- Philox4x32-10 (Salmon et al., SC'11) ---------------------------------------------------------------
@@ -752,7 +747,7 @@ struct DriverLaunch {
     PersistArgs p;
     DriverLaunch(rc_scene* scene, hipStream_t st, uint64_t n_items)
         : guard(scene, st), s(scene), stream(st), partial(rc_partial_driver_ok(scene)), lds(partial || rc_lds_driver_ok(scene)),
-          blocks(lds ? rc_lds_driver_blocks(scene, n_items) : rc_persistent_blocks(scene, n_items)) {
+          blocks(lds ? rc_grid_blocks(scene, n_items, kMidBlock, LdsShape<>::kBlocksPerCu) : rc_grid_blocks(scene, n_items, kBlock, PlainShape<>::kBlocksPerCu)) {
         const uint32_t threads = blocks * (lds ? (uint32_t)kMidBlock : (uint32_t)kBlock);
         v = rc_scene_view(guard, threads);
         p = rc_persist_args(guard, n_items, threads);
@@ -761,12 +756,12 @@ struct DriverLaunch {
     void run(const Job& job) {
         if (partial) {
             rc_partial_driver_args(s, p);
-            rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&k_driver_partial<ANY, Job>), kPartialLdsBytes);
-            hipLaunchKernelGGL((k_driver_partial<ANY, Job>), dim3(blocks), dim3(kMidBlock), kPartialLdsBytes, stream, v, p, job);
+            rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&k_driver_partial<ANY, Job>), PartialShape<>::kLdsBytes);
+            hipLaunchKernelGGL((k_driver_partial<ANY, Job>), dim3(blocks), dim3(kMidBlock), PartialShape<>::kLdsBytes, stream, v, p, job);
         } else if (lds) {
             rc_lds_driver_args(s, p);
-            rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&k_driver_lds<ANY, Job>), kMidLdsBytes);
-            hipLaunchKernelGGL((k_driver_lds<ANY, Job>), dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, v, p, job);
+            rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&k_driver_lds<ANY, Job>), LdsShape<>::kLdsBytes);
+            hipLaunchKernelGGL((k_driver_lds<ANY, Job>), dim3(blocks), dim3(kMidBlock), LdsShape<>::kLdsBytes, stream, v, p, job);
         } else
             hipLaunchKernelGGL((k_driver<ANY, Job>), dim3(blocks), dim3(kBlock), 0, stream, v, p, job);
     }

@@ -131,7 +131,7 @@ constexpr int kTlasLdsInst = 256;
 //  * the TLAS leaf -> instance index table (kTlasLdsInst words);
 //  * the instance records as seven float2 planes of kTlasLdsInst entries (inverse transform, nodes offset, leaf count).
 constexpr int kLdsPlaneNodes = 310;
-constexpr int kPartialPlaneNodes = 585;  // node planes of the PARTIAL_LDS kernel (no leaf table, no instance planes): 32 760 bytes
+constexpr int kPartialPlaneNodes = 585;  // node planes of the Top::PartialLds shapes (no leaf table, no instance planes): 32 760 bytes
 // Scenes whose trees ALL have fewer than 65 534 nodes (every BLAS <= 32 767 triangles, <= 32 767 instances) run the STACK16 shape of the
 // same kernels (round 5): lane-stack entries of 16 bits, and the 24 KiB of LDS that frees per workgroup holds more of the tree.
 #ifndef RC_LDS_PLANES16        // dev: tools/lds_bound_probe.py builds a variant with 1 278 entries (every interior node of a 1 024-triangle BLAS; one workgroup per CU)
@@ -143,12 +143,11 @@ constexpr uint32_t kStack16MaxLeaves = 32767;
 }  // namespace rc
 
 struct TraceOptions {
-    int64_t kernel = -1;       // -1 = auto, 0 = one-ray-per-lane, 1 = persistent wave-refill, 2 = persistent + voted path scheduling, 3 = persistent + phased (while-while), 4 = 3 with the TLAS + instance records staged in LDS (1024-thread blocks, <= 256 instances), 5 = 3 with the TLAS staged in LDS at 24 waves/CU (2 x 768 threads)
-    int64_t blocks_per_cu = 0; // 0 = derive from the LDS stack depth
-    int64_t lds_stack = 24;    // per-lane stack entries kept in LDS: 12, 16, 24 or 32
+    int64_t kernel = -1;       // -1 = auto, 0 = one-ray-per-lane, 1 = persistent wave-refill, 3 = persistent + phased (while-while), 5 = 3 with the TLAS + instance records staged in LDS at 24 waves/CU (2 x 768 threads, <= 256 instances), 6 = 5's shape with only the tops of the trees staged (rc_set_option stores the retired ids 2 and 4 as 3 and 5)
+    int64_t blocks_per_cu = 0; // 0 = 6 blocks of 256 threads (6 x 24 KiB of LDS stacks), two of 768
     int64_t pool = 0;          // persistent kernels: ray indices per atomic claim (0 = auto 64..512)
     int64_t refill = 20;       // persistent kernel: refill when this many lanes of a wave are idle
-    int64_t sched_thr = 36;    // kernel 2: lanes that must wait for a leaf/switch batch; kernel 3: interior lanes below which the wave serves the waiting lanes
+    int64_t sched_thr = 36;    // phased kernels: interior lanes below which the wave serves the waiting lanes
     int64_t stats = 0;         // dev instrumentation (persistent kernels only)
     int64_t onesweep_min = 1000000;  // builds: key counts from here up are sorted by Onesweep radix passes, smaller ones by rocPRIM's merge sort (measured: 0.22 vs 0.25 ms at 250 k keys, 0.437 vs 0.425 ms at 1 M)
     int64_t stack16 = 1;       // scenes whose trees all have fewer than 65 534 nodes: 16-bit lane-stack entries, the freed LDS holds more of the tree (kernels 5 / 6)
@@ -484,7 +483,7 @@ void rc_memset_now(void* p, int value, size_t bytes);
 void rc_note_stage_launch(rc_scene* s, hipStream_t stream);  // after a kernel outside RcLaunchGuard that reads scene memory
 void rc_timing_fixed(rc_scene* s, float ms);
 float rc_timing_read(rc_scene* s);  // the calling thread's latest timed operation on the scene, else the scene's latest
-uint32_t rc_persistent_blocks(rc_scene* s, uint64_t n_items);
+uint32_t rc_grid_blocks(rc_scene* s, uint64_t n_items, int block, int64_t per_cu);  // the grid rule of the persistent kernels (per_cu: TraceShape::kBlocksPerCu, rc_traverse_core.h)
 void rc_ensure_vf_order(rc_scene* s);  // builds vf_order / vf_meta_sorted if the scene has been rebuilt since
 void rc_vf_source_range(rc_scene* s, uint32_t row_begin, uint32_t row_end, uint32_t& pos_begin, uint32_t& pos_end);  // positions in the metadata order whose metadata - 1 is in [row_begin, row_end)
 // rc_multi.hip

@@ -11,9 +11,9 @@
 // raw buffer loads, the per-lane traversal stack in LDS ([entry][lane] layout => conflict-free ds_read/ds_write_b32)
 // with a global spill area for the rare deep path, persistent waves that refill finished lanes from a global ray
 // counter (ballot + mbcnt prefix sums), and phase-structured execution so a wave only issues the block its lanes
-// actually need.  Kernel variants (rc_set_option "kernel"): 0 simple, 1 persistent, 2 voted scheduling, 3 phased
-// (core in rc_traverse_core.h), 4 / 5 phased with the top level -- TLAS interior nodes, instance records, a single BLAS's top nodes --
-// staged in LDS (5 = default when the scene has <= 256 instances).  All return identical results.
+// actually need.  Kernel variants (rc_set_option "kernel"): 0 simple, 1 persistent, 3 phased (core in rc_traverse_core.h), 5 phased with
+// the top level -- TLAS interior nodes, instance records, a single BLAS's top nodes -- staged in LDS (the default when the scene has <= 256
+// instances), 6 phased with the breadth-first tops staged (the default for larger scenes).  All return identical results.
 #include <algorithm>
 #include <cstdlib>
 
@@ -27,11 +27,11 @@ namespace {
 using namespace rc;
 
 // ---- kernel 0: one ray per lane, grid-stride --------------------------------------------------------
-template <bool ANY, int LDS_N, int MINW>
-__global__ __launch_bounds__(kBlock, MINW) void k_trace_simple(TraceArgs a) {
-    __shared__ uint32_t lds_stack[LDS_N * kBlock];
+template <bool ANY>
+__global__ __launch_bounds__(kBlock, 6) void k_trace_simple(TraceArgs a) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     const uint32_t gtid = blockIdx.x * kBlock + threadIdx.x;
-    LaneStackT<LDS_N> st(lds_stack + threadIdx.x, a.v.overflow + gtid, a.v.total_threads, a.v.status);
+    LaneStack st(lds_stack + threadIdx.x, a.v.overflow + gtid, a.v.total_threads, a.v.status);
     for (uint64_t i = gtid; i < a.n_rays; i += a.v.total_threads) {
         RayState s;
         init_ray(s, load_ray(a.rays, i), ANY, st, a.v.tlas_off);
@@ -48,11 +48,11 @@ __global__ __launch_bounds__(kBlock, MINW) void k_trace_simple(TraceArgs a) {
 // __ballot, each idle lane's rank from mbcnt (a prefix popcount), so no lane waits for the slowest ray of
 // its original 64-ray packet.
 
-template <bool ANY, int LDS_N, int MINW, bool STATS>
-__global__ __launch_bounds__(kBlock, MINW) void k_trace_persistent(TraceArgs a) {
-    __shared__ uint32_t lds_stack[LDS_N * kBlock];
+template <bool ANY, bool STATS>
+__global__ __launch_bounds__(kBlock, 6) void k_trace_persistent(TraceArgs a) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     const uint32_t gtid = blockIdx.x * kBlock + threadIdx.x;
-    LaneStackT<LDS_N> st(lds_stack + threadIdx.x, a.v.overflow + gtid, a.v.total_threads, a.v.status);
+    LaneStack st(lds_stack + threadIdx.x, a.v.overflow + gtid, a.v.total_threads, a.v.status);
     const int lane = threadIdx.x & 63;
     if (a.v.n_tlas_nodes == 0) {  // empty TLAS: every ray misses (test/test_tlas_stress.jl:808-831)
         RayState miss;
@@ -108,260 +108,32 @@ __global__ __launch_bounds__(kBlock, MINW) void k_trace_persistent(TraceArgs a) 
     }
 }
 
-// ---- kernels 4 / 5: kernel 3 with the top level staged in LDS (LdsTop, rc_traverse_core.h) -------------------------------
-// kernel 4 = <1024, 24>: one 1024-thread workgroup per CU (16 waves), 96 KiB of lane stacks; kernel 5 = <768, 16>: two workgroups per
-// CU keep the 24 waves per CU of kernel 3 (the shallower LDS stack costs < 2 %, measured).  Used when the scene has <= 256 instances.
-constexpr int kBigBlock = 1024;
-constexpr size_t kBigStackBytes = (size_t)kLdsStack * kBigBlock * 4;
-constexpr size_t kBigLdsBytes = kBigStackBytes + kLdsTopBytes;
-
-template <bool ANY, int BLOCK, int LDS_N, int MINW, bool TIMELINE = false, bool STATS = false, bool STACK16 = false>
-__global__ __launch_bounds__(BLOCK, MINW) void k_trace_phased_lds(TraceArgs a) {
+// ---- kernel 5: kernel 3 with the whole top level staged in LDS (LdsShape, rc_traverse_core.h): two 768-thread workgroups per CU keep the 24
+// waves per CU of kernel 3 (the shallower LDS stack costs < 2 %, measured).  Used when the scene has <= 256 instances.
+template <bool ANY, unsigned FLAGS = 0u>
+__global__ __launch_bounds__(kMidBlock, 6) void k_trace_phased_lds(TraceArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    typedef typename std::conditional<STACK16, uint16_t, uint32_t>::type entry_t;
-    constexpr size_t stack_bytes = (size_t)LDS_N * BLOCK * sizeof(entry_t);
-    constexpr int kPlanes = STACK16 ? kLdsPlaneNodes16 : kLdsPlaneNodes;
-    entry_t* lds_stack = reinterpret_cast<entry_t*>(smem);
-    const LdsTop top(smem + stack_bytes, (size_t)7 * kPlanes * sizeof(float2));
-    if (a.v.n_tlas_nodes) stage_lds_top<BLOCK, kPlanes>(top, a.v, a.blas_k, a.lds_blas_base);
-    __syncthreads();
+    const LdsTop top = LdsShape<FLAGS>::prologue(smem, a.v, a.blas_k, a.lds_blas_base, 0u, a.v.n_tlas_nodes != 0);  // (the drivers never run this shape on an empty scene; a trace launch may)
     PersistArgs p{a.n_rays, a.claim, a.refill, a.sched_thr, a.stats, a.blas_k, a.lds_blas_base, 0u, a.timeline};
-    phased_trace<ANY, LDS_N, STATS, ArraySource, HitWriter, BLOCK, true, true, false, TIMELINE, STACK16>(a.v, p, lds_stack, ArraySource{a.rays}, HitWriter{a.v.inst, a.hits}, top);
+    phased_trace<ANY, LdsShape<FLAGS>>(a.v, p, LdsShape<FLAGS>::stacks(smem), ArraySource{a.rays}, HitWriter{a.v.inst, a.hits}, top);
 }
 
 // ---- kernel 6: kernel 5's shape for top levels that do not fit (more than 256 instances): only the breadth-first tops of the TLAS and
-// of a single BLAS are staged (PARTIAL_LDS, rc_traverse_core.h); TLAS leaves and instance records come from memory as in kernel 3.
-template <bool ANY, bool STACK16 = false>
+// of a single BLAS are staged (PartialShape, rc_traverse_core.h); TLAS leaves and instance records come from memory as in kernel 3.
+template <bool ANY, unsigned FLAGS = 0u>
 __global__ __launch_bounds__(kMidBlock, 6) void k_trace_phased_partial(TraceArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    typedef typename std::conditional<STACK16, uint16_t, uint32_t>::type entry_t;
-    entry_t* lds_stack = reinterpret_cast<entry_t*>(smem);
-    LdsTop top;
-    top.tl = reinterpret_cast<float2*>(smem + (size_t)kMidStack * kMidBlock * sizeof(entry_t));
-    stage_partial_top<kMidBlock, STACK16 ? kPartialPlaneNodes16 : kPartialPlaneNodes>(top.tl, a.v, a.tlas_k, a.blas_k, a.lds_blas_base);
-    __syncthreads();
+    const LdsTop top = PartialShape<FLAGS>::prologue(smem, a.v, a.blas_k, a.lds_blas_base, a.tlas_k);
     PersistArgs p{a.n_rays, a.claim, a.refill, a.sched_thr, a.stats, a.blas_k, a.lds_blas_base, a.tlas_k};
-    phased_trace<ANY, kMidStack, false, ArraySource, HitWriter, kMidBlock, false, false, true, false, STACK16>(a.v, p, lds_stack, ArraySource{a.rays}, HitWriter{a.v.inst, a.hits}, top);
-}
-
-// ---- kernel 2: persistent waves + per-wave path scheduling --------------------------------------------
-// Kernel 1 runs the reference's three-way loop body as written, so a wave executes the interior-node,
-// triangle, instance-entry and hit-write blocks whenever ANY of its lanes needs them.  Measured on C3
-// (round 1): ~95 % of wave steps run the instance-entry block for 1-3 lanes -- half of all vector-memory
-// instructions and ~45 % of the VALU issue slots go to masked-off lanes, and both the texture path
-// (TA/TD ~75-85 % busy) and the VALU (~85 %) are what bound the kernel (the tree is cache resident).
-//
-// Here every lane carries the KIND of its next action, known before the fetch because the node numbering
-// encodes it (internal nodes 1..n-1, leaves n..2n-1, src/instanced-bvh.jl:1293-1295):
-//   INTERIOR  box tests of a TLAS/BLAS interior node          LEAF    Moeller-Trumbore on a BLAS leaf
-//   SWITCH    enter an instance (TLAS leaf) or return to the top level (sentinel popped)
-//   DONE      traversal finished, result not yet written      EMPTY   no ray
-// Per iteration the wave ballots the kinds and runs ONE block: a LEAF / SWITCH batch once `sched_thr` lanes
-// wait for it, otherwise the interior block; DONE lanes are written out and refilled together.  Waiting
-// lanes cost no issue slots.  A lane's own sequence of visits, box tests, pushes and pops is exactly the
-// reference's -- only WHEN it happens relative to other lanes moves -- so results stay bit-identical.
-// TLAS and BLAS nodes live in one array (TLAS appended) so a lane needs a single offset, and the interior
-// and leaf blocks never touch the ray registers (only SWITCH does), which keeps them free of copies.
-enum : int { K_EMPTY = 0, K_INTERIOR = 1, K_LEAF = 2, K_SWITCH = 3, K_DONE = 4 };
-
-template <bool ANY, int LDS_N, int MINW, bool STATS>
-__global__ __launch_bounds__(kBlock, MINW) void k_trace_sched(TraceArgs a) {
-    __shared__ uint32_t lds_stack[LDS_N * kBlock];
-    const uint32_t gtid = blockIdx.x * kBlock + threadIdx.x;
-    LaneStackT<LDS_N> st(lds_stack + threadIdx.x, a.v.overflow + gtid, a.v.total_threads, a.v.status);
-    const int lane = threadIdx.x & 63;
-    if (a.v.n_tlas_nodes == 0) {
-        RayState miss;
-        miss.closest_inst = -1;
-        for (uint64_t i = gtid; i < a.n_rays; i += a.v.total_threads) write_hit(miss, a.v, a.hits, i);
-        return;
-    }
-    const uint32_t n_instances = (a.v.n_tlas_nodes + 1u) >> 1;
-    const uint32_t tlas_off = a.v.tlas_off;          // TLAS nodes sit behind the BLAS nodes in a.v.blas_nodes
-    const RcNode* const nodes = a.v.blas_nodes;
-    unsigned long long pool_next = 0, pool_end = 0;
-    bool exhausted = false;
-    uint64_t my_ray = 0;
-    // per-lane ray state (see RayState); kept in scalars so each block touches only what it owns
-    float3_ wo = mk3(0, 0, 0), wd = mk3(0, 0, 0);
-    float3_ o = mk3(0, 0, 0), d = mk3(0, 0, 0), inv = mk3(0, 0, 0), ox = mk3(0, 0, 0);
-    float tmin = 0.f, closest_t = 0.f, hit_u = 0.f, hit_v = 0.f;
-    uint32_t closest_prim = RC_INVALID_NODE, node = RC_INVALID_NODE, cur_off = 0, n_level = 0;
-    int closest_inst = -1, cur_inst = -1, sp = 0, kind = K_EMPTY;
-    unsigned long long st_iter[4] = {0, 0, 0, 0}, st_lane[4] = {0, 0, 0, 0};
-
-    auto classify = [&](uint32_t nd) -> int {
-        if (nd == RC_INVALID_NODE) return K_DONE;
-        if (nd == RC_TOP_LEVEL_SENTINEL) return K_SWITCH;
-        if (nd < n_level) return K_INTERIOR;
-        return cur_inst < 0 ? K_SWITCH : K_LEAF;
-    };
-
-    for (;;) {
-        const unsigned long long m_int = __ballot(kind == K_INTERIOR), m_leaf = __ballot(kind == K_LEAF),
-                                 m_sw = __ballot(kind == K_SWITCH), m_done = __ballot(kind == K_DONE);
-        const int n_int = __popcll(m_int), n_leaf = __popcll(m_leaf), n_sw = __popcll(m_sw), n_done = __popcll(m_done);
-        const int n_live = n_int + n_leaf + n_sw;
-        const bool can_refill = !(exhausted && pool_next == pool_end);
-        if (n_live == 0 && n_done == 0 && !can_refill) break;
-        if ((can_refill && 64 - n_live >= a.refill) || n_live == 0) {
-            // write out finished lanes together, then hand the free lanes new rays
-            if (kind == K_DONE) {
-                uint4 w0, w1;
-                if (closest_inst >= 0) {  // :2010-2017
-                    const uint4 m3 = *(reinterpret_cast<const uint4*>(a.v.inst + closest_inst) + 3);
-                    w0 = make_uint4(1u, __float_as_uint(closest_t), m3.y + closest_prim - 1u, m3.z);
-                    w1 = make_uint4(__float_as_uint(hit_u), __float_as_uint(hit_v), (uint32_t)closest_inst, 0u);
-                } else {  // :2018-2023
-                    w0 = make_uint4(0u, 0u, RC_INVALID_NODE, 0u);
-                    w1 = make_uint4(0u, 0u, RC_INVALID_NODE, 0u);
-                }
-                uint4* out = reinterpret_cast<uint4*>(a.hits + my_ray);
-                out[0] = w0;
-                out[1] = w1;
-                kind = K_EMPTY;
-            }
-            for (;;) {
-                const unsigned long long free_mask = __ballot(kind == K_EMPTY);
-                const int n_free = __popcll(free_mask);
-                if (n_free == 0) break;
-                if (pool_next == pool_end) {
-                    if (exhausted) break;
-                    // one chunk of rays from this wave's shard of the interleaved chunk counters (RcClaim, rc_traverse_core.h)
-                    if (!rc_claim_chunk(a.claim, nullptr, (blockIdx.x * kBlock + threadIdx.x) >> 6, lane, a.n_rays, pool_next, pool_end)) { exhausted = true; break; }
-                }
-                const unsigned long long left = pool_end - pool_next;
-                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(free_mask >> 32),
-                                                                __builtin_amdgcn_mbcnt_lo((unsigned)free_mask, 0u));
-                if (kind == K_EMPTY && rank < left) {
-                    my_ray = pool_next + rank;
-                    const RcRay r = load_ray(a.rays, my_ray);
-                    // init (:1904-1927); check_direction (src/ray.jl:39-49)
-                    wo = mk3(r.ox, r.oy, r.oz);
-                    wd = mk3(r.dx == 0.0f ? 0.0f : r.dx, r.dy == 0.0f ? 0.0f : r.dy, r.dz == 0.0f ? 0.0f : r.dz);
-                    o = wo; d = wd;
-                    inv = mk3(safe_inv1(d.x), safe_inv1(d.y), safe_inv1(d.z));
-                    ox = mk3(-o.x * inv.x, -o.y * inv.y, -o.z * inv.z);
-                    tmin = ANY ? 0.0f : r.tmin;
-                    closest_t = r.tmax;
-                    hit_u = hit_v = 0.0f;
-                    closest_prim = RC_INVALID_NODE;
-                    closest_inst = -1; cur_inst = -1;
-                    cur_off = tlas_off; n_level = n_instances;
-                    sp = 0;
-                    st.push(sp, RC_INVALID_NODE);
-                    node = 1;
-                    kind = classify(node);
-                }
-                pool_next += ((unsigned long long)n_free < left) ? (unsigned long long)n_free : left;
-            }
-            continue;
-        }
-        int path;
-        if (n_leaf >= a.sched_thr && n_leaf >= n_sw) path = K_LEAF;
-        else if (n_sw >= a.sched_thr) path = K_SWITCH;
-        else if (n_int > 0) path = K_INTERIOR;
-        else path = (n_leaf >= n_sw) ? K_LEAF : K_SWITCH;
-        if (STATS) { st_iter[path] += 1; st_lane[path] += (kind == path) ? 1 : 0; st_lane[0] += (kind >= K_INTERIOR && kind <= K_SWITCH) ? 1 : 0; st_iter[0] += 1; }
-
-        if (path == K_INTERIOR) {
-            if (kind == K_INTERIOR) {
-                // intersect_internal_node (:1807-1832) + push far / descend near / pop (:1946-1960, 1991-1993)
-                const float4* q = reinterpret_cast<const float4*>(nodes + (cur_off + node - 1));
-                const float4 na = q[0], nb = q[1], nc = q[2];
-                const uint2 ch = *reinterpret_cast<const uint2*>(q + 3);
-                // packed node (rc_pack_node): na = child-0 (min.x,min.y,max.x,max.y), nb = child-1 likewise, nc = z of both
-                const v2f ixy = {inv.x, inv.y}, oxy = {ox.x, ox.y}, izz = {inv.z, inv.z}, ozz = {ox.z, ox.z};
-                const v2f n0xy = v2f{na.x, na.y} * ixy + oxy, f0xy = v2f{na.z, na.w} * ixy + oxy;
-                const v2f n1xy = v2f{nb.x, nb.y} * ixy + oxy, f1xy = v2f{nb.z, nb.w} * ixy + oxy;
-                const v2f nf0z = v2f{nc.x, nc.y} * izz + ozz, nf1z = v2f{nc.z, nc.w} * izz + ozz;
-                const float f0x = f0xy.x, f0y = f0xy.y, f0z = nf0z.y, n0x = n0xy.x, n0y = n0xy.y, n0z = nf0z.x;
-                const float f1x = f1xy.x, f1y = f1xy.y, f1z = nf1z.y, n1x = n1xy.x, n1y = n1xy.y, n1z = nf1z.x;
-                const float t0_max = jl_minf(jl_minf(jl_minf(jl_maxf(f0x, n0x), jl_maxf(f0y, n0y)), jl_maxf(f0z, n0z)), closest_t);
-                const float t0_min = jl_maxf(jl_maxf(jl_maxf(jl_minf(f0x, n0x), jl_minf(f0y, n0y)), jl_minf(f0z, n0z)), tmin);
-                const float t1_max = jl_minf(jl_minf(jl_minf(jl_maxf(f1x, n1x), jl_maxf(f1y, n1y)), jl_maxf(f1z, n1z)), closest_t);
-                const float t1_min = jl_maxf(jl_maxf(jl_maxf(jl_minf(f1x, n1x), jl_minf(f1y, n1y)), jl_minf(f1z, n1z)), tmin);
-                const uint32_t trav0 = (t0_min <= t0_max) ? ch.x : RC_INVALID_NODE;
-                const uint32_t trav1 = (t1_min <= t1_max) ? ch.y : RC_INVALID_NODE;
-                const bool first0 = (t0_min < t1_min) && (trav0 != RC_INVALID_NODE);
-                const uint32_t near_c = first0 ? trav0 : trav1, far_c = first0 ? trav1 : trav0;
-                if (far_c != RC_INVALID_NODE) st.push(sp, far_c);
-                node = (near_c != RC_INVALID_NODE) ? near_c : st.pop(sp);
-                kind = classify(node);
-            }
-        } else if (path == K_LEAF) {
-            if (kind == K_LEAF) {
-                // intersect_leaf_node -> fast_intersect_triangle (:1756-1797, 1868-1881), then pop
-                const RcNode* np = nodes + (cur_off + node - 1);
-                const float4* q = reinterpret_cast<const float4*>(np);
-                const float4 na = q[0];
-                const float4 nb = q[1];
-                const float4 nc = q[2];
-                const float3_ v0 = mk3(na.w, na.x, na.y), e1 = mk3(nb.y, nb.z, nb.x), e2 = mk3(nc.y, nc.z, nc.x);  // rc_pack_leaf: v0 and the edges
-                const float3_ s1 = cross3(d, e2);
-                const float det = dot3(s1, e1);
-                const float invd = 1.0f / det;
-                const float3_ dd = sub3(o, v0);
-                const float u = dot3(dd, s1) * invd;
-                const float3_ s2 = cross3(dd, e1);
-                const float v = dot3(d, s2) * invd;
-                const float t = dot3(e2, s2) * invd;
-                const bool hit = !(u < 0.0f || u > 1.0f) && !(v < 0.0f || (u + v) > 1.0f) && !(t < tmin || t > closest_t);
-                if (hit) {
-                    closest_t = t;
-                    closest_inst = cur_inst;
-                    closest_prim = node - n_level + 1u;  // leaf of sorted primitive j sits at n-1+j (child1 = j)
-                    hit_u = u; hit_v = v;
-                }
-                if (ANY && hit) node = RC_INVALID_NODE;  // :2106-2115
-                else node = st.pop(sp);
-                kind = classify(node);
-            }
-        } else {
-            if (kind == K_SWITCH) {
-                if (node == RC_TOP_LEVEL_SENTINEL) {
-                    // back to the top level (:1996-2006)
-                    node = st.pop(sp);
-                    cur_inst = -1;
-                    cur_off = tlas_off; n_level = n_instances;
-                    o = wo; d = wd;
-                    inv = mk3(safe_inv1(d.x), safe_inv1(d.y), safe_inv1(d.z));
-                    ox = mk3(-o.x * inv.x, -o.y * inv.y, -o.z * inv.z);
-                } else {
-                    // top-level leaf: enter the instance (:1961-1977)
-                    cur_inst = (int)(nodes + (cur_off + node - 1))->child1;
-                    st.push(sp, RC_TOP_LEVEL_SENTINEL);
-                    node = 1;
-                    const float4* q = reinterpret_cast<const float4*>(a.v.inst + cur_inst);
-                    const float4 m0 = q[0], m1 = q[1], m2 = q[2];
-                    const uint4 m3 = *reinterpret_cast<const uint4*>(q + 3);
-                    cur_off = m3.x;
-                    n_level = m3.w;
-                    o = mk3(m0.x * wo.x + m0.y * wo.y + m0.z * wo.z + m0.w, m1.x * wo.x + m1.y * wo.y + m1.z * wo.z + m1.w,
-                            m2.x * wo.x + m2.y * wo.y + m2.z * wo.z + m2.w);
-                    d = mk3(m0.x * wd.x + m0.y * wd.y + m0.z * wd.z, m1.x * wd.x + m1.y * wd.y + m1.z * wd.z,
-                            m2.x * wd.x + m2.y * wd.y + m2.z * wd.z);
-                    inv = mk3(safe_inv1(d.x), safe_inv1(d.y), safe_inv1(d.z));
-                    ox = mk3(-o.x * inv.x, -o.y * inv.y, -o.z * inv.z);
-                }
-                kind = classify(node);
-            }
-        }
-    }
-    if (STATS) {
-        for (int k = 0; k < 4; ++k) {
-            if (lane == 0) atomicAdd(&a.stats[2 * k], st_iter[k]);
-            atomicAdd(&a.stats[2 * k + 1], st_lane[k]);
-        }
-    }
+    phased_trace<ANY, PartialShape<FLAGS>>(a.v, p, PartialShape<FLAGS>::stacks(smem), ArraySource{a.rays}, HitWriter{a.v.inst, a.hits}, top);
 }
 
 // ---- kernel 3: the phase-structured persistent core (rc_traverse_core.h) on a ray array ------------------------
-template <bool ANY, int LDS_N, int MINW, bool STATS>
-__global__ __launch_bounds__(kBlock, MINW) void k_trace_phased(TraceArgs a) {
-    __shared__ uint32_t lds_stack[LDS_N * kBlock];
+template <bool ANY, unsigned FLAGS = 0u>
+__global__ __launch_bounds__(kBlock, 6) void k_trace_phased(TraceArgs a) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     PersistArgs p{a.n_rays, a.claim, a.refill, a.sched_thr, a.stats, 0u, 0u, 0u};
-    phased_trace<ANY, LDS_N, STATS>(a.v, p, lds_stack, ArraySource{a.rays}, HitWriter{a.v.inst, a.hits});
+    phased_trace<ANY, PlainShape<FLAGS>>(a.v, p, lds_stack, ArraySource{a.rays}, HitWriter{a.v.inst, a.hits});
 }
 
 }  // namespace
@@ -584,9 +356,6 @@ void rc_ensure_dynamic_lds(rc_scene* s, const void* fn, size_t bytes) {
 bool rc_lds_driver_ok(rc_scene* s) {
     return s->opt.kernel != 3 && s->n_tlas_nodes > 0 && s->n_tlas_nodes <= (uint32_t)kTlasLdsNodes && (uint64_t)(s->n_flat_nodes + s->n_tlas_nodes) * 64u < (1ull << 32);
 }
-uint32_t rc_lds_driver_blocks(rc_scene* s, uint64_t n_items) {
-    return (uint32_t)std::min<uint64_t>((n_items + kMidBlock - 1) / kMidBlock, (uint64_t)s->n_cus * 2);
-}
 // ... and the partial-LDS variants under the conditions of trace kernel 6: a larger top level with something to stage
 bool rc_partial_driver_ok(rc_scene* s) {
     return s->opt.kernel != 3 && s->n_tlas_nodes > (uint32_t)kTlasLdsNodes && s->tlas_top_k32 + s->blas_top_k32 > 0 &&
@@ -599,73 +368,50 @@ void rc_lds_driver_args(rc_scene* s, rc::PersistArgs& p) {
     if (s->opt.blas_top) { p.blas_k = s->blas_top_k32; p.lds_blas_base = (s->n_tlas_nodes + 1) / 2 - 1; }
 }
 
-uint32_t rc_persistent_blocks(rc_scene* s, uint64_t n_items) {
-    const int per_cu = s->opt.blocks_per_cu > 0 ? (int)s->opt.blocks_per_cu : 6;  // 6 x 24 KiB LDS stacks per CU
-    uint64_t want = (n_items + kBlock - 1) / kBlock, cap = (uint64_t)s->n_cus * per_cu;
-    return (uint32_t)(want < cap ? want : cap);
+// The grid of a persistent launch over n_items: a block per `block` items, at most the blocks that are resident together -- `per_cu` a
+// CU (TraceShape::kBlocksPerCu), for the 256-thread shapes what option "blocks_per_cu" says, else 6 (6 x 24 KiB of LDS stacks per CU).
+uint32_t rc_grid_blocks(rc_scene* s, uint64_t n_items, int block, int64_t per_cu) {
+    if (per_cu == 0) per_cu = s->opt.blocks_per_cu > 0 ? s->opt.blocks_per_cu : 6;
+    return (uint32_t)std::min<uint64_t>((n_items + block - 1) / block, (uint64_t)s->n_cus * per_cu);
 }
 
 // kernels 5 / 6 in their STACK16 shape: the scene's trees are all small enough, nobody asked for counters or a timeline (dev builds keep the 32-bit shape)
 static bool rc_stack16(rc_scene* s) { return s->small_trees && s->opt.stack16 && !s->opt.timeline_ptr; }
 
+// Which instantiation runs a launch of `kernel` (0, 1, 3, 5 or 6: rc_launch_trace has applied the fall-back rules).
 template <bool ANY>
 static void launch_variant(RcLaunchGuard& g, int64_t kernel, const TraceArgs& a, uint32_t blocks) {
     rc_scene* s = g.s;
-    const hipStream_t stream = g.stream;
-    const int64_t lds = s->opt.lds_stack;
-    const bool stats = s->opt.stats != 0;
+    const bool stats = s->opt.stats != 0, s16 = rc_stack16(s);
     // The launch's timing / ordering events ride on the kernel's own dispatch (hipExtLaunchKernelGGL binds them to its start and end): no
     // event packets of their own around the kernel -- they cost ~3 us each between two back-to-back launches.  (Null outside RcLaunchGuard::bind.)
     hipEvent_t e0 = g.carry_t0, e1 = g.carry_t1;
     g.carried = e0 != nullptr;
-#define RC_LAUNCH_P(L, W) hipExtLaunchKernelGGL((k_trace_persistent<ANY, L, W, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a)
-#define RC_LAUNCH_S(L, W) hipExtLaunchKernelGGL((k_trace_simple<ANY, L, W>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a)
-// a kernel with dynamic LDS: the function's limit is raised first, once per scene = per device (the attribute belongs to the function on one device)
-#define RC_LAUNCH_LDS(K, BLOCK, BYTES) do { rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&K), BYTES); hipExtLaunchKernelGGL(K, dim3(blocks), dim3(BLOCK), BYTES, stream, e0, e1, 0u, a); } while (0)
-    if (kernel == 4) {
-        RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kBigBlock, kLdsStack, 4>), kBigBlock, kBigLdsBytes);
-    } else if (kernel == 5) {
-        rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6>), kMidLdsBytes);  // (as before: whichever variant runs)
-        if (stats && rc_stack16(s))  // dev: the same kernel with per-phase pass / lane counters (option "stats"; tools/isa_mix.py weights the phases' static opcode histograms with them)
-            RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, true, true>), kMidBlock, kMidLdsBytes16);
-        else if (stats)
-            RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, true>), kMidBlock, kMidLdsBytes);
-        else if (a.timeline)  // dev: the same kernel with per-wave event times written to the caller's buffer (option "timeline_ptr")
-            RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, true>), kMidBlock, kMidLdsBytes);
-        else if (rc_stack16(s))
-            RC_LAUNCH_LDS((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6, false, false, true>), kMidBlock, kMidLdsBytes16);
-        else
-            hipExtLaunchKernelGGL((k_trace_phased_lds<ANY, kMidBlock, kMidStack, 6>), dim3(blocks), dim3(kMidBlock), kMidLdsBytes, stream, e0, e1, 0u, a);
-    } else if (kernel == 6 && rc_stack16(s)) {
-        RC_LAUNCH_LDS((k_trace_phased_partial<ANY, true>), kMidBlock, kPartialLdsBytes16);
+    // a kernel with dynamic LDS: the function's limit is raised first, once per scene = per device (the attribute belongs to the function on one device)
+    auto launch = [&](void (*k)(TraceArgs), auto shape) {
+        if (shape.kLdsBytes) rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(k), shape.kLdsBytes);
+        hipExtLaunchKernelGGL(k, dim3(blocks), dim3(shape.kBlock), (uint32_t)shape.kLdsBytes, g.stream, e0, e1, 0u, a);
+    };
+    if (kernel == 5) {
+        // dev: the same kernel with per-phase pass / lane counters (option "stats"; tools/isa_mix.py weights the phases' static opcode histograms
+        // with them), or with per-wave event times written to the caller's buffer (option "timeline_ptr")
+        if (stats && s16) launch(k_trace_phased_lds<ANY, ShapeStats | ShapeStack16>, LdsShape<ShapeStats | ShapeStack16>());
+        else if (stats) launch(k_trace_phased_lds<ANY, ShapeStats>, LdsShape<ShapeStats>());
+        else if (a.timeline) launch(k_trace_phased_lds<ANY, ShapeTimeline>, LdsShape<ShapeTimeline>());
+        else if (s16) launch(k_trace_phased_lds<ANY, ShapeStack16>, LdsShape<ShapeStack16>());
+        else launch(k_trace_phased_lds<ANY>, LdsShape<>());
     } else if (kernel == 6) {
-        RC_LAUNCH_LDS((k_trace_phased_partial<ANY>), kMidBlock, kPartialLdsBytes);
+        if (s16) launch(k_trace_phased_partial<ANY, ShapeStack16>, PartialShape<ShapeStack16>());
+        else launch(k_trace_phased_partial<ANY>, PartialShape<>());
     } else if (kernel == 3) {
-        if (stats) hipExtLaunchKernelGGL((k_trace_phased<ANY, 24, 6, true>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
-        else if (lds == 16) hipExtLaunchKernelGGL((k_trace_phased<ANY, 16, 8, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
-        else if (lds == 20) hipExtLaunchKernelGGL((k_trace_phased<ANY, 20, 7, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
-        else if (lds == 17) hipExtLaunchKernelGGL((k_trace_phased<ANY, 16, 6, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
-        else if (lds == 13) hipExtLaunchKernelGGL((k_trace_phased<ANY, 12, 6, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
-        else hipExtLaunchKernelGGL((k_trace_phased<ANY, 24, 6, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
-    } else if (kernel == 2) {
-        if (stats) hipExtLaunchKernelGGL((k_trace_sched<ANY, 24, 6, true>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
-        else if (lds == 16) hipExtLaunchKernelGGL((k_trace_sched<ANY, 16, 8, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
-        else hipExtLaunchKernelGGL((k_trace_sched<ANY, 24, 6, false>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
+        if (stats) launch(k_trace_phased<ANY, ShapeStats>, PlainShape<ShapeStats>());
+        else launch(k_trace_phased<ANY>, PlainShape<>());
     } else if (kernel == 0) {
-        if (lds == 12) RC_LAUNCH_S(12, 8); else if (lds == 16) RC_LAUNCH_S(16, 8); else if (lds == 32) RC_LAUNCH_S(32, 4); else RC_LAUNCH_S(24, 6);
-    } else if (stats) {
-        hipExtLaunchKernelGGL((k_trace_persistent<ANY, 24, 6, true>), dim3(blocks), dim3(kBlock), 0, stream, e0, e1, 0u, a);
+        launch(k_trace_simple<ANY>, PlainShape<>());
     } else {
-        if (lds == 12) RC_LAUNCH_P(12, 8); else if (lds == 16) RC_LAUNCH_P(16, 8); else if (lds == 32) RC_LAUNCH_P(32, 4); else RC_LAUNCH_P(24, 6);
+        if (stats) launch(k_trace_persistent<ANY, true>, PlainShape<>());
+        else launch(k_trace_persistent<ANY, false>, PlainShape<>());
     }
-#undef RC_LAUNCH_P
-#undef RC_LAUNCH_S
-#undef RC_LAUNCH_LDS
-}
-
-uint32_t rc_blocks_per_cu(rc_scene* s) {
-    if (s->opt.blocks_per_cu > 0) return (uint32_t)s->opt.blocks_per_cu;
-    switch (s->opt.lds_stack) { case 12: case 16: return 8; case 20: return 7; case 32: return 4; default: return 6; }
 }
 
 // ---- cost-ordered claiming (RcClaim::order / cost / hist) -------------------------------------------------------------------------------
@@ -932,22 +678,16 @@ bool rc_cost_order_setup(RcLaunchGuard& g, uint64_t n, int any_hit, rc::RcClaim&
 void rc_launch_trace(rc_scene* s, const RcRay* d_rays, RcHit* d_hits, uint64_t n, int any_hit, hipStream_t stream, bool learn_order) {
     if (n == 0) return;
     RcLaunchGuard launch(s, stream);  // serialises the enqueue: trace calls on one scene may come from several host threads
-    uint64_t want = (n + kBlock - 1) / kBlock, cap = (uint64_t)s->n_cus * rc_blocks_per_cu(s);
-    uint32_t blocks = (uint32_t)(want < cap ? want : cap);
+    uint32_t blocks = rc_grid_blocks(s, n, kBlock, PlainShape<>::kBlocksPerCu);
     uint32_t total_threads = blocks * kBlock;
     int64_t kernel = s->opt.kernel;  // the fall-back rules below choose for this launch only
     if (kernel < 0)  // auto: tiny batches gain nothing from refilling; a TLAS that fits the LDS planes (<= 256 instances) is read from there
         kernel = (n < (uint64_t)total_threads * 5 / 4) ? 0 : (s->n_tlas_nodes <= (uint32_t)kTlasLdsNodes ? 5 : 6);  // measured crossover (tools/archive/small_batch_probe.py): ~1.2 rays per resident lane
-    if (kernel == 4 && (s->n_tlas_nodes > (uint32_t)kTlasLdsNodes || s->n_static_instances > (uint32_t)kTlasLdsInst)) kernel = 3;
     if (kernel == 5 && s->n_tlas_nodes > (uint32_t)kTlasLdsNodes) kernel = 3;
     if (kernel == 6 && s->tlas_top_k + s->blas_top_k == 0) kernel = 3;  // nothing to stage
     if (kernel >= 3 && ((uint64_t)(s->n_flat_nodes + s->n_tlas_nodes) * 64u >= (1ull << 32) || n >= (1ull << 38))) kernel = 1;  // buffer offsets and chunk ids are 32-bit
-    if (kernel == 4) {  // one 1024-thread workgroup per CU
-        blocks = (uint32_t)std::min<uint64_t>((n + kBigBlock - 1) / kBigBlock, (uint64_t)s->n_cus);
-        total_threads = blocks * kBigBlock;
-    }
-    if (kernel == 5 || kernel == 6) {  // two 768-thread workgroups per CU
-        blocks = (uint32_t)std::min<uint64_t>((n + kMidBlock - 1) / kMidBlock, (uint64_t)s->n_cus * (s->opt.blocks_per_cu == 1 ? 1 : 2));
+    if (kernel == 5 || kernel == 6) {  // two 768-thread workgroups per CU (LdsShape and PartialShape share the grid)
+        blocks = rc_grid_blocks(s, n, kMidBlock, s->opt.blocks_per_cu == 1 ? 1 : LdsShape<>::kBlocksPerCu);
         total_threads = blocks * kMidBlock;
     }
     TraceArgs a;
@@ -956,11 +696,11 @@ void rc_launch_trace(rc_scene* s, const RcRay* d_rays, RcHit* d_hits, uint64_t n
     a.rays = d_rays; a.hits = d_hits; a.n_rays = n;
     rc_claim_fill(launch, n, total_threads / 64u, a.claim);
     a.refill = (int)s->opt.refill;
-    a.sched_thr = kernel == 2 ? 32 : (int)s->opt.sched_thr;  // kernel 2's vote threshold is its own (lanes that must wait for a batch), tuned at 32
+    a.sched_thr = (int)s->opt.sched_thr;
     a.stats = rc_stats_words(s);
     a.timeline = reinterpret_cast<unsigned long long*>(s->opt.timeline_ptr);
     const bool wide = rc_stack16(s);  // the STACK16 shape stages all of the renumbered tops, the 32-bit shape a prefix
-    if ((kernel == 5 || kernel == 4) && s->opt.blas_top) { a.blas_k = (wide && kernel == 5) ? s->blas_top_k : s->blas_top_k32; a.lds_blas_base = (s->n_tlas_nodes + 1) / 2 - 1; }
+    if (kernel == 5 && s->opt.blas_top) { a.blas_k = wide ? s->blas_top_k : s->blas_top_k32; a.lds_blas_base = (s->n_tlas_nodes + 1) / 2 - 1; }
     if (kernel == 6) {  // a plan made for the full-LDS kernels (<= 256 instances) has no TLAS renumbering: tlas_k = 0, its blas_k still fits
         a.tlas_k = wide ? s->tlas_top_k : s->tlas_top_k32; a.blas_k = s->opt.blas_top ? (wide ? s->blas_top_k : s->blas_top_k32) : 0; a.lds_blas_base = a.tlas_k;
     }

@@ -264,7 +264,7 @@ struct TraceArgs {
     uint64_t n_rays;
     RcClaim claim;                     // persistent kernels: how waves claim ray chunks
     int refill;                        // persistent kernel: refill when this many lanes are idle
-    int sched_thr;                     // scheduled kernel: run a leaf/entry batch once this many lanes wait for it
+    int sched_thr;                     // phased kernels: PersistArgs::int_thr
     unsigned long long* stats;         // optional instrumentation (dev builds), else nullptr
     uint32_t blas_k = 0, lds_blas_base = 0, tlas_k = 0;
     unsigned long long* timeline = nullptr;  // dev (option "timeline_ptr"): per-wave event record of kernel 5
@@ -530,8 +530,8 @@ struct HitWriter {
 };
 
 // ---- persistent waves, phase-structured ("while-while") scheduling: the core of trace kernel 3 and of the drivers ----
-// Same idea as kernel 2 -- run one block at a time for the lanes that need it -- but with a fixed phase order
-// instead of a per-iteration vote: an inner loop walks interior nodes for as long as at least `int_thr`
+// Run one block of the loop body at a time, for the lanes that need it, in a fixed phase order:
+// an inner loop walks interior nodes for as long as at least `int_thr`
 // lanes have one pending (always at least once), then ONE pass each over the BLAS-leaf lanes, the level-switch
 // lanes (instance entry / return to top level) and the finished lanes (write-out + refill).  The inner loop
 // only touches {node, sp} so the compiler keeps the ray registers untouched across it.  Per-lane order of
@@ -564,45 +564,42 @@ struct PersistArgs {
     int refill;                        // refill when this many lanes are free
     int int_thr;                       // leave the interior loop when fewer lanes than this have an interior node pending
     unsigned long long* stats;
-    uint32_t blas_k = 0;               // TLAS_LDS kernels: BLAS nodes 1..blas_k are staged in the planes at entry lds_blas_base + node - 1
+    uint32_t blas_k = 0;               // Top::Lds shapes: BLAS nodes 1..blas_k are staged in the planes at entry lds_blas_base + node - 1
     uint32_t lds_blas_base = 0;
-    uint32_t tlas_k = 0;               // PARTIAL_LDS kernels: TLAS nodes 1..tlas_k are staged at entry node - 1 (the rest comes from memory)
+    uint32_t tlas_k = 0;               // Top::PartialLds shapes: TLAS nodes 1..tlas_k are staged at entry node - 1 (the rest comes from memory)
     unsigned long long* timeline = nullptr;  // TIMELINE builds (dev): 8 words per wave, see the end of phased_trace
 };
 
-// TLAS_LDS / INST_LDS: the block has staged the top level in LDS before the call (LdsTop below; layout and sizes in rc_internal.h):
-// packed nodes as seven float2 planes (dword pairs 0-1, 2-3, ... 12-13 of each node; a plane read is one ds_read_b64 with lane
-// addresses 8 bytes apart per node), the TLAS leaf -> instance table, and the instance records as float2 planes.  TLAS-level visits
-// and instance entries then never touch the vector-memory path, which is what bounds the kernel.
-// kTlasLdsNodes, kTlasLdsInst, kLdsPlaneNodes: rc_internal.h (the TLAS build needs them too)
-
-// Shape of the two-workgroups-per-CU LDS kernels (trace kernel 5 and the LDS variants of the drivers): 768 threads, 16-entry LDS lane
-// stacks (48 KiB) + node planes (17 KiB) + leaf table (1 KiB) + instance planes (14 KiB) = 79.95 KiB per workgroup.
-constexpr int kMidBlock = 768, kMidStack = 16;
-constexpr size_t kNodePlaneBytes = (size_t)7 * kLdsPlaneNodes * sizeof(float2);
+// What a workgroup stages in LDS before it calls phased_trace (TraceShape::prologue below; layout and sizes in rc_internal.h):
+//   Top::Memory      nothing: every node and instance record comes through the vector-memory path.
+//   Top::Lds         the whole top level: packed nodes as seven float2 planes (dword pairs 0-1, 2-3, ... 12-13 of each node; a plane read is
+//                    one ds_read_b64 with lane addresses 8 bytes apart per node), the TLAS leaf -> instance table, and the instance records
+//                    as float2 planes.  TLAS-level visits and instance entries then never touch the vector-memory path, which is what bounds
+//                    the kernel.  Scenes of at most kTlasLdsInst instances.
+//   Top::PartialLds  larger top levels: the planes hold only the breadth-first top of the TLAS -- rc_build_tlas renumbers the TLAS's
+//                    internal nodes in the traversal copy the way it does for a single BLAS -- and of a single BLAS; TLAS leaves, instance
+//                    records and everything below the tops are read from memory as with Top::Memory.
+// kTlasLdsNodes, kTlasLdsInst, k*PlaneNodes*: rc_internal.h (the TLAS build needs them too)
+enum class Top { Memory, Lds, PartialLds };
+enum ShapeFlags : unsigned {
+    ShapeStack16 = 1u,   // 16-bit lane-stack entries (scenes whose trees all have fewer than 65 534 nodes); the LDS they give up holds more node planes
+    ShapeStats = 2u,     // dev: per-phase pass / lane counters (option "stats")
+    ShapeTimeline = 4u,  // dev: per-wave event times (option "timeline_ptr")
+};
+constexpr int kMidBlock = 768, kMidStack = 16;  // the two-workgroups-per-CU shapes: 24 waves per CU as with six 256-thread blocks
 constexpr size_t kLeafTableBytes = (size_t)kTlasLdsInst * sizeof(uint32_t);
 constexpr size_t kInstPlaneBytes = (size_t)7 * kTlasLdsInst * sizeof(float2);
-constexpr size_t kLdsTopBytes = kNodePlaneBytes + kLeafTableBytes + kInstPlaneBytes;
-constexpr size_t kMidLdsBytes = (size_t)kMidStack * kMidBlock * 4 + kLdsTopBytes;
-// STACK16 shape (scenes whose trees all have fewer than 65 534 nodes: 16-bit lane stacks, 24 KiB instead of 48): kLdsPlaneNodes16 node-plane entries
-constexpr size_t kNodePlaneBytes16 = (size_t)7 * kLdsPlaneNodes16 * sizeof(float2);
-constexpr size_t kMidLdsBytes16 = (size_t)kMidStack * kMidBlock * 2 + kNodePlaneBytes16 + kLeafTableBytes + kInstPlaneBytes;
-#if RC_LDS_PLANES16 == 748
-static_assert(kMidLdsBytes <= 81920 && kMidLdsBytes16 <= 81920, "two workgroups per CU share 160 KiB of LDS");
-#else   // dev variant (tools/lds_bound_probe.py): one workgroup per CU
-static_assert(kMidLdsBytes <= 81920 && kMidLdsBytes16 <= 163840, "one workgroup per CU has 160 KiB of LDS");
-#endif
 struct LdsTop {
     float2* tl;    // node planes: plane p of entry e at tl[p * (plane entries) + e]
     uint32_t* lt;  // lt[j] = instance index of TLAS leaf n - 1 + j + 1 (node index n + j)
     float2* il;    // instance planes: plane p of instance i at il[p * kTlasLdsInst + i]; planes 0-5 = inverse transform, 6 = (nodes offset, leaf count)
-    __device__ inline explicit LdsTop(unsigned char* base, size_t node_plane_bytes = kNodePlaneBytes)
+    __device__ inline LdsTop(unsigned char* base, size_t node_plane_bytes)
         : tl(reinterpret_cast<float2*>(base)), lt(reinterpret_cast<uint32_t*>(base + node_plane_bytes)),
           il(reinterpret_cast<float2*>(base + node_plane_bytes + kLeafTableBytes)) {}
     __device__ inline LdsTop() : tl(nullptr), lt(nullptr), il(nullptr) {}
 };
-// Fill it (all threads of the workgroup; caller synchronises).  n_inst <= kTlasLdsInst, blas_k <= kLdsPlaneNodes - (n_inst - 1).
-template <int BLOCK, int PLANE_NODES = kLdsPlaneNodes>
+// Fill it (all threads of the workgroup; caller synchronises).  n_inst <= kTlasLdsInst, blas_k <= PLANE_NODES - (n_inst - 1).
+template <int BLOCK, int PLANE_NODES>
 __device__ inline void stage_lds_top(const LdsTop& t, const SceneView& v, uint32_t blas_k, uint32_t lds_blas_base) {
     const RcNode* tnodes = v.blas_nodes + v.tlas_off;
     const uint32_t n_inst = (v.n_tlas_nodes + 1u) >> 1;
@@ -623,16 +620,7 @@ __device__ inline void stage_lds_top(const LdsTop& t, const SceneView& v, uint32
         t.il[p * kTlasLdsInst + in] = make_float2(__uint_as_float(a), __uint_as_float(b));
     }
 }
-
-// PARTIAL_LDS (top levels too large for TLAS_LDS): the planes (kPartialPlaneNodes entries) hold only the breadth-first top of the TLAS
-// -- rc_build_tlas renumbers the TLAS's internal nodes in the traversal copy the way it does for a single BLAS -- and of a single BLAS;
-// TLAS leaves, instance records and everything below the tops are read from memory as in the plain kernel.
-constexpr size_t kPartialPlaneBytes = (size_t)7 * kPartialPlaneNodes * sizeof(float2);
-constexpr size_t kPartialLdsBytes = (size_t)kMidStack * kMidBlock * 4 + kPartialPlaneBytes;
-constexpr size_t kPartialPlaneBytes16 = (size_t)7 * kPartialPlaneNodes16 * sizeof(float2);
-constexpr size_t kPartialLdsBytes16 = (size_t)kMidStack * kMidBlock * 2 + kPartialPlaneBytes16;
-static_assert(kPartialLdsBytes <= 81920 && kPartialLdsBytes16 <= 81920, "two workgroups per CU share 160 KiB of LDS");
-template <int BLOCK, int PLANE_NODES = kPartialPlaneNodes>
+template <int BLOCK, int PLANE_NODES>
 __device__ inline void stage_partial_top(float2* tl, const SceneView& v, uint32_t tlas_k, uint32_t blas_k, uint32_t lds_blas_base) {
     const RcNode* tnodes = v.blas_nodes + v.tlas_off;
     for (uint32_t i = threadIdx.x; i < tlas_k * 7u; i += BLOCK) {
@@ -644,6 +632,51 @@ __device__ inline void stage_partial_top(float2* tl, const SceneView& v, uint32_
         tl[p * PLANE_NODES + lds_blas_base + nd] = reinterpret_cast<const float2*>(v.blas_nodes + nd)[p];
     }
 }
+
+// Everything that tells one instantiation of phased_trace and its shell from another: workgroup size, LDS depth of the lane stacks, what
+// is staged in LDS, the flags -- and what follows from them.
+template <int BLOCK, int LDS_N, Top TOP, unsigned FLAGS = 0u>
+struct TraceShape {
+    static constexpr int kBlock = BLOCK, kLdsDepth = LDS_N;
+    static constexpr Top top = TOP;
+    static constexpr bool kStack16 = (FLAGS & ShapeStack16) != 0, kStats = (FLAGS & ShapeStats) != 0, kTimeline = (FLAGS & ShapeTimeline) != 0;
+    typedef typename std::conditional<kStack16, uint16_t, uint32_t>::type entry_t;  // a lane-stack entry in LDS
+    static constexpr int kBlocksPerCu = BLOCK == rc::kBlock ? 0 : 2;  // workgroups the grid rule (rc_grid_blocks) puts on a CU; 0: option "blocks_per_cu"
+    // entries per node plane: 310 / 748 (32- / 16-bit stacks) beside the leaf table and the instance planes, 585 / 1 023 alone
+    static constexpr int kPlaneNodes = TOP == Top::PartialLds ? (kStack16 ? kPartialPlaneNodes16 : kPartialPlaneNodes) : (kStack16 ? kLdsPlaneNodes16 : kLdsPlaneNodes);
+    static constexpr size_t kStackBytes = (size_t)LDS_N * BLOCK * sizeof(entry_t);
+    static constexpr size_t kPlaneBytes = (size_t)7 * kPlaneNodes * sizeof(float2);
+    // dynamic LDS of a workgroup (0: the shell declares its lane stacks statically).  768 x 16 entries of stacks (48 / 24 KiB) + node planes
+    // + leaf table (1 KiB) + instance planes (14 KiB) = 79.95 KiB for Top::Lds
+    static constexpr size_t kLdsBytes = TOP == Top::Memory ? 0 : kStackBytes + kPlaneBytes + (TOP == Top::Lds ? kLeafTableBytes + kInstPlaneBytes : 0);
+#if RC_LDS_PLANES16 == 748
+    static_assert(kLdsBytes <= 81920, "two workgroups per CU share 160 KiB of LDS");
+#else   // dev variant (tools/lds_bound_probe.py): one workgroup per CU
+    static_assert(kLdsBytes <= (TOP == Top::Lds && kStack16 ? 163840 : 81920), "one workgroup per CU has 160 KiB of LDS");
+#endif
+    // What the shell of a shape with dynamic LDS does first (all threads of the workgroup): carve `smem` into lane stacks (in front) and planes,
+    // stage the top level, synchronise.  `stage` = false: an empty scene, which has nothing to read (phased_trace then writes the misses).
+    // (The stacks are not returned with the planes: through a struct the compiler loses sight of where they start, and the spill path's
+    // depth computation turns into a signed 64-bit one.)
+    static __device__ inline entry_t* stacks(unsigned char* smem) { return reinterpret_cast<entry_t*>(smem); }
+    static __device__ inline LdsTop prologue(unsigned char* smem, const SceneView& v, uint32_t blas_k, uint32_t lds_blas_base, uint32_t tlas_k, bool stage = true) {
+        static_assert(TOP != Top::Memory, "nothing to stage");
+        LdsTop t;
+        if (TOP == Top::Lds) {
+            t = LdsTop(smem + kStackBytes, kPlaneBytes);
+            if (stage) stage_lds_top<BLOCK, kPlaneNodes>(t, v, blas_k, lds_blas_base);
+        } else {
+            t.tl = reinterpret_cast<float2*>(smem + kStackBytes);
+            if (stage) stage_partial_top<BLOCK, kPlaneNodes>(t.tl, v, tlas_k, blas_k, lds_blas_base);
+        }
+        __syncthreads();
+        return t;
+    }
+};
+// The product's three shapes: kernel 3 and the plain drivers; kernel 5 and the LDS drivers; kernel 6 and the partial-LDS drivers.
+template <unsigned FLAGS = 0u> using PlainShape = TraceShape<kBlock, kLdsStack, Top::Memory, FLAGS>;
+template <unsigned FLAGS = 0u> using LdsShape = TraceShape<kMidBlock, kMidStack, Top::Lds, FLAGS>;
+template <unsigned FLAGS = 0u> using PartialShape = TraceShape<kMidBlock, kMidStack, Top::PartialLds, FLAGS>;
 
 // safe_invdir (src/instanced-bvh.jl:1742-1748) of three components with the division written out.  hipcc's correctly rounded 1.0f / x is
 // v_div_scale x 2, v_rcp, six fma / mul steps, v_div_fmas, v_div_fixup; for a denominator in [1e-5, 2^60) (the clamp guarantees the lower
@@ -680,18 +713,18 @@ __device__ inline float3_ safe_inv3(const float3_ d) {
 #define RC_MARK(name) ((void)0)
 #endif
 
-template <bool ANY, int LDS_N, bool STATS, class Source, class Sink, int BLOCK = kBlock, bool TLAS_LDS = false, bool INST_LDS = TLAS_LDS, bool PARTIAL_LDS = false,
-          bool TIMELINE = false, bool STACK16 = false>
-__device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, typename std::conditional<STACK16, uint16_t, uint32_t>::type* lds_stack, const Source& src,
-                                    const Sink& sink, const LdsTop top = LdsTop()) {
-    typedef typename std::conditional<STACK16, uint16_t, uint32_t>::type stack_entry_t;
+template <bool ANY, class Shape, class Source, class Sink>
+__device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, typename Shape::entry_t* lds_stack, const Source& src, const Sink& sink, const LdsTop top = LdsTop()) {
+    constexpr int BLOCK = Shape::kBlock;
+    constexpr bool STATS = Shape::kStats, TIMELINE = Shape::kTimeline, STACK16 = Shape::kStack16;
+    typedef LaneStackP<Shape::kLdsDepth, BLOCK, typename Shape::entry_t> Stack;
     // node values that are not nodes: the 32-bit INVALID / sentinel of the reference, or their low halves where everything fits 16 bits
     constexpr uint32_t kInv = STACK16 ? 0xFFFFu : RC_INVALID_NODE, kSent = STACK16 ? 0xFFFEu : RC_TOP_LEVEL_SENTINEL;
     const float2* const tl = top.tl;
     const uint32_t* const lt = top.lt;
     const float2* const il = top.il;
     const uint32_t gtid = blockIdx.x * BLOCK + threadIdx.x;
-    LaneStackP<LDS_N, BLOCK, stack_entry_t> st(lds_stack + threadIdx.x, av.overflow + gtid, av.total_threads, av.status);
+    Stack st(lds_stack + threadIdx.x, av.overflow + gtid, av.total_threads, av.status);
     const int lane = threadIdx.x & 63;
     if (av.n_tlas_nodes == 0) {  // empty TLAS: every ray misses (test/test_tlas_stress.jl:808-831)
         for (uint64_t i = gtid; i < a.n_items; i += av.total_threads) sink(i, false, 0.0f, 0.0f, 0.0f, RC_INVALID_NODE, -1);
@@ -739,7 +772,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
         }
         if (blockIdx.x == 0 && threadIdx.x < 64) order_commit(a.claim, od, lane, smp);  // the header's other copy: read by the shape's next launch
     }
-    typename LaneStackP<LDS_N, BLOCK, stack_entry_t>::pos_t sp = st.empty();
+    typename Stack::pos_t sp = st.empty();
     bool live = false;
     unsigned long long st_iter[4] = {0, 0, 0, 0}, st_lane[4] = {0, 0, 0, 0}, st_outer = 0, st_sub[4] = {0, 0, 0, 0}, st_cull = 0;  // st_sub: passes with an exit lane / an entry lane / a result to write / rays to start
     unsigned long long st_t0 = STATS ? wall_clock64() : 0ull, st_tx = 0ull;
@@ -777,8 +810,8 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
 #endif
                 float4 na, nb, nc;
                 u2v ch;
-                constexpr int PS = PARTIAL_LDS ? (STACK16 ? kPartialPlaneNodes16 : kPartialPlaneNodes) : (STACK16 ? kLdsPlaneNodes16 : kLdsPlaneNodes);  // plane stride
-                if ((TLAS_LDS && (cur_inst < 0 || node <= a.blas_k)) || (PARTIAL_LDS && node <= (cur_inst < 0 ? a.tlas_k : a.blas_k))) {
+                constexpr int PS = Shape::kPlaneNodes;  // plane stride
+                if ((Shape::top == Top::Lds && (cur_inst < 0 || node <= a.blas_k)) || (Shape::top == Top::PartialLds && node <= (cur_inst < 0 ? a.tlas_k : a.blas_k))) {
                     const float2* q = tl + ((node - 1u) + (cur_inst < 0 ? 0u : a.lds_blas_base));
                     const float2 p0 = q[0], p1 = q[PS], p2 = q[2 * PS], p3 = q[3 * PS], p4 = q[4 * PS], p5 = q[5 * PS], p6 = q[6 * PS];
                     na = make_float4(p0.x, p0.y, p1.x, p1.y); nb = make_float4(p2.x, p2.y, p3.x, p3.y); nc = make_float4(p4.x, p4.y, p5.x, p5.y);
@@ -876,7 +909,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
                     else node = st.pop(sp);
                 }
             } else if (is_entry) {  // cull off: the instance index alone
-                if (TLAS_LDS) cur_inst = (int)lt[node - n_level];  // leaf of sorted instance j is node n - 1 + j; its child1 word
+                if (Shape::top == Top::Lds) cur_inst = (int)lt[node - n_level];  // leaf of sorted instance j is node n - 1 + j; its child1 word
                 else cur_inst = (int)__builtin_amdgcn_raw_buffer_load_b32(nrs1, (cur_off + node) << 6, 52, 0);
                 enter = true;
             }
@@ -901,7 +934,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
                 RC_MARK("entry_begin");
                 float4 m0, m1, m2;
                 u4v m3;
-                if (INST_LDS) {
+                if (Shape::top == Top::Lds) {
                     const float2* q = il + cur_inst;
                     const float2 p0 = q[0], p1 = q[kTlasLdsInst], p2 = q[2 * kTlasLdsInst], p3 = q[3 * kTlasLdsInst],
                                  p4 = q[4 * kTlasLdsInst], p5 = q[5 * kTlasLdsInst], p6 = q[6 * kTlasLdsInst];
@@ -1058,5 +1091,4 @@ bool rc_cost_order_setup(RcLaunchGuard& g, uint64_t n_items, int kind, rc::RcCla
 bool rc_lds_driver_ok(rc_scene* s);
 bool rc_partial_driver_ok(rc_scene* s);
 void rc_partial_driver_args(rc_scene* s, rc::PersistArgs& p);
-uint32_t rc_lds_driver_blocks(rc_scene* s, uint64_t n_items);
 void rc_lds_driver_args(rc_scene* s, rc::PersistArgs& p);

@@ -77,7 +77,7 @@ def test_small_pools_trace_every_ray(rc, oracle, pool):
     for n in (1, 63, 256, 300, 1000, 5000):
         rays = random_rays(rc, n, 100 + n, wb[:3], wb[3:])
         want, want_any = o.trace(rays), o.trace(rays, mode="any")
-        for k in (1, 2, 3, 4, 5, 6):
+        for k in (1, 3, 5, 6):
             t.set_option("kernel", k)
             out = np.full(n, 0xAB, dtype=np.uint8).repeat(32).view(rc.HIT_DT)  # poisoned: an untraced ray cannot look like a result
             assert_hits_equal(t.trace(rays, out=out), want, f"pool {pool} n {n} kernel {k}")

@@ -216,7 +216,7 @@ def test_build_parity_1m_repeated(rc, oracle):
 
 
 # ---- traversal parity -----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kernel", [0, 1, 2, 3, 4, 5, 6, -1])
+@pytest.mark.parametrize("kernel", [0, 1, 3, 5, 6, -1])
 def test_trace_parity_c1(rc, oracle, kernel):
     cfg = rc.scenes.config_c1()
     t, o = build_product(rc, cfg), build_oracle(oracle, cfg)
@@ -228,7 +228,7 @@ def test_trace_parity_c1(rc, oracle, kernel):
     assert_hits_equal(t.trace(rays, mode="any"), o.trace(rays, mode="any"), "C1 any")
 
 
-@pytest.mark.parametrize("kernel", [0, 1, 2, 3, 4, 5, 6, -1])
+@pytest.mark.parametrize("kernel", [0, 1, 3, 5, 6, -1])
 def test_trace_parity_random_scene(rc, oracle, kernel):
     sc = rc.scenes
     xf, _, _ = sc.lattice_transforms(3, 3, 2, 1.2, 77)
@@ -246,7 +246,7 @@ def test_trace_parity_random_scene(rc, oracle, kernel):
     assert_hits_equal(t.trace(rays, mode="any"), o.trace(rays, mode="any", nthreads=8), "random any")
 
 
-@pytest.mark.parametrize("kernel", [1, 2, 3, 4, 5, 6, -1])
+@pytest.mark.parametrize("kernel", [1, 3, 5, 6, -1])
 def test_trace_parity_c3_and_shadow(rc, oracle, kernel):
     cfg = rc.scenes.config_c3()
     t, o = build_product(rc, cfg), build_oracle(oracle, cfg)
@@ -279,7 +279,7 @@ def test_blas_top_renumbering(rc, oracle, n_tris, n_inst):
     rays = random_rays(rc, 150_000, n_tris, wb[:3], wb[3:])
     want, want_any = o.trace(rays, nthreads=8), o.trace(rays, mode="any", nthreads=8)
     assert want["hit"].any()
-    for kernel, top, s16 in ((5, 1, 1), (5, 0, 1), (0, 1, 1), (1, 1, 1), (3, 1, 1), (4, 1, 1), (6, 1, 1), (6, 0, 1), (5, 1, 0), (6, 1, 0), (-1, 1, 0)):
+    for kernel, top, s16 in ((5, 1, 1), (5, 0, 1), (0, 1, 1), (1, 1, 1), (3, 1, 1), (6, 1, 1), (6, 0, 1), (5, 1, 0), (6, 1, 0), (-1, 1, 0)):
         t.set_option("kernel", kernel)
         t.set_option("blas_top", top)
         t.set_option("stack16", s16)     # 0: the 32-bit shape stages a PREFIX of the same renumbered top
@@ -383,7 +383,7 @@ def test_trace_edge_cases(rc, oracle):
             os_.append([x, 0.5, 0.0]); ds.append([1.0, 0.0, 0.0])      # in the plane of the quad
     rays = rc.scenes.make_rays(os_, ds)
     want = o.trace(rays)
-    for k in (-1, 0, 1, 2, 3, 4, 5, 6):
+    for k in (-1, 0, 1, 3, 5, 6):
         t.set_option("kernel", k)
         assert_hits_equal(t.trace(rays), want, f"edge closest k{k}")
         assert_hits_equal(t.trace(rays, mode="any"), o.trace(rays, mode="any"), f"edge any k{k}")
@@ -426,7 +426,7 @@ def test_weird_rays_and_scales(rc, oracle):
     rays["d"][9 * k + 50:9 * k + 100] = [np.inf, 0.0, 0.0]
     want_c, want_a = o.trace(rays, nthreads=8), o.trace(rays, mode="any", nthreads=8)
     assert 0 < want_c["hit"].sum() < n
-    for kern in (-1, 0, 1, 2, 3, 4, 5, 6):
+    for kern in (-1, 0, 1, 3, 5, 6):
         t.set_option("kernel", kern)
         got_c, got_a = t.trace(rays), t.trace(rays, mode="any")
         ok = ~(np.isnan(want_c["t"]) | np.isnan(got_c["t"]))  # NaN != NaN bitwise is fine to compare too, but keep ids strict
@@ -470,7 +470,7 @@ def test_nan_and_inf_rays(rc, oracle):
     for name, cfg in (("multi", multi), ("single", single), ("two", two), ("nan_geometry", nan_geom)):
         t, o = build_product(rc, cfg), build_oracle(oracle, cfg)
         want_c, want_a = o.trace(rays, nthreads=4), o.trace(rays, mode="any", nthreads=4)
-        for kern in (-1, 0, 1, 2, 3, 4, 5, 6):
+        for kern in (-1, 0, 1, 3, 5, 6):
             t.set_option("kernel", kern)
             assert_hits_equal(t.trace(rays), want_c, f"nan {name} closest k{kern}")
             assert_hits_equal(t.trace(rays, mode="any"), want_a, f"nan {name} any k{kern}")
@@ -514,10 +514,40 @@ def test_deep_trees_use_the_stack_spill_path(rc, oracle):
     assert max_sp > 24, f"scene too shallow to reach the spill path (max stack {max_sp})"
     assert t.get_option("stack16_in_use") == 1   # small trees: kernels 5 / 6 keep 16-bit lane-stack entries in LDS; the spill area beyond the LDS depth holds the same values in 32-bit words
     want_any = o.trace(rays, mode="any", nthreads=8)
-    for k, s16 in ((-1, 1), (0, 1), (2, 1), (3, 1), (4, 1), (5, 1), (6, 1), (5, 0), (6, 0)):
+    for k, s16 in ((-1, 1), (0, 1), (3, 1), (5, 1), (6, 1), (5, 0), (6, 0)):
         t.set_option("kernel", k); t.set_option("stack16", s16)
         assert_hits_equal(t.trace(rays), want, f"deep k{k} stack16 {s16}")
         assert_hits_equal(t.trace(rays, mode="any"), want_any, f"deep any k{k} stack16 {s16}")
+
+
+def test_retired_kernel_ids_and_lds_stack_option(rc, oracle):
+    """Kernel ids 2 and 4 are aliases of their successors: the option stores 3 and 5.  Option "lds_stack" is accepted, reads back 24 and
+    changes nothing.  Results stay the oracle's bit for bit on a scene of 64 instances and on one of 300, where what used to be kernel 4
+    follows kernel 5's fall-back rule (more than 256 instances: kernel 3)."""
+    sc = rc.scenes
+    small = {"blas": [(sc.fan_sphere(10, 6, radius=0.5), None)],
+             "instances": [(1, sc.lattice_transforms(4, 4, 4, 0.8, 22)[0], np.arange(64, dtype=np.uint32))]}
+    large = {"blas": [(sc.random_triangles(12, 9, lo=-0.5, hi=0.5, edge=0.3), None)],
+             "instances": [(1, sc.lattice_transforms(10, 6, 5, 0.8, 24)[0], np.arange(300, dtype=np.uint32))]}
+    for name, cfg in (("64", small), ("300x12", large)):
+        t, o = build_product(rc, cfg), build_oracle(oracle, cfg)
+        wb = o.world_bound
+        rays = random_rays(rc, 20_000, 5, wb[:3], wb[3:])
+        want, want_any = o.trace(rays, nthreads=8), o.trace(rays, mode="any", nthreads=8)
+        assert 0 < want["hit"].sum() < len(rays)
+        for asked, stored in ((2, 3), (4, 5)):
+            t.set_option("kernel", asked)
+            assert t.get_option("kernel") == stored
+            assert_hits_equal(t.trace(rays), want, f"scene {name} kernel id {asked} closest")
+            assert_hits_equal(t.trace(rays, mode="any"), want_any, f"scene {name} kernel id {asked} any")
+        for depth in (12, 16, 20, 32):
+            t.set_option("lds_stack", depth)  # (raises unless the call returns RC_OK)
+            assert t.get_option("lds_stack") == 24
+            for k in (0, 1, 3):
+                t.set_option("kernel", k)
+                assert_hits_equal(t.trace(rays), want, f"scene {name} lds_stack {depth} kernel {k} closest")
+                assert_hits_equal(t.trace(rays, mode="any"), want_any, f"scene {name} lds_stack {depth} kernel {k} any")
+        t.free()
 
 
 def test_full_size_c2_properties(rc, oracle):
@@ -535,7 +565,7 @@ def test_full_size_c2_properties(rc, oracle):
     perm = rc.scenes.rng(5).permutation(len(rays))
     assert_hits_equal(t.trace(rays[perm]), got[perm], "C2 permuted")
     # every kernel variant agrees
-    for k in (0, 1, 2, 3, 4, 5, 6):
+    for k in (0, 1, 3, 5, 6):
         t.set_option("kernel", k)
         assert_hits_equal(t.trace(rays), got, f"C2 kernel {k}")
         assert np.array_equal(t.trace(rays, mode="any")["hit"], got["hit"])

@@ -55,7 +55,7 @@ def build(cfg):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variants", default="kernel=0;kernel=1", help="';'-separated option sets, each 'k=v,k=v'")
+    ap.add_argument("--variants", default="kernel=0;kernel=1", help="';'-separated option sets, each 'k=v,k=v' (kernel: -1 auto, 0, 1, 3, 5, 6)")
     ap.add_argument("--c3res", type=int, default=2048)
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--workloads", default="c2,c3,shadow,c4")
@@ -116,7 +116,7 @@ def main():
                 first_hits[w] = hits.copy()
             elif hits.tobytes() != first_hits[w].tobytes():
                 extra = f" !!! {int((hits.view(np.uint8).reshape(len(hits), -1) != first_hits[w].view(np.uint8).reshape(len(hits), -1)).any(axis=1).sum())} HITS DIFFER from the first variant"
-            if args.stats and opts["kernel"] in (1, 2, 3):
+            if args.stats and opts["kernel"] in (1, 3):
                 t.set_option("stats", 1)
                 ms_stats = time_trace(t, rays, mode, 2)[0]
                 v = [t.get_option(f"stat{i}") for i in range(8)]
@@ -124,16 +124,13 @@ def main():
                 t.set_option("stats", 0)
                 if opts["kernel"] == 1:
                     extra = f" wave_steps={v[0]} lanes/step={v[1]/max(v[0],1):.1f} max_sp={v[2]}"
-                elif opts["kernel"] == 3:
+                else:
                     extra = f" | I {v[2]} x{v[3]/max(v[2],1):.1f} | L {v[4]} x{v[5]/max(v[4],1):.1f} | S {v[6]} x{v[7]/max(v[6],1):.1f} | refills {v[0]}"
                     m64 = (1 << 64) - 1
                     t0, tx, te = m64 - (tv[0] & m64), m64 - (tv[1] & m64), tv[2]
                     nw = max(tv[5], 1)
                     extra += (f" | stats run {ms_stats * 1e3:.0f} us; ticks/100: total {(te - t0) / 100:.0f}, first wave out of work at {(tx - t0) / 100:.0f}, mean wave idle-at-end "
                               f"{(te - t0 - tv[4] / nw) / 100:.0f}, mean wave drain {tv[3] / nw / 100:.0f}")
-                else:
-                    extra = (f" iters={v[0]} live/iter={v[1]/max(v[0],1):.1f} | I {v[2]} x{v[3]/max(v[2],1):.1f} | L {v[4]} x{v[5]/max(v[4],1):.1f}"
-                             f" | E {v[6]} x{v[7]/max(v[6],1):.1f}")
             extra += f" drift={t.get_option('claim_drift')}"
             print(f"[{var:40s}] {name:14s} n={len(rays):9d} {ms:9.3f} ms  {len(rays)/ms/1e3:9.1f} Mrays/s  hit={hits['hit'].mean():.3f}{extra}", flush=True)
 
