@@ -635,7 +635,11 @@ int rc_rebuild_tlas_device_async(rc_scene* scene, void* stream);
  * read the box back first, and fail while the update's stream is being captured; while a graph that captured an update may live (until a
  * rebuilding rc_sync or "release_captures") they read it back on every use.
  * At call time the geometry's BLAS4 is dropped (rc_trace_*4 behave as for a geometry whose BLAS4 was never built, until rc_blas4_build)
- * and the view-factor source order is invalidated.  A captured update refreshes the shading attributes only if they existed at capture
+ * and the view-factor source order (RC_VF_SOURCES_BY_METADATA) is invalidated: the next call that needs it waits on the host for the
+ * eager updates enqueued so far and sorts again.  While a graph that captured an update may live, every replay re-sorts the primitives at
+ * a time the library does not see, so the order is rebuilt ON EVERY USE (one small sort and a host wait per rc_view_factors* call): such a
+ * call is a host-side read -- the caller waits for the replay first -- and on a stream that is being captured it fails with
+ * RC_ERR_NOT_SYNCED ("stale view-factor source order") instead of using an old order.  A captured update refreshes the shading attributes only if they existed at capture
  * time: while such a graph may live, a call that would have to build them fails with RC_ERR_NOT_SYNCED -- use
  * rc_shading_attributes_device once before capturing.  A captured update also holds the addresses of the geometry's OWN arrays: a host-side
  * rc_update_geometry / rc_update_geometry_mesh of that geometry frees them at once -- the graph is dead from that call on, not only

@@ -953,9 +953,16 @@ void emit_tree(hipStream_t st, const ChainBufs& b, RcNode* nodes, uint32_t n) {
     else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, st, nodes, 1u);  // single leaf: empty node, the leaf kernel fills the payload
 }
 
+// The arrival counters are zeroed by a kernel, not by hipMemsetAsync: as a node of a captured graph the memset left the counters of a
+// 1 520-primitive BLAS (6 080 bytes) partly at their old values on the second and later replays, and k_refit then took a first arrival for
+// a second one (docs/EXPERIMENTS.md, "Kernel shapes after device-side updates"); a kernel node is ordered like every other kernel of the chain.
+__global__ void k_zero_words(uint32_t* p, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = 0u;
+}
 void run_refit(hipStream_t st, const ChainBufs& b, RcNode* nodes, const RcPrim* prims, uint32_t n, int tlas) {
     const size_t words = (size_t)(b.arrive - b.zeroed) + (n - 1);
-    if (words) RC_HIP(hipMemsetAsync(b.zeroed, 0, sizeof(uint32_t) * words, st));
+    if (words) hipLaunchKernelGGL(k_zero_words, dim3(grid_for(words)), dim3(kBlock), 0, st, b.zeroed, words);
     if (n < 2) return;
     hipLaunchKernelGGL(k_refit, dim3((n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, nodes, prims, b.arrive, b.ranges, n, tlas);
 }

@@ -1325,7 +1325,7 @@ int rc_set_option(rc_scene* s, const char* name, int64_t value) {
             s->capture_slots.clear();
             s->last_capture = -1;
             if (s->captured_refit) { s->captured_refit = false; s->bound_stale = true; }  // (no replay can move the root box any more: one more read-back settles it)
-            if (s->captured_deform) { s->captured_deform = false; s->blas_bounds_stale = true; }
+            if (s->captured_deform) { s->captured_deform = false; s->blas_bounds_stale = true; s->vf_order_valid = false; }  // (one more read-back / sort settles them)
             if (s->captured_update) { s->captured_update = false; s->host_instances_stale = s->host_instances_stale || !s->mirror_edited; }
         }
     }
@@ -1464,6 +1464,7 @@ int rc_view_factors_device(rc_scene* s, uint32_t rays_per_triangle, uint64_t see
     return guarded([&] {
         use_device(s);
         require_synced(s);
+        if (flags & RC_VF_SOURCES_BY_METADATA) rc_ensure_vf_order(s, (hipStream_t)stream);
         rc_launch_view_factors(s, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, d_matrix, row_stride, col_stride, row_offset, flags, (hipStream_t)stream);
     });
 }

@@ -793,19 +793,33 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
 }
 
 // RC_VF_SOURCES_BY_METADATA: the flat primitives' indices sorted by (metadata, index) -- and the sorted metadata themselves on the host --
-// cached until the next rebuild.  Built on the scene's own stream, which also owns the sort scratch.
-void rc_ensure_vf_order(rc_scene* s) {
+// cached until the next rebuild or geometry update.  Built on the scene's own stream, which also owns the sort scratch, behind every EAGER
+// asynchronous update (host wait, as the host-buffer queries do).  captured_deform: a graph that captured a geometry update re-sorts the
+// primitives on every replay, at times the library does not see -- the order is rebuilt on every use, like the root boxes
+// (rc_ensure_blas_bounds); the caller has waited for the replay (raycore_mi355x.h).  for_stream: the stream the order is wanted for; while it
+// is being captured nothing can be sorted, read back or waited for.
+// The sort lands in scratch and is COPIED into vf_order: a launch of an earlier call that still reads the order on another stream sees
+// the same words before, during and after the copy unless the primitives moved -- and then its caller had to wait for it first anyway.
+void rc_ensure_vf_order(rc_scene* s, hipStream_t for_stream) {
     std::lock_guard<std::mutex> g(s->launch_mu);
-    if (s->vf_order_valid) return;
+    if (s->vf_order_valid && !s->captured_deform) return;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (for_stream && hipStreamIsCapturing(for_stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive)
+        throw RcError(6, s->captured_deform
+                             ? "stale view-factor source order: a graph that captured rc_update_geometry_device_async may have re-sorted the primitives, and the order cannot be rebuilt while the stream is being captured -- release the graph (\"release_captures\") or address the sources by primitive"
+                             : "stale view-factor source order: it cannot be built while the stream is being captured -- call rc_view_factors_device with RC_VF_SOURCES_BY_METADATA once before the capture");
+    (void)hipGetLastError();
+    rc_wait_async_mutations(s);  // (an eager geometry update on a caller's stream may still be writing the primitives sorted here)
     const uint32_t np = s->n_flat_prims;
     s->vf_meta_sorted.assign(np, 0u);
     if (np) {
-        s->keys_a.reserve(np); s->keys_b.reserve(np); s->vals_a.reserve(np); s->vf_order.reserve(np);
+        s->keys_a.reserve(np); s->keys_b.reserve(np); s->vals_a.reserve(np); s->vals_b.reserve(np); s->vf_order.reserve(np);
         hipLaunchKernelGGL(k_meta_keys, dim3((np + 255) / 256), dim3(256), 0, s->stream, s->flat_prims.p, np, s->keys_a.p, s->vals_a.p);
         size_t tmp = 0;
-        RC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vf_order.p, (int)np, 0, 32, s->stream));
+        RC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, (int)np, 0, 32, s->stream));
         s->sort_tmp.reserve(tmp ? tmp : 1);
-        RC_HIP(hipcub::DeviceRadixSort::SortPairs(s->sort_tmp.p, tmp, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vf_order.p, (int)np, 0, 32, s->stream));  // stable: ties keep the flat order
+        RC_HIP(hipcub::DeviceRadixSort::SortPairs(s->sort_tmp.p, tmp, s->keys_a.p, s->keys_b.p, s->vals_a.p, s->vals_b.p, (int)np, 0, 32, s->stream));  // stable: ties keep the flat order
+        RC_HIP(hipMemcpyAsync(s->vf_order.p, s->vals_b.p, sizeof(uint32_t) * np, hipMemcpyDeviceToDevice, s->stream));
         RC_HIP(hipMemcpyAsync(s->vf_meta_sorted.data(), s->keys_b.p, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, s->stream));
         RC_HIP(hipStreamSynchronize(s->stream));  // the launches that read the order run on other streams
     }
@@ -825,8 +839,7 @@ void rc_launch_view_factors(rc_scene* s, uint32_t rays_per_triangle, uint64_t se
     if (src_begin >= src_end || ray_begin >= ray_end) return;
     check_buffer_range(s);
     uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
-    if (flags & 2u) rc_ensure_vf_order(s);  // RC_VF_SOURCES_BY_METADATA
-    const uint32_t* order = (flags & 2u) ? s->vf_order.p : nullptr;
+    const uint32_t* order = (flags & 2u) ? s->vf_order.p : nullptr;  // RC_VF_SOURCES_BY_METADATA: the caller has called rc_ensure_vf_order, once per job
     DriverLaunch launch(s, stream, total);
     launch.guard.start();
     launch.run<false>(ViewFactorJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, d_matrix, row_stride, col_stride, row_offset, flags, order});

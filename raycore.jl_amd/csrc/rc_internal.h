@@ -484,7 +484,7 @@ void rc_note_stage_launch(rc_scene* s, hipStream_t stream);  // after a kernel o
 void rc_timing_fixed(rc_scene* s, float ms);
 float rc_timing_read(rc_scene* s);  // the calling thread's latest timed operation on the scene, else the scene's latest
 uint32_t rc_grid_blocks(rc_scene* s, uint64_t n_items, int block, int64_t per_cu);  // the grid rule of the persistent kernels (per_cu: TraceShape::kBlocksPerCu, rc_traverse_core.h)
-void rc_ensure_vf_order(rc_scene* s);  // builds vf_order / vf_meta_sorted if the scene has been rebuilt since
+void rc_ensure_vf_order(rc_scene* s, hipStream_t for_stream = nullptr);  // builds vf_order / vf_meta_sorted if the scene has been rebuilt or its geometry updated since (captured_deform: on every use)
 void rc_vf_source_range(rc_scene* s, uint32_t row_begin, uint32_t row_end, uint32_t& pos_begin, uint32_t& pos_end);  // positions in the metadata order whose metadata - 1 is in [row_begin, row_end)
 // rc_multi.hip
 void rc_launch_vf_totals(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin,

@@ -22,6 +22,11 @@ order) are compared with the from-scratch yardsticks whenever the ORACLE's own t
 otherwise with a restatement of the refit on the oracle's data (refit_restatement: the oracle's initial tree, the oracle's new leaf
 boxes, unions bottom-up) resp. on the `hit` word alone; the same scene then gets a rebuild_device_async and must equal both yardsticks
 in full.
+
+WHICH KERNEL RUNS HERE: kernel 0 (option `kernel` at -1, 65 536 rays: test_gpu_dynamic.py's docstring has the arithmetic).  It reads the
+BLAS slices of the traversal copy from memory in their renumbered order, but neither the entry-cull spheres and the per-BLAS cull radius
+nor the prefixes kernels 5 and 6 stage into LDS.  Those, kernels 3, 5 and 6 after every frame, and a captured update of a BLAS of more
+than 1 024 primitives ("top") are in tests/test_gpu_update_kernels.py.
 """
 import ctypes as C
 

@@ -9,7 +9,13 @@ Two yardsticks, neither of them the code under test:
   (fan spheres under generic rotations: no exact ties), bit for bit.
 
 Every frame's inputs are checked on the ORACLE's output first (oracle_frame): at least a fifth of the rays hit, and at least a tenth of
-the hit records differ from the previous frame's -- so a stale cull sphere, leaf box or inverse cannot go unnoticed.
+the hit records differ from the previous frame's -- so a stale leaf box or inverse cannot go unnoticed.
+
+WHICH KERNEL RUNS HERE: option `kernel` stays at -1 and a batch is 65 536 rays, below the 6 * 256 * n_cus * 5/4 (491 520 on 256 CUs) from
+which the default dispatch leaves kernel 0 (rc_launch_trace).  Kernel 0 reads the traversal copy from memory and never tests an
+entry-cull sphere, so nothing in this file reads the spheres, their copies in the TLAS leaf records, the LDS planes or the renumbered
+tops.  The kernel matrix (0, 1, 3, 5, 6, both stack shapes, entry_cull 1 / 0 / 2) after every frame of these paths, and the derived
+arrays themselves, are in tests/test_gpu_update_kernels.py.
 """
 import ctypes as C
 
@@ -20,8 +26,8 @@ from helpers import assert_hits_equal
 
 pytestmark = pytest.mark.gpu
 
-SMALL = (6, 6, 4)     # 144 instances: at most kTlasLdsInst = 256, the whole TLAS sits in LDS
-LARGE = (12, 12, 6)   # 864 instances: LDS-top renumbering (tlas_top_k > 0)
+SMALL = (6, 6, 4)     # 144 instances: at most kTlasLdsInst = 256 (kernel 5 would stage the whole TLAS in LDS: test_gpu_update_kernels.py)
+LARGE = (12, 12, 6)   # 864 instances: the TLAS's top is renumbered (tlas_top_k > 0) for kernel 6, which this file does not run either
 N_FRAMES = 4
 SCALED_FRAME = 2      # the frame whose linear part carries a non-uniform scale
 W = H = 256

@@ -13,7 +13,11 @@ at f == 2, the translation column permuted among the instances by Philox(key = 9
 of instance 0 (equal Morton codes, coincident triangles: the sort's stability and the tie order are pinned).  Conditions on the inputs,
 asserted on the oracle's output alone (oracle_frame): >= 0.9 of the TLAS leaf slots hold another instance than in the previous frame's
 tree, hit fraction >= 0.2, >= 0.1 of the hit records differ from the previous frame's -- a rebuild that silently refits, or leaves the
-instance -> leaf table or the renumbering stale, cannot pass.
+instance -> leaf table stale, cannot pass.
+
+WHICH KERNEL RUNS HERE: kernel 0 (option `kernel` at -1, 65 536 rays: test_gpu_dynamic.py's docstring has the arithmetic), which reads
+neither the entry-cull spheres nor the renumbered top of the TLAS.  The exported TLAS nodes pin the topology; the renumbering, the
+spheres in the rebuilt leaf records and kernels 3, 5 and 6 on the rebuilt tree are checked in tests/test_gpu_update_kernels.py.
 """
 import numpy as np
 import pytest
