@@ -611,6 +611,64 @@ int rc_refit_device_async(rc_scene* scene, void* stream);
  * (never synced, or pending host-side mutations).  Structural changes (instances or geometry added / deleted) stay with rc_sync. */
 int rc_rebuild_tlas_device_async(rc_scene* scene, void* stream);
 
+/* WHEN to rebuild, decided on the device: refit_tlas! every frame, rebuild_bvh! (src/instanced-bvh.jl:968-992) only on the frames whose
+ * refitted tree has degraded.  A captured frame can then refit while instances drift and rebuild on the replay in which they scatter; the
+ * host never reads the tree.
+ *
+ * rc_tlas_cost_device: the cost of the TLAS as it is WHEN THE KERNELS RUN, one f64 written to caller-owned device memory on `stream`.  For
+ * n >= 2 instances, internal node i (1 <= i <= n - 1 of rc_export_tlas_nodes) has the box of the union of its two child boxes and
+ * A_i = 2 (ex ey + ey ez + ez ex), the extents formed in f64 from the f32 corners; cost = sum A_i / A_1, the summed surface area of the
+ * internal boxes relative to the root's (about what a ray pays per unit of root area it crosses).  n == 1: exactly 1.0.  n == 0: success,
+ * nothing enqueued.  DETERMINISTIC: no floating-point atomics; per-block partial sums and their fold run in an order fixed by n alone, so
+ * two evaluations of one tree give the same 8 bytes.  No allocation, host copy, event or synchronisation: legal on a capturing stream,
+ * once the stream has run it eagerly.  Calls on different streams at the same time share its partial sums: one stream at a time.
+ * LIFETIME: the call records no event, so rc_scene_destroy waits for it only as the scene's latest eager asynchronous work -- when an
+ * update, refit or rebuild is still pending on ANOTHER stream, that stream is the one waited for, and the caller synchronises the cost
+ * call's stream itself before destroying the scene.
+ * Errors: RC_ERR_INVALID_ARGUMENT (NULL scene or d_cost), RC_ERR_NOT_SYNCED (never synced, or pending host-side mutations).
+ *
+ * rc_refit_or_rebuild_tlas_device_async: on `stream`,
+ *   1. exactly what rc_refit_device_async does (the per-instance pass under the same rule);
+ *   2. the cost pass, which stores `cost` and a gate word = (cost > ratio * cost_built), compared in f64 as written -- a NaN cost never
+ *      rebuilds.  The gate is written on every run, 0 as well as 1: a replay never sees the previous frame's decision;
+ *   3. the rebuild of rc_rebuild_tlas_device_async, taken only if the gate is set;
+ *   4. if it was taken: cost_built = the new tree's cost, the rebuild counter advances, the gate is cleared.
+ * All of that state is a small block in device memory; nothing is read back.
+ * RESULT: after a run whose gate was clear, everything a trace, an export or a later refit reads is byte-identical to what
+ * rc_refit_device_async leaves; after a run whose gate was set, to what rc_rebuild_tlas_device_async leaves, and therefore to a fresh
+ * scene after rc_sync.  In place in both cases: earlier captures of updates, refits, rebuilds and traces stay valid.
+ * BOTH DEVICE PATHS take the gate.  2 .. 256 instances with "tlas_rebuild_fused" = 1: one workgroup reads the refitted tree's cost,
+ * decides, and either returns or rebuilds in LDS and records -- a drifting frame is a refit plus one small dispatch.  Otherwise the cost
+ * pass is two small kernels and every kernel of the build's chain that writes outside the rebuild scratch (TLAS nodes, topology records,
+ * instance -> leaf table, top renumbering, traversal copy) returns when it reads a clear gate; the ones that touch only the scratch,
+ * the sort included, run regardless: a skipped rebuild costs their time and nothing else.  The gate crosses a kernel boundary on one
+ * stream, never a launch in flight.
+ * THE STATE BLOCK (cost, cost_built, gate, evaluations, rebuilds, last decision) is reserved, zeroed and DISARMED by every rebuilding
+ * rc_sync.  The host cannot know what an earlier sequence of refits left, so the first call after such a sync ARMS it: refit ->
+ * unconditional rebuild -> record cost_built, counted as one evaluation and one rebuild.  That call must be eager: on a capturing stream
+ * it returns RC_ERR_NOT_SYNCED and says so.  While armed, rc_rebuild_tlas_device_async appends the same record step, so the baseline
+ * follows explicit rebuilds; while not armed it enqueues exactly what it always did.  A graph that captured an unconditional rebuild
+ * BEFORE arming does not record: replayed after arming it leaves cost_built at the previous tree's cost.
+ * n == 1: refit only (the arming call aside), cost 1.0, never rebuilt.  n == 0: success, nothing enqueued.
+ * Scene state (world bound, host mirror, captured-refit rule, the host wait of the host-buffer queries, no-op rc_sync): as after
+ * rc_refit_device_async.  No allocation, host copy, event or synchronisation: legal on a capturing stream once armed and run eagerly.
+ * Errors, all before anything is enqueued: RC_ERR_INVALID_ARGUMENT (NULL scene; ratio not finite or <= 0), RC_ERR_NOT_SYNCED (never
+ * synced, pending host-side mutations, or the arming call on a capturing stream), RC_ERR_HIP (the rebuild scratch does not match the
+ * instance count).  Structural changes stay with rc_sync.
+ *
+ * rc_tlas_quality: the block, read on the host under the rules of the other lazy reads: it waits for the EAGER asynchronous work
+ * enqueued so far; while a graph that captured the call may live, the caller waits for its replay first.  cost: what the latest evaluation
+ * measured (the refitted tree's, also when a rebuild followed; the arming call: the built tree's); cost_built: the tree's cost at the latest
+ * recorded rebuild; evaluations, rebuilds: counts since the last rebuilding rc_sync (the arming call is
+ * one of each); last_rebuilt: the latest evaluation's decision; armed: 0 until the arming call. */
+typedef struct rc_tlas_quality_info {
+    double cost, cost_built;
+    uint32_t evaluations, rebuilds, last_rebuilt, armed;
+} rc_tlas_quality_info;
+int rc_tlas_cost_device(rc_scene* scene, double* d_cost, void* stream);
+int rc_refit_or_rebuild_tlas_device_async(rc_scene* scene, double ratio, void* stream);
+int rc_tlas_quality(rc_scene* scene, rc_tlas_quality_info* out);
+
 /* update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) with backend-resident vertices: build_blas (:1376-1443) -- degenerate
  * filter, Morton codes, stable sort, gather, Karras tree, leaves, refit -- enqueued on the caller's `stream` with no host wait, for meshes
  * whose vertices move every frame (skinning, cloth, simulation output).  update -> [rc_update_transforms_device] -> refit -> trace can run

@@ -35,6 +35,14 @@ RC_OK, RC_ERR_INVALID_ARGUMENT, RC_ERR_INVALID_HANDLE, RC_ERR_NO_DEVICE = 0, 1, 
 RC_ERR_GEOMETRY_CHANGED = 8  # reported once by rc_wait after an in-place geometry update that met another face count
 RC_INVALID_ID = 0xFFFFFFFF
 
+
+class TlasQualityInfo(C.Structure):  # rc_tlas_quality_info
+    _fields_ = [("cost", C.c_double), ("cost_built", C.c_double), ("evaluations", C.c_uint32), ("rebuilds", C.c_uint32),
+                ("last_rebuilt", C.c_uint32), ("armed", C.c_uint32)]
+
+
+assert C.sizeof(TlasQualityInfo) == 32
+
 # every symbol include/raycore_mi355x.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i64, _int = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int64, C.c_int
 _pu32, _pint, _pf = C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_float)
@@ -119,6 +127,9 @@ SYMBOLS = [
     ("rc_update_transforms_device", _int, [_vp, _u32, _vp, _u32, _vp]),
     ("rc_refit_device_async", _int, [_vp, _vp]),
     ("rc_rebuild_tlas_device_async", _int, [_vp, _vp]),
+    ("rc_tlas_cost_device", _int, [_vp, _vp, _vp]),
+    ("rc_refit_or_rebuild_tlas_device_async", _int, [_vp, C.c_double, _vp]),
+    ("rc_tlas_quality", _int, [_vp, _vp]),
     ("rc_update_geometry_device_async", _int, [_vp, _u32, _vp, _vp, _u32, _vp]),
     ("rc_update_mesh_vertices_device_async", _int, [_vp, _u32, _vp, _vp, _u32, _vp]),
     ("rc_host_register", _int, [_vp, _vp, _u64]),

@@ -348,6 +348,37 @@ class TLAS:
         check(lib().rc_rebuild_tlas_device_async(self._h, ptr(stream) if stream else None))
         return self
 
+    def tlas_cost_device(self, out, stream=None):
+        """The cost of the TLAS as it is when the kernels run on `stream` (rc_tlas_cost_device): the summed surface area of the internal
+        nodes' boxes relative to the root's, one float64 written to `out` -- a float64 CUDA tensor of one element on the scene's device,
+        or a raw device pointer.  Deterministic (no floating-point atomics); no host wait; capturable once run eagerly."""
+        p = out
+        if hasattr(out, "data_ptr"):
+            if str(out.dtype) != "torch.float64" or out.numel() != 1 or not out.is_cuda or out.device.index != self.device:
+                raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, "out must be a float64 tensor of one element on the scene's device")
+            p = out.data_ptr()
+        check(lib().rc_tlas_cost_device(self._h, ptr(p) if p else None, ptr(stream) if stream else None))
+        return self
+
+    def refit_or_rebuild_device_async(self, ratio, stream=None):
+        """refit_device_async(), then rebuild_device_async() if the refitted tree costs more than `ratio` x what it cost when it was last
+        built -- measured and decided on the device (rc_refit_or_rebuild_tlas_device_async), so one captured frame refits while instances
+        drift and rebuilds on the replay in which they scatter.  The first call after a structural sync() arms the state (refit,
+        unconditional rebuild, baseline cost) and must run eagerly.  tlas_quality() reads the decision back."""
+        ratio = float(ratio)
+        if not (np.isfinite(ratio) and ratio > 0.0):
+            raise RaycoreError(_capi.RC_ERR_INVALID_ARGUMENT, f"ratio must be finite and > 0, got {ratio}")
+        check(lib().rc_refit_or_rebuild_tlas_device_async(self._h, ratio, ptr(stream) if stream else None))
+        return self
+
+    def tlas_quality(self):
+        """rc_tlas_quality: dict(cost, cost_built, evaluations, rebuilds, last_rebuilt, armed) of refit_or_rebuild_device_async.  A
+        host-side read: waits for eager asynchronous work; replays of a graph that captured the call are the caller's to wait for."""
+        q = _capi.TlasQualityInfo()
+        check(lib().rc_tlas_quality(self._h, C.byref(q)))
+        return {"cost": q.cost, "cost_built": q.cost_built, "evaluations": int(q.evaluations), "rebuilds": int(q.rebuilds),
+                "last_rebuilt": bool(q.last_rebuilt), "armed": bool(q.armed)}
+
     def _device_f32(self, t, what, inner):
         """(rows, address) of a contiguous float32 torch tensor on the scene's device whose trailing shape multiplies to `inner`."""
         if str(t.dtype) != "torch.float32" or not t.is_contiguous() or not t.is_cuda or t.device.index != self.device:

@@ -264,8 +264,14 @@ __global__ void k_reflection_rays(const RcRay* rays, const RcHit* hits, uint64_t
     q[1] = make_float4(rr.dx, rr.dy, rr.dz, rr.tmax);
 }
 
+// The optional GATE of the TLAS chain's kernels (rc_refit_or_rebuild_tlas_async): a word an EARLIER kernel on the same stream wrote.  Every
+// kernel that writes anything outside the rebuild scratch -- TLAS nodes, topology records, instance -> leaf table, top renumbering,
+// traversal copy -- returns when it reads 0, the whole grid alike and before any barrier; nullptr = run, which every other caller passes.
+__device__ inline bool gate_closed(const uint32_t* gate) { return gate && *gate == 0u; }
+
 // fill_bvhnode2_kernel! (src/instanced-bvh-kernels.jl:19-22) with the empty node of :1407-1410
-__global__ void k_fill_nodes(RcNode* nodes, uint32_t n_nodes) {
+__global__ void k_fill_nodes(RcNode* nodes, uint32_t n_nodes, const uint32_t* gate) {
+    if (gate_closed(gate)) return;
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_nodes) return;
     RcNode e;
@@ -333,7 +339,8 @@ __device__ inline void topology_node(int idx, RcNode* nodes, const uint32_t* cod
     nodes[child1 - 1].parent = (uint32_t)idx;
     if (idx == 1) nodes[0].parent = RC_INVALID_NODE;
 }
-__global__ void k_topology(RcNode* nodes, const uint32_t* codes, int n, uint4* meta) {
+__global__ void k_topology(RcNode* nodes, const uint32_t* codes, int n, uint4* meta, const uint32_t* gate) {
+    if (gate_closed(gate)) return;
     int idx = blockIdx.x * blockDim.x + threadIdx.x + 1;
     if (idx >= n) return;
     topology_node(idx, nodes, codes, n, meta);
@@ -391,7 +398,8 @@ __device__ inline void join_boxes(bool first_slot, float3_& mn, float3_& mx, flo
     mx = first_slot ? max3v(mx, smx) : max3v(smx, mx);
 }
 constexpr int kRefitBlock = 1024;
-__global__ __launch_bounds__(kRefitBlock) void k_refit(RcNode* nodes, const RcPrim* prims, uint32_t* flags, const uint4* meta, uint32_t n, int tlas) {
+__global__ __launch_bounds__(kRefitBlock) void k_refit(RcNode* nodes, const RcPrim* prims, uint32_t* flags, const uint4* meta, uint32_t n, int tlas, const uint32_t* gate) {
+    if (gate_closed(gate)) return;
     __shared__ uint32_t l_flags[kRefitBlock];
     __shared__ float l_box[kRefitBlock][2][6];
     // Topology of the window's own internal nodes (indices base+1 .. base+kRefitBlock), fetched once with every thread's loads in
@@ -536,7 +544,8 @@ __device__ inline void tlas_leaf_node(RcNode* nd, uint32_t orig, const float* tr
 // create_tlas_leaf_nodes_kernel! (src/instanced-bvh-kernels.jl:332-375).  sorted == nullptr => refit path:
 // update_tlas_leaf_aabbs_kernel! (:487-519), the instance index is read back from child1.
 __global__ void k_tlas_leaves(RcNode* nodes, const uint32_t* sorted, const RcInstanceDesc* inst, const RcBlasDesc* descs,
-                              uint32_t n) {
+                              uint32_t n, const uint32_t* gate) {
+    if (gate_closed(gate)) return;
     uint32_t j = blockIdx.x * blockDim.x + threadIdx.x + 1;
     if (j > n) return;
     RcNode* nd = &nodes[(n - 1 + j) - 1];
@@ -548,12 +557,14 @@ __global__ void k_tlas_leaves(RcNode* nodes, const uint32_t* sorted, const RcIns
 // ---- single-BLAS scenes: breadth-first renumbering of the BLAS's top internal nodes in the traversal copy (rc_traverse_core.h,
 // kLdsPlaneNodes).  remap[old - 1] = new index of internal node `old`: the first K nodes of a breadth-first walk (child0 before
 // child1, internal nodes only) get 1..K in that order, the nodes they displace take the vacated indices, everything else stays.
-__global__ void k_iota1(uint32_t* out, uint32_t n) {
+__global__ void k_iota1(uint32_t* out, uint32_t n, const uint32_t* gate) {
+    if (gate_closed(gate)) return;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = i + 1u;
 }
 constexpr int kTopBlock = 1024;
-__global__ __launch_bounds__(kTopBlock) void k_top_remap(const RcNode* nodes, uint32_t n_leaves, uint32_t K, uint32_t* remap) {
+__global__ __launch_bounds__(kTopBlock) void k_top_remap(const RcNode* nodes, uint32_t n_leaves, uint32_t K, uint32_t* remap, const uint32_t* gate) {
+    if (gate_closed(gate)) return;
     typedef hipcub::BlockScan<uint32_t, kTopBlock> Scan;
     __shared__ typename Scan::TempStorage tmp;
     __shared__ uint32_t top[rc::kPartialPlaneNodes16], in_top[rc::kPartialPlaneNodes16 + 1], d_list[rc::kPartialPlaneNodes16], v_list[rc::kPartialPlaneNodes16];  // K <= kPartialPlaneNodes16 < kTopBlock
@@ -611,7 +622,9 @@ __device__ inline void pack_node_renumbered(RcNode nd, uint32_t i, uint32_t n_le
     }
     dst[at] = pack_node_or_leaf(nd, i + 1u >= n_leaves, tlas_cull);
 }
-__global__ void k_pack_nodes_remap(const RcNode* src, RcNode* dst, uint32_t n_nodes, uint32_t n_leaves, const uint32_t* remap, const float4* tlas_cull) {
+__global__ void k_pack_nodes_remap(const RcNode* src, RcNode* dst, uint32_t n_nodes, uint32_t n_leaves, const uint32_t* remap, const float4* tlas_cull,
+                                   const uint32_t* gate) {
+    if (gate_closed(gate)) return;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_nodes) return;
     pack_node_renumbered(src[i], i, n_leaves, remap, tlas_cull, dst);
@@ -619,7 +632,8 @@ __global__ void k_pack_nodes_remap(const RcNode* src, RcNode* dst, uint32_t n_no
 
 // Traversal copy of a node array: interior nodes in the packed order of rc_pack_node, the leaves -- nodes n_leaves .. of a tree with n_leaves
 // leaves -- as rc_pack_leaf (the triangles of a BLAS: tlas_cull == nullptr) or rc_pack_tlas_leaf (a TLAS).
-__global__ void k_pack_nodes(const RcNode* src, RcNode* dst, uint32_t n, uint32_t n_leaves, const float4* tlas_cull) {
+__global__ void k_pack_nodes(const RcNode* src, RcNode* dst, uint32_t n, uint32_t n_leaves, const float4* tlas_cull, const uint32_t* gate) {
+    if (gate_closed(gate)) return;
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = pack_node_or_leaf(src[i], i + 1u >= n_leaves, tlas_cull);
 }
@@ -798,9 +812,68 @@ __global__ __launch_bounds__(kBlock) void k_update_instances(const float* __rest
     *reinterpret_cast<float2*>(nd->f + 4) = make_float2(mx.y, mx.z);
 }
 // leaf_of[sorted[j - 1]] = j: where each instance's leaf sits in the Morton order of the last rebuild
-__global__ void k_inst_leaf(const uint32_t* sorted, uint32_t n, uint32_t* leaf_of) {
+__global__ void k_inst_leaf(const uint32_t* sorted, uint32_t n, uint32_t* leaf_of, const uint32_t* gate) {
+    if (gate_closed(gate)) return;
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) leaf_of[sorted[j]] = j + 1u;
+}
+
+// ---- the cost of a TLAS and the decision to rebuild it (rc_tlas_cost_async, rc_refit_or_rebuild_tlas_async).  cost = sum over the internal
+// nodes i = 1 .. n - 1 of A_i / A_1, A = 2 (ex ey + ey ez + ez ex) of the union of the node's two child boxes, extents in f64 from the f32
+// corners (tools/probes/tlas_rebuild_probe.py, relative_area); n == 1: exactly 1.  No floating-point atomics: a block's threads take the
+// nodes in a grid-stride order fixed by n alone and fold through LDS in a fixed tree, one block folds the partials the same way, so two
+// evaluations of one tree give the same 8 bytes.
+constexpr int kCostBlock = 256;
+enum QualityMode : int { kCostOnly = 0, kDecide = 1, kRecord = 2, kArm = 3 };
+__device__ inline double node_area(const RcNode& nd) {
+    const double ex = (double)jl_maxf(nd.f[3], nd.f[9]) - (double)jl_minf(nd.f[0], nd.f[6]);
+    const double ey = (double)jl_maxf(nd.f[4], nd.f[10]) - (double)jl_minf(nd.f[1], nd.f[7]);
+    const double ez = (double)jl_maxf(nd.f[5], nd.f[11]) - (double)jl_minf(nd.f[2], nd.f[8]);
+    return 2.0 * (ex * ey + ey * ez + ez * ex);
+}
+// (every thread of a block of kCostBlock calls it; sh: kCostBlock doubles)
+__device__ inline double block_sum_fixed(double v, double* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t w = kCostBlock / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    return sh[0];
+}
+// What ONE thread does with a finished cost.  kCostOnly: *out.  kDecide: the cost and the gate, cost > ratio * cost_built in f64 as written (a
+// NaN never rebuilds), written on every run -- a replay must not see the previous frame's decision.  kRecord, behind a rebuild: the new
+// tree's cost becomes the baseline and the gate is cleared.  kArm: kRecord as the first evaluation after a sync.
+__device__ inline uint32_t quality_commit(RcTlasQuality* q, double* out, double cost, double ratio, int mode, bool may_rebuild) {
+    if (mode == kCostOnly) { *out = cost; return 0u; }
+    if (mode == kDecide) {
+        const uint32_t g = (may_rebuild && cost > ratio * q->cost_built) ? 1u : 0u;
+        q->cost = cost; q->gate = g; q->last_rebuilt = g;
+        q->evaluations += 1u;
+        return g;
+    }
+    q->cost_built = cost; q->gate = 0u;  // (`cost` stays what the evaluation measured: the refitted tree's, which led to this rebuild)
+    q->rebuilds += 1u;
+    if (mode == kArm) { q->cost = cost; q->evaluations += 1u; q->last_rebuilt = 1u; }
+    return 0u;
+}
+__global__ __launch_bounds__(kCostBlock) void k_tlas_cost_partials(const RcNode* __restrict__ nodes, uint32_t n, double* __restrict__ partials) {
+    __shared__ double sh[kCostBlock];
+    double a = 0.0;
+    for (uint32_t i = blockIdx.x * kCostBlock + threadIdx.x; i + 1u < n; i += gridDim.x * kCostBlock) a += node_area(nodes[i]);
+    const double sum = block_sum_fixed(a, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+// `gate` (kRecord behind a gated chain): nothing was rebuilt, nothing to record
+__global__ __launch_bounds__(kCostBlock) void k_tlas_cost_fold(const RcNode* __restrict__ nodes, uint32_t n, const double* __restrict__ partials, uint32_t n_blocks,
+                                                              double* out, RcTlasQuality* q, double ratio, int mode, const uint32_t* gate) {
+    if (gate_closed(gate)) return;
+    __shared__ double sh[kCostBlock];
+    double a = 0.0;
+    for (uint32_t b = threadIdx.x; b < n_blocks; b += kCostBlock) a += partials[b];
+    const double sum = block_sum_fixed(a, sh);
+    if (threadIdx.x == 0) quality_commit(q, out, n < 2u ? 1.0 : sum / node_area(nodes[0]), ratio, mode, n >= 2u);
 }
 
 // ---- the whole TLAS rebuild as ONE workgroup (rc_rebuild_tlas_async; 2 <= n <= kFusedInst = kTlasLdsInst instances, the scenes whose top
@@ -814,16 +887,33 @@ __global__ void k_inst_leaf(const uint32_t* sorted, uint32_t n, uint32_t* leaf_o
 //  * refit: the in-window protocol of k_refit (LDS arrival counters, the second arrival carries the union up) with the box slots in the
 //    LDS copy of the node itself.  Every word of nodes 1..2n-1 is written before the copy-out: child / pad / parent words by topology_node,
 //    leaves by tlas_leaf_node, both boxes of every internal node by its two arrivals.
+// kQuality (rc_refit_or_rebuild_tlas_async; rc_rebuild_tlas_async on an armed scene): the same workgroup does the whole conditional step.
+// kDecide: it first takes the cost of the tree in memory -- the refit's, an earlier kernel on the stream -- decides (quality_commit) and
+// returns, all of it, unless the gate is set; then, as in kRecord / kArm, it builds as always, takes the new tree's cost from the LDS copy
+// before the copy-out and records it.  The decision crosses no launch: it is shared inside one workgroup, behind a barrier.
 constexpr int kFusedInst = rc::kTlasLdsInst;
+static_assert(kFusedInst == kCostBlock, "block_sum_fixed folds kCostBlock slots");
+template <bool kQuality>
 __global__ __launch_bounds__(kFusedInst) void k_rebuild_tlas_fused(const RcInstanceDesc* __restrict__ inst, const RcBlasDesc* __restrict__ descs, uint32_t n,
                                                                    RcNode* __restrict__ nodes, RcNode* __restrict__ packed, uint4* __restrict__ ranges,
-                                                                   uint32_t* __restrict__ leaf_of, const float4* __restrict__ cull) {
+                                                                   uint32_t* __restrict__ leaf_of, const float4* __restrict__ cull,
+                                                                   RcTlasQuality* quality, double ratio, int mode) {
     __shared__ RcNode l_nodes[2 * kFusedInst - 1];
     __shared__ uint4 l_meta[(kFusedInst - 1) + kFusedInst / 4];  // k_topology's compact records, then one parent word per leaf
-    __shared__ float l_x[kFusedInst * 12];
+    __shared__ alignas(8) float l_x[kFusedInst * 12];  // (8-byte aligned: the quality form folds its f64 partial sums through it)
     __shared__ uint32_t l_blas[kFusedInst], l_codes[kFusedInst], l_sorted_codes[kFusedInst], l_sorted[kFusedInst], l_flags[kFusedInst];
     __shared__ uint32_t l_enc[8];
     const uint32_t t = threadIdx.x;
+    if constexpr (kQuality) {
+        if (mode == kDecide) {
+            double* l_red = reinterpret_cast<double*>(l_x);  // (the transforms are staged after the decision)
+            const double sum = block_sum_fixed(t + 1u < n ? node_area(nodes[t]) : 0.0, l_red);
+            if (t == 0) l_enc[7] = quality_commit(quality, nullptr, sum / node_area(nodes[0]), ratio, kDecide, true);
+            __syncthreads();
+            if (l_enc[7] == 0u) return;
+            __syncthreads();  // (l_red is l_x)
+        }
+    }
     for (uint32_t w = t; w < n * 12u; w += kFusedInst) l_x[w] = inst[w / 12u].transform[w % 12u];
     if (t < n) l_blas[t] = inst[t].blas_index;
     l_flags[t] = 0u;
@@ -871,6 +961,10 @@ __global__ __launch_bounds__(kFusedInst) void k_rebuild_tlas_fused(const RcInsta
         }
     }
     __syncthreads();
+    if constexpr (kQuality) {  // the new tree's cost, from the LDS copy (l_x is free: the leaves were made from it before the refit)
+        const double sum = block_sum_fixed(t + 1u < n ? node_area(l_nodes[t]) : 0.0, reinterpret_cast<double*>(l_x));
+        if (t == 0) quality_commit(quality, nullptr, sum / node_area(l_nodes[0]), ratio, mode == kDecide ? (int)kRecord : mode, true);
+    }
     for (uint32_t i = t; i < 2u * n - 1u; i += kFusedInst) {  // canonical node and traversal copy (k_pack_nodes), 16-byte stores
         const RcNode nd = l_nodes[i];
         const RcNode pk = pack_node_or_leaf(nd, i + 1u >= n, cull);  // (the spheres are in place before the rebuild: k_inst_recs / k_update_instances)
@@ -948,9 +1042,9 @@ ChainBufs rebuild_bufs(rc_scene* s) {
 }
 
 // Karras topology + parents for n items with sorted keys in b.keys_b
-void emit_tree(hipStream_t st, const ChainBufs& b, RcNode* nodes, uint32_t n) {
-    if (n > 1) hipLaunchKernelGGL(k_topology, dim3(grid_for(n - 1)), dim3(kBlock), 0, st, nodes, b.keys_b, (int)n, b.ranges);
-    else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, st, nodes, 1u);  // single leaf: empty node, the leaf kernel fills the payload
+void emit_tree(hipStream_t st, const ChainBufs& b, RcNode* nodes, uint32_t n, const uint32_t* gate = nullptr) {
+    if (n > 1) hipLaunchKernelGGL(k_topology, dim3(grid_for(n - 1)), dim3(kBlock), 0, st, nodes, b.keys_b, (int)n, b.ranges, gate);
+    else hipLaunchKernelGGL(k_fill_nodes, dim3(1), dim3(kBlock), 0, st, nodes, 1u, gate);  // single leaf: empty node, the leaf kernel fills the payload
 }
 
 // The arrival counters are zeroed by a kernel, not by hipMemsetAsync: as a node of a captured graph the memset left the counters of a
@@ -960,17 +1054,18 @@ __global__ void k_zero_words(uint32_t* p, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = 0u;
 }
-void run_refit(hipStream_t st, const ChainBufs& b, RcNode* nodes, const RcPrim* prims, uint32_t n, int tlas) {
+// (the arrival counters are the refit's own scratch: zeroed whatever the gate says)
+void run_refit(hipStream_t st, const ChainBufs& b, RcNode* nodes, const RcPrim* prims, uint32_t n, int tlas, const uint32_t* gate = nullptr) {
     const size_t words = (size_t)(b.arrive - b.zeroed) + (n - 1);
     if (words) hipLaunchKernelGGL(k_zero_words, dim3(grid_for(words)), dim3(kBlock), 0, st, b.zeroed, words);
     if (n < 2) return;
-    hipLaunchKernelGGL(k_refit, dim3((n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, nodes, prims, b.arrive, b.ranges, n, tlas);
+    hipLaunchKernelGGL(k_refit, dim3((n + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, nodes, prims, b.arrive, b.ranges, n, tlas, gate);
 }
 
 // old -> new index of a tree's internal nodes when its top K go to the front in breadth-first order (k_top_remap); depends on the topology only
-void top_renumber(hipStream_t st, const RcNode* nodes, uint32_t n_leaves, uint32_t K, uint32_t* remap) {
-    hipLaunchKernelGGL(k_iota1, dim3(grid_for(n_leaves - 1)), dim3(kBlock), 0, st, remap, n_leaves - 1);
-    hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, st, nodes, n_leaves, K, remap);
+void top_renumber(hipStream_t st, const RcNode* nodes, uint32_t n_leaves, uint32_t K, uint32_t* remap, const uint32_t* gate = nullptr) {
+    hipLaunchKernelGGL(k_iota1, dim3(grid_for(n_leaves - 1)), dim3(kBlock), 0, st, remap, n_leaves - 1, gate);
+    hipLaunchKernelGGL(k_top_remap, dim3(1), dim3(kTopBlock), 0, st, nodes, n_leaves, K, remap, gate);
 }
 
 // The degenerate filter over n faces: flags, their exclusive scan `pos` (storage `tmp`, sized by the caller), the valid ones compacted into `out`
@@ -1024,35 +1119,37 @@ void read_root_aabb(rc_scene* s, const RcNode* d_root, bool tlas, float mn[3], f
 
 // What a TLAS derives per instance from the descriptors in s->d_instances: with `recs` the traversal records and entry-cull spheres, with
 // `leaves` the leaf nodes -- in the order of `sorted` (a build), or each leaf for the instance it already names (a refit: nullptr).
-void per_instance_pass(rc_scene* s, hipStream_t st, uint32_t n, bool recs, bool leaves, const uint32_t* sorted = nullptr) {
+void per_instance_pass(rc_scene* s, hipStream_t st, uint32_t n, bool recs, bool leaves, const uint32_t* sorted = nullptr, const uint32_t* gate = nullptr) {
     if (recs) hipLaunchKernelGGL(k_inst_recs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, s->d_blas_nprims.p, n, s->inst_recs.p,
                                  (const uint32_t*)s->blas_cull_bits.p, s->inst_cull.p);
-    if (leaves) hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, st, s->tlas_nodes.p, sorted, s->d_instances.p, s->d_descs.p, n);
+    if (leaves) hipLaunchKernelGGL(k_tlas_leaves, dim3(grid_for(n)), dim3(kBlock), 0, st, s->tlas_nodes.p, sorted, s->d_instances.p, s->d_descs.p, n, gate);
 }
 
 // The TLAS part of the traversal copy (behind the BLAS nodes), renumbered when the scene keeps the TLAS's top in LDS (tlas_top_k).  Its
 // leaves copy the entry-cull spheres: every chain that changes a sphere (k_inst_recs, k_update_instances, k_deform_instances) ends here
 // or in the fused rebuild's copy-out before a trace may run.
-void pack_tlas(rc_scene* s, hipStream_t st) {
+void pack_tlas(rc_scene* s, hipStream_t st, const uint32_t* gate = nullptr) {
     const uint32_t n = (s->n_tlas_nodes + 1) / 2;
-    if (s->tlas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, s->tlas_remap.p, (const float4*)s->inst_cull.p);
-    else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, (const float4*)s->inst_cull.p);
+    if (s->tlas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, s->tlas_remap.p, (const float4*)s->inst_cull.p, gate);
+    else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->n_tlas_nodes)), dim3(kBlock), 0, st, s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->n_tlas_nodes, n, (const float4*)s->inst_cull.p, gate);
 }
 
 // build_tlas_topology (src/instanced-bvh.jl:1485-1594) from the n descriptors in s->d_instances, into the scene's TLAS arrays: tree,
 // instance -> leaf table, top renumbering, traversal copy.  Every array it writes was reserved by rc_build_tlas.
-void tlas_chain(rc_scene* s, hipStream_t st, const ChainBufs& b, uint32_t n) {
+// `gate` (see gate_closed): the kernels that write any of those arrays return when it reads 0; the ones that touch only the chain's scratch,
+// the sort included, run regardless -- a skipped rebuild costs their time and nothing else.
+void tlas_chain(rc_scene* s, hipStream_t st, const ChainBufs& b, uint32_t n, const uint32_t* gate = nullptr) {
     hipLaunchKernelGGL(k_instance_aabbs, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, n, b.aabbs, b.partials);
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(384), 0, st, b.partials, grid_for(n), b.enc);
     hipLaunchKernelGGL(k_tlas_morton, dim3(grid_for(n)), dim3(kBlock), 0, st, s->d_instances.p, s->d_descs.p, n, b.enc, b.keys_a, b.vals_a);
     sort_pairs(st, b, n);
-    emit_tree(st, b, s->tlas_nodes.p, n);
+    emit_tree(st, b, s->tlas_nodes.p, n, gate);
     // n == 1 (:1553-1570): the single leaf holds the scene AABB == the instance's world AABB (same min/max set)
-    per_instance_pass(s, st, n, false, true, b.vals_b);
-    run_refit(st, b, s->tlas_nodes.p, nullptr, n, 1);
-    hipLaunchKernelGGL(k_inst_leaf, dim3(grid_for(n)), dim3(kBlock), 0, st, b.vals_b, n, s->inst_leaf.p);  // instance -> leaf (rc_update_instances_async)
-    if (s->tlas_top_k) top_renumber(st, s->tlas_nodes.p, n, s->tlas_top_k, s->tlas_remap.p);  // topology only: computed here, reused by every refit
-    pack_tlas(s, st);
+    per_instance_pass(s, st, n, false, true, b.vals_b, gate);
+    run_refit(st, b, s->tlas_nodes.p, nullptr, n, 1, gate);
+    hipLaunchKernelGGL(k_inst_leaf, dim3(grid_for(n)), dim3(kBlock), 0, st, b.vals_b, n, s->inst_leaf.p, gate);  // instance -> leaf (rc_update_instances_async)
+    if (s->tlas_top_k) top_renumber(st, s->tlas_nodes.p, n, s->tlas_top_k, s->tlas_remap.p, gate);  // topology only: computed here, reused by every refit
+    pack_tlas(s, st, gate);
 }
 
 // refit_tlas! (src/instanced-bvh.jl:2197-2222) in place: per-instance data (unless it is in place already) -> bottom-up refit -> traversal copy
@@ -1252,8 +1349,8 @@ void rc_build_tlas(rc_scene* s) {
         top_renumber(s->stream, s->blas[0].nodes.p, n_leaves, s->blas_top_k, s->top_remap.p);
     }
     for (uint32_t i = 0; i < nb; ++i) {
-        if (s->blas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->blas[i].n_nodes)), dim3(kBlock), 0, s->stream, s->blas[i].nodes.p, s->flat_nodes.p + s->descs[i].nodes_offset, s->blas[i].n_nodes, s->blas[i].n_prims, s->top_remap.p, (const float4*)nullptr);
-        else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->blas[i].n_nodes)), dim3(kBlock), 0, s->stream, s->blas[i].nodes.p, s->flat_nodes.p + s->descs[i].nodes_offset, s->blas[i].n_nodes, s->blas[i].n_prims, (const float4*)nullptr);
+        if (s->blas_top_k) hipLaunchKernelGGL(k_pack_nodes_remap, dim3(grid_for(s->blas[i].n_nodes)), dim3(kBlock), 0, s->stream, s->blas[i].nodes.p, s->flat_nodes.p + s->descs[i].nodes_offset, s->blas[i].n_nodes, s->blas[i].n_prims, s->top_remap.p, (const float4*)nullptr, (const uint32_t*)nullptr);
+        else hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for(s->blas[i].n_nodes)), dim3(kBlock), 0, s->stream, s->blas[i].nodes.p, s->flat_nodes.p + s->descs[i].nodes_offset, s->blas[i].n_nodes, s->blas[i].n_prims, (const float4*)nullptr, (const uint32_t*)nullptr);
         RC_HIP(hipMemcpyAsync(s->flat_prims.p + s->descs[i].primitives_offset, s->blas[i].prims.p, sizeof(RcPrim) * s->blas[i].n_prims, hipMemcpyDeviceToDevice, s->stream));
     }
     if (nb) RC_HIP(hipMemcpyAsync(s->d_descs.p, s->descs.data(), sizeof(RcBlasDesc) * nb, hipMemcpyHostToDevice, s->stream));
@@ -1270,6 +1367,7 @@ void rc_build_tlas(rc_scene* s) {
     s->captured_deform = false;
     s->blas_bounds_stale = false;  // (rc_sync refreshed the host copies before this rebuild read them)
     for (auto& b : s->blas) b.root_on_device = false;
+    s->quality_armed = false;
     if (n == 0) {  // :969-977
         s->bound_stale = false;
         s->n_tlas_nodes = 0;
@@ -1290,6 +1388,8 @@ void rc_build_tlas(rc_scene* s) {
         r.onesweep = (int64_t)n >= s->opt.onesweep_min;
         r.sort_bytes = 0;
         sort_pairs(s->stream, rebuild_bufs(s), n, &r.sort_bytes);
+        s->quality.reserve(kQualityStateWords + 2 * (size_t)kQualityMaxBlocks);  // (rc_refit_or_rebuild_tlas_async: disarmed above, zeroed here)
+        RC_HIP(hipMemsetAsync(s->quality.p, 0, sizeof(RcTlasQuality), s->stream));
     }
     RC_HIP(hipMemcpyAsync(s->d_instances.p, s->instances.data(), sizeof(RcInstanceDesc) * n, hipMemcpyHostToDevice, s->stream));
     per_instance_pass(s, s->stream, n, true, false);
@@ -1355,22 +1455,80 @@ void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
 // rebuild_bvh! (src/instanced-bvh.jl:968-992, build_tlas_topology :1485-1594) on `st` from the descriptors the device holds, in place --
 // same buffers, same addresses, so captured updates, refits and traces stay valid -- with the scratch reserved at sync time and without
 // the root read-back.  per_instance as for rc_refit_tlas_async.
-void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
-    const uint32_t n = (uint32_t)s->instances.size();
-    if (n == 0) return;
-    if (s->rebuild.n != n) throw RcError(4, "rebuild scratch does not match the instance count");  // (reserved by every rebuilding rc_sync)
-    if (per_instance) per_instance_pass(s, st, n, true, false);
+static RcTlasQuality* quality_block(rc_scene* s) { return reinterpret_cast<RcTlasQuality*>(s->quality.p); }
+// The cost of the tree in s->tlas_nodes (n >= 1 leaves) as it is when the kernels run, committed in `mode` (quality_commit).  area: which of
+// the two partial areas behind the block -- 0 the rebuild's, 1 rc_tlas_cost_async's, so that the two may run on different streams
+static void cost_pass(rc_scene* s, hipStream_t st, uint32_t n, int area, double* out, double ratio, int mode, const uint32_t* gate) {
+    double* partials = s->quality.p + kQualityStateWords + (size_t)area * kQualityMaxBlocks;
+    const uint32_t nb = n >= 2 ? std::min(grid_for(n - 1), (unsigned)kQualityMaxBlocks) : 0u;
+    if (nb) hipLaunchKernelGGL(k_tlas_cost_partials, dim3(nb), dim3(kCostBlock), 0, st, (const RcNode*)s->tlas_nodes.p, n, partials);
+    hipLaunchKernelGGL(k_tlas_cost_fold, dim3(1), dim3(kCostBlock), 0, st, (const RcNode*)s->tlas_nodes.p, n, (const double*)partials, nb, out, quality_block(s),
+                       ratio, mode, gate);
+}
+// The rebuild itself, on either device path.  mode < 0: what rc_rebuild_tlas_async always did.  kRecord / kArm: followed by the record step.
+// kDecide: taken only if the tree in memory costs more than ratio x the baseline -- decided on the device, in front
+static void rebuild_launch(rc_scene* s, hipStream_t st, uint32_t n, int mode, double ratio) {
     if (s->opt.tlas_rebuild_fused && n >= 2 && n <= (uint32_t)kFusedInst && s->tlas_top_k == 0) {
-        hipLaunchKernelGGL(k_rebuild_tlas_fused, dim3(1), dim3(kFusedInst), 0, st, (const RcInstanceDesc*)s->d_instances.p, (const RcBlasDesc*)s->d_descs.p, n,
-                           s->tlas_nodes.p, s->flat_nodes.p + s->n_flat_nodes, s->tlas_ranges.p, s->inst_leaf.p, (const float4*)s->inst_cull.p);
-    } else {
-        tlas_chain(s, st, rebuild_bufs(s), n);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(1), dim3(kFusedInst), 0, st, (const RcInstanceDesc*)s->d_instances.p, (const RcBlasDesc*)s->d_descs.p, n, s->tlas_nodes.p,
+                               s->flat_nodes.p + s->n_flat_nodes, s->tlas_ranges.p, s->inst_leaf.p, (const float4*)s->inst_cull.p, quality_block(s), ratio, mode);
+        };
+        if (mode < 0) launch(k_rebuild_tlas_fused<false>); else launch(k_rebuild_tlas_fused<true>);
+        return;
     }
+    const uint32_t* gate = nullptr;
+    if (mode == kDecide) {
+        cost_pass(s, st, n, 0, nullptr, ratio, kDecide, nullptr);
+        if (n < 2) return;  // (a single leaf: cost 1, never rebuilt)
+        gate = &quality_block(s)->gate;  // written by the kernel above, read by the ones below: a kernel boundary on one stream
+    }
+    tlas_chain(s, st, rebuild_bufs(s), n, gate);
+    if (mode >= 0) cost_pass(s, st, n, 0, nullptr, ratio, mode == kDecide ? (int)kRecord : mode, gate);
+}
+static void after_async_commit(rc_scene* s, hipStream_t st) {
     RC_HIP(hipGetLastError());
     s->host_instances_stale = true;
     s->bound_stale = true;
     if (stream_capturing(st)) s->captured_refit = true;  // (replays move the root box, as a captured refit's do)
     note_async_mutation(s, st);
+}
+void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
+    const uint32_t n = (uint32_t)s->instances.size();
+    if (n == 0) return;
+    if (s->rebuild.n != n) throw RcError(4, "rebuild scratch does not match the instance count");  // (reserved by every rebuilding rc_sync)
+    if (per_instance) per_instance_pass(s, st, n, true, false);
+    rebuild_launch(s, st, n, s->quality_armed ? (int)kRecord : -1, 0.0);  // (armed: the baseline follows explicit rebuilds)
+    after_async_commit(s, st);
+}
+
+// rc_refit_tlas_async, then the rebuild above if the refitted tree has degraded: cost > ratio x cost_built, evaluated and acted on by the
+// device (RcTlasQuality, rc_internal.h).  The first call after a rebuilding rc_sync arms the block: the host cannot know what an earlier
+// sequence of refits left, so it enqueues refit -> unconditional rebuild -> record, eagerly.
+void rc_refit_or_rebuild_tlas_async(rc_scene* s, bool per_instance, double ratio, hipStream_t st) {
+    const uint32_t n = (uint32_t)s->instances.size();
+    if (n == 0) return;
+    if (s->rebuild.n != n) throw RcError(4, "rebuild scratch does not match the instance count");
+    if (!s->quality_armed && stream_capturing(st))
+        throw RcError(6, "the first rc_refit_or_rebuild_tlas_device_async after a rebuilding rc_sync records the tree's baseline cost and must run eagerly: call it once before capturing it");
+    refit_chain(s, st, rebuild_bufs(s), n, per_instance);
+    rebuild_launch(s, st, n, s->quality_armed ? (int)kDecide : (int)kArm, ratio);
+    s->quality_armed = true;
+    after_async_commit(s, st);
+}
+
+void rc_tlas_cost_async(rc_scene* s, double* d_cost, hipStream_t st) {
+    const uint32_t n = (uint32_t)s->instances.size();
+    if (n == 0) return;
+    cost_pass(s, st, n, 1, d_cost, 0.0, kCostOnly, nullptr);
+    RC_HIP(hipGetLastError());
+    if (!s->async_pending || s->async_stream == st) note_async_mutation(s, st);  // no mutation, but rc_scene_destroy waits for it like one (a flag, no event; with work pending on another stream that stream stays the one waited for: the header's LIFETIME note)
+}
+
+void rc_tlas_quality_read(rc_scene* s, RcTlasQuality* out) {
+    memset(out, 0, sizeof(*out));
+    if (s->instances.empty() || !s->quality.p) return;
+    rc_wait_async_mutations(s);
+    rc_copy_now(out, s->quality.p, sizeof(*out), hipMemcpyDeviceToHost);
 }
 
 // Host wait for the EAGER asynchronous updates and refits enqueued so far.  Replays of a graph that captured them are the caller's to
@@ -1544,7 +1702,7 @@ void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_ver
         // filter had dropped get the default, their index)
         if (capturing) throw RcError(1, "the first rc_update_mesh_vertices_device_async of a loaded geometry recovers its per-face metadata and cannot be captured: run the call eagerly once first");
         b.m_face_meta.reserve(b.n_mesh_faces);
-        hipLaunchKernelGGL(k_iota1, dim3(grid_for(b.n_mesh_faces)), dim3(kBlock), 0, st, b.m_face_meta.p, b.n_mesh_faces);
+        hipLaunchKernelGGL(k_iota1, dim3(grid_for(b.n_mesh_faces)), dim3(kBlock), 0, st, b.m_face_meta.p, b.n_mesh_faces, (const uint32_t*)nullptr);
         hipLaunchKernelGGL(k_face_meta_of, dim3(grid_for(np)), dim3(kBlock), 0, st, (const RcPrim*)b.prims.p, (const uint32_t*)b.src_face.p, np, b.m_face_meta.p);
     }
     // ---- the filter over the n faces, then the build over np slots into the staged arrays

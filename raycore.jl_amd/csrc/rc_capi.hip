@@ -1258,6 +1258,40 @@ int rc_rebuild_tlas_device_async(rc_scene* s, void* stream) {
     return commit_device_async(s, stream, "scene has pending host-side mutations: call rc_sync (rc_rebuild_tlas_device_async rebuilds from device-side transforms only)", rc_rebuild_tlas_async);
 }
 
+// rc_refit_device_async, then rc_rebuild_tlas_device_async if the refitted tree costs more than ratio x what it cost when it was built: the
+// cost pass and the decision run on the device, so one captured frame refits while instances drift and rebuilds when they scatter.
+int rc_refit_or_rebuild_tlas_device_async(rc_scene* s, double ratio, void* stream) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (!(ratio > 0.0) || !std::isfinite(ratio)) return fail(RC_ERR_INVALID_ARGUMENT, "ratio must be finite and > 0");
+    return guarded([&] {
+        require_device_resident(s, "scene has pending host-side mutations: call rc_sync (rc_refit_or_rebuild_tlas_device_async commits device-side updates only)");
+        use_device(s);
+        rc_refit_or_rebuild_tlas_async(s, !s->device_dirty, ratio, (hipStream_t)stream);
+        note_device_commit(s);
+    });
+}
+// The cost the decision is made from, for a caller's own policy: one f64 to caller-owned device memory, on `stream`
+int rc_tlas_cost_device(rc_scene* s, double* d_cost, void* stream) {
+    if (!s || !d_cost) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded([&] {
+        require_device_resident(s, "rc_tlas_cost_device reads the tree where the last rc_sync put it: the scene has pending host-side mutations, call rc_sync first");
+        use_device(s);
+        rc_tlas_cost_async(s, d_cost, (hipStream_t)stream);
+    });
+}
+int rc_tlas_quality(rc_scene* s, rc_tlas_quality_info* out) {
+    if (!s || !out) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded([&] {
+        require_device_resident(s, "scene has pending host-side mutations: call rc_sync (rc_tlas_quality reads the state of the synced scene)");
+        use_device(s);
+        RcTlasQuality q;
+        rc_tlas_quality_read(s, &q);
+        out->cost = q.cost; out->cost_built = q.cost_built;
+        out->evaluations = q.evaluations; out->rebuilds = q.rebuilds; out->last_rebuilt = q.last_rebuilt;
+        out->armed = s->quality_armed ? 1u : 0u;
+    });
+}
+
 // update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) with a backend-resident soup, on the caller's stream and in place
 // (rc_update_geometry_async, rc_build.hip).  State afterwards: as after rc_update_transforms_device.
 static void update_geometry_device(rc_scene* s, uint32_t handle, const float* d_verts, const uint32_t* d_meta, uint32_t n, const float* d_mesh_verts,

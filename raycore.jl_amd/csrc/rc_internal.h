@@ -116,6 +116,17 @@ struct Blas {  // one geometry: build_blas output (src/instanced-bvh.jl:111-118)
     bool root_on_device = false;  // updated in place on the device since root_min / root_max were last read back (rc_ensure_blas_bounds)
 };
 
+// Device-side record of the TLAS's quality (rc_refit_or_rebuild_tlas_async): cost = summed surface area of the internal nodes' boxes relative
+// to the root's, as of the latest evaluation; cost_built = the cost the tree had when it was last built; gate = "the evaluation on this
+// stream asks for a rebuild", read by the chain's kernels across a kernel boundary and cleared by the record step that ends the rebuild.
+struct RcTlasQuality {
+    double cost, cost_built;
+    uint32_t gate, evaluations, rebuilds, last_rebuilt;
+};
+static_assert(sizeof(RcTlasQuality) == 32, "RcTlasQuality is read back as 32 bytes");
+// the block sits at the front of rc_scene::quality, in front of two areas of per-block partial sums (f64): the gated call's, rc_tlas_cost_device's
+constexpr uint32_t kQualityStateWords = sizeof(RcTlasQuality) / sizeof(double), kQualityMaxBlocks = 1024;
+
 struct HandleRange {
     uint32_t first = 0, count = 0;  // 0-based range in the instance array
 };
@@ -263,6 +274,12 @@ struct rc_scene {
         DevBuf<unsigned char> tmp;      // scan / sort storage
         std::map<uint32_t, size_t> scan_bytes, sort_bytes;  // per item count, queried by eager calls
     } deform;
+    // state of rc_refit_or_rebuild_tlas_async: an RcTlasQuality, then 2 x kQualityMaxBlocks partial sums.  Reserved, zeroed and disarmed by every
+    // rebuilding rc_sync (rc_build_tlas), beside the rebuild scratch.  quality_armed: the block's cost_built describes the tree the device
+    // holds -- set by the first rc_refit_or_rebuild_tlas_async after such a sync (eager: refit, unconditional rebuild, record); while set,
+    // rc_rebuild_tlas_async appends the record step
+    DevBuf<double> quality;
+    bool quality_armed = false;
     // blas_bounds_stale  set: rc_update_geometry_async (the root boxes in d_descs are newer than descs / Blas::root_min,max).  cleared: rc_ensure_blas_bounds
     //                    (read-back), rebuilding rc_sync.  captured_deform: the call was captured -- re-read on every use, like captured_refit
     bool blas_bounds_stale = false, captured_deform = false;
@@ -393,6 +410,10 @@ void rc_mat3x4_inverse(const float m[12], float out[12]);
 void rc_update_instances_async(rc_scene* s, uint32_t first, uint32_t m, const float* d_xforms, hipStream_t stream);  // transforms -> descriptors, records, cull spheres, leaf boxes
 void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t stream);  // refit_tlas! on `stream`, no read-back: leaves the world bound stale
 void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t stream);  // rebuild_bvh! on `stream` from the device descriptors, in place, no read-back
+// refit_tlas! on `stream`, then rebuild_bvh! there if the tree's cost exceeds ratio x the cost it had when built: decided on the device
+void rc_refit_or_rebuild_tlas_async(rc_scene* s, bool per_instance, double ratio, hipStream_t stream);
+void rc_tlas_cost_async(rc_scene* s, double* d_cost, hipStream_t stream);  // the cost of the tree as it is when the kernels run -> *d_cost
+void rc_tlas_quality_read(rc_scene* s, RcTlasQuality* out);                 // the block, behind the eager asynchronous work (host wait)
 // build_blas on `stream` from a device soup (or, with d_mesh_verts, the geometry's stored faces), committed in place when the valid-face count is unchanged
 void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_verts, const uint32_t* d_meta, uint32_t n, const float* d_mesh_verts, const float* d_mesh_normals, hipStream_t stream);
 void rc_ensure_blas_bounds(rc_scene* s);  // descs / Blas::root_min,max current after rc_update_geometry_async (waits; throws while its stream is being captured)

@@ -501,6 +501,27 @@ refit_tlas_async!(t::MI355XTLAS; stream::Ptr{Cvoid} = C_NULL) =
 # sync! does after structural changes; this method is the one for instances that moved far from where they were sorted.)
 Raycore.rebuild_bvh!(t::MI355XTLAS, stream::Ptr{Cvoid}) =
     (check(ccall((:rc_rebuild_tlas_device_async, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), t.ptr, stream)); t)
+# WHEN to rebuild, decided on the device: refit_tlas_async!, then the rebuild above only if the refitted tree costs more than `ratio` x what
+# it cost when it was last built (summed surface area of the internal boxes relative to the root's).  One captured frame then refits while
+# instances drift and rebuilds on the replay in which they scatter.  The first call after a structural sync! arms the state and must be
+# eager.  tlas_cost! writes that cost (one Float64) to device memory on `stream`; tlas_quality reads the decisions back on the host.
+refit_or_rebuild_tlas_async!(t::MI355XTLAS, ratio::Real; stream::Ptr{Cvoid} = C_NULL) =
+    (check(ccall((:rc_refit_or_rebuild_tlas_device_async, LIB), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Cvoid}), t.ptr, Float64(ratio), stream)); t)
+tlas_cost!(t::MI355XTLAS, d_cost::Ptr{Float64}; stream::Ptr{Cvoid} = C_NULL) =
+    (check(ccall((:rc_tlas_cost_device, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), t.ptr, d_cost, stream)); t)
+struct TLASQuality  # rc_tlas_quality_info
+    cost::Float64
+    cost_built::Float64
+    evaluations::UInt32
+    rebuilds::UInt32
+    last_rebuilt::UInt32
+    armed::UInt32
+end
+function tlas_quality(t::MI355XTLAS)
+    q = Ref(TLASQuality(0.0, 0.0, 0, 0, 0, 0))
+    check(ccall((:rc_tlas_quality, LIB), Cint, (Ptr{Cvoid}, Ref{TLASQuality}), t.ptr, q))
+    q[]
+end
 
 # update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) with a backend-resident soup: `d_verts` points at n x 9 Float32 in
 # device memory, read when the kernels run on `stream`; the BLAS is rebuilt there and committed in place when the number of non-degenerate

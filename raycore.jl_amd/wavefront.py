@@ -51,6 +51,15 @@ class WavefrontPaths:
     default and calls accel.rebuild_device_async(stream) eagerly between replays of the captured refit frame: the rebuild works in place,
     so the captured graph stays valid and refits the new topology from then on.
 
+    rebuild="auto" (needs `dynamic`): the head of every frame calls refit_or_rebuild_device_async(self.rebuild_ratio) -- a refit, and a
+    rebuild only on the frames whose refitted tree costs more than rebuild_ratio x what the tree cost when it was last built, decided on
+    the device, so one captured frame takes either path from replay to replay.  The constructor makes the eager arming call (a refit and
+    a rebuild of the accel's current transforms on the current stream, waited for), so capture() works at once; accel.tlas_quality()
+    reads the decisions back.  The ratio is the attribute rebuild_ratio, 1.5 unless the caller sets it before run() / capture() (a
+    captured frame keeps the ratio it was captured with; the constructor's parameter list is pinned by tests/test_soft_shadow_api.py, so
+    it is not a keyword).  1.5 is a judgement: no measurement stands behind it.  profiles/tlas_auto_rebuild.json (tools/probes/tlas_rebuild_probe.py)
+    has one curve of cost and trace time against the fraction of instances exchanged, on C3, from which a later change can choose.
+
     deform: a list of (handle, soup tensor) pairs -- float32 (n, 9) or (n, 3, 3) on the accel's device.  Every frame then starts with
     update_geometry_device_async for each pair, before the `dynamic` transform updates and the refit (or rebuild) that ends the head of
     the frame; `deform` without `dynamic` still ends it with a refit.  A soup must keep its number of non-degenerate faces.
@@ -71,6 +80,8 @@ class WavefrontPaths:
                  deform=None, lights=None, fused_shadows=False, shadow_samples=1, light_radii=None):
         if depth < 1:
             raise ValueError("depth must be at least 1")
+        if isinstance(rebuild, (str, tuple)) and rebuild != "auto":
+            raise ValueError('rebuild must be False, True or "auto"')
         if rebuild and not dynamic:
             raise ValueError("rebuild=True needs dynamic: the rebuild follows the transform updates at the head of the frame")
         self.fused_shadows = bool(fused_shadows)
@@ -112,7 +123,8 @@ class WavefrontPaths:
         self.light = None if light is None else np.ascontiguousarray(light, dtype=np.float32)
         self.seed, self.bias, self.compact = int(seed), float(bias), bool(compact)
         self.dynamic = list(dynamic) if dynamic else []
-        self.rebuild = bool(rebuild)
+        self.rebuild = "auto" if rebuild == "auto" else bool(rebuild)
+        self.rebuild_ratio = 1.5
         self.deform = list(deform) if deform else []
         dev = torch.device("cuda", accel.device)
         rec = lambda: torch.zeros(self.n * 32, dtype=torch.uint8, device=dev)  # noqa: E731
@@ -149,6 +161,9 @@ class WavefrontPaths:
         self._streams = set()
         self.graph = None
         self._graph_stream = None
+        if self.rebuild == "auto" and not accel.tlas_quality()["armed"]:  # the arming call is eager by contract: here, so that capture() works
+            accel.refit_or_rebuild_device_async(self.rebuild_ratio, stream=torch.cuda.current_stream(dev).cuda_stream)
+            torch.cuda.current_stream(dev).synchronize()
 
     def buffers(self):
         fused = self.visible + [self.lights] if self.fused_shadows else []
@@ -172,7 +187,9 @@ class WavefrontPaths:
         if self.dynamic or self.deform:
             for handle, xf in self.dynamic:
                 a.update_transforms_device(handle, xf, stream=st)
-            if self.rebuild:
+            if self.rebuild == "auto":
+                a.refit_or_rebuild_device_async(self.rebuild_ratio, stream=st)
+            elif self.rebuild:
                 a.rebuild_device_async(stream=st)
             else:
                 a.refit_device_async(stream=st)
