@@ -317,18 +317,22 @@ struct LaneStackP {
     typedef lds_e* pos_t;
     lds_e* base;         // &lds_stack[threadIdx.x]: entry k at base + k * BLOCK
     lds_e* limit;        // base + LDS_N * BLOCK
-    glb_u32* ovf;
+    glb_u32* ovf;        // the spill area (wave-uniform: a scalar register pair; the lane's own column is added on the rare path only)
+    uint32_t ovf_lane;   // this lane's column of it
     uint32_t ovf_stride;
     uint32_t* status;
-    __device__ inline LaneStackP(E* lds_base, uint32_t* ovf_base, uint32_t stride, uint32_t* st)
-        : base((lds_e*)lds_base), limit((lds_e*)lds_base + LDS_N * BLOCK), ovf((glb_u32*)ovf_base), ovf_stride(stride), status(st) {}
+    __device__ inline LaneStackP(E* lds_base, uint32_t* ovf_base, uint32_t lane_column, uint32_t stride, uint32_t* st)
+        : base((lds_e*)lds_base), limit((lds_e*)lds_base + LDS_N * BLOCK), ovf((glb_u32*)ovf_base), ovf_lane(lane_column), ovf_stride(stride), status(st) {}
     __device__ inline pos_t empty() const { return base; }
     __device__ inline int depth(pos_t top) const { return (int)(top - base) / BLOCK; }
+    // entry k >= LDS_N in the spill area, as a 32-bit element index: the persistent grids that use this stack have far fewer than
+    // 2^32 / kTotalStack threads, and nothing lane-varying and 64 bits wide is left for the compiler to keep in registers across the loop
+    __device__ inline uint32_t slot(int k) const { return (uint32_t)(k - LDS_N) * ovf_stride + ovf_lane; }
     __device__ inline void push(pos_t& top, uint32_t v) {
         if (__builtin_expect(top < limit, 1)) *top = (E)v;
         else {
             const int k = depth(top);
-            if (k < kTotalStack) ovf[(size_t)(k - LDS_N) * ovf_stride] = v;
+            if (k < kTotalStack) ovf[slot(k)] = v;
             else { *status = 1u; return; }
         }
         top += BLOCK;
@@ -336,7 +340,27 @@ struct LaneStackP {
     __device__ inline uint32_t pop(pos_t& top) {
         top -= BLOCK;
         if (__builtin_expect(top < limit, 1)) return *top;
-        return ovf[(size_t)(depth(top) - LDS_N) * ovf_stride];
+        return ovf[slot(depth(top))];
+    }
+    // The branch-free forms below serve lanes whose next free slot lies below the LDS depth: with top < limit the slot at `top` is a free LDS
+    // slot of the lane's own column, and a pop after a push reads at most the slot just written.  push and pop above test `top < limit` per
+    // lane, which the compiler turns into an exec-mask save / restore and a skip branch per site and pass -- for a spill path that is almost
+    // never taken.  phased_trace keeps the lanes at or beyond the LDS depth out of its interior loop and serves them with push / pop in a pass
+    // of their own: LDS, the spill area and the status word see the same bytes either way.
+    // -DRC_STACK_BRANCHY (dev, tools/ab_build.sh): push / pop everywhere, the form before docs/EXPERIMENTS.md "stack fast path".
+#if defined(RC_STACK_BRANCHY)
+    static constexpr bool kFast = false;
+#else
+    static constexpr bool kFast = true;
+#endif
+    // `if (do_push) push(v); return keep ? keep_v : pop();` -- the slot above the top is free, so it is written whether or not the lane
+    // pushes; LDS operations of a wave complete in order, so a lane that pushes and pops in one pass reads `v` back
+    __device__ inline uint32_t push_pop_lds(pos_t& top, bool do_push, uint32_t v, bool keep, uint32_t keep_v) {
+        *top = (E)v;
+        top += do_push ? BLOCK : 0;
+        const uint32_t popped = *(top - BLOCK);
+        top -= keep ? 0 : BLOCK;
+        return keep ? keep_v : popped;
     }
 };
 
@@ -724,7 +748,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
     const uint32_t* const lt = top.lt;
     const float2* const il = top.il;
     const uint32_t gtid = blockIdx.x * BLOCK + threadIdx.x;
-    Stack st(lds_stack + threadIdx.x, av.overflow + gtid, av.total_threads, av.status);
+    Stack st(lds_stack + threadIdx.x, av.overflow, gtid, av.total_threads, av.status);
     const int lane = threadIdx.x & 63;
     if (av.n_tlas_nodes == 0) {  // empty TLAS: every ray misses (test/test_tlas_stress.jl:808-831)
         for (uint64_t i = gtid; i < a.n_items; i += av.total_threads) sink(i, false, 0.0f, 0.0f, 0.0f, RC_INVALID_NODE, -1);
@@ -789,60 +813,82 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
         }
 #endif
         // ---- interior phase: intersect_internal_node (:1807-1832) + push far / descend near / pop (:1946-1960, 1991-1993)
-        for (;;) {
-            RC_MARK("interior_begin");
-            const bool is_int = node < n_level;  // sentinels and INVALID are >= 0xFFFFFFFE, never below a leaf threshold
-            const int n_int = __popcll(__ballot(is_int));
-            if (n_int == 0) break;
-            it_total += 1u;
-            if (STATS) { st_iter[1] += 1; st_lane[1] += is_int ? 1 : 0; }
-            if (TIMELINE) { tl_int += 1; if (tl_tx) tl_int_x += 1; }
-            if (is_int) {
+        // One pass over an interior node.  DEEP = false: every participating lane's next free stack slot lies below the LDS depth (the loop
+        // below admits no other lane), so push and pop are the branch-free LDS forms; DEEP = true: the general push / pop with the spill path.
+        auto interior_pass = [&](auto deep_tag) {
+            constexpr bool DEEP = decltype(deep_tag)::value;
 #if defined(RC_EXP_VALU)  // dev experiment (tools/probes/build_variants.sh; profiles/r05_bound_probe.txt): RC_EXP_VALU extra slow-class VALU instructions (one dependent chain) per interior pass
-                { float dummy = tmin;
+            { float dummy = tmin;
 #pragma unroll
-                  for (int k = 0; k < RC_EXP_VALU; ++k) asm volatile("v_max_f32 %0, %0, %1" : "+v"(dummy) : "v"(closest_t));
-                  if (dummy == 1.2345e-30f) tmin = dummy; }
+              for (int k = 0; k < RC_EXP_VALU; ++k) asm volatile("v_max_f32 %0, %0, %1" : "+v"(dummy) : "v"(closest_t));
+              if (dummy == 1.2345e-30f) tmin = dummy; }
 #endif
 #if defined(RC_EXP_NOP)   // ... RC_EXP_NOP x 16 idle cycles in the pass
 #pragma unroll
-                for (int k = 0; k < RC_EXP_NOP; ++k) asm volatile("s_nop 15");
+            for (int k = 0; k < RC_EXP_NOP; ++k) asm volatile("s_nop 15");
 #endif
-                float4 na, nb, nc;
-                u2v ch;
-                constexpr int PS = Shape::kPlaneNodes;  // plane stride
-                if ((Shape::top == Top::Lds && (cur_inst < 0 || node <= a.blas_k)) || (Shape::top == Top::PartialLds && node <= (cur_inst < 0 ? a.tlas_k : a.blas_k))) {
-                    const float2* q = tl + ((node - 1u) + (cur_inst < 0 ? 0u : a.lds_blas_base));
-                    const float2 p0 = q[0], p1 = q[PS], p2 = q[2 * PS], p3 = q[3 * PS], p4 = q[4 * PS], p5 = q[5 * PS], p6 = q[6 * PS];
-                    na = make_float4(p0.x, p0.y, p1.x, p1.y); nb = make_float4(p2.x, p2.y, p3.x, p3.y); nc = make_float4(p4.x, p4.y, p5.x, p5.y);
-                    ch = u2v{__float_as_uint(p6.x), __float_as_uint(p6.y)};
-                } else {
-                    const uint32_t off = (cur_off + node) << 6;  // the record of 1-based node index `node`: rsrc base is one record early
-                    na = buf_f4(nrs1, off); nb = buf_f4(nrs1, off, 16); nc = buf_f4(nrs1, off, 32);
-                    ch = __builtin_amdgcn_raw_buffer_load_b64(nrs1, off, 48, 0);
-                }
-                // packed node (rc_pack_node): na = child-0 (min.x,min.y,max.x,max.y), nb = child-1 likewise, nc = z of both
-                const v2f ixy = {inv.x, inv.y}, oxy = {ox.x, ox.y}, izz = {inv.z, inv.z}, ozz = {ox.z, ox.z};
-                const v2f n0xy = v2f{na.x, na.y} * ixy + oxy, f0xy = v2f{na.z, na.w} * ixy + oxy;
-                const v2f n1xy = v2f{nb.x, nb.y} * ixy + oxy, f1xy = v2f{nb.z, nb.w} * ixy + oxy;
-                const v2f nf0z = v2f{nc.x, nc.y} * izz + ozz, nf1z = v2f{nc.z, nc.w} * izz + ozz;
-                const float f0x = f0xy.x, f0y = f0xy.y, f0z = nf0z.y, n0x = n0xy.x, n0y = n0xy.y, n0z = nf0z.x;
-                const float f1x = f1xy.x, f1y = f1xy.y, f1z = nf1z.y, n1x = n1xy.x, n1y = n1xy.y, n1z = nf1z.x;
-                const float t0_max = jl_minf(jl_minf(jl_minf(jl_maxf(f0x, n0x), jl_maxf(f0y, n0y)), jl_maxf(f0z, n0z)), closest_t);
-                const float t0_min = jl_maxf(jl_maxf(jl_maxf(jl_minf(f0x, n0x), jl_minf(f0y, n0y)), jl_minf(f0z, n0z)), tmin);
-                const float t1_max = jl_minf(jl_minf(jl_minf(jl_maxf(f1x, n1x), jl_maxf(f1y, n1y)), jl_maxf(f1z, n1z)), closest_t);
-                const float t1_min = jl_maxf(jl_maxf(jl_maxf(jl_minf(f1x, n1x), jl_minf(f1y, n1y)), jl_minf(f1z, n1z)), tmin);
-                // intersect_internal_node's INVALID-or-child values, kept as predicates (an interior node has two valid children):
-                // traverse0 = h0 ? child0 : INVALID, traverse1 likewise; near first iff t0_min < t1_min && traverse0 valid
-                const bool h0 = t0_min <= t0_max, h1 = t1_min <= t1_max;
-                const bool first0 = (t0_min < t1_min) & h0;
-                const uint32_t near_c = first0 ? ch.x : ch.y, far_c = first0 ? ch.y : ch.x;
-                const bool near_ok = first0 | h1, far_ok = h0 & (h1 | !first0);  // = first0 ? h1 : h0 (first0 implies h0), as lane-mask logic
+            float4 na, nb, nc;
+            u2v ch;
+            constexpr int PS = Shape::kPlaneNodes;  // plane stride
+            if ((Shape::top == Top::Lds && (cur_inst < 0 || node <= a.blas_k)) || (Shape::top == Top::PartialLds && node <= (cur_inst < 0 ? a.tlas_k : a.blas_k))) {
+                const float2* q = tl + ((node - 1u) + (cur_inst < 0 ? 0u : a.lds_blas_base));
+                const float2 p0 = q[0], p1 = q[PS], p2 = q[2 * PS], p3 = q[3 * PS], p4 = q[4 * PS], p5 = q[5 * PS], p6 = q[6 * PS];
+                na = make_float4(p0.x, p0.y, p1.x, p1.y); nb = make_float4(p2.x, p2.y, p3.x, p3.y); nc = make_float4(p4.x, p4.y, p5.x, p5.y);
+                ch = u2v{__float_as_uint(p6.x), __float_as_uint(p6.y)};
+            } else {
+                const uint32_t off = (cur_off + node) << 6;  // the record of 1-based node index `node`: rsrc base is one record early
+                na = buf_f4(nrs1, off); nb = buf_f4(nrs1, off, 16); nc = buf_f4(nrs1, off, 32);
+                ch = __builtin_amdgcn_raw_buffer_load_b64(nrs1, off, 48, 0);
+            }
+            // packed node (rc_pack_node): na = child-0 (min.x,min.y,max.x,max.y), nb = child-1 likewise, nc = z of both
+            const v2f ixy = {inv.x, inv.y}, oxy = {ox.x, ox.y}, izz = {inv.z, inv.z}, ozz = {ox.z, ox.z};
+            const v2f n0xy = v2f{na.x, na.y} * ixy + oxy, f0xy = v2f{na.z, na.w} * ixy + oxy;
+            const v2f n1xy = v2f{nb.x, nb.y} * ixy + oxy, f1xy = v2f{nb.z, nb.w} * ixy + oxy;
+            const v2f nf0z = v2f{nc.x, nc.y} * izz + ozz, nf1z = v2f{nc.z, nc.w} * izz + ozz;
+            const float f0x = f0xy.x, f0y = f0xy.y, f0z = nf0z.y, n0x = n0xy.x, n0y = n0xy.y, n0z = nf0z.x;
+            const float f1x = f1xy.x, f1y = f1xy.y, f1z = nf1z.y, n1x = n1xy.x, n1y = n1xy.y, n1z = nf1z.x;
+            const float t0_max = jl_minf(jl_minf(jl_minf(jl_maxf(f0x, n0x), jl_maxf(f0y, n0y)), jl_maxf(f0z, n0z)), closest_t);
+            const float t0_min = jl_maxf(jl_maxf(jl_maxf(jl_minf(f0x, n0x), jl_minf(f0y, n0y)), jl_minf(f0z, n0z)), tmin);
+            const float t1_max = jl_minf(jl_minf(jl_minf(jl_maxf(f1x, n1x), jl_maxf(f1y, n1y)), jl_maxf(f1z, n1z)), closest_t);
+            const float t1_min = jl_maxf(jl_maxf(jl_maxf(jl_minf(f1x, n1x), jl_minf(f1y, n1y)), jl_minf(f1z, n1z)), tmin);
+            // intersect_internal_node's INVALID-or-child values, kept as predicates (an interior node has two valid children):
+            // traverse0 = h0 ? child0 : INVALID, traverse1 likewise; near first iff t0_min < t1_min && traverse0 valid
+            const bool h0 = t0_min <= t0_max, h1 = t1_min <= t1_max;
+            const bool first0 = (t0_min < t1_min) & h0;
+            const uint32_t near_c = first0 ? ch.x : ch.y, far_c = first0 ? ch.y : ch.x;
+            const bool near_ok = first0 | h1, far_ok = h0 & (h1 | !first0);  // = first0 ? h1 : h0 (first0 implies h0), as lane-mask logic
+            if (DEEP) {
                 if (far_ok) st.push(sp, far_c);
                 node = near_ok ? near_c : st.pop(sp);
-            }
+            } else node = st.push_pop_lds(sp, far_ok, far_c, near_ok, near_c);
+        };
+        // sentinels and INVALID are >= 0xFFFFFFFE, never below a leaf threshold.  A lane whose stack has reached the LDS depth waits for the
+        // deep pass behind the loop: the order of ITS visits, pushes and pops is what it was, only when they happen changes.
+        // (The vote is taken from the lane masks of the two compares themselves: a vote on their conjunction costs a select and a compare more.)
+        for (;;) {
+            RC_MARK("interior_begin");
+            const bool is_int = node < n_level && (!Stack::kFast || sp < st.limit);
+            const unsigned long long m_int = __builtin_amdgcn_ballot_w64(node < n_level) & (Stack::kFast ? __builtin_amdgcn_ballot_w64(sp < st.limit) : ~0ull);
+            if (m_int == 0ull) break;
+            const int n_int = __popcll(m_int);
+            it_total += 1u;
+            if (STATS) { st_iter[1] += 1; st_lane[1] += is_int ? 1 : 0; }
+            if (TIMELINE) { tl_int += 1; if (tl_tx) tl_int_x += 1; }
+            if (is_int) interior_pass(std::integral_constant<bool, !Stack::kFast>());
             RC_MARK("interior_end");
             if (n_int < thr_eff) break;  // too few interior lanes left: serve the waiting ones first
+        }
+        // One vote per outer iteration: is any lane of the wave at or beyond the LDS depth?  If so (rare), those lanes get one interior pass
+        // of their own with the general push / pop.  The stack sites of the record and switch phases keep the general forms: their
+        // branch-free variants behind this vote measured no gain (docs/EXPERIMENTS.md, "stack fast path").
+        if (Stack::kFast && __builtin_expect(__ballot(!(sp < st.limit)) != 0ull, 0)) {
+            const bool deep = node < n_level && !(sp < st.limit);
+            if (__ballot(deep)) {
+                it_total += 1u;
+                if (STATS) { st_iter[1] += 1; st_lane[1] += deep ? 1 : 0; }
+                if (TIMELINE) { tl_int += 1; if (tl_tx) tl_int_x += 1; }
+                if (deep) interior_pass(std::true_type());
+            }
         }
         // ---- record phase: the lanes whose node is a leaf of their level.  A BLAS leaf's record holds a triangle (rc_pack_leaf), a TLAS
         // leaf's the entry-cull sphere and the index of its instance (rc_pack_tlas_leaf) -- at the same offset expression in the same
