@@ -440,7 +440,10 @@ int rc_blas4_build(rc_scene* scene, uint32_t blas_id, uint32_t* n_nodes);
 int rc_export_blas4_nodes(rc_scene* scene, uint32_t blas_id, rc_bvh4_node* out, uint32_t capacity, uint32_t* count);
 /* closest_hit4 (src/bvh4.jl:606-689) / any_hit4 (:696-766) over a host ray batch.  Both ignore rc_ray.tmin (the
  * reference starts from t_min = 0, :610/:700).  rc_hit: primitive_id = 0-based index into the BLAS's sorted primitives,
- * instance_id = RC_INVALID_ID, instance_custom_index = 0; miss as rc_trace_closest. */
+ * instance_id = RC_INVALID_ID, instance_custom_index = 0; miss as rc_trace_closest.  A geometry without a BLAS4 (never built, replaced by
+ * rc_update_geometry*, or updated in place by rc_update_geometry_device_async / rc_update_mesh_vertices_device_async since): RC_ERR_NOT_SYNCED,
+ * from these, their _device forms and rc_export_blas4_nodes, until rc_blas4_build.  The BLAS4 entry points look at the geometry alone:
+ * pending mutations of the scene do not refuse them. */
 int rc_trace_closest4(rc_scene* scene, uint32_t blas_id, const rc_ray* rays, rc_hit* hits, uint64_t n);
 int rc_trace_any4(rc_scene* scene, uint32_t blas_id, const rc_ray* rays, rc_hit* hits, uint64_t n);
 /* Same on device buffers, enqueued on `stream` (NULL = default stream), no host synchronisation. */
@@ -660,7 +663,9 @@ int rc_rebuild_tlas_device_async(rc_scene* scene, void* stream);
  * enqueued so far; while a graph that captured the call may live, the caller waits for its replay first.  cost: what the latest evaluation
  * measured (the refitted tree's, also when a rebuild followed; the arming call: the built tree's); cost_built: the tree's cost at the latest
  * recorded rebuild; evaluations, rebuilds: counts since the last rebuilding rc_sync (the arming call is
- * one of each); last_rebuilt: the latest evaluation's decision; armed: 0 until the arming call. */
+ * one of each); last_rebuilt: the latest evaluation's decision; armed: 0 until the arming call.  n == 0: all zero.
+ * Errors: RC_ERR_INVALID_ARGUMENT (NULL scene or out), RC_ERR_NOT_SYNCED (never synced, or pending host-side mutations: the block belongs
+ * to the synced scene).  A device-side update that still waits for its commit does not refuse the read. */
 typedef struct rc_tlas_quality_info {
     double cost, cost_built;
     uint32_t evaluations, rebuilds, last_rebuilt, armed;
@@ -692,7 +697,9 @@ int rc_tlas_quality(rc_scene* scene, rc_tlas_quality_info* out);
  * lazily under the rules of the asynchronous refit: rc_export_blas_descs, rc_scene_save and a structural rc_sync wait for the update and
  * read the box back first, and fail while the update's stream is being captured; while a graph that captured an update may live (until a
  * rebuilding rc_sync or "release_captures") they read it back on every use.
- * At call time the geometry's BLAS4 is dropped (rc_trace_*4 behave as for a geometry whose BLAS4 was never built, until rc_blas4_build)
+ * At call time the geometry's BLAS4 is dropped (rc_trace_*4 behave as for a geometry whose BLAS4 was never built, until rc_blas4_build;
+ * a BLAS4 built while a graph that captured an update of the geometry may live describes the tree of that moment: the next replay leaves
+ * it stale without dropping it, so build it again after the replay it should follow)
  * and the view-factor source order (RC_VF_SOURCES_BY_METADATA) is invalidated: the next call that needs it waits on the host for the
  * eager updates enqueued so far and sorts again.  While a graph that captured an update may live, every replay re-sorts the primitives at
  * a time the library does not see, so the order is rebuilt ON EVERY USE (one small sort and a host wait per rc_view_factors* call): such a
