@@ -214,7 +214,7 @@ int rc_trace_any_device_batches(rc_scene* scene, const rc_ray* const* d_rays, rc
  * eighths; in eighths of (part size x waves) still to hand out per piece, default 12, 0 = whole chunks only), "cost_order" (1 = the
  * chunks that held long-lived rays in earlier launches of the same BATCH are claimed first: the batch is recognised on the device by sample
  * rays among up to four remembered per launch shape -- chunk count, mode, stream --, records its chunk costs in its launches 2-4 (never the first: a batch that does not come back pays nothing) and
- * then in one launch of eight; default 1),
+ * then in one launch of eight; default 1), "order_close_repeats" (1 = a launch with a remembered batch's ray origins and nearly its directions -- jittered re-renders of a still view -- continues that batch's history like an exact repeat; 0 = exact repeats only; default 1),
  * "cost_thr" (its initial reporting threshold), "entry_cull" (1 = an instance whose conservative sphere the ray's segment misses is
  * not entered: the reference's traversal of it would test no triangle; 0 = off, 1 = closest_hit and the drivers (default),
  * 2 = any_hit batches too), "vf_chunk_bytes" (device block per row chunk of the host-matrix view factors), "vf_first_touch" (ROWS on several devices: each device's

@@ -1349,6 +1349,7 @@ int rc_set_option(rc_scene* s, const char* name, int64_t value) {
     else if (k == "taper") s->opt.taper = value < 0 ? 0 : (value > 64 ? 64 : value);
     else if (k == "entry_cull") s->opt.entry_cull = value < 0 ? 0 : (value > 2 ? 2 : value);
     else if (k == "cost_order") s->opt.cost_order = value != 0;
+    else if (k == "order_close_repeats") s->opt.order_close_repeats = value != 0;
     else if (k == "cost_thr") s->opt.cost_thr = value < 1 ? 1 : (value > 4096 ? 4096 : value);
     else if (k == "sched_thr") s->opt.sched_thr = value < 1 ? 1 : (value > 64 ? 64 : value);
     else if (k == "vf_first_touch") s->opt.vf_first_touch = value ? 1 : 0;
@@ -1417,6 +1418,7 @@ int rc_get_option(rc_scene* s, const char* name, int64_t* value) {
     else if (k == "taper") *value = s->opt.taper;
     else if (k == "entry_cull") *value = s->opt.entry_cull;
     else if (k == "cost_order") *value = s->opt.cost_order;
+    else if (k == "order_close_repeats") *value = s->opt.order_close_repeats;
     else if (k == "debug_order_ptr" || k == "debug_order_n" || k == "debug_ctl_ptr" || k == "debug_cost_ptr") {  // dev: the claim order of the most recently used launch shape
         const rc_scene::ChunkHistory* h = nullptr;
         for (const auto& e : s->histories) if (!h || e.last_use > h->last_use) h = &e;

@@ -167,6 +167,7 @@ struct TraceOptions {
     int64_t taper = 12;        // persistent kernels: guided chunk sizes at the end of a batch, in eighths of (chunk size x waves) still to hand out per piece (RcClaim); 0 = all chunks of `pool` items
     int64_t entry_cull = 1;    // phased kernels: an instance whose entry-cull sphere the ray's segment misses is not entered (k_inst_recs, rc_build.hip); results never change.  1 = closest_hit and the drivers, 2 = any_hit too
     int64_t cost_order = 1;    // phased kernels: chunks that held long rays in the previous launch of the same shape (batch size, mode, stream) are claimed first (RcClaim::order)
+    int64_t order_close_repeats = 1;  //   a launch with the same ray origins and nearly the same directions as a remembered batch (jittered re-renders of one view) continues that batch's history like an exact repeat (order_select); 0 = only exact repeats do
     int64_t cost_thr = 64;     //   initial reporting threshold, in interior-loop iterations of a ray's wave while the ray was in flight (adapted from launch to launch)
     int64_t claim_shards = 16; // phased kernels: chunk counters in use (a power of two <= kClaimShards)
     int64_t vf_first_touch = 1;          // ROWS on several devices: each device's host thread joins the device's NUMA node and faults in its own row block (rc_multi.hip)

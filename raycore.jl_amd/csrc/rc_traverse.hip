@@ -290,7 +290,7 @@ void rc_claim_fill(RcLaunchGuard& g, uint64_t n_items, uint32_t total_waves, rc:
     out.g1 = (uint32_t)chunks[0]; out.g2 = (uint32_t)(chunks[0] + 2 * chunks[1]); out.g3 = (uint32_t)(chunks[0] + 2 * chunks[1] + 4 * chunks[2]);
     out.c1 = (uint32_t)chunks[0]; out.c2 = (uint32_t)(chunks[0] + chunks[1]); out.c3 = (uint32_t)(chunks[0] + chunks[1] + chunks[2]);
     out.order = nullptr; out.cost = nullptr; out.hist = nullptr;
-    out.sample_rays = nullptr; out.n_sample = 0; out.inv_l2 = 0.f; out.samples = nullptr; out.host_streak = nullptr; out.init_thr = 0; out.want_record = 0; out.host_gen = 0;
+    out.sample_rays = nullptr; out.n_sample = 0; out.inv_l2 = 0.f; out.samples = nullptr; out.host_streak = nullptr; out.init_thr = 0; out.want_record = 0; out.host_gen = 0; out.close_dir_max = 0.f;
     for (int k = 0; k < 8; ++k) out.sample_host[k] = 0.f;
     out.pool_shift = 0;
     while ((2u << out.pool_shift) <= out.pool) ++out.pool_shift;
@@ -445,6 +445,12 @@ static void launch_variant(RcLaunchGuard& g, int64_t kernel, const TraceArgs& a,
 #define RC_ORDER_RAISE_PCT 70
 #define RC_ORDER_LOWER_PCT 30
 #endif
+// Close repeats (order_select): the largest direction term -- mean over the 64 samples of |dd|^2 / |d|^2 -- at which a launch with the slot's
+// own origins still continues the slot's history.  Jitter inside a pixel gives 4e-8 at 2048^2, 2.4e-7 at 1280 x 800, 2.7e-6 at 256^2 (45
+// degrees); a camera turned in place by 0.15 / 0.2 / 5 degrees 6.7e-6 / 1.2e-5 / 7.3e-3.  tools/probes/close_repeat_predictor.py
+// (profiles/close_repeat_predictor.txt): up to 6.7e-6 the order learned from the predecessor leaves at most twice as many of the truly
+// longest chunks to the end of the launch as the order learned from another jitter seed of the same view does; from 1.2e-5 on, more.
+constexpr float kCloseDirMax = 6e-6f;
 namespace {
 constexpr int kOrderThreads = 256, kOrderPerThread = 4, kOrderTile = kOrderThreads * kOrderPerThread, kOrderClasses = RC_ORDER_CLASSES, kOrderMaxBlocks = 256;
 constexpr int kOrderPacked = (kOrderClasses + 4) / 5;  // u64 words of 12-bit per-class counters (k_order_scatter)
@@ -667,6 +673,7 @@ bool rc_cost_order_setup(RcLaunchGuard& g, uint64_t n, int any_hit, rc::RcClaim&
     c.host_streak = h->fresh_streak.p;
     c.host_gen = (uint32_t)h->gen & 0xFFFFFFu;
     c.init_thr = (uint32_t)s->opt.cost_thr;
+    c.close_dir_max = (s->opt.order_close_repeats && d_rays) ? kCloseDirMax : 0.f;  // (generated rays, described by one host sample, keep the exact rule)
     c.order = h->order.p;
     c.cost = h->cost.p;
     c.hist = h->ctl.p;

@@ -79,6 +79,8 @@ struct RcClaim {
     uint32_t want_record;          // the host's cadence: a slot past its fourth launch records in this launch
     uint32_t host_gen;             // the host's count of launches of this shape (24 bits): written back next to the pause word, so that a host that has enqueued
                                    // far ahead of the device knows HOW OLD the pause count it reads is (each launch since takes one off it)
+    float close_dir_max;           // order_select: a launch whose sample origins equal a slot's and whose direction term lies below this bound continues the slot's
+                                   // history as a CLOSE REPEAT (jittered re-renders of one view); 0 = only exact repeats do (option "order_close_repeats" off, generated rays)
 };
 // A history (rc_scene::ChunkHistory) remembers up to kHistSlots different BATCHES of one launch shape, told apart on the device by
 // kHistSamples sample rays (VERDICT r3 #5a: two cameras alternating on one stream each learn from their OWN previous launch, and a
@@ -89,6 +91,7 @@ constexpr uint32_t kHistSlotStride = 1u << 18;  // words between the slots' cost
 // that writes (order_commit) can do it at the START of the launch, while every other wave is still reading, and nothing is left to do at the
 // end.  The host flips `parity` with every launch of the shape; the rebuild kernels work in place on the copy the next launch reads.
 constexpr int kHistSel = 0, kHistOrderValid = 1, kHistLifeThr = 2, kHistClock = 3, kHistFresh = 4, kHistRecorded = 5,  // of the latest launch (tests, tools)
+              kHistClose = 6 /* the latest launch continued its slot as a close repeat (order_select) */,
               kHistFreshStreak = 36 /* consecutive launches that were not a repeat (identical sample rays) of a remembered batch */,
               kHistSkipLeft = 38 /* launches of the shape still to go out OUTSIDE the mechanism (its batches do not repeat: order_commit) */,
               kHistStamp = 8 /* [kHistSlots] */, kHistGen = 12 /* [kHistSlots] */,
@@ -143,12 +146,12 @@ __device__ inline bool rc_claim_chunk(const RcClaim& c, const uint32_t* order, u
 
 // Which batch is this launch, and what does it do with the batch's slot?  A pure function of the history's header, the remembered sample
 // rays and the launch's own: every wave evaluates it (64 lanes, one sample ray each) and gets the same answer.  The closest slot below the
-// threshold is the batch's -- to continue if the launch repeats the slot's batch, to start over in otherwise; none: the least recently used
-// slot is given to it.  A launch that starts a slot is "fresh": natural order, nothing recorded.  A slot records in
+// threshold is the batch's -- to continue if the launch repeats the slot's batch (exactly, or closely: the same origins and directions
+// within RcClaim::close_dir_max), to start over in otherwise; none: the least recently used slot is given to it.  A launch that starts a slot is "fresh": natural order, nothing recorded.  A slot records in
 // its launches 2-4 (never the first: a batch that does not come back pays nothing; the reporting threshold needs two rounds to settle) and
 // then when the host's cadence says so (one launch in eight).
 struct OrderDecision {
-    uint32_t sel, fresh, exact, gen, record, valid, life_thr, paused;
+    uint32_t sel, fresh, exact, close, gen, record, valid, life_thr, paused;
 };
 // A shape whose batches never repeat learns nothing and should pay nothing: after kGiveUpAfter consecutive launches that were not repeats
 // the shape's next kGiveUpFor launches go out in natural order without looking at their rays, then the shape is tried again.  Counted and
@@ -159,7 +162,7 @@ __device__ inline OrderDecision order_select(const RcClaim& c, int lane, float r
     const float* samples = c.samples + c.parity * kHistSampleFloats;
     if (hist[kHistSkipLeft] != 0u) {  // (a header word: the same answer in every wave)
         OrderDecision o;
-        o.sel = 0u; o.fresh = 1u; o.exact = 0u; o.gen = 0u; o.record = 0u; o.valid = 0u; o.life_thr = 0xFFFFFFFFu; o.paused = 1u;
+        o.sel = 0u; o.fresh = 1u; o.exact = 0u; o.close = 0u; o.gen = 0u; o.record = 0u; o.valid = 0u; o.life_thr = 0xFFFFFFFFu; o.paused = 1u;
         for (int k = 0; k < 8; ++k) r[k] = 0.f;
         return o;
     }
@@ -175,6 +178,7 @@ __device__ inline OrderDecision order_select(const RcClaim& c, int lane, float r
     // (Loading all four slots' samples and header words up front -- one memory round trip instead of two or three -- was measured 0.7 %
     // SLOWER on C3: the launch's first claims wait behind 8 more vector loads per lane of every wave.)
     int best = -1;
+    bool best_same_o = false;  // every sample's origin equals the slot's (then best_d is the direction term alone: each lane added an exact 0)
     float best_d = 0.02f;  // mean over the samples of |dd|^2 / |d|^2 + |do|^2 / diagonal^2: ~0.1 rad of rotation, or a tenth of the scene of travel
     for (int k = 0; k < kHistSlots; ++k) {
         if (hist[kHistStamp + k] == 0u) continue;
@@ -184,15 +188,20 @@ __device__ inline OrderDecision order_select(const RcClaim& c, int lane, float r
         float d = (dx * dx + dy * dy + dz * dz) / fmaxf(fmaxf(na, nb), 1e-30f) + (ox * ox + oy * oy + oz * oz) * c.inv_l2;
         for (int m = 32; m > 0; m >>= 1) d += __shfl_xor(d, m);  // (a NaN anywhere: the sum is NaN and the comparison fails -- no match)
         d *= 1.0f / kHistSamples;
-        if (d < best_d) { best_d = d; best = k; }
+        const bool same_o = __ballot(ox != 0.f || oy != 0.f || oz != 0.f) == 0ull;
+        if (d < best_d) { best_d = d; best = k; best_same_o = same_o; }
     }
     OrderDecision o;
-    // Only a REPEAT -- the same sample rays bit for bit -- continues a slot's history.  A batch that merely resembles a remembered one (a
-    // camera that moves every frame) starts over IN that slot (it replaces what it resembles instead of evicting somebody else): natural
-    // order, nothing recorded, exactly like a batch never seen.  An order learned from similar rays was measured slower than natural order
+    // Two kinds of launch continue a slot's history.  The REPEAT: the same sample rays bit for bit.  The CLOSE REPEAT: the same sample
+    // origins in all 64 samples and a direction term (mean |dd|^2 / |d|^2) below close_dir_max -- a still camera re-rendering its view through
+    // other points of the same pixels, whose chunks cost what the previous frame's did (rank correlation 0.95 against 0.96 for an exact
+    // repeat, profiles/close_repeat_predictor.txt).  A batch that merely resembles a remembered one (a camera that translates or turns by
+    // degrees every frame) starts over IN that slot (it replaces what it resembles instead of evicting somebody else): natural order, nothing
+    // recorded, exactly like a batch never seen.  An order that is several frames of camera motion old was measured slower than natural order
     // (docs/EXPERIMENTS.md), and deciding this here rather than on the host makes it hold for a caller that enqueues far ahead of the device.
     o.exact = (best >= 0 && best_d == 0.0f) ? 1u : 0u;
-    o.fresh = o.exact ? 0u : 1u;
+    o.close = (best >= 0 && !o.exact && best_same_o && best_d < c.close_dir_max) ? 1u : 0u;
+    o.fresh = (o.exact | o.close) ? 0u : 1u;
     int sel = best;
     if (best < 0) {  // an empty slot, else the least recently used one
         uint32_t oldest = 0xFFFFFFFFu;
@@ -238,11 +247,11 @@ __device__ inline void order_commit(const RcClaim& c, const OrderDecision& o, in
     if (o.fresh) { put(sc, c.init_thr); put(sc + 2, c.init_thr); put(sc + 1, c.init_thr + 8u); put(sc + 3, c.init_thr + 8u); put(kHistPending + (int)o.sel, 0u); put(kHistHasOrder + (int)o.sel, 0u); }
     else if (o.record) { put(sc, old_h[sc + 2]); put(sc + 1, old_h[sc + 3]); }  // the rebuild classes the costs with the scale they were recorded under
     if (o.record) put(kHistPending + (int)o.sel, 1u);
-    put(kHistSel, o.sel); put(kHistFresh, o.fresh); put(kHistOrderValid, o.valid); put(kHistLifeThr, o.life_thr); put(kHistRecorded, o.record);
-    // The run of launches that were not REPEATS of a remembered batch -- a path tracer's bounce rays (never matched), a camera that moves
+    put(kHistSel, o.sel); put(kHistFresh, o.fresh); put(kHistOrderValid, o.valid); put(kHistLifeThr, o.life_thr); put(kHistRecorded, o.record); put(kHistClose, o.close);
+    // The run of launches that were not REPEATS (exact or close) of a remembered batch -- a path tracer's bounce rays (never matched), a camera that moves
     // every frame (matched, never identical) -- and the pause it leads to.  The host reads the pinned copies to decide about the rebuild
     // kernels: [0] the run (a new batch is starting: its launches 2-4 will record), [1] a recording waits, [2] the pause.
-    uint32_t streak = o.exact ? 0u : old_h[kHistFreshStreak] + 1u;
+    uint32_t streak = (o.exact | o.close) ? 0u : old_h[kHistFreshStreak] + 1u;
     uint32_t skip = 0u;
     if (streak >= kGiveUpAfter) { streak = 0u; skip = kGiveUpFor; }
     put(kHistFreshStreak, streak);
