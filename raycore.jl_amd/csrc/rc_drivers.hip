@@ -147,10 +147,15 @@ struct IlluminationJob {
     __device__ inline HistogramSink sink(const SceneView& v) const { return HistogramSink{v.inst, v.prims, v.n_prims, scratch, n8}; }
 };
 // The three shapes every driver runs in (DriverLaunch picks one): they differ in what sits in LDS when phased_trace starts.
+// The closest-hit illumination job keeps the late pop in the plain and the partial shell: beside the sink's own arrays they have no register
+// for the peeked stack top (80 VGPRs either way; with the peek their private segments grow from 92 to 124 and from 96 to 100 bytes).  The
+// LDS shell peeks like the trace kernels.  Neither the LDS layout nor its size depends on the flag.
+template <bool ANY, class Job>
+constexpr unsigned kShellLatePop = (!ANY && std::is_same<Job, IlluminationJob>::value) ? ShapeLatePop : 0u;
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kBlock, 6) void k_driver(SceneView v, PersistArgs p, Job j) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    phased_trace<ANY, PlainShape<>>(v, p, lds_stack, j.source(v), j.sink(v));
+    phased_trace<ANY, PlainShape<kShellLatePop<ANY, Job>>>(v, p, lds_stack, j.source(v), j.sink(v));
 }
 // Small top level (<= kTlasLdsNodes nodes): the shape of trace kernel 5 -- two 768-thread workgroups per CU, TLAS (and a single BLAS's
 // top nodes) in LDS planes.
@@ -163,9 +168,10 @@ __global__ __launch_bounds__(kMidBlock, 6) void k_driver_lds(SceneView v, Persis
 // Larger top levels (the shape of trace kernel 6): only the breadth-first tops of the TLAS and of a single BLAS are staged.
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kMidBlock, 6) void k_driver_partial(SceneView v, PersistArgs p, Job j) {
+    typedef PartialShape<kShellLatePop<ANY, Job>> Shape;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LdsTop top = PartialShape<>::prologue(smem, v, p.blas_k, p.lds_blas_base, p.tlas_k);
-    phased_trace<ANY, PartialShape<>>(v, p, PartialShape<>::stacks(smem), j.source(v), j.sink(v), top);
+    const LdsTop top = Shape::prologue(smem, v, p.blas_k, p.lds_blas_base, p.tlas_k);
+    phased_trace<ANY, Shape>(v, p, Shape::stacks(smem), j.source(v), j.sink(v), top);
 }
 
 // ---- Philox4x32-10 (Salmon et al., SC'11) ---------------------------------------------------------------

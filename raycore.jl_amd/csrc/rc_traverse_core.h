@@ -371,6 +371,25 @@ struct LaneStackP {
         top -= keep ? 0 : BLOCK;
         return keep ? keep_v : popped;
     }
+    // The same with the pop's read taken off the chain: what `*(top - BLOCK)` returns after the write is `v` when the lane pushes and the
+    // OLD top otherwise, and the old top's address is known before the pass fetches its node.  peek_lds reads it there, together with
+    // the node, so that its latency overlaps the node fetch's; the overload below then needs no read behind the slab test.  Relies on: every
+    // lane the interior loop admits has at least one entry below `top` (the INVALID pushed at refill, or the sentinel pushed at instance
+    // entry), so `top - BLOCK` lies in the lane's own column; LDS operations of a wave complete in order, so the peek sees the previous
+    // pass's write.  The slots hold the same bytes as with the late read.
+    // -DRC_STACK_LATE_POP (dev, tools/ab_build.sh): the read behind the write, the form before docs/EXPERIMENTS.md "stack peek".
+#if defined(RC_STACK_LATE_POP)
+    static constexpr bool kPeek = false;
+#else
+    static constexpr bool kPeek = true;
+#endif
+    __device__ inline uint32_t peek_lds(pos_t top) const { return *(top - BLOCK); }
+    __device__ inline uint32_t push_pop_lds(pos_t& top, bool do_push, uint32_t v, bool keep, uint32_t keep_v, uint32_t old_top) {
+        *top = (E)v;
+        top += do_push ? BLOCK : 0;
+        top -= keep ? 0 : BLOCK;
+        return keep ? keep_v : (do_push ? v : old_top);  // (a pushed `v` is a node index: it fits E, the read-back would return it unchanged)
+    }
 };
 
 struct NodeRegs {
@@ -618,6 +637,7 @@ enum ShapeFlags : unsigned {
     ShapeStack16 = 1u,   // 16-bit lane-stack entries (scenes whose trees all have fewer than 65 534 nodes); the LDS they give up holds more node planes
     ShapeStats = 2u,     // dev: per-phase pass / lane counters (option "stats")
     ShapeTimeline = 4u,  // dev: per-wave event times (option "timeline_ptr")
+    ShapeLatePop = 8u,   // the interior pass reads its pop behind the write (no LaneStackP::peek_lds): for a shell that would spill the peeked value
 };
 constexpr int kMidBlock = 768, kMidStack = 16;  // the two-workgroups-per-CU shapes: 24 waves per CU as with six 256-thread blocks
 constexpr size_t kLeafTableBytes = (size_t)kTlasLdsInst * sizeof(uint32_t);
@@ -673,6 +693,7 @@ struct TraceShape {
     static constexpr int kBlock = BLOCK, kLdsDepth = LDS_N;
     static constexpr Top top = TOP;
     static constexpr bool kStack16 = (FLAGS & ShapeStack16) != 0, kStats = (FLAGS & ShapeStats) != 0, kTimeline = (FLAGS & ShapeTimeline) != 0;
+    static constexpr bool kLatePop = (FLAGS & ShapeLatePop) != 0;
     typedef typename std::conditional<kStack16, uint16_t, uint32_t>::type entry_t;  // a lane-stack entry in LDS
     static constexpr int kBlocksPerCu = BLOCK == rc::kBlock ? 0 : 2;  // workgroups the grid rule (rc_grid_blocks) puts on a CU; 0: option "blocks_per_cu"
     // entries per node plane: 310 / 748 (32- / 16-bit stacks) beside the leaf table and the instance planes, 585 / 1 023 alone
@@ -751,6 +772,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
     constexpr int BLOCK = Shape::kBlock;
     constexpr bool STATS = Shape::kStats, TIMELINE = Shape::kTimeline, STACK16 = Shape::kStack16;
     typedef LaneStackP<Shape::kLdsDepth, BLOCK, typename Shape::entry_t> Stack;
+    constexpr bool PEEK = Stack::kPeek && !Shape::kLatePop;
     // node values that are not nodes: the 32-bit INVALID / sentinel of the reference, or their low halves where everything fits 16 bits
     constexpr uint32_t kInv = STACK16 ? 0xFFFFu : RC_INVALID_NODE, kSent = STACK16 ? 0xFFFEu : RC_TOP_LEVEL_SENTINEL;
     const float2* const tl = top.tl;
@@ -839,6 +861,15 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
             float4 na, nb, nc;
             u2v ch;
             constexpr int PS = Shape::kPlaneNodes;  // plane stride
+            // the value a pop in this pass returns unless the pass pushes (LaneStackP::peek_lds), off the chain.  Requested right BEHIND the node
+            // fetch: the buffer arm waits for every LDS operation in flight before it issues its loads (they write the registers the plane
+            // reads write), so a peek in front of the fetch puts its latency in front of the loads in every pass that has no LDS lane.  The
+            // scheduling barrier keeps the compiler from sinking the read behind the fetch's waits, next to its use.
+            // -DRC_STACK_PEEK_AT_HEAD (dev, tools/ab_build.sh): the peek in front of the fetch (docs/EXPERIMENTS.md "stack peek")
+            uint32_t old_top = 0u;
+#if defined(RC_STACK_PEEK_AT_HEAD)
+            if (!DEEP && PEEK) old_top = st.peek_lds(sp);
+#endif
             if ((Shape::top == Top::Lds && (cur_inst < 0 || node <= a.blas_k)) || (Shape::top == Top::PartialLds && node <= (cur_inst < 0 ? a.tlas_k : a.blas_k))) {
                 const float2* q = tl + ((node - 1u) + (cur_inst < 0 ? 0u : a.lds_blas_base));
                 const float2 p0 = q[0], p1 = q[PS], p2 = q[2 * PS], p3 = q[3 * PS], p4 = q[4 * PS], p5 = q[5 * PS], p6 = q[6 * PS];
@@ -849,6 +880,9 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
                 na = buf_f4(nrs1, off); nb = buf_f4(nrs1, off, 16); nc = buf_f4(nrs1, off, 32);
                 ch = __builtin_amdgcn_raw_buffer_load_b64(nrs1, off, 48, 0);
             }
+#if !defined(RC_STACK_PEEK_AT_HEAD)
+            if (!DEEP && PEEK) { old_top = st.peek_lds(sp); __builtin_amdgcn_sched_barrier(0); }
+#endif
             // packed node (rc_pack_node): na = child-0 (min.x,min.y,max.x,max.y), nb = child-1 likewise, nc = z of both
             const v2f ixy = {inv.x, inv.y}, oxy = {ox.x, ox.y}, izz = {inv.z, inv.z}, ozz = {ox.z, ox.z};
             const v2f n0xy = v2f{na.x, na.y} * ixy + oxy, f0xy = v2f{na.z, na.w} * ixy + oxy;
@@ -869,7 +903,8 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
             if (DEEP) {
                 if (far_ok) st.push(sp, far_c);
                 node = near_ok ? near_c : st.pop(sp);
-            } else node = st.push_pop_lds(sp, far_ok, far_c, near_ok, near_c);
+            } else if (PEEK) node = st.push_pop_lds(sp, far_ok, far_c, near_ok, near_c, old_top);
+            else node = st.push_pop_lds(sp, far_ok, far_c, near_ok, near_c);
         };
         // sentinels and INVALID are >= 0xFFFFFFFE, never below a leaf threshold.  A lane whose stack has reached the LDS depth waits for the
         // deep pass behind the loop: the order of ITS visits, pushes and pops is what it was, only when they happen changes.
