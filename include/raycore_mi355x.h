@@ -217,7 +217,7 @@ int rc_trace_any_device_batches(rc_scene* scene, const rc_ray* const* d_rays, rc
  * then in one launch of eight; default 1), "order_close_repeats" (1 = a launch with a remembered batch's ray origins and nearly its directions -- jittered re-renders of a still view -- continues that batch's history like an exact repeat; 0 = exact repeats only; default 1),
  * "cost_thr" (its initial reporting threshold), "entry_cull" (1 = an instance whose conservative sphere the ray's segment misses is
  * not entered: the reference's traversal of it would test no triangle; 0 = off, 1 = closest_hit and the drivers (default),
- * 2 = any_hit batches too), "vf_chunk_bytes" (device block per row chunk of the host-matrix view factors), "vf_first_touch" (ROWS on several devices: each device's
+ * 2 = any_hit batches too), "vf_chunk_bytes" (device block per row chunk of the host-matrix view factors), "illum_scratch_bytes" (rc_get_illumination_dirs_device: histogram scratch per launch, which bounds its group of directions; default 256 MiB), "vf_first_touch" (ROWS on several devices: each device's
  * host thread joins the device's NUMA node and faults in its own row block; default 1), "release_captures" (set to 1 when the hipGraphs that
  * captured launches of this scene have been destroyed: frees their stack spill regions and counter slots, 16 per scene; get: how many are held),
  * "blas_top" (1 = a scene with a single BLAS keeps that BLAS's top internal
@@ -747,6 +747,49 @@ int rc_last_kernel_ms(rc_scene* scene, float* ms);
  * enqueues a run of launches back to back and wants every one's duration afterwards without putting events of its own between them (the
  * reference times its kernels the same way, one by one: docs/src/hw_acceleration.md:198-218).  Captured launches have no events: 0. */
 int rc_recent_kernel_ms(rc_scene* scene, uint32_t max_launches, float* ms, uint32_t* n);
+
+/* ---- illumination over MANY DIRECTIONS in one call, the grids laid out on the device -------------------------------------------------
+ * get_illumination (src/kernels.jl:10-72,112-124: generate_ray_grid, hits_from_grid and the histogram) for n_dirs view directions at once.
+ * The reference's users integrate over directions -- the sun's course over a day, a few dozen sky sectors, each weighted by its irradiance
+ * (docs/src/viewfactors_content.md:84-92) -- which with rc_get_illumination_device is n_dirs host-driven calls, each laying its grid out on
+ * the host from the host copy of the world bound.
+ *
+ * d_dirs: n_dirs x 3 f32 in DEVICE memory; the directions need not be normalised.  Both d_dirs and the TLAS root box the grids are laid
+ * out from are read WHEN THE KERNEL RUNS, not when the call is made, by the same code that lays the one-direction grid out on the host
+ * (one host/device function, no contraction, IEEE divide and square root: the same bits).  The host copy of the world bound is neither read
+ * nor refreshed.  This is THE EXCEPTION to the "stale world bound" rule spelled out at rc_refit_device_async: after rc_refit_device_async,
+ * rc_rebuild_tlas_device_async or rc_refit_or_rebuild_tlas_device_async on the same stream these two calls need no host wait, and they are
+ * legal on a capturing stream -- a captured call replays with its capture-time n_dirs and grid, with the CURRENT contents of d_dirs and the
+ * CURRENT TLAS root, so an animated scene's illumination can be computed inside its frame graph.
+ *
+ * rc_get_illumination_dirs_device.  WORK-ITEM LAYOUT: item i = d * grid^2 + cell, cell = the ray index of rc_generate_ray_grid_device;
+ * ray (d, cell) is bit for bit the ray that call writes for d_dirs[d].  Items are claimed in natural order.
+ * d_counts[d * row_stride + (meta - 1)] += the number of rays of direction d whose closest hit is a primitive with metadata `meta`;
+ * metadata outside 1..n_prims is dropped, as in get_illumination (src/kernels.jl:123).  row_stride >= n_prims, in u32 words; words of a
+ * row beyond n_prims are not touched.  The call ACCUMULATES (the convention of rc_get_illumination_device and rc_view_factors_device): the
+ * caller zeroes the matrix; the adds are u32 atomics, exact in any order, so calls on several streams may share a matrix.
+ * Counts are u32, NOT the reference's saturating f32: row d equals what rc_get_illumination_device adds for d_dirs[d] whenever that count
+ * is below 2^24, where the reference's Float32 sum stops.  Weighting the rows is the caller's: a float weight inside the kernel would make
+ * the sum depend on the order of the atomics.
+ * The directions are traced in groups of G consecutive ones, one persistent launch per group behind one memset and one small grid-layout
+ * kernel, in front of one fold; G is the largest count with G * grid^2 < 2^32 whose private histogram copies (G * 512 * ceil(n_prims / 8)
+ * bytes) fit option "illum_scratch_bytes" (default 256 MiB; at least one direction's worth is always used).  The option changes no result.
+ * The plan (G, the scratch size) is fixed at call time.  Scratch is the per-stream area of rc_get_illumination_device; a captured call owns
+ * its own, one capture slot per group, under the rules of the other driver launches (the stream must have run the call eagerly before).
+ *
+ * rc_generate_ray_grid_dirs_device writes n_dirs x grid^2 rays: direction d starts at d * grid^2, in the layout of
+ * rc_generate_ray_grid_device.  One kernel, no scratch.
+ * A direction whose normalisation is not finite (zero, NaN) gives whatever the one-direction entry points give for it.
+ *
+ * Scene state: as the *_device queries.  n_dirs == 0, grid == 0 or an empty scene: success, nothing enqueued.
+ * Errors, all before anything is enqueued and with the output untouched: RC_ERR_INVALID_ARGUMENT (NULL scene; NULL d_dirs or output while
+ * n_dirs and grid are non-zero; grid >= 65536; row_stride < n_prims), RC_ERR_NOT_SYNCED (never synced, pending host-side mutations, or
+ * transforms-dirty from the device with no refit / rebuild yet).  A stack overflow is reported by rc_wait.
+ * Register and scratch figures of the three new kernel shells and the comparison with a loop of one-direction calls: docs/EXPERIMENTS.md,
+ * "Illumination over many directions". */
+int rc_get_illumination_dirs_device(rc_scene* scene, const float* d_dirs, uint32_t n_dirs, uint32_t grid, uint32_t* d_counts,
+                                    uint64_t row_stride, void* stream);
+int rc_generate_ray_grid_dirs_device(rc_scene* scene, const float* d_dirs, uint32_t n_dirs, uint32_t grid, rc_ray* d_rays, void* stream);
 
 #ifdef __cplusplus
 }

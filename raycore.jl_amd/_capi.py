@@ -136,6 +136,8 @@ SYMBOLS = [
     ("rc_host_unregister", _int, [_vp, _vp]),
     ("rc_last_kernel_ms", _int, [_vp, _pf]),
     ("rc_recent_kernel_ms", _int, [_vp, _u32, _pf, _pu32]),
+    ("rc_get_illumination_dirs_device", _int, [_vp, _vp, _u32, _u32, _vp, _u64, _vp]),
+    ("rc_generate_ray_grid_dirs_device", _int, [_vp, _vp, _u32, _u32, _vp, _vp]),
 ]
 
 _lib = None

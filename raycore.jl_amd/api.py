@@ -568,6 +568,20 @@ class TLAS:
                                                      int(samples), int(seed), int(depth), ptr(d_path_in) if d_path_in else None, int(path_base),
                                                      float(bias), ptr(d_count), ptr(stream) if stream else None))
 
+    def illumination_dirs_device(self, d_dirs, n_dirs, grid, d_counts, row_stride=None, stream=None):
+        """get_illumination for n_dirs directions in one call (rc_get_illumination_dirs_device).  d_dirs: device pointer to n_dirs x 3 f32
+        (need not be normalised), read WHEN THE KERNELS RUN, like the TLAS root the grids are laid out from: no host copy of the world
+        bound is involved, so the call follows refit_device_async / rebuild_device_async without a host wait and may be captured.
+        d_counts: device pointer to n_dirs rows of `row_stride` (default: the primitive count) u32, ACCUMULATED:
+        d_counts[d * row_stride + meta - 1] += the hits of direction d.  Weighting the rows is the caller's."""
+        rs = self.n_primitives() if row_stride is None else int(row_stride)
+        check(lib().rc_get_illumination_dirs_device(self._h, ptr(d_dirs), int(n_dirs), int(grid), ptr(d_counts), rs, ptr(stream) if stream else None))
+
+    def ray_grid_dirs_device(self, d_dirs, n_dirs, grid, d_rays, stream=None):
+        """The ray grids of n_dirs device-resident directions (rc_generate_ray_grid_dirs_device): n_dirs x grid^2 RTRay records, direction
+        d's at d * grid^2 in generate_ray_grid's layout, laid out on the device from the TLAS root as it is when the kernel runs."""
+        check(lib().rc_generate_ray_grid_dirs_device(self._h, ptr(d_dirs), int(n_dirs), int(grid), ptr(d_rays), ptr(stream) if stream else None))
+
     def last_kernel_ms(self):
         ms = C.c_float()
         check(lib().rc_last_kernel_ms(self._h, C.byref(ms)))
@@ -847,6 +861,34 @@ def get_illumination(accel, viewdir, grid_size=1000):
     vd = np.ascontiguousarray(viewdir, dtype=np.float32)
     check(lib().rc_get_illumination(t._h, ptr(vd), int(grid_size), ptr(out)))
     return out
+
+
+def get_illumination_dirs(accel, viewdirs, grid_size=1000, weights=None):
+    """get_illumination (src/kernels.jl:112-124) for D view directions in one call: a (D, N) float32 array whose row d equals
+    get_illumination(accel, viewdirs[d], grid_size) -- the integration over the sun's course or over sky sectors that the reference's users
+    write as a loop.  With `weights` (length D, e.g. each direction's irradiance) the length-N float64 vector weights @ counts instead,
+    formed on the host: inside the kernel a float weight would make the sum depend on the order of the atomics."""
+    vd = np.ascontiguousarray(viewdirs, dtype=np.float32)
+    if vd.ndim != 2 or vd.shape[1] != 3:
+        raise ValueError("viewdirs must be a (D, 3) array of directions")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (vd.shape[0],):
+            raise ValueError("weights must hold one value per direction")
+    import torch
+    t = _owner(accel)
+    n, d = t.n_primitives(), vd.shape[0]
+    dev = f"cuda:{t.device}"
+    torch.cuda.synchronize(t.device)  # (the call runs on the default stream: behind whatever the caller enqueued on streams of its own)
+    dirs = torch.from_numpy(vd).to(dev)
+    counts = torch.zeros(max(d * n, 1), dtype=torch.int32, device=dev)
+    t.illumination_dirs_device(dirs.data_ptr(), d, grid_size, counts.data_ptr(), n)
+    torch.cuda.synchronize(t.device)
+    t.wait_for_gpu()  # (reports a traversal stack overflow, like the host-buffer get_illumination)
+    rows = counts.cpu().numpy().view(np.uint32)[:d * n].reshape(d, n)
+    rows = np.minimum(rows, np.uint32(1 << 24)).astype(np.float32)  # the reference's Float32 sums stop at 2^24
+    return rows if w is None else w @ rows.astype(np.float64)
 
 
 def _vf_out(n, out):

@@ -1093,21 +1093,6 @@ void blas_tree_chain(hipStream_t st, const ChainBufs& b, const RcPrim* prims, ui
     run_refit(st, b, nodes, prims, n, 0);
 }
 
-__host__ __device__ inline void host_root_aabb(const RcNode& root, bool tlas, float mn[3], float mx[3]) {
-    bool interior = root.child0 != RC_INVALID_NODE;
-    float3_ a, b;
-    if (interior) {
-        a = min3v(mk3(root.f[0], root.f[1], root.f[2]), mk3(root.f[6], root.f[7], root.f[8]));
-        b = max3v(mk3(root.f[3], root.f[4], root.f[5]), mk3(root.f[9], root.f[10], root.f[11]));
-    } else if (tlas) {
-        a = mk3(root.f[0], root.f[1], root.f[2]); b = mk3(root.f[3], root.f[4], root.f[5]);
-    } else {
-        float3_ v0 = mk3(root.f[0], root.f[1], root.f[2]), v1 = mk3(root.f[3], root.f[4], root.f[5]), v2 = mk3(root.f[6], root.f[7], root.f[8]);
-        a = min3v(min3v(v0, v1), v2); b = max3v(max3v(v0, v1), v2);
-    }
-    mn[0] = a.x; mn[1] = a.y; mn[2] = a.z; mx[0] = b.x; mx[1] = b.y; mx[2] = b.z;
-}
-
 // The box of the tree at d_root, behind everything enqueued on the scene's stream: the one host wait of a synchronous build or refit
 void read_root_aabb(rc_scene* s, const RcNode* d_root, bool tlas, float mn[3], float mx[3]) {
     RcNode root;

@@ -1371,6 +1371,7 @@ int rc_set_option(rc_scene* s, const char* name, int64_t value) {
         s->capture_slots[value - 1] = rc_scene::CaptureSlot();
     }
     else if (k == "vf_chunk_bytes") s->opt.vf_chunk_bytes = value < 4096 ? 4096 : (value > (int64_t(4) << 30) ? (int64_t(4) << 30) : value);
+    else if (k == "illum_scratch_bytes") s->opt.illum_scratch_bytes = value < 1 ? 1 : (value > (int64_t(4) << 30) ? (int64_t(4) << 30) : value);  // (a launch always gets one direction's worth)
     else if (k == "timeline_ptr") s->opt.timeline_ptr = value;  // dev instrumentation: the caller owns the buffer and its size (8 x u64 per wave of the launch)
     else if (k == "debug_set_overflow") {  // test hook: raise the sticky stack-overflow word as a kernel would (no LBVH is deep enough to do it for real)
         const char* hooks = getenv("RC_ENABLE_DEBUG_HOOKS");  // not part of the product's interface: only a process that asks for the hooks gets them
@@ -1443,6 +1444,7 @@ int rc_get_option(rc_scene* s, const char* name, int64_t* value) {
         *value = b;
     }
     else if (k == "vf_chunk_bytes") *value = s->opt.vf_chunk_bytes;
+    else if (k == "illum_scratch_bytes") *value = s->opt.illum_scratch_bytes;
     else if (k == "blas_top_k") *value = s->blas_top_k;
     else if (k == "tlas_top_k") *value = s->tlas_top_k;
     else if (k.rfind("stat", 0) == 0 && ((k.size() == 5 && ((k[4] >= '0' && k[4] <= '9') || (k[4] >= 'a' && k[4] <= 'f'))) ||
@@ -1759,6 +1761,32 @@ int rc_recent_kernel_ms(rc_scene* s, uint32_t max_launches, float* ms, uint32_t*
             ms[i] = t;
         }
         *n_out = (uint32_t)n;
+    });
+}
+
+// What the two many-direction calls check before anything is enqueued (0: go on)
+static int dirs_args(const char* name, rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, const void* d_out) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (n_dirs && grid && (!d_dirs || !d_out)) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": NULL argument");
+    if (grid >= 65536u) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": grid * grid must be below 2^32");
+    return 0;
+}
+int rc_get_illumination_dirs_device(rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, uint32_t* d_counts, uint64_t row_stride, void* stream) {
+    if (int e = dirs_args("rc_get_illumination_dirs_device", s, d_dirs, n_dirs, grid, d_counts)) return e;
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        if (n_dirs && grid && row_stride < s->n_flat_prims) throw RcError(RC_ERR_INVALID_ARGUMENT, "rc_get_illumination_dirs_device: row_stride is smaller than the number of primitives");
+        rc_launch_illumination_dirs(s, d_dirs, n_dirs, grid, d_counts, row_stride, (hipStream_t)stream);
+    });
+}
+int rc_generate_ray_grid_dirs_device(rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, rc_ray* d_rays, void* stream) {
+    if (int e = dirs_args("rc_generate_ray_grid_dirs_device", s, d_dirs, n_dirs, grid, d_rays)) return e;
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        if (s->n_tlas_nodes == 0) return;  // an empty scene: nothing enqueued
+        rc_launch_ray_grid_dirs(s, d_dirs, n_dirs, grid, reinterpret_cast<RcRay*>(d_rays), (hipStream_t)stream);
     });
 }
 

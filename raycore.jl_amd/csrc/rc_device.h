@@ -151,6 +151,23 @@ __host__ __device__ inline float jl_max(float a, float b) {
 __host__ __device__ inline float3_ min3v(float3_ a, float3_ b) { return mk3(jl_min(a.x, b.x), jl_min(a.y, b.y), jl_min(a.z, b.z)); }
 __host__ __device__ inline float3_ max3v(float3_ a, float3_ b) { return mk3(jl_max(a.x, b.x), jl_max(a.y, b.y), jl_max(a.z, b.z)); }
 
+// The box of a tree from its root record: the union of an interior root's two child boxes, a TLAS leaf's own box (a one-instance scene), or
+// the triangle of a one-primitive BLAS.  Host (after a read-back) and device (k_grid_params) alike.
+__host__ __device__ inline void host_root_aabb(const RcNode& root, bool tlas, float mn[3], float mx[3]) {
+    bool interior = root.child0 != RC_INVALID_NODE;
+    float3_ a, b;
+    if (interior) {
+        a = min3v(mk3(root.f[0], root.f[1], root.f[2]), mk3(root.f[6], root.f[7], root.f[8]));
+        b = max3v(mk3(root.f[3], root.f[4], root.f[5]), mk3(root.f[9], root.f[10], root.f[11]));
+    } else if (tlas) {
+        a = mk3(root.f[0], root.f[1], root.f[2]); b = mk3(root.f[3], root.f[4], root.f[5]);
+    } else {
+        float3_ v0 = mk3(root.f[0], root.f[1], root.f[2]), v1 = mk3(root.f[3], root.f[4], root.f[5]), v2 = mk3(root.f[6], root.f[7], root.f[8]);
+        a = min3v(min3v(v0, v1), v2); b = max3v(max3v(v0, v1), v2);
+    }
+    mn[0] = a.x; mn[1] = a.y; mn[2] = a.z; mx[0] = b.x; mx[1] = b.y; mx[2] = b.z;
+}
+
 // The same semantics in one instruction on the device: gfx950 has v_minimum3_f32 / v_maximum3_f32 (IEEE 754-2019 minimum / maximum:
 // NaN-propagating, -0 < +0), which is what Julia's min / max are; v_min_f32 / v_max_f32 (fminf / fmaxf) drop NaNs instead.
 __device__ inline float jl_minf(float a, float b) { return __builtin_elementwise_minimum(a, b); }

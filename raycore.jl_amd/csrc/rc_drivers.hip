@@ -23,11 +23,65 @@ namespace {
 
 using namespace rc;
 
+// norm(a) = sqrt(dot(a,a)); normalize(a) = a ./ norm(a) (GeometryBasics 0.5 fixed_arrays; SURVEY.md 8c).
+// sqrtf and / are the IEEE correctly-rounded forms here (-fhip-fp32-correctly-rounded-divide-sqrt); HIP's __fsqrt_rn is
+// the NATIVE (approximate) square root unless OCML_BASIC_ROUNDED_OPERATIONS is defined, so it is not used.  On the host the builtin is sqrtf.
+__host__ __device__ inline float3_ normalize3(float3_ a) {
+    float n = __builtin_sqrtf(dot3(a, a));
+    return mk3((a.x / n), (a.y / n), (a.z / n));
+}
+
 struct GridParams {  // everything generate_ray_grid computes before its double loop
     float gc[3], b1[3], b2[3], dir[3];
     float cell_w, cell_h;
     uint32_t grid;
 };
+
+// generate_ray_grid up to its loop (:10-46), as called from hits_from_grid (:58-61): ONE body for the host (the one-direction drivers, from
+// the host copy of the world bound) and the device (k_grid_params, from the TLAS root as it is when the kernel runs).  Both sides are
+// compiled with -ffp-contract=off and IEEE divide / square root, so they give the same bits; jl_min/jl_max give extrema() its Julia semantics.
+__host__ __device__ inline GridParams grid_params(const float root_min[3], const float root_max[3], const float viewdir[3], uint32_t grid) {
+    float3_ ray_direction = normalize3(mk3(viewdir[0], viewdir[1], viewdir[2]));
+    float3_ direction = normalize3(ray_direction);
+    float3_ o = mk3(root_min[0], root_min[1], root_min[2]);
+    float3_ w = sub3(mk3(root_max[0], root_max[1], root_max[2]), o);
+    float3_ temp = __builtin_fabsf(direction.x) < 0.9f ? mk3(1, 0, 0) : mk3(0, 1, 0);
+    float3_ b1 = normalize3(cross3(direction, temp));
+    float3_ b2 = normalize3(cross3(direction, b1));
+    float min1 = INFINITY, max1 = -INFINITY, min2 = INFINITY, max2 = -INFINITY, mind = INFINITY;
+    for (int c = 0; c < 8; ++c) {
+        float3_ p = mk3(o.x + ((c & 1) ? 1.0f : 0.0f) * w.x, o.y + ((c & 2) ? 1.0f : 0.0f) * w.y, o.z + ((c & 4) ? 1.0f : 0.0f) * w.z);
+        float p1 = dot3(p, b1), p2 = dot3(p, b2), pd = dot3(p, direction);
+        min1 = jl_min(min1, p1); max1 = jl_max(max1, p1);
+        min2 = jl_min(min2, p2); max2 = jl_max(max2, p2);
+        mind = jl_min(mind, pd);
+    }
+    float margin = 0.05f * jl_max(max1 - min1, max2 - min2);
+    float grid_width = max1 - min1 + 2.0f * margin, grid_height = max2 - min2 + 2.0f * margin;
+    float min_depth = mind - margin;
+    float c1 = (min1 + max1) / 2.0f, c2 = (min2 + max2) / 2.0f;
+    float3_ gc = add3(add3(add3(mk3(0, 0, 0), scale3(direction, min_depth)), scale3(b1, c1)), scale3(b2, c2));
+    GridParams g;
+    g.gc[0] = gc.x; g.gc[1] = gc.y; g.gc[2] = gc.z;
+    g.b1[0] = b1.x; g.b1[1] = b1.y; g.b1[2] = b1.z;
+    g.b2[0] = b2.x; g.b2[1] = b2.y; g.b2[2] = b2.z;
+    g.dir[0] = ray_direction.x; g.dir[1] = ray_direction.y; g.dir[2] = ray_direction.z;
+    g.cell_w = grid_width / (float)grid; g.cell_h = grid_height / (float)grid;
+    g.grid = grid;
+    return g;
+}
+// The same for direction d of a DEVICE array, from the TLAS root as it is now (node 0; a one-instance scene's root is a leaf): what the
+// many-direction drivers use, so that they follow an asynchronous refit or rebuild without the host ever reading the bound.
+__device__ inline GridParams grid_params_device(const RcNode* tlas_nodes, uint32_t n_tlas_nodes, const float* dirs, uint32_t d, uint32_t grid) {
+    float mn[3] = {0.f, 0.f, 0.f}, mx[3] = {0.f, 0.f, 0.f};
+    if (n_tlas_nodes) host_root_aabb(tlas_nodes[0], true, mn, mx);
+    const float v[3] = {dirs[3u * (size_t)d], dirs[3u * (size_t)d + 1u], dirs[3u * (size_t)d + 2u]};
+    return grid_params(mn, mx, v, grid);
+}
+__global__ void k_grid_params(const RcNode* tlas_nodes, uint32_t n_tlas_nodes, const float* dirs, uint32_t n_dirs, uint32_t grid, GridParams* out) {
+    const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d < n_dirs) out[d] = grid_params_device(tlas_nodes, n_tlas_nodes, dirs, d, grid);
+}
 
 // generate_ray_grid body (:47-55): u, v and the sum are Float64 ((grid_size+1)/2 is Float64) and round
 // once into the Float32 point.
@@ -51,6 +105,24 @@ __global__ __launch_bounds__(kBlock) void k_ray_grid(GridParams g, RcRay* out) {
         float4* q = reinterpret_cast<float4*>(out + i);
         q[0] = make_float4(r.ox, r.oy, r.oz, r.tmin);
         q[1] = make_float4(r.dx, r.dy, r.dz, r.tmax);
+    }
+}
+
+// The grids of n_dirs directions in one launch: direction d's rays start at d * grid^2, in k_ray_grid's layout.  Every workgroup lays out
+// the grid of the direction it writes (thread 0, into LDS) from the device arrays, so the call needs no scratch and no host copy of the bound.
+__global__ __launch_bounds__(kBlock) void k_ray_grid_dirs(const RcNode* tlas_nodes, uint32_t n_tlas_nodes, const float* dirs, uint32_t n_dirs, uint32_t grid, RcRay* out) {
+    __shared__ GridParams g;
+    const uint64_t n = (uint64_t)grid * grid;
+    for (uint32_t d = blockIdx.y; d < n_dirs; d += gridDim.y) {
+        if (threadIdx.x == 0) g = grid_params_device(tlas_nodes, n_tlas_nodes, dirs, d, grid);
+        __syncthreads();
+        for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+            RcRay r = grid_ray(g, i);
+            float4* q = reinterpret_cast<float4*>(out + (uint64_t)d * n + i);
+            q[0] = make_float4(r.ox, r.oy, r.oz, r.tmin);
+            q[1] = make_float4(r.dx, r.dy, r.dz, r.tmax);
+        }
+        __syncthreads();
     }
 }
 
@@ -146,10 +218,62 @@ struct IlluminationJob {
     __device__ inline GridSource source(const SceneView&) const { return GridSource{g, ray_begin}; }
     __device__ inline HistogramSink sink(const SceneView& v) const { return HistogramSink{v.inst, v.prims, v.n_prims, scratch, n8}; }
 };
+// get_illumination for a GROUP of directions in one launch: work item i = d_local * grid^2 + cell.  The source reads direction d_local's
+// GridParams (k_grid_params wrote them in front of the launch) and makes grid_ray()'s ray, bit for bit k_ray_grid's and GridSource's for that
+// direction; the sink is HistogramSink with a base of d_local * kHistCopies * 8 * n8 -- folded into wave_count's index, not into its
+// pointer: a wave straddles directions, and lanes are combined by index.  items = G * grid^2 < 2^32, so both divide in 32 bits.
+struct DirsGridSource {
+    const GridParams* params;
+    uint32_t cells;  // grid^2
+    __device__ inline RcRay operator()(uint64_t i) const {
+        const uint32_t d = (uint32_t)i / cells, cell = (uint32_t)i - d * cells;
+        return grid_ray(params[d], cell);
+    }
+    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
+};
+struct DirsHistogramSink {
+    const RcInstRec* inst;
+    const RcPrim* prims;
+    uint32_t n_prims;
+    uint32_t* scratch;  // G x kHistCopies x 8 x n8 counters, zeroed by the launcher
+    uint32_t n8, cells;
+    __device__ inline void operator()(uint64_t i, bool hit, float, float, float, uint32_t prim, int instance) const {
+        uint32_t meta = 0;
+        if (hit) {
+            const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
+            meta = prims[m3.y + prim - 1u].meta;
+        }
+        const bool counted = hit && meta >= 1 && meta <= n_prims;  // metadata outside 1..N is dropped (src/kernels.jl:123)
+        const uint32_t j = meta - 1u, d = (uint32_t)i / cells;
+        const unsigned long long copy = (unsigned long long)d * kHistCopies + (blockIdx.x & (kHistCopies - 1u));
+        wave_count(scratch, counted ? copy * 8u * n8 + ((j & 7u) * n8 + (j >> 3)) : 0ull, counted);
+    }
+};
+// Adds the group's sums into the caller's u32 matrix: one thread per (direction, primitive).  ACCUMULATES, atomically, like the other
+// counting drivers: calls on several streams may share a matrix, and integer adds are exact in any order.
+__global__ void k_illumination_dirs_fold(const uint32_t* scratch, uint32_t n8, uint32_t n, uint32_t n_dirs, uint32_t* counts, uint64_t row_stride) {
+    const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (t >= (uint64_t)n_dirs * n) return;
+    const uint32_t d = (uint32_t)(t / n), j = (uint32_t)(t - (uint64_t)d * n);
+    const uint32_t* base = scratch + (size_t)d * kHistCopies * 8u * n8;
+    uint32_t sum = 0;  // (a direction traces grid^2 < 2^32 rays)
+    for (uint32_t c = 0; c < kHistCopies; ++c) sum += base[(size_t)c * 8u * n8 + (j & 7u) * n8 + (j >> 3)];
+    if (sum) atomicAdd(counts + (uint64_t)d * row_stride + j, sum);
+}
+struct IlluminationDirsJob {
+    const GridParams* params;
+    uint32_t cells;
+    uint32_t* scratch;
+    uint32_t n8;
+    __device__ inline DirsGridSource source(const SceneView&) const { return DirsGridSource{params, cells}; }
+    __device__ inline DirsHistogramSink sink(const SceneView& v) const { return DirsHistogramSink{v.inst, v.prims, v.n_prims, scratch, n8, cells}; }
+};
 // The three shapes every driver runs in (DriverLaunch picks one): they differ in what sits in LDS when phased_trace starts.
 // The closest-hit illumination job keeps the late pop in the plain and the partial shell: beside the sink's own arrays they have no register
 // for the peeked stack top (80 VGPRs either way; with the peek their private segments grow from 92 to 124 and from 96 to 100 bytes).  The
-// LDS shell peeks like the trace kernels.  Neither the LDS layout nor its size depends on the flag.
+// LDS shell peeks like the trace kernels.  Neither the LDS layout nor its size depends on the flag.  The many-direction job needs no such
+// treatment: its source keeps a pointer where GridSource keeps fifteen grid words, and its shells peek in 74 / 75 / 77 VGPRs (plain / LDS /
+// partial) with no private segment (docs/EXPERIMENTS.md, "Illumination over many directions").
 template <bool ANY, class Job>
 constexpr unsigned kShellLatePop = (!ANY && std::is_same<Job, IlluminationJob>::value) ? ShapeLatePop : 0u;
 template <bool ANY, class Job>
@@ -229,14 +353,6 @@ __device__ inline double acos_f64(double x) {  // 0 <= x < 1
     double r = p / q;
     double w = r * s + c;
     return 2.0 * (df + w);
-}
-
-// norm(a) = sqrt(dot(a,a)); normalize(a) = a ./ norm(a) (GeometryBasics 0.5 fixed_arrays; SURVEY.md 8c).
-// sqrtf and / are the IEEE correctly-rounded forms here (-fhip-fp32-correctly-rounded-divide-sqrt); HIP's __fsqrt_rn is
-// the NATIVE (approximate) square root unless OCML_BASIC_ROUNDED_OPERATIONS is defined, so it is not used.
-__device__ inline float3_ normalize3(float3_ a) {
-    float n = __builtin_sqrtf(dot3(a, a));
-    return mk3((a.x / n), (a.y / n), (a.z / n));
 }
 
 // get_orthogonal_basis (src/math.jl:143-156): argmin(abs.(normal)) keeps the FIRST minimum on ties.
@@ -666,54 +782,26 @@ __global__ void k_scatter_hit_indices(const uint32_t* flags, const uint32_t* pos
     if (i == n - 1) *count = pos[i] + flags[i];
 }
 
-float3_ h_normalize(float3_ a) {
-    float n = sqrtf(dot3(a, a));
-    return mk3(a.x / n, a.y / n, a.z / n);
-}
-
-// generate_ray_grid up to its loop (:10-46), as called from hits_from_grid (:58-61).  Host code compiled
-// with -ffp-contract=off; jl_min/jl_max give extrema() its Julia semantics.
-GridParams grid_params(rc_scene* s, const float viewdir[3], uint32_t grid) {
-    float3_ ray_direction = h_normalize(mk3(viewdir[0], viewdir[1], viewdir[2]));
-    float3_ direction = h_normalize(ray_direction);
-    float3_ o = mk3(s->root_min[0], s->root_min[1], s->root_min[2]);
-    float3_ w = sub3(mk3(s->root_max[0], s->root_max[1], s->root_max[2]), o);
-    float3_ temp = fabsf(direction.x) < 0.9f ? mk3(1, 0, 0) : mk3(0, 1, 0);
-    float3_ b1 = h_normalize(cross3(direction, temp));
-    float3_ b2 = h_normalize(cross3(direction, b1));
-    float min1 = INFINITY, max1 = -INFINITY, min2 = INFINITY, max2 = -INFINITY, mind = INFINITY;
-    for (int c = 0; c < 8; ++c) {
-        float3_ p = mk3(o.x + ((c & 1) ? 1.0f : 0.0f) * w.x, o.y + ((c & 2) ? 1.0f : 0.0f) * w.y, o.z + ((c & 4) ? 1.0f : 0.0f) * w.z);
-        float p1 = dot3(p, b1), p2 = dot3(p, b2), pd = dot3(p, direction);
-        min1 = jl_min(min1, p1); max1 = jl_max(max1, p1);
-        min2 = jl_min(min2, p2); max2 = jl_max(max2, p2);
-        mind = jl_min(mind, pd);
-    }
-    float margin = 0.05f * jl_max(max1 - min1, max2 - min2);
-    float grid_width = max1 - min1 + 2.0f * margin, grid_height = max2 - min2 + 2.0f * margin;
-    float min_depth = mind - margin;
-    float c1 = (min1 + max1) / 2.0f, c2 = (min2 + max2) / 2.0f;
-    float3_ gc = add3(add3(add3(mk3(0, 0, 0), scale3(direction, min_depth)), scale3(b1, c1)), scale3(b2, c2));
-    GridParams g;
-    g.gc[0] = gc.x; g.gc[1] = gc.y; g.gc[2] = gc.z;
-    g.b1[0] = b1.x; g.b1[1] = b1.y; g.b1[2] = b1.z;
-    g.b2[0] = b2.x; g.b2[1] = b2.y; g.b2[2] = b2.z;
-    g.dir[0] = ray_direction.x; g.dir[1] = ray_direction.y; g.dir[2] = ray_direction.z;
-    g.cell_w = grid_width / (float)grid; g.cell_h = grid_height / (float)grid;
-    g.grid = grid;
-    return g;
-}
-
 }  // namespace
 
 void rc_launch_ray_grid(rc_scene* s, const float viewdir[3], uint32_t grid, RcRay* d_rays, hipStream_t stream) {
     rc_ensure_world_bound(s, stream);  // the grid is laid out from the world bound: after an asynchronous refit it is read back first
-    GridParams g = grid_params(s, viewdir, grid);
+    GridParams g = grid_params(s->root_min, s->root_max, viewdir, grid);
     uint64_t n = (uint64_t)grid * grid;
     uint32_t blocks = (uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)s->n_cus * 8);
     if (blocks == 0) return;
     hipLaunchKernelGGL(k_ray_grid, dim3(blocks), dim3(kBlock), 0, stream, g, d_rays);
     RC_HIP(hipGetLastError());
+}
+
+// n_dirs x grid^2 rays from device-resident directions and the TLAS root as it is when the kernel runs: no host copy of the bound is read.
+void rc_launch_ray_grid_dirs(rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, RcRay* d_rays, hipStream_t stream) {
+    const uint64_t n = (uint64_t)grid * grid;
+    if (n == 0 || n_dirs == 0) return;
+    const uint32_t per_dir = (uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, std::max<uint64_t>(((uint64_t)s->n_cus * 8 + n_dirs - 1) / n_dirs, 1));
+    hipLaunchKernelGGL(k_ray_grid_dirs, dim3(per_dir, std::min<uint32_t>(n_dirs, 65535u)), dim3(kBlock), 0, stream, s->tlas_nodes.p, s->n_tlas_nodes, d_dirs, n_dirs, grid, d_rays);
+    RC_HIP(hipGetLastError());
+    rc_note_stage_launch(s, stream);
 }
 
 static void check_buffer_range(rc_scene* s) {
@@ -779,7 +867,7 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
     if (ray_end <= ray_begin) return;
     check_buffer_range(s);
     rc_ensure_world_bound(s, stream);
-    GridParams g = grid_params(s, viewdir, grid);
+    GridParams g = grid_params(s->root_min, s->root_max, viewdir, grid);
     DriverLaunch launch(s, stream, ray_end - ray_begin);
     const uint32_t np = s->n_flat_prims, n8 = (np + 7u) / 8u;
     uint32_t* scratch = reinterpret_cast<uint32_t*>(rc_totals_scratch(launch.guard, ((size_t)kHistCopies * 8u * n8 + 1u) / 2u));  // private copies of the histogram (HistogramSink)
@@ -796,6 +884,36 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
     launch.run<false>(IlluminationJob{g, ray_begin, scratch, n8});
     if (np) hipLaunchKernelGGL(k_illumination_fold, dim3((np + 255) / 256), dim3(256), 0, stream, scratch, n8, np, d_counts);
     launch.guard.finish();
+}
+
+// get_illumination for n_dirs device-resident directions, ACCUMULATED into d_counts[d * row_stride + (meta - 1)] (u32).  The directions are
+// traced in groups of G consecutive ones, one persistent launch per group (IlluminationDirsJob); G is the largest count with
+// G * grid^2 < 2^32 (the source divides in 32 bits) whose private histogram copies fit option "illum_scratch_bytes" (at least one
+// direction's worth).  Per group: the copies are zeroed, k_grid_params lays the group's grids out from d_dirs and the TLAS root AS THEY
+// ARE WHEN IT RUNS -- nothing here reads the host copy of the world bound, so the call follows an asynchronous refit or rebuild without a
+// host wait and may be captured --, the launch counts, the fold adds.  Items are claimed in natural order: the plan is fixed at call time,
+// the rays are not known before the kernels run.  grid^2 < 2^32 (checked by the caller).
+void rc_launch_illumination_dirs(rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, uint32_t* d_counts, uint64_t row_stride, hipStream_t stream) {
+    const uint32_t np = s->n_flat_prims, n8 = (np + 7u) / 8u;
+    const uint64_t cells = (uint64_t)grid * grid;
+    if (n_dirs == 0 || cells == 0 || np == 0) return;
+    check_buffer_range(s);
+    const uint64_t dir_bytes = sizeof(uint32_t) * (uint64_t)kHistCopies * 8u * n8;
+    const uint64_t group = std::min<uint64_t>(n_dirs, std::min<uint64_t>(((1ull << 32) - 1u) / cells, std::max<uint64_t>((uint64_t)s->opt.illum_scratch_bytes / dir_bytes, 1)));
+    for (uint32_t d0 = 0; d0 < n_dirs; d0 += (uint32_t)group) {
+        const uint32_t nd = (uint32_t)std::min<uint64_t>(group, n_dirs - d0);
+        DriverLaunch launch(s, stream, nd * cells);
+        const size_t hist_bytes = (size_t)(nd * dir_bytes);  // (a multiple of 16: the grids sit behind the copies)
+        uint32_t* scratch = reinterpret_cast<uint32_t*>(rc_totals_scratch(launch.guard, (hist_bytes + sizeof(GridParams) * nd + 7u) / 8u));
+        GridParams* params = reinterpret_cast<GridParams*>(reinterpret_cast<unsigned char*>(scratch) + hist_bytes);
+        RC_HIP(hipMemsetAsync(scratch, 0, hist_bytes, stream));
+        hipLaunchKernelGGL(k_grid_params, dim3((nd + 63u) / 64u), dim3(64), 0, stream, s->tlas_nodes.p, s->n_tlas_nodes, d_dirs + 3u * (size_t)d0, nd, grid, params);
+        launch.guard.start();
+        launch.run<false>(IlluminationDirsJob{params, (uint32_t)cells, scratch, n8});
+        const uint64_t fold_items = (uint64_t)nd * np;
+        hipLaunchKernelGGL(k_illumination_dirs_fold, dim3((uint32_t)((fold_items + 255u) / 256u)), dim3(256), 0, stream, scratch, n8, np, nd, d_counts + (uint64_t)d0 * row_stride, row_stride);
+        launch.guard.finish();
+    }
 }
 
 // RC_VF_SOURCES_BY_METADATA: the flat primitives' indices sorted by (metadata, index) -- and the sorted metadata themselves on the host --

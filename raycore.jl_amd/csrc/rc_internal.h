@@ -172,6 +172,7 @@ struct TraceOptions {
     int64_t claim_shards = 16; // phased kernels: chunk counters in use (a power of two <= kClaimShards)
     int64_t vf_first_touch = 1;          // ROWS on several devices: each device's host thread joins the device's NUMA node and faults in its own row block (rc_multi.hip)
     int64_t vf_chunk_bytes = 192 << 20;  // host-matrix view factors (rc_multi.hip): device block per row chunk -- large enough for full-rate launches and 2-D copies, small enough that the exposed first trace / last copy are a few ms
+    int64_t illum_scratch_bytes = 256 << 20;  // rc_get_illumination_dirs_device: private histogram copies of one launch's group of directions: a bound on memory, the measured curve only falls with larger groups (docs/EXPERIMENTS.md); at least one direction's worth is always used
     int64_t tlas_rebuild_fused = 1;  // rc_rebuild_tlas_device_async on scenes of at most kTlasLdsInst instances: 1 = one workgroup builds the whole TLAS in LDS (k_rebuild_tlas_fused), 0 = the chain of rc_build_tlas's kernels
     int64_t timeline_ptr = 0;  // dev: device address of 8 x u64 per wave (n_cus x 24 waves) that kernel 5 fills with its waves' event times; 0 = off
 };
@@ -438,6 +439,9 @@ uint64_t rc_collide_instances_launch(rc_scene* s, uint2* d_out, uint64_t capacit
 void rc_launch_ray_grid(rc_scene* s, const float viewdir[3], uint32_t grid, RcRay* d_rays, hipStream_t stream);
 void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, uint64_t ray_begin, uint64_t ray_end,
                             float* d_counts, hipStream_t stream);
+// the same for n_dirs device-resident directions, laid out on the device from the TLAS root: no host copy of the world bound is read; grid^2 < 2^32
+void rc_launch_ray_grid_dirs(rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, RcRay* d_rays, hipStream_t stream);
+void rc_launch_illumination_dirs(rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, uint32_t* d_counts, uint64_t row_stride, hipStream_t stream);
 void rc_launch_view_factors(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end,
                             uint32_t ray_begin, uint32_t ray_end, uint32_t* d_matrix, uint64_t row_stride,
                             uint64_t col_stride, uint32_t row_offset, uint32_t flags, hipStream_t stream);

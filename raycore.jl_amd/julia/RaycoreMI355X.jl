@@ -379,6 +379,10 @@ end
 device_free(p::Ptr{Cvoid}) = (ccall((:hipFree, HIP), Cint, (Ptr{Cvoid},), p); nothing)
 device_download!(dst::Vector, src::Ptr{Cvoid}) =
     (ccall((:hipMemcpy, HIP), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint), dst, src, sizeof(dst), 2) == 0 || error("hipMemcpy failed"); dst)
+device_upload!(dst::Ptr{Cvoid}, src::Array) =
+    (ccall((:hipMemcpy, HIP), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint), dst, src, sizeof(src), 1) == 0 || error("hipMemcpy failed"); dst)
+device_zero!(p::Ptr{Cvoid}, bytes::Integer) =
+    (ccall((:hipMemset, HIP), Cint, (Ptr{Cvoid}, Cint, Csize_t), p, 0, bytes) == 0 || error("hipMemset failed"); p)
 
 "closest_hit / any_hit over device-resident RTRay / RTHitResult arrays, asynchronous on `stream` (errors surface at wait_for_gpu!)."
 trace_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n::Integer; any::Bool = false, stream::Ptr{Cvoid} = C_NULL) =
@@ -397,6 +401,41 @@ illumination_device!(a::MI355XStaticTLAS, viewdir, grid_size::Integer, ray_begin
                      stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_get_illumination_device, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, UInt32, UInt64, UInt64, Ptr{Float32}, Ptr{Cvoid}),
                 a.owner.ptr, Float32[viewdir...], grid_size, ray_begin, ray_end, d_counts, stream))
+
+"get_illumination for `n_dirs` directions in one call: `d_dirs` is a device array of n_dirs x 3 Float32 (need not be normalised), read
+ when the kernels run, like the TLAS root the grids are laid out from -- no host copy of the world bound is involved, so the call follows
+ `refit_device_async!` / `rebuild_tlas_device_async!` without a host wait and may be captured.  `d_counts[d * row_stride + meta - 1]`
+ (0-based, UInt32, ACCUMULATED: zero it first) += the hits of direction `d`; weighting the rows is the caller's."
+illumination_dirs_device!(a::MI355XStaticTLAS, d_dirs::Ptr{Float32}, n_dirs::Integer, grid_size::Integer, d_counts::Ptr{UInt32},
+                          row_stride::Integer = counts(a.owner)[4]; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_get_illumination_dirs_device, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, UInt32, UInt32, Ptr{UInt32}, UInt64, Ptr{Cvoid}),
+                a.owner.ptr, d_dirs, n_dirs, grid_size, d_counts, row_stride, stream))
+"The ray grids of `n_dirs` device-resident directions: n_dirs x grid^2 RTRay records, direction `d`'s (0-based) from `d * grid^2` on."
+ray_grid_dirs_device!(a::MI355XStaticTLAS, d_dirs::Ptr{Float32}, n_dirs::Integer, grid_size::Integer, d_rays::Ptr{RTRay};
+                      stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_generate_ray_grid_dirs_device, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, UInt32, UInt32, Ptr{RTRay}, Ptr{Cvoid}),
+                a.owner.ptr, d_dirs, n_dirs, grid_size, d_rays, stream))
+"get_illumination (src/kernels.jl:112-124) over several view directions in one call: an N x D Matrix{Float32} whose column `d` equals
+ `get_illumination(a, viewdirs[d]; grid_size)`; with `weights` (one per direction, e.g. its irradiance) the length-N Float64 vector
+ `counts * weights`, formed on the host."
+function get_illumination_dirs(a::MI355XStaticTLAS, viewdirs::AbstractVector; grid_size = 1000, weights = nothing)
+    nd, np = length(viewdirs), Int(counts(a.owner)[4])
+    all(v -> length(v) == 3, viewdirs) || error("every view direction needs three components")
+    weights === nothing || length(weights) == nd || error("weights must hold one value per direction")
+    dirs = Float32[v[k] for k in 1:3, v in viewdirs]                 # 3 x D column-major = D x 3 row-major
+    rows = zeros(UInt32, np, nd)
+    if nd > 0 && np > 0
+        d_dirs, d_counts = device_alloc(sizeof(dirs)), device_alloc(sizeof(rows))
+        device_upload!(d_dirs, dirs)
+        device_zero!(d_counts, sizeof(rows))
+        illumination_dirs_device!(a, Ptr{Float32}(d_dirs), nd, grid_size, Ptr{UInt32}(d_counts), np)
+        Raycore.wait_for_gpu!(a.owner)
+        device_download!(vec(rows), d_counts)
+        device_free(d_dirs); device_free(d_counts)
+    end
+    out = Float32.(min.(rows, UInt32(1) << 24))                      # the reference's Float32 sums stop at 2^24
+    return weights === nothing ? out : Float64.(out) * Float64[weights...]
+end
 
 "One shard of view_factors! (src/kernels.jl:80-104): source primitives [src_begin, src_end) x rays [ray_begin, ray_end), counts
  ACCUMULATED into d_matrix at row * row_stride + col * col_stride (row = src_meta - 1, or the source's sorted position - row_offset
