@@ -276,18 +276,26 @@ struct IlluminationDirsJob {
 // partial) with no private segment (docs/EXPERIMENTS.md, "Illumination over many directions").
 template <bool ANY, class Job>
 constexpr unsigned kShellLatePop = (!ANY && std::is_same<Job, IlluminationJob>::value) ? ShapeLatePop : 0u;
+// ... and in the LDS shell, which peeks, it keeps the pointer form of the interior loop's stack position: with the integer address
+// (LaneStackP::addr_t) its private segment would grow from 92 to 108 bytes (docs/EXPERIMENTS.md, "VALU trims").
+template <bool ANY, class Job>
+constexpr unsigned kShellPtrStack = (!ANY && std::is_same<Job, IlluminationJob>::value) ? ShapePtrStack : 0u;
+struct ViewFactorTotalsJob;  // (below)
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kBlock, 6) void k_driver(SceneView v, PersistArgs p, Job j) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    phased_trace<ANY, PlainShape<kShellLatePop<ANY, Job>>>(v, p, lds_stack, j.source(v), j.sink(v));
+    // (the view-factor totals job likewise keeps the pointer form in this shell: 79 VGPRs, 36 bytes of private segment with the integer form)
+    constexpr unsigned kPtr = (!ANY && std::is_same<Job, ViewFactorTotalsJob>::value) ? ShapePtrStack : 0u;
+    phased_trace<ANY, PlainShape<kShellLatePop<ANY, Job> | kPtr>>(v, p, lds_stack, j.source(v), j.sink(v));
 }
 // Small top level (<= kTlasLdsNodes nodes): the shape of trace kernel 5 -- two 768-thread workgroups per CU, TLAS (and a single BLAS's
 // top nodes) in LDS planes.
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kMidBlock, 6) void k_driver_lds(SceneView v, PersistArgs p, Job j) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LdsTop top = LdsShape<>::prologue(smem, v, p.blas_k, p.lds_blas_base, p.tlas_k);
-    phased_trace<ANY, LdsShape<>>(v, p, LdsShape<>::stacks(smem), j.source(v), j.sink(v), top);
+    typedef LdsShape<kShellPtrStack<ANY, Job>> Shape;
+    const LdsTop top = Shape::prologue(smem, v, p.blas_k, p.lds_blas_base, p.tlas_k);
+    phased_trace<ANY, Shape>(v, p, Shape::stacks(smem), j.source(v), j.sink(v), top);
 }
 // Larger top levels (the shape of trace kernel 6): only the breadth-first tops of the TLAS and of a single BLAS are staged.
 template <bool ANY, class Job>

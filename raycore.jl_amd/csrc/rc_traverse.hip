@@ -122,10 +122,13 @@ __global__ __launch_bounds__(kMidBlock, 6) void k_trace_phased_lds(TraceArgs a) 
 // of a single BLAS are staged (PartialShape, rc_traverse_core.h); TLAS leaves and instance records come from memory as in kernel 3.
 template <bool ANY, unsigned FLAGS = 0u>
 __global__ __launch_bounds__(kMidBlock, 6) void k_trace_phased_partial(TraceArgs a) {
+    // (closest-hit with 32-bit stack entries keeps the pointer form of the interior loop's stack position: at 78 VGPRs it has no room for the
+    // integer form's two stride registers -- 12 bytes of private segment otherwise; neither the LDS layout nor its size depends on the flag)
+    typedef PartialShape<FLAGS | ((!ANY && (FLAGS & ShapeStack16) == 0u) ? ShapePtrStack : 0u)> Shape;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LdsTop top = PartialShape<FLAGS>::prologue(smem, a.v, a.blas_k, a.lds_blas_base, a.tlas_k);
+    const LdsTop top = Shape::prologue(smem, a.v, a.blas_k, a.lds_blas_base, a.tlas_k);
     PersistArgs p{a.n_rays, a.claim, a.refill, a.sched_thr, a.stats, a.blas_k, a.lds_blas_base, a.tlas_k};
-    phased_trace<ANY, PartialShape<FLAGS>>(a.v, p, PartialShape<FLAGS>::stacks(smem), ArraySource{a.rays}, HitWriter{a.v.inst, a.hits}, top);
+    phased_trace<ANY, Shape>(a.v, p, Shape::stacks(smem), ArraySource{a.rays}, HitWriter{a.v.inst, a.hits}, top);
 }
 
 // ---- kernel 3: the phase-structured persistent core (rc_traverse_core.h) on a ray array ------------------------

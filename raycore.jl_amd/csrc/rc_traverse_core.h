@@ -390,6 +390,39 @@ struct LaneStackP {
         top -= keep ? 0 : BLOCK;
         return keep ? keep_v : (do_push ? v : old_top);  // (a pushed `v` is a node index: it fits E, the read-back would return it unchanged)
     }
+    // The interior loop's own form of the stack position (docs/EXPERIMENTS.md "VALU trims"): the LDS byte address of the lane's TOP ENTRY as an
+    // integer, one stride below the next free slot.  The peek then reads at the address itself and the write goes to address + stride through
+    // the instruction's offset field: no address arithmetic in the pass.  (With the pointer form the compiler keeps an offset from `base` and
+    // pays one add per pass for the write's address and one more for the peek's.)  Only lanes with at least one entry below `top` ever
+    // dereference it -- the lanes the interior loop admits --, so the address that is dereferenced is never below the lane's column; for the
+    // other lanes it is a number that converts back (from_addr) to the pointer it came from.
+    typedef uint32_t addr_t;
+    static constexpr uint32_t kStrideBytes = (uint32_t)(BLOCK * sizeof(E));
+    __device__ inline addr_t top_addr(pos_t top) const { return (uint32_t)(uintptr_t)top - kStrideBytes; }
+    __device__ inline pos_t from_addr(addr_t a) const { return (pos_t)(uintptr_t)(a + kStrideBytes); }
+    // `top < limit`, against a WAVE-UNIFORM bound (a scalar operand of the compare, as the pointer form's offset compare has): entry k of lane t
+    // lies at stacks + k * stride + t * sizeof(E) with t * sizeof(E) < stride, so the top entry's index is below LDS_N - 1 exactly when its
+    // address is below stacks + (LDS_N - 1) * stride, whatever the lane.  `stacks_addr` = LDS address of the workgroup's first stack entry.
+    static __device__ inline bool below_limit(addr_t a, uint32_t stacks_addr) { return (int32_t)a < (int32_t)(stacks_addr + (uint32_t)(LDS_N - 1) * kStrideBytes); }
+    __device__ inline uint32_t peek_lds(addr_t a) const { return *(lds_e*)(uintptr_t)a; }
+    // push_pop_lds for an interior node with the children's hit predicates h0, h1 and first0 = "child 0 first" (implies h0):
+    //   far child = first0 ? c1 : c0, pushed iff h0 & (h1 | !first0);  near child = first0 ? c0 : c1, descended to iff first0 | h1;
+    // the position moves by d = h0 + h1 - 1 entries -- two hits push, no hit pops, one hit either descends or pushes and pops at once -- and the
+    // next node is c0 when child 0 is first or the only hit, else c1 when hit, else the old top.
+    // The position: a select by lane mask has no room for a literal, so `h0 ? stride : 0` and `h1 ? 0 : -stride` cost a v_mov of the constant
+    // each in every pass when the compiler is left to it (the form before).  `up` / `down` hold +stride / -stride in two registers the caller
+    // keeps across the loop: two independent selects and one three-operand add, two levels deep.  (d = h0 + h1 - 1 from inline constants and
+    // one 24-bit multiply-add by the stride in a scalar register needs no vector register, and was measured: a chain of three, a quarter to
+    // a half of this form's gain -- docs/EXPERIMENTS.md "VALU trims".  -DRC_TRIM_MAD builds it.)
+    __device__ inline uint32_t push_pop_lds(addr_t& a, bool h0, bool h1, bool first0, uint32_t c0, uint32_t c1, uint32_t old_top, uint32_t up, uint32_t down) {
+        *(lds_e*)(uintptr_t)(a + kStrideBytes) = (E)(first0 ? c1 : c0);
+#if defined(RC_TRIM_MAD)   // (`up` = the stride in a scalar register the caller keeps opaque, `down` unused)
+        a = (uint32_t)(__mul24((h0 ? 1 : 0) - (h1 ? 0 : 1), (int)up) + (int)a);
+#else
+        a = a + (h0 ? up : 0u) + (h1 ? 0u : down);
+#endif
+        return (first0 | (h0 & !h1)) ? c0 : (h1 ? c1 : old_top);
+    }
 };
 
 struct NodeRegs {
@@ -638,6 +671,7 @@ enum ShapeFlags : unsigned {
     ShapeStats = 2u,     // dev: per-phase pass / lane counters (option "stats")
     ShapeTimeline = 4u,  // dev: per-wave event times (option "timeline_ptr")
     ShapeLatePop = 8u,   // the interior pass reads its pop behind the write (no LaneStackP::peek_lds): for a shell that would spill the peeked value
+    ShapePtrStack = 16u, // the interior loop keeps the stack position as a pointer (no LaneStackP::addr_t): for a shell whose private segment would grow with the integer form
 };
 constexpr int kMidBlock = 768, kMidStack = 16;  // the two-workgroups-per-CU shapes: 24 waves per CU as with six 256-thread blocks
 constexpr size_t kLeafTableBytes = (size_t)kTlasLdsInst * sizeof(uint32_t);
@@ -693,7 +727,7 @@ struct TraceShape {
     static constexpr int kBlock = BLOCK, kLdsDepth = LDS_N;
     static constexpr Top top = TOP;
     static constexpr bool kStack16 = (FLAGS & ShapeStack16) != 0, kStats = (FLAGS & ShapeStats) != 0, kTimeline = (FLAGS & ShapeTimeline) != 0;
-    static constexpr bool kLatePop = (FLAGS & ShapeLatePop) != 0;
+    static constexpr bool kLatePop = (FLAGS & ShapeLatePop) != 0, kPtrStack = (FLAGS & ShapePtrStack) != 0;
     typedef typename std::conditional<kStack16, uint16_t, uint32_t>::type entry_t;  // a lane-stack entry in LDS
     static constexpr int kBlocksPerCu = BLOCK == rc::kBlock ? 0 : 2;  // workgroups the grid rule (rc_grid_blocks) puts on a CU; 0: option "blocks_per_cu"
     // entries per node plane: 310 / 748 (32- / 16-bit stacks) beside the leaf table and the instance planes, 585 / 1 023 alone
@@ -773,6 +807,13 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
     constexpr bool STATS = Shape::kStats, TIMELINE = Shape::kTimeline, STACK16 = Shape::kStack16;
     typedef LaneStackP<Shape::kLdsDepth, BLOCK, typename Shape::entry_t> Stack;
     constexpr bool PEEK = Stack::kPeek && !Shape::kLatePop;
+    // The interior loop keeps the stack position as the integer address of the top entry (LaneStackP::addr_t) wherever it peeks.
+    // -DRC_NO_TRIM_INTERIOR (dev, tools/ab_build.sh): the pointer form, as before docs/EXPERIMENTS.md "VALU trims"
+#if defined(RC_NO_TRIM_INTERIOR)
+    constexpr bool ADDR = false;
+#else
+    constexpr bool ADDR = Stack::kFast && PEEK && !Shape::kPtrStack;
+#endif
     // node values that are not nodes: the 32-bit INVALID / sentinel of the reference, or their low halves where everything fits 16 bits
     constexpr uint32_t kInv = STACK16 ? 0xFFFFu : RC_INVALID_NODE, kSent = STACK16 ? 0xFFFEu : RC_TOP_LEVEL_SENTINEL;
     const float2* const tl = top.tl;
@@ -808,6 +849,9 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
     // cost-ordered claiming (RcClaim::cost): a ray's cost = the interior-loop iterations its wave ran while the ray was in flight -- the time
     // the ray occupied its lane, in the unit the launch's tail is made of.  The wave's iteration count lives in a scalar register and every
     // lane remembers the count at which its ray started: no per-iteration vector work.
+    // (In the ISA the count is a per-lane v_add_u32 all the same: the interior loop's exits come out of the structurizer as lane masks, which makes
+    // every value the loop carries divergent in the compiler's eyes.  readfirstlane inside or behind the loop only adds a v_mov + v_readfirstlane
+    // round trip to the add -- docs/EXPERIMENTS.md "VALU trims".)
     uint32_t it_total = 0, start_it = 0;
     // which batch slot of the history this launch belongs to (order_select): its cost array, whether `order` is valid, its threshold
     const uint32_t* claim_order = a.claim.order;
@@ -835,6 +879,19 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
     // TIMELINE (dev, tools/archive/timeline_probe.py): per-wave event times and scalar counts, cheap enough not to move the schedule
     unsigned long long tl_t0 = TIMELINE ? wall_clock64() : 0ull, tl_tx = 0ull, tl_t16 = 0ull, tl_t4 = 0ull;
     uint32_t tl_outer = 0, tl_outer_x = 0, tl_live_x = 0, tl_int = 0, tl_int_x = 0;
+    // for the interior pass's position update (LaneStackP::push_pop_lds): +stride / -stride of the lane stacks in registers whose values the
+    // compiler does not know -- it would rebuild both constants with a v_mov in every pass --, and the LDS address of the workgroup's first
+    // stack entry (wave-uniform)
+    uint32_t step_up = Stack::kStrideBytes, step_down = 0u - Stack::kStrideBytes;
+#if defined(RC_TRIM_MAD)
+    if (ADDR) asm volatile("" : "+s"(step_up));
+#else
+    if (ADDR) asm volatile("" : "+v"(step_up), "+v"(step_down));
+#endif
+    const uint32_t stacks_addr = (uint32_t)(uintptr_t)(typename Stack::lds_e*)lds_stack;
+#if defined(RC_EXP_VALU_FREE)
+    float exp_free = 1.0f;  // (lives across the whole loop; the volatile asm statements that update it are what keeps it)
+#endif
 
     for (;;) {
 #if defined(RC_AGE_PRIO)  // dev experiment (VERDICT r4 #2a): a wave that carries a ray older than RC_AGE_PRIO interior iterations issues ahead of its SIMD's other waves
@@ -846,6 +903,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
         // ---- interior phase: intersect_internal_node (:1807-1832) + push far / descend near / pop (:1946-1960, 1991-1993)
         // One pass over an interior node.  DEEP = false: every participating lane's next free stack slot lies below the LDS depth (the loop
         // below admits no other lane), so push and pop are the branch-free LDS forms; DEEP = true: the general push / pop with the spill path.
+        typename Stack::addr_t ta = ADDR ? st.top_addr(sp) : 0u;  // the interior loop's form of `sp`; converted back behind the loop
         auto interior_pass = [&](auto deep_tag) {
             constexpr bool DEEP = decltype(deep_tag)::value;
 #if defined(RC_EXP_VALU)  // dev experiment (tools/probes/build_variants.sh; profiles/r05_bound_probe.txt): RC_EXP_VALU extra slow-class VALU instructions (one dependent chain) per interior pass
@@ -868,7 +926,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
             // -DRC_STACK_PEEK_AT_HEAD (dev, tools/ab_build.sh): the peek in front of the fetch (docs/EXPERIMENTS.md "stack peek")
             uint32_t old_top = 0u;
 #if defined(RC_STACK_PEEK_AT_HEAD)
-            if (!DEEP && PEEK) old_top = st.peek_lds(sp);
+            if (!DEEP && PEEK) old_top = ADDR ? st.peek_lds(ta) : st.peek_lds(sp);
 #endif
             if ((Shape::top == Top::Lds && (cur_inst < 0 || node <= a.blas_k)) || (Shape::top == Top::PartialLds && node <= (cur_inst < 0 ? a.tlas_k : a.blas_k))) {
                 const float2* q = tl + ((node - 1u) + (cur_inst < 0 ? 0u : a.lds_blas_base));
@@ -881,7 +939,22 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
                 ch = __builtin_amdgcn_raw_buffer_load_b64(nrs1, off, 48, 0);
             }
 #if !defined(RC_STACK_PEEK_AT_HEAD)
-            if (!DEEP && PEEK) { old_top = st.peek_lds(sp); __builtin_amdgcn_sched_barrier(0); }
+            if (!DEEP && PEEK) { old_top = ADDR ? st.peek_lds(ta) : st.peek_lds(sp); __builtin_amdgcn_sched_barrier(0); }
+#endif
+#if defined(RC_EXP_VALU_FREE)  // dev experiment (profiles/valu_slot_price.txt): RC_EXP_VALU_FREE extra VALU instructions per interior pass that nothing in the pass reads -- an
+            // accumulator of their own, issued in the shadow of the node fetch: the price of an issue slot, where RC_EXP_VALU's chain prices latency.
+            // Slow class (v_max_f32) by default, -DRC_EXP_VALU_FREE_MUL: the full-rate class (v_mul_f32)
+            {
+#pragma unroll
+                for (int k = 0; k < RC_EXP_VALU_FREE; ++k) {
+#if defined(RC_EXP_VALU_FREE_MUL)
+                    asm volatile("v_mul_f32 %0, %0, %1" : "+v"(exp_free) : "v"(closest_t));
+#else
+                    asm volatile("v_max_f32 %0, %0, %1" : "+v"(exp_free) : "v"(closest_t));
+#endif
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #endif
             // packed node (rc_pack_node): na = child-0 (min.x,min.y,max.x,max.y), nb = child-1 likewise, nc = z of both
             const v2f ixy = {inv.x, inv.y}, oxy = {ox.x, ox.y}, izz = {inv.z, inv.z}, ozz = {ox.z, ox.z};
@@ -898,6 +971,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
             // traverse0 = h0 ? child0 : INVALID, traverse1 likewise; near first iff t0_min < t1_min && traverse0 valid
             const bool h0 = t0_min <= t0_max, h1 = t1_min <= t1_max;
             const bool first0 = (t0_min < t1_min) & h0;
+            if (!DEEP && ADDR) { node = st.push_pop_lds(ta, h0, h1, first0, ch.x, ch.y, old_top, step_up, step_down); return; }
             const uint32_t near_c = first0 ? ch.x : ch.y, far_c = first0 ? ch.y : ch.x;
             const bool near_ok = first0 | h1, far_ok = h0 & (h1 | !first0);  // = first0 ? h1 : h0 (first0 implies h0), as lane-mask logic
             if (DEEP) {
@@ -911,8 +985,9 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
         // (The vote is taken from the lane masks of the two compares themselves: a vote on their conjunction costs a select and a compare more.)
         for (;;) {
             RC_MARK("interior_begin");
-            const bool is_int = node < n_level && (!Stack::kFast || sp < st.limit);
-            const unsigned long long m_int = __builtin_amdgcn_ballot_w64(node < n_level) & (Stack::kFast ? __builtin_amdgcn_ballot_w64(sp < st.limit) : ~0ull);
+            const bool shallow = ADDR ? Stack::below_limit(ta, stacks_addr) : sp < st.limit;
+            const bool is_int = node < n_level && (!Stack::kFast || shallow);
+            const unsigned long long m_int = __builtin_amdgcn_ballot_w64(node < n_level) & (Stack::kFast ? __builtin_amdgcn_ballot_w64(shallow) : ~0ull);
             if (m_int == 0ull) break;
             const int n_int = __popcll(m_int);
             it_total += 1u;
@@ -922,6 +997,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
             RC_MARK("interior_end");
             if (n_int < thr_eff) break;  // too few interior lanes left: serve the waiting ones first
         }
+        if (ADDR) sp = st.from_addr(ta);
         // One vote per outer iteration: is any lane of the wave at or beyond the LDS depth?  If so (rare), those lanes get one interior pass
         // of their own with the general push / pop.  The stack sites of the record and switch phases keep the general forms: their
         // branch-free variants behind this vote measured no gain (docs/EXPERIMENTS.md, "stack fast path").
