@@ -16,7 +16,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "rc_internal.h"
+#include "rc_traverse_core.h"
 
 namespace {
 
@@ -243,7 +243,7 @@ __global__ void k_reflection_rays(const RcRay* rays, const RcHit* hits, uint64_t
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const RcHit h = hits[i];
-    RcRay rr{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+    RcRay rr = RC_DUMMY_RAY;
     if (h.hit) {
         const RcRay r = rays[i];
         const float* a = attrs + 15 * (size_t)h.primitive_id;
@@ -259,9 +259,7 @@ __global__ void k_reflection_rays(const RcRay* rays, const RcHit* hits, uint64_t
         const float3_ ro = add3(hp, scale3(nrm, bias));
         rr = RcRay{ro.x, ro.y, ro.z, 0.0f, rd.x, rd.y, rd.z, INFINITY};
     }
-    float4* q = reinterpret_cast<float4*>(out + i);
-    q[0] = make_float4(rr.ox, rr.oy, rr.oz, rr.tmin);
-    q[1] = make_float4(rr.dx, rr.dy, rr.dz, rr.tmax);
+    rc::store_ray(out, i, rr);
 }
 
 // The optional GATE of the TLAS chain's kernels (rc_refit_or_rebuild_tlas_async): a word an EARLIER kernel on the same stream wrote.  Every

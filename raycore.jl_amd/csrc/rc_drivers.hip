@@ -100,12 +100,7 @@ __device__ inline RcRay grid_ray(const GridParams& g, uint64_t idx) {
 
 __global__ __launch_bounds__(kBlock) void k_ray_grid(GridParams g, RcRay* out) {
     uint64_t n = (uint64_t)g.grid * g.grid;
-    for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        RcRay r = grid_ray(g, i);
-        float4* q = reinterpret_cast<float4*>(out + i);
-        q[0] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-        q[1] = make_float4(r.dx, r.dy, r.dz, r.tmax);
-    }
+    for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) store_ray(out, i, grid_ray(g, i));
 }
 
 // The grids of n_dirs directions in one launch: direction d's rays start at d * grid^2, in k_ray_grid's layout.  Every workgroup lays out
@@ -116,12 +111,7 @@ __global__ __launch_bounds__(kBlock) void k_ray_grid_dirs(const RcNode* tlas_nod
     for (uint32_t d = blockIdx.y; d < n_dirs; d += gridDim.y) {
         if (threadIdx.x == 0) g = grid_params_device(tlas_nodes, n_tlas_nodes, dirs, d, grid);
         __syncthreads();
-        for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-            RcRay r = grid_ray(g, i);
-            float4* q = reinterpret_cast<float4*>(out + (uint64_t)d * n + i);
-            q[0] = make_float4(r.ox, r.oy, r.oz, r.tmin);
-            q[1] = make_float4(r.dx, r.dy, r.dz, r.tmax);
-        }
+        for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) store_ray(out + (uint64_t)d * n, i, grid_ray(g, i));
         __syncthreads();
     }
 }
@@ -161,63 +151,129 @@ __device__ inline void wave_count(T* acc, unsigned long long index, bool counted
 
 // get_illumination's histogram is a HOT vector (a few large, well-lit triangles take most of the hits: C5 seen from outside counts 6 852 rays on
 // one wall triangle), and atomics onto a few cache lines serialise: the call took 0.59 ms where tracing the same rays takes 0.19.  The kernel
-// counts into kHistCopies private u32 copies (by workgroup), each laid out transposed in rows of eight, and k_illumination_fold adds them into
+// counts into kHistCopies private u32 copies (by workgroup), each laid out transposed in rows of eight, and k_hist_fold (FoldF32Saturating) adds them into
 // the caller's f32 vector with the reference's arithmetic: `counts[k] += 1f0` per ray (src/kernels.jl:119-121) is exact up to 2^24 and stays
 // there, so counts = min(counts + hits, 2^24) in integers is the same number.  (Also tried: the traversal only STORES each ray's hit
 // metadata and a streaming kernel counts afterwards -- two more launches and a 16 MB round trip: C3 0.62 ms instead of 0.57, C5 0.34 instead of 0.24.)
+//
+// The copy histogram, shared with the view-factor totals (`received` is as hot: 2 x 10^8 atomics onto a few hundred cache lines ran at HALF the
+// rate of the matrix's scattered ones, C5 81 ms against 39): kHistCopies copies of 8 x n8 counters; a workgroup counts into copy blockIdx & 15;
+// metadata index j sits at (j & 7) * n8 + (j >> 3), so neighbouring triangles -- a wall's two halves, a sphere's ring -- are in different cache lines.
 constexpr uint32_t kHistCopies = 16;
-struct HistogramSink {
+struct CopyHist {
+    uint32_t n8;  // ceil(n_prims / 8)
+    __host__ __device__ __forceinline__ static CopyHist of(uint32_t n_prims) { return CopyHist{(n_prims + 7u) / 8u}; }
+    __host__ __device__ __forceinline__ unsigned long long base(unsigned long long copy) const { return copy * 8u * n8; }  // first word of a copy
+    __host__ __device__ __forceinline__ unsigned long long words() const { return base(kHistCopies); }                     // of one histogram
+    __device__ __forceinline__ uint32_t slot(uint32_t j) const { return (j & 7u) * n8 + (j >> 3); }
+    __device__ __forceinline__ static uint32_t copy() { return blockIdx.x & (kHistCopies - 1u); }
+};
+// The primitive metadata of a hit: the instance record's fourth 16 bytes hold its first flat primitive in .y (HitWriter reads the same words).
+__device__ __forceinline__ uint32_t hit_meta(const RcInstRec* inst, const RcPrim* prims, int instance, uint32_t prim) {
+    const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
+    return prims[m3.y + prim - 1u].meta;
+}
+// The sink of both illumination jobs: one count per hit on the slot of its primitive's metadata.  The one-direction job (DIRS = false) folds
+// its copy's base into wave_count's pointer -- it has no register for a division by `cells`; the many-direction job folds direction and
+// copy into the index: a wave straddles directions, and lanes are combined by index.
+template <bool DIRS>
+struct HistogramSinkT {
     const RcInstRec* inst;
     const RcPrim* prims;
     uint32_t n_prims;
-    uint32_t* scratch;  // kHistCopies x 8 x n8 counters, zeroed by the launcher
-    uint32_t n8;        // ceil(n_prims / 8)
-    __device__ inline void operator()(uint64_t, bool hit, float, float, float, uint32_t prim, int instance) const {
+    uint32_t* scratch;  // one histogram (DIRS: one per direction of the group), zeroed by the launcher
+    CopyHist h;
+    uint32_t cells;     // DIRS: grid^2, item i belongs to direction i / cells
+    __device__ inline void operator()(uint64_t i, bool hit, float, float, float, uint32_t prim, int instance) const {
         uint32_t meta = 0;
-        if (hit) {
-            const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
-            meta = prims[m3.y + prim - 1u].meta;
-        }
+        if (hit) meta = hit_meta(inst, prims, instance, prim);
         const bool counted = hit && meta >= 1 && meta <= n_prims;  // metadata outside 1..N is dropped (src/kernels.jl:123)
         const uint32_t j = meta - 1u;
-        wave_count(scratch + (size_t)(blockIdx.x & (kHistCopies - 1u)) * 8u * n8, counted ? (unsigned long long)((j & 7u) * n8 + (j >> 3)) : 0ull, counted);
+        if (DIRS) {
+            const uint32_t d = (uint32_t)i / cells;
+            const unsigned long long copy = (unsigned long long)d * kHistCopies + h.copy();
+            wave_count(scratch, counted ? h.base(copy) + h.slot(j) : 0ull, counted);
+        } else
+            wave_count(scratch + h.base(h.copy()), counted ? (unsigned long long)h.slot(j) : 0ull, counted);
     }
 };
-__global__ void k_illumination_fold(const uint32_t* scratch, uint32_t n8, uint32_t n, float* counts) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    unsigned long long sum = 0;
-    for (uint32_t c = 0; c < kHistCopies; ++c) sum += scratch[(size_t)c * 8u * n8 + (j & 7u) * n8 + (j >> 3)];
-    if (sum == 0) return;
-    // ACCUMULATES, atomically (shards traced concurrently on several streams into ONE vector used to be safe when the kernel itself
-    // added with atomics; N compare-and-swaps per launch cost nothing): counts = min(counts + hits, 2^24) in integers
-    uint32_t* word = reinterpret_cast<uint32_t*>(counts + j);
-    uint32_t seen = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (;;) {
-        const float before = __uint_as_float(seen);  // an integer below 2^24 unless the caller put something else there
-        float after;
-        if (before >= 0.0f && before <= 16777216.0f && before == (float)(uint32_t)before) {
-            const unsigned long long total = (unsigned long long)(uint32_t)before + sum;
-            after = total >= 16777216ull ? 16777216.0f : (float)(uint32_t)total;
-        } else {  // not a count: add one by one like the reference would, up to where f32 stops moving
-            after = before;
-            for (unsigned long long k = 0; k < sum && k < 16777216ull; ++k) { const float nv = after + 1.0f; if (nv == after) break; after = nv; }
-        }
-        const uint32_t prev = atomicCAS(word, seen, __float_as_uint(after));
-        if (prev == seen) break;
-        seen = prev;
-    }
+typedef HistogramSinkT<false> HistogramSink;
+typedef HistogramSinkT<true> DirsHistogramSink;
+// Adds the copies of `rows` histograms into the caller's array: one thread per (row, metadata index), Rule::add accumulates the sum.
+// ACCUMULATES, atomically, under every rule: calls on several streams may share an array (shards traced concurrently into ONE vector
+// used to be safe when the kernels themselves added with atomics).  A one-row rule indexes in 32 bits and never divides.
+template <class Word, class Rule>
+__global__ void k_hist_fold(const Word* scratch, CopyHist h, uint32_t n, Rule rule) {
+    const typename Rule::Index t = blockIdx.x * (typename Rule::Index)blockDim.x + threadIdx.x;
+    if (t >= (typename Rule::Index)rule.rows() * n) return;
+    const uint32_t d = Rule::kRows ? (uint32_t)(t / n) : 0u, j = (uint32_t)(t - (typename Rule::Index)d * n);
+    const Word* base = scratch + d * h.words();
+    typename Rule::Sum sum = 0;
+    // (h.base(c) + h.slot(j), written out and summed in 64 bits: through the helpers the address adds reassociate)
+    for (uint32_t c = 0; c < kHistCopies; ++c) sum += base[(size_t)c * 8u * h.n8 + (j & 7u) * h.n8 + (j >> 3)];
+    if (sum) rule.add(d, j, sum);
 }
+struct FoldOneRow {
+    typedef uint32_t Index;
+    typedef unsigned long long Sum;
+    static constexpr bool kRows = false;
+    __host__ __device__ static inline uint32_t rows() { return 1u; }
+};
+// get_illumination's f32 vector, with the reference's arithmetic: counts = min(counts + hits, 2^24) in integers (N compare-and-swaps per launch cost nothing)
+struct FoldF32Saturating : FoldOneRow {
+    float* counts;
+    __device__ inline void add(uint32_t, uint32_t j, unsigned long long sum) const {
+        uint32_t* word = reinterpret_cast<uint32_t*>(counts + j);
+        uint32_t seen = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (;;) {
+            const float before = __uint_as_float(seen);  // an integer below 2^24 unless the caller put something else there
+            float after;
+            if (before >= 0.0f && before <= 16777216.0f && before == (float)(uint32_t)before) {
+                const unsigned long long total = (unsigned long long)(uint32_t)before + sum;
+                after = total >= 16777216ull ? 16777216.0f : (float)(uint32_t)total;
+            } else {  // not a count: add one by one like the reference would, up to where f32 stops moving
+                after = before;
+                for (unsigned long long k = 0; k < sum && k < 16777216ull; ++k) { const float nv = after + 1.0f; if (nv == after) break; after = nv; }
+            }
+            const uint32_t prev = atomicCAS(word, seen, __float_as_uint(after));
+            if (prev == seen) break;
+            seen = prev;
+        }
+    }
+};
+struct FoldAddU64 : FoldOneRow {  // the view-factor totals' `received`
+    unsigned long long* out;
+    __device__ inline void add(uint32_t, uint32_t j, unsigned long long sum) const { atomicAdd(out + j, sum); }
+};
+struct FoldAddU32Rows {  // the many-direction matrix: row d = direction d of the group
+    typedef uint64_t Index;
+    typedef uint32_t Sum;  // (a direction traces grid^2 < 2^32 rays)
+    static constexpr bool kRows = true;
+    uint32_t n_rows;
+    uint32_t* counts;
+    uint64_t row_stride;
+    __host__ __device__ inline uint32_t rows() const { return n_rows; }
+    __device__ inline void add(uint32_t d, uint32_t j, uint32_t sum) const { atomicAdd(counts + (uint64_t)d * row_stride + j, sum); }
+};
 // A driver job is the kernel argument of the three shells below: a trivially copyable struct of the job's own parameters that makes the
 // Source and the Sink next to the kernel's SceneView.
+// A job whose shells need another shape than the default says so in a specialisation of JobShapeFlags, next to the job (Shape* flags, rc_traverse_core.h).
+template <class Job>
+struct JobShapeFlags { static constexpr unsigned kPlain = 0u, kLds = 0u, kPartial = 0u; };
 struct IlluminationJob {
     GridParams g;
     uint64_t ray_begin;
     uint32_t* scratch;
-    uint32_t n8;
+    CopyHist h;
     __device__ inline GridSource source(const SceneView&) const { return GridSource{g, ray_begin}; }
-    __device__ inline HistogramSink sink(const SceneView& v) const { return HistogramSink{v.inst, v.prims, v.n_prims, scratch, n8}; }
+    __device__ inline HistogramSink sink(const SceneView& v) const { return HistogramSink{v.inst, v.prims, v.n_prims, scratch, h, 0u}; }
 };
+// Keeps the late pop in the plain and the partial shell: beside the sink's own arrays they have no register for the peeked stack top (80 VGPRs
+// either way; with the peek their private segments grow from 92 to 124 and from 96 to 100 bytes).  The LDS shell peeks like the trace kernels,
+// but keeps the pointer form of the interior loop's stack position: with the integer address (LaneStackP::addr_t) its private segment would
+// grow from 92 to 108 bytes (docs/EXPERIMENTS.md, "VALU trims").  Neither the LDS layout nor its size depends on the flags.
+template <>
+struct JobShapeFlags<IlluminationJob> { static constexpr unsigned kPlain = ShapeLatePop, kLds = ShapePtrStack, kPartial = ShapeLatePop; };
 // get_illumination for a GROUP of directions in one launch: work item i = d_local * grid^2 + cell.  The source reads direction d_local's
 // GridParams (k_grid_params wrote them in front of the launch) and makes grid_ray()'s ray, bit for bit k_ray_grid's and GridSource's for that
 // direction; the sink is HistogramSink with a base of d_local * kHistCopies * 8 * n8 -- folded into wave_count's index, not into its
@@ -231,76 +287,35 @@ struct DirsGridSource {
     }
     static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
 };
-struct DirsHistogramSink {
-    const RcInstRec* inst;
-    const RcPrim* prims;
-    uint32_t n_prims;
-    uint32_t* scratch;  // G x kHistCopies x 8 x n8 counters, zeroed by the launcher
-    uint32_t n8, cells;
-    __device__ inline void operator()(uint64_t i, bool hit, float, float, float, uint32_t prim, int instance) const {
-        uint32_t meta = 0;
-        if (hit) {
-            const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
-            meta = prims[m3.y + prim - 1u].meta;
-        }
-        const bool counted = hit && meta >= 1 && meta <= n_prims;  // metadata outside 1..N is dropped (src/kernels.jl:123)
-        const uint32_t j = meta - 1u, d = (uint32_t)i / cells;
-        const unsigned long long copy = (unsigned long long)d * kHistCopies + (blockIdx.x & (kHistCopies - 1u));
-        wave_count(scratch, counted ? copy * 8u * n8 + ((j & 7u) * n8 + (j >> 3)) : 0ull, counted);
-    }
-};
-// Adds the group's sums into the caller's u32 matrix: one thread per (direction, primitive).  ACCUMULATES, atomically, like the other
-// counting drivers: calls on several streams may share a matrix, and integer adds are exact in any order.
-__global__ void k_illumination_dirs_fold(const uint32_t* scratch, uint32_t n8, uint32_t n, uint32_t n_dirs, uint32_t* counts, uint64_t row_stride) {
-    const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (t >= (uint64_t)n_dirs * n) return;
-    const uint32_t d = (uint32_t)(t / n), j = (uint32_t)(t - (uint64_t)d * n);
-    const uint32_t* base = scratch + (size_t)d * kHistCopies * 8u * n8;
-    uint32_t sum = 0;  // (a direction traces grid^2 < 2^32 rays)
-    for (uint32_t c = 0; c < kHistCopies; ++c) sum += base[(size_t)c * 8u * n8 + (j & 7u) * n8 + (j >> 3)];
-    if (sum) atomicAdd(counts + (uint64_t)d * row_stride + j, sum);
-}
+// The many-direction job needs no shape flags: its source keeps a pointer where GridSource keeps fifteen grid words, and its shells peek in
+// 76 / 77 / 80 VGPRs (plain / LDS / partial) with no private segment (docs/EXPERIMENTS.md, "Illumination over many directions").
 struct IlluminationDirsJob {
     const GridParams* params;
     uint32_t cells;
     uint32_t* scratch;
-    uint32_t n8;
+    CopyHist h;
     __device__ inline DirsGridSource source(const SceneView&) const { return DirsGridSource{params, cells}; }
-    __device__ inline DirsHistogramSink sink(const SceneView& v) const { return DirsHistogramSink{v.inst, v.prims, v.n_prims, scratch, n8, cells}; }
+    __device__ inline DirsHistogramSink sink(const SceneView& v) const { return DirsHistogramSink{v.inst, v.prims, v.n_prims, scratch, h, cells}; }
 };
 // The three shapes every driver runs in (DriverLaunch picks one): they differ in what sits in LDS when phased_trace starts.
-// The closest-hit illumination job keeps the late pop in the plain and the partial shell: beside the sink's own arrays they have no register
-// for the peeked stack top (80 VGPRs either way; with the peek their private segments grow from 92 to 124 and from 96 to 100 bytes).  The
-// LDS shell peeks like the trace kernels.  Neither the LDS layout nor its size depends on the flag.  The many-direction job needs no such
-// treatment: its source keeps a pointer where GridSource keeps fifteen grid words, and its shells peek in 74 / 75 / 77 VGPRs (plain / LDS /
-// partial) with no private segment (docs/EXPERIMENTS.md, "Illumination over many directions").
-template <bool ANY, class Job>
-constexpr unsigned kShellLatePop = (!ANY && std::is_same<Job, IlluminationJob>::value) ? ShapeLatePop : 0u;
-// ... and in the LDS shell, which peeks, it keeps the pointer form of the interior loop's stack position: with the integer address
-// (LaneStackP::addr_t) its private segment would grow from 92 to 108 bytes (docs/EXPERIMENTS.md, "VALU trims").
-template <bool ANY, class Job>
-constexpr unsigned kShellPtrStack = (!ANY && std::is_same<Job, IlluminationJob>::value) ? ShapePtrStack : 0u;
-struct ViewFactorTotalsJob;  // (below)
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kBlock, 6) void k_driver(SceneView v, PersistArgs p, Job j) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    // (the view-factor totals job likewise keeps the pointer form in this shell: 79 VGPRs, 36 bytes of private segment with the integer form)
-    constexpr unsigned kPtr = (!ANY && std::is_same<Job, ViewFactorTotalsJob>::value) ? ShapePtrStack : 0u;
-    phased_trace<ANY, PlainShape<kShellLatePop<ANY, Job> | kPtr>>(v, p, lds_stack, j.source(v), j.sink(v));
+    phased_trace<ANY, PlainShape<JobShapeFlags<Job>::kPlain>>(v, p, lds_stack, j.source(v), j.sink(v));
 }
 // Small top level (<= kTlasLdsNodes nodes): the shape of trace kernel 5 -- two 768-thread workgroups per CU, TLAS (and a single BLAS's
 // top nodes) in LDS planes.
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kMidBlock, 6) void k_driver_lds(SceneView v, PersistArgs p, Job j) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    typedef LdsShape<kShellPtrStack<ANY, Job>> Shape;
+    typedef LdsShape<JobShapeFlags<Job>::kLds> Shape;
     const LdsTop top = Shape::prologue(smem, v, p.blas_k, p.lds_blas_base, p.tlas_k);
     phased_trace<ANY, Shape>(v, p, Shape::stacks(smem), j.source(v), j.sink(v), top);
 }
 // Larger top levels (the shape of trace kernel 6): only the breadth-first tops of the TLAS and of a single BLAS are staged.
 template <bool ANY, class Job>
 __global__ __launch_bounds__(kMidBlock, 6) void k_driver_partial(SceneView v, PersistArgs p, Job j) {
-    typedef PartialShape<kShellLatePop<ANY, Job>> Shape;
+    typedef PartialShape<JobShapeFlags<Job>::kPartial> Shape;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const LdsTop top = Shape::prologue(smem, v, p.blas_k, p.lds_blas_base, p.tlas_k);
     phased_trace<ANY, Shape>(v, p, Shape::stacks(smem), j.source(v), j.sink(v), top);
@@ -414,6 +429,10 @@ struct ViewFactorSource {
     }
     static constexpr bool kPrefetch = false;
 };
+// The counting rule of view_factors! (:93-97): the hit primitive's metadata differs from the source's, and both are in 1..N.
+__device__ __forceinline__ bool vf_counted(uint32_t hit_meta, uint32_t src_meta, uint32_t n_prims) {
+    return hit_meta != src_meta && src_meta >= 1 && src_meta <= n_prims && hit_meta >= 1 && hit_meta <= n_prims;
+}
 struct ViewFactorSink {
     const RcInstRec* inst;
     const RcPrim* prims;
@@ -428,11 +447,10 @@ struct ViewFactorSink {
         if (hit) {
             const uint32_t pos = src_begin + (uint32_t)(w / n_ray);
             const uint32_t src = order ? order[pos] : pos;
-            const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
-            const uint32_t hit_meta = prims[m3.y + prim - 1u].meta, src_meta = prims[src].meta;
-            counted = hit_meta != src_meta && src_meta >= 1 && src_meta <= n_prims && hit_meta >= 1 && hit_meta <= n_prims;
+            const uint32_t to_meta = hit_meta(inst, prims, instance, prim), src_meta = prims[src].meta;
+            counted = vf_counted(to_meta, src_meta, n_prims);
             const uint32_t row = (flags & 4u) ? src_meta - 1 : ((flags & 2u) ? pos : ((flags & 1u) ? src : src_meta - 1));
-            if (counted) index = (uint64_t)(row - row_offset) * row_stride + (uint64_t)(hit_meta - 1) * col_stride;
+            if (counted) index = (uint64_t)(row - row_offset) * row_stride + (uint64_t)(to_meta - 1) * col_stride;
         }
         wave_count(matrix, index, counted);
     }
@@ -441,49 +459,39 @@ struct ViewFactorSink {
 // use of the matrix reads off it (docs/src/viewfactors_content.md:62-68: sum(view(viewf_matrix, :, i))) -- and the row sums emitted[i] = sum_j
 // result[i, j], accumulated directly: two u64 atomics per counted ray, no N x N array anywhere.  Same rays, same counting rule as
 // ViewFactorSink (:93-97); 64-bit so that N x rays_per_triangle may pass 2^32.
-// `received` is the hot vector: most rays of a closed scene end on a few large triangles, and 2 x 10^8 atomics onto a few hundred cache
-// lines ran at HALF the rate of the matrix's scattered ones (C5: 81 ms against 39).  The kernel therefore counts into kTotalsCopies private
-// copies (by workgroup), each laid out TRANSPOSED in rows of eight (neighbouring triangles -- a wall's two halves, a sphere's ring -- sit in
-// different cache lines), and k_vf_totals_fold adds the copies into the caller's vector afterwards.
-constexpr uint32_t kTotalsCopies = 16;
+// `received` is the hot vector -- most rays of a closed scene end on a few large triangles --, so the kernel counts it into a copy histogram
+// of u64 words (CopyHist), and k_hist_fold adds the copies into the caller's vector afterwards.
 struct ViewFactorTotalsSink {
     const RcInstRec* inst;
     const RcPrim* prims;
     uint32_t n_prims, src_begin, n_ray;
-    unsigned long long* received;  // kTotalsCopies x 8 x n8 scratch counters (zeroed by the launcher), or nullptr
-    uint32_t n8;                   // ceil(n_prims / 8)
+    unsigned long long* received;  // one histogram of scratch counters (zeroed by the launcher), or nullptr
+    CopyHist h;
     unsigned long long* emitted;   // [n_prims] or nullptr: per source, nearly wave-uniform -- one atomic per group (wave_count)
     __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
         bool counted = false;
-        uint32_t hit_meta = 1, src_meta = 1;
-        if (hit) {
+        uint32_t to_meta = 1, src_meta = 1;
+        if (hit) {  // hit_meta() and vf_counted(), written out: through either helper the three shells of this job come out differently
             const uint32_t src = src_begin + (uint32_t)(w / n_ray);
             const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
-            hit_meta = prims[m3.y + prim - 1u].meta; src_meta = prims[src].meta;
-            counted = hit_meta != src_meta && src_meta >= 1 && src_meta <= n_prims && hit_meta >= 1 && hit_meta <= n_prims;
+            to_meta = prims[m3.y + prim - 1u].meta; src_meta = prims[src].meta;
+            counted = to_meta != src_meta && src_meta >= 1 && src_meta <= n_prims && to_meta >= 1 && to_meta <= n_prims;
         }
-        if (received) {
-            const uint32_t j = hit_meta - 1u;
-            wave_count(received + (size_t)(blockIdx.x & (kTotalsCopies - 1u)) * 8u * n8, (unsigned long long)((j & 7u) * n8 + (j >> 3)), counted);
-        }
+        if (received) wave_count(received + h.base(h.copy()), (unsigned long long)h.slot(to_meta - 1u), counted);
         if (emitted) wave_count(emitted, (unsigned long long)(src_meta - 1u), counted);
     }
 };
-__global__ void k_vf_totals_fold(const unsigned long long* scratch, uint32_t n8, uint32_t n, unsigned long long* received) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    unsigned long long sum = 0;
-    for (uint32_t c = 0; c < kTotalsCopies; ++c) sum += scratch[(size_t)c * 8u * n8 + (j & 7u) * n8 + (j >> 3)];
-    if (sum) atomicAdd(received + j, sum);  // (ACCUMULATES; atomic, so that shards traced concurrently on several streams may share one vector -- ADVICE r4)
-}
 struct ViewFactorTotalsJob {
     uint32_t k0, k1, src_begin, ray_begin, n_ray;
     unsigned long long* received;
-    uint32_t n8;
+    CopyHist h;
     unsigned long long* emitted;
     __device__ inline ViewFactorSource source(const SceneView& v) const { return ViewFactorSource{v.prims, nullptr, k0, k1, src_begin, ray_begin, n_ray}; }
-    __device__ inline ViewFactorTotalsSink sink(const SceneView& v) const { return ViewFactorTotalsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, received, n8, emitted}; }
+    __device__ inline ViewFactorTotalsSink sink(const SceneView& v) const { return ViewFactorTotalsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, received, h, emitted}; }
 };
+// Keeps the pointer form of the interior loop's stack position in the plain shell: 79 VGPRs, 36 bytes of private segment with the integer form.
+template <>
+struct JobShapeFlags<ViewFactorTotalsJob> { static constexpr unsigned kPlain = ShapePtrStack, kLds = 0u, kPartial = 0u; };
 struct ViewFactorJob {
     uint32_t k0, k1, src_begin, ray_begin, n_ray;
     uint32_t* matrix;
@@ -548,12 +556,10 @@ __device__ inline RcRay shadow_ray(const SceneView& v, const RcRay& r, const RcH
 }
 __global__ void k_shadow_rays(SceneView v, const RcRay* rays, const RcHit* hits, uint64_t n, float lx, float ly, float lz, float bias, RcRay* out) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        RcRay s{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+        RcRay s = RC_DUMMY_RAY;
         const RcHit h = hits[i];
         if (h.hit) s = shadow_ray(v, rays[i], h, mk3(lx, ly, lz), bias);
-        float4* q = reinterpret_cast<float4*>(out + i);
-        q[0] = make_float4(s.ox, s.oy, s.oz, s.tmin);
-        q[1] = make_float4(s.dx, s.dy, s.dz, s.tmax);
+        store_ray(out, i, s);
     }
 }
 
@@ -561,8 +567,8 @@ __global__ void k_shadow_rays(SceneView v, const RcRay* rays, const RcHit* hits,
 // j = i * n_lights + l is hit i seen from light l (the reference's slot (idx-1)*NLights + light_idx), so neighbouring lanes share a hit's
 // records.  The shadow ray is made when a lane is refilled and never stored; a finished any_hit writes the one byte the shading reads.
 // test_shadow_rays! (:353-358) is `ray.t_max > 0 ? !any_hit(...) : false`: an item whose primary ray missed, or whose shadow ray has a t_max
-// that is not > 0 (0: the light sits on the shadow origin; NaN: a NaN t or normal out of a singular instance), gets the bounce stage's dead
-// ray (t_max = -1, misses everything, costs no traversal) and the byte 0.  The ray is never stored, so only the kernel can apply that gate.
+// that is not > 0 (0: the light sits on the shadow origin; NaN: a NaN t or normal out of a singular instance), gets the dead ray and the
+// byte 0.  The ray is never stored, so only the kernel can apply that gate.
 struct ShadowSource {
     const SceneView& v;
     const RcRay* rays;
@@ -573,10 +579,10 @@ struct ShadowSource {
     __device__ inline RcRay operator()(uint64_t j) const {
         const uint32_t i = (uint32_t)j / n_lights, l = (uint32_t)j - i * n_lights;  // (n * n_lights < 2^32)
         const RcHit h = hits[i];
-        if (!h.hit) return RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
+        if (!h.hit) return RC_DEAD_RAY;
         const float* lp = lights + 3u * (size_t)l;
         const RcRay s = shadow_ray(v, load_ray(rays, i), h, mk3(lp[0], lp[1], lp[2]), bias);
-        return s.tmax > 0.0f ? s : RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
+        return s.tmax > 0.0f ? s : RC_DEAD_RAY;
     }
     static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
 };
@@ -649,12 +655,10 @@ __global__ void k_soft_shadow_rays(SceneView v, SoftShadowParams q, uint64_t tot
     for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t il = (uint32_t)j / q.samples, s = (uint32_t)j - il * q.samples;  // (total < 2^32)
         const uint32_t i = il / q.n_lights, l = il - i * q.n_lights;
-        RcRay sr{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+        RcRay sr = RC_DUMMY_RAY;
         const RcHit h = q.hits[i];
         if (h.hit) sr = soft_shadow_ray(v, q, i, l, s, q.rays[i], h);
-        float4* o4 = reinterpret_cast<float4*>(out + j);
-        o4[0] = make_float4(sr.ox, sr.oy, sr.oz, sr.tmin);
-        o4[1] = make_float4(sr.dx, sr.dy, sr.dz, sr.tmax);
+        store_ray(out, j, sr);
     }
 }
 // The fused driver: work item j = (i * n_lights + l) * samples + s, so the samples of a (hit, light) pair and the lights of a hit sit in
@@ -663,12 +667,14 @@ struct SoftShadowSource {
     const SceneView& v;
     SoftShadowParams q;
     __device__ inline RcRay operator()(uint64_t j) const {
+        // (the stage kernel's split and ShadowSource's gate, written out: through a shared function -- the item returned as a struct or through
+        // references, the gate by reference or by value -- this job's three shells come out of the compiler differently)
         const uint32_t il = (uint32_t)j / q.samples, s = (uint32_t)j - il * q.samples;  // (n * n_lights * samples < 2^32)
         const uint32_t i = il / q.n_lights, l = il - i * q.n_lights;
         const RcHit h = q.hits[i];
-        if (!h.hit) return RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
+        if (!h.hit) return RC_DEAD_RAY;
         const RcRay sr = soft_shadow_ray(v, q, i, l, s, load_ray(q.rays, i), h);
-        return sr.tmax > 0.0f ? sr : RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
+        return sr.tmax > 0.0f ? sr : RC_DEAD_RAY;
     }
     static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
 };
@@ -726,7 +732,7 @@ __global__ void k_bounce_rays(SceneView v, const RcRay* rays, const RcHit* hits,
             else if (wrap) { s = src[i % c]; k = i / c; }
             else s = src[i];
         }
-        RcRay b{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f};
+        RcRay b = RC_DEAD_RAY;
         uint32_t path_id = 0xFFFFFFFFu;  // RC_INVALID_ID
         if (live) {
             const RcHit h = hits[s];
@@ -742,9 +748,7 @@ __global__ void k_bounce_rays(SceneView v, const RcRay* rays, const RcHit* hits,
                 b = RcRay{o.x, o.y, o.z, 0.f, d.x, d.y, d.z, INFINITY};
             }
         }
-        float4* q = reinterpret_cast<float4*>(out + i);
-        q[0] = make_float4(b.ox, b.oy, b.oz, b.tmin);
-        q[1] = make_float4(b.dx, b.dy, b.dz, b.tmax);
+        store_ray(out, i, b);
         if (path_out) path_out[i] = path_id;
     }
 }
@@ -792,14 +796,20 @@ __global__ void k_scatter_hit_indices(const uint32_t* flags, const uint32_t* pos
 
 }  // namespace
 
+// A wavefront stage: a grid-stride kernel over n items in 256-thread workgroups, at most kPerCu per CU.  kReadsScene: the kernel reads scene
+// memory, so the scene remembers the stream's launch (rc_note_stage_launch, below).
+template <uint32_t kPerCu = 8, bool kReadsScene = true, class Kernel, class... Args>
+static void launch_stage(rc_scene* s, hipStream_t stream, uint64_t n, Kernel kernel, Args... args) {
+    if (n == 0) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cus * kPerCu);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, args...);
+    RC_HIP(hipGetLastError());
+    if (kReadsScene) rc_note_stage_launch(s, stream);
+}
+
 void rc_launch_ray_grid(rc_scene* s, const float viewdir[3], uint32_t grid, RcRay* d_rays, hipStream_t stream) {
     rc_ensure_world_bound(s, stream);  // the grid is laid out from the world bound: after an asynchronous refit it is read back first
-    GridParams g = grid_params(s->root_min, s->root_max, viewdir, grid);
-    uint64_t n = (uint64_t)grid * grid;
-    uint32_t blocks = (uint32_t)std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)s->n_cus * 8);
-    if (blocks == 0) return;
-    hipLaunchKernelGGL(k_ray_grid, dim3(blocks), dim3(kBlock), 0, stream, g, d_rays);
-    RC_HIP(hipGetLastError());
+    launch_stage<8, false>(s, stream, (uint64_t)grid * grid, k_ray_grid, grid_params(s->root_min, s->root_max, viewdir, grid), d_rays);
 }
 
 // n_dirs x grid^2 rays from device-resident directions and the TLAS root as it is when the kernel runs: no host copy of the bound is read.
@@ -812,9 +822,10 @@ void rc_launch_ray_grid_dirs(rc_scene* s, const float* d_dirs, uint32_t n_dirs, 
     rc_note_stage_launch(s, stream);
 }
 
-static void check_buffer_range(rc_scene* s) {
+static rc_scene* range_checked(rc_scene* s) {
     if ((uint64_t)(s->n_flat_nodes + s->n_tlas_nodes) * 64u >= (1ull << 32))
         throw RcError(1, "driver kernels address nodes with 32-bit buffer offsets: scenes above 64 M nodes are not supported yet");
+    return s;
 }
 
 // Scratch counters of the launch's totals kernel: launches on one stream are ordered and share an area; another stream gets its own (up to
@@ -836,9 +847,30 @@ static unsigned long long* rc_totals_scratch(RcLaunchGuard& g, size_t words) {
 }
 
 namespace {
-// What every driver launch on the persistent phased core shares.  Construction takes the launch guard, picks the shape the scene gets (plain
-// 256 threads, top level in LDS, partial tops in LDS) and its grid, and fills the view and the persistent arguments; run() adds the shape's
-// own arguments and launches that shape's shell for the job.  The caller keeps what is its own around guard.start() / run() / guard.finish().
+// The launch's scratch: `rows` copy histograms of Word counters, zeroed on the launch's stream, and room for n_params GridParams behind them.
+template <class Word>
+struct HistScratch {
+    Word* hist;
+    GridParams* params;
+};
+template <class Word>
+HistScratch<Word> rc_hist_scratch(RcLaunchGuard& g, CopyHist h, uint32_t rows = 1, uint32_t n_params = 0) {
+    const size_t hist_bytes = sizeof(Word) * (size_t)(rows * h.words());
+    unsigned char* p = reinterpret_cast<unsigned char*>(rc_totals_scratch(g, (hist_bytes + sizeof(GridParams) * n_params + 7u) / 8u));
+    RC_HIP(hipMemsetAsync(p, 0, hist_bytes, g.stream));
+    return HistScratch<Word>{reinterpret_cast<Word*>(p), reinterpret_cast<GridParams*>(p + hist_bytes)};
+}
+template <class Word, class Rule>
+void rc_hist_fold(hipStream_t stream, const Word* hist, CopyHist h, uint32_t n, Rule rule) {
+    const uint64_t items = (uint64_t)rule.rows() * n;
+    if (items) hipLaunchKernelGGL((k_hist_fold<Word, Rule>), dim3((uint32_t)((items + 255u) / 256u)), dim3(256), 0, stream, hist, h, n, rule);
+}
+struct Nothing { void operator()() const {} };
+
+// What every driver launch on the persistent phased core shares.  Construction checks the node count (before the launch guard takes anything),
+// takes the guard, picks the shape the scene gets (plain 256 threads, top level in LDS, partial tops in LDS) and its grid, and fills the view and
+// the persistent arguments.  The caller reserves its scratch and enqueues what must run first; go<ANY>(job, between, behind) starts the guard,
+// runs `between`, launches the job's shell of that shape (run() adds the shape's own arguments), runs `behind` (the fold) and finishes the guard.
 struct DriverLaunch {
     RcLaunchGuard guard;
     rc_scene* s;
@@ -848,7 +880,7 @@ struct DriverLaunch {
     SceneView v;
     PersistArgs p;
     DriverLaunch(rc_scene* scene, hipStream_t st, uint64_t n_items)
-        : guard(scene, st), s(scene), stream(st), partial(rc_partial_driver_ok(scene)), lds(partial || rc_lds_driver_ok(scene)),
+        : guard(range_checked(scene), st), s(scene), stream(st), partial(rc_partial_driver_ok(scene)), lds(partial || rc_lds_driver_ok(scene)),
           blocks(lds ? rc_grid_blocks(scene, n_items, kMidBlock, LdsShape<>::kBlocksPerCu) : rc_grid_blocks(scene, n_items, kBlock, PlainShape<>::kBlocksPerCu)) {
         const uint32_t threads = blocks * (lds ? (uint32_t)kMidBlock : (uint32_t)kBlock);
         v = rc_scene_view(guard, threads);
@@ -856,6 +888,7 @@ struct DriverLaunch {
     }
     template <bool ANY, class Job>
     void run(const Job& job) {
+        if (ANY && s->opt.entry_cull < 2) v.entry_cull = 0u;  // any_hit: the rule of rc_launch_trace
         if (partial) {
             rc_partial_driver_args(s, p);
             rc_ensure_dynamic_lds(s, reinterpret_cast<const void*>(&k_driver_partial<ANY, Job>), PartialShape<>::kLdsBytes);
@@ -867,31 +900,37 @@ struct DriverLaunch {
         } else
             hipLaunchKernelGGL((k_driver<ANY, Job>), dim3(blocks), dim3(kBlock), 0, stream, v, p, job);
     }
+    template <bool ANY, class Job, class Between = Nothing, class Behind = Nothing>
+    void go(const Job& job, Between between = Between(), Behind behind = Behind()) {
+        guard.start();
+        between();
+        run<ANY>(job);
+        behind();
+        guard.finish();
+    }
 };
 }  // namespace
 
 void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, uint64_t ray_begin, uint64_t ray_end,
                             float* d_counts, hipStream_t stream) {
     if (ray_end <= ray_begin) return;
-    check_buffer_range(s);
     rc_ensure_world_bound(s, stream);
     GridParams g = grid_params(s->root_min, s->root_max, viewdir, grid);
     DriverLaunch launch(s, stream, ray_end - ray_begin);
-    const uint32_t np = s->n_flat_prims, n8 = (np + 7u) / 8u;
-    uint32_t* scratch = reinterpret_cast<uint32_t*>(rc_totals_scratch(launch.guard, ((size_t)kHistCopies * 8u * n8 + 1u) / 2u));  // private copies of the histogram (HistogramSink)
-    RC_HIP(hipMemsetAsync(scratch, 0, sizeof(uint32_t) * kHistCopies * 8u * n8, stream));
-    launch.guard.start();
-    // a repeated get_illumination (same grid: item i is the same cell every time) claims the chunks that held long rays last time first
-    if (!launch.guard.capturing && ray_begin == 0) {
-        // (the rays are generated: the batch is described by its view direction and grid size -- another direction is another batch)
-        const float diag = sqrtf((s->root_max[0] - s->root_min[0]) * (s->root_max[0] - s->root_min[0]) + (s->root_max[1] - s->root_min[1]) * (s->root_max[1] - s->root_min[1]) +
-                                 (s->root_max[2] - s->root_min[2]) * (s->root_max[2] - s->root_min[2]));
-        const float stand_in[8] = {(float)grid * diag, 0.f, 0.f, 0.f, g.dir[0], g.dir[1], g.dir[2], 0.f};
-        rc_cost_order_setup(launch.guard, ray_end, 2, launch.p.claim, nullptr, stand_in);
-    }
-    launch.run<false>(IlluminationJob{g, ray_begin, scratch, n8});
-    if (np) hipLaunchKernelGGL(k_illumination_fold, dim3((np + 255) / 256), dim3(256), 0, stream, scratch, n8, np, d_counts);
-    launch.guard.finish();
+    const uint32_t np = s->n_flat_prims;
+    const CopyHist h = CopyHist::of(np);
+    uint32_t* scratch = rc_hist_scratch<uint32_t>(launch.guard, h).hist;
+    launch.go<false>(
+        IlluminationJob{g, ray_begin, scratch, h},
+        [&] {  // a repeated get_illumination (same grid: item i is the same cell every time) claims the chunks that held long rays last time first
+            if (launch.guard.capturing || ray_begin != 0) return;
+            // (the rays are generated: the batch is described by its view direction and grid size -- another direction is another batch)
+            const float diag = sqrtf((s->root_max[0] - s->root_min[0]) * (s->root_max[0] - s->root_min[0]) + (s->root_max[1] - s->root_min[1]) * (s->root_max[1] - s->root_min[1]) +
+                                     (s->root_max[2] - s->root_min[2]) * (s->root_max[2] - s->root_min[2]));
+            const float stand_in[8] = {(float)grid * diag, 0.f, 0.f, 0.f, g.dir[0], g.dir[1], g.dir[2], 0.f};
+            rc_cost_order_setup(launch.guard, ray_end, 2, launch.p.claim, nullptr, stand_in);
+        },
+        [&] { rc_hist_fold(stream, scratch, h, np, FoldF32Saturating{{}, d_counts}); });
 }
 
 // get_illumination for n_dirs device-resident directions, ACCUMULATED into d_counts[d * row_stride + (meta - 1)] (u32).  The directions are
@@ -902,25 +941,19 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
 // host wait and may be captured --, the launch counts, the fold adds.  Items are claimed in natural order: the plan is fixed at call time,
 // the rays are not known before the kernels run.  grid^2 < 2^32 (checked by the caller).
 void rc_launch_illumination_dirs(rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, uint32_t* d_counts, uint64_t row_stride, hipStream_t stream) {
-    const uint32_t np = s->n_flat_prims, n8 = (np + 7u) / 8u;
+    const uint32_t np = s->n_flat_prims;
+    const CopyHist h = CopyHist::of(np);
     const uint64_t cells = (uint64_t)grid * grid;
     if (n_dirs == 0 || cells == 0 || np == 0) return;
-    check_buffer_range(s);
-    const uint64_t dir_bytes = sizeof(uint32_t) * (uint64_t)kHistCopies * 8u * n8;
+    const uint64_t dir_bytes = sizeof(uint32_t) * h.words();
     const uint64_t group = std::min<uint64_t>(n_dirs, std::min<uint64_t>(((1ull << 32) - 1u) / cells, std::max<uint64_t>((uint64_t)s->opt.illum_scratch_bytes / dir_bytes, 1)));
     for (uint32_t d0 = 0; d0 < n_dirs; d0 += (uint32_t)group) {
         const uint32_t nd = (uint32_t)std::min<uint64_t>(group, n_dirs - d0);
         DriverLaunch launch(s, stream, nd * cells);
-        const size_t hist_bytes = (size_t)(nd * dir_bytes);  // (a multiple of 16: the grids sit behind the copies)
-        uint32_t* scratch = reinterpret_cast<uint32_t*>(rc_totals_scratch(launch.guard, (hist_bytes + sizeof(GridParams) * nd + 7u) / 8u));
-        GridParams* params = reinterpret_cast<GridParams*>(reinterpret_cast<unsigned char*>(scratch) + hist_bytes);
-        RC_HIP(hipMemsetAsync(scratch, 0, hist_bytes, stream));
-        hipLaunchKernelGGL(k_grid_params, dim3((nd + 63u) / 64u), dim3(64), 0, stream, s->tlas_nodes.p, s->n_tlas_nodes, d_dirs + 3u * (size_t)d0, nd, grid, params);
-        launch.guard.start();
-        launch.run<false>(IlluminationDirsJob{params, (uint32_t)cells, scratch, n8});
-        const uint64_t fold_items = (uint64_t)nd * np;
-        hipLaunchKernelGGL(k_illumination_dirs_fold, dim3((uint32_t)((fold_items + 255u) / 256u)), dim3(256), 0, stream, scratch, n8, np, nd, d_counts + (uint64_t)d0 * row_stride, row_stride);
-        launch.guard.finish();
+        const HistScratch<uint32_t> scratch = rc_hist_scratch<uint32_t>(launch.guard, h, nd, nd);  // the group's grids sit behind its histograms
+        hipLaunchKernelGGL(k_grid_params, dim3((nd + 63u) / 64u), dim3(64), 0, stream, s->tlas_nodes.p, s->n_tlas_nodes, d_dirs + 3u * (size_t)d0, nd, grid, scratch.params);
+        launch.go<false>(IlluminationDirsJob{scratch.params, (uint32_t)cells, scratch.hist, h}, Nothing(),
+                         [&] { rc_hist_fold(stream, scratch.hist, h, np, FoldAddU32Rows{nd, d_counts + (uint64_t)d0 * row_stride, row_stride}); });
     }
 }
 
@@ -969,13 +1002,9 @@ void rc_launch_view_factors(rc_scene* s, uint32_t rays_per_triangle, uint64_t se
     if (src_end > s->n_flat_prims) src_end = s->n_flat_prims;
     if (ray_end > rays_per_triangle) ray_end = rays_per_triangle;
     if (src_begin >= src_end || ray_begin >= ray_end) return;
-    check_buffer_range(s);
     uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
     const uint32_t* order = (flags & 2u) ? s->vf_order.p : nullptr;  // RC_VF_SOURCES_BY_METADATA: the caller has called rc_ensure_vf_order, once per job
-    DriverLaunch launch(s, stream, total);
-    launch.guard.start();
-    launch.run<false>(ViewFactorJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, d_matrix, row_stride, col_stride, row_offset, flags, order});
-    launch.guard.finish();
+    DriverLaunch(s, stream, total).go<false>(ViewFactorJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, d_matrix, row_stride, col_stride, row_offset, flags, order});
 }
 
 // Totals of rays [ray_begin, ray_end) of the sources with flat indices [src_begin, src_end), ACCUMULATED into d_received / d_emitted
@@ -985,19 +1014,14 @@ void rc_launch_vf_totals(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
     if (src_end > s->n_flat_prims) src_end = s->n_flat_prims;
     if (ray_end > rays_per_triangle) ray_end = rays_per_triangle;
     if (src_begin >= src_end || ray_begin >= ray_end || (!d_received && !d_emitted)) return;
-    check_buffer_range(s);
     const uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
     DriverLaunch launch(s, stream, total);
-    const uint32_t np = s->n_flat_prims, n8 = (np + 7u) / 8u;
-    unsigned long long* scratch = nullptr;
-    if (d_received) {  // the private copies of the hot vector (see ViewFactorTotalsSink): one scratch area per stream, launches on one stream are ordered
-        scratch = rc_totals_scratch(launch.guard, (size_t)kTotalsCopies * 8u * n8);
-        RC_HIP(hipMemsetAsync(scratch, 0, sizeof(unsigned long long) * kTotalsCopies * 8u * n8, stream));
-    }
-    launch.guard.start();
-    launch.run<false>(ViewFactorTotalsJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, scratch, n8, d_emitted});
-    if (d_received) hipLaunchKernelGGL(k_vf_totals_fold, dim3((np + 255) / 256), dim3(256), 0, stream, scratch, n8, np, d_received);
-    launch.guard.finish();
+    const uint32_t np = s->n_flat_prims;
+    const CopyHist h = CopyHist::of(np);
+    // the private copies of the hot vector (see ViewFactorTotalsSink): one scratch area per stream, launches on one stream are ordered
+    unsigned long long* scratch = d_received ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
+    launch.go<false>(ViewFactorTotalsJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, scratch, h, d_emitted}, Nothing(),
+                     [&] { if (d_received) rc_hist_fold(stream, scratch, h, np, FoldAddU64{{}, d_received}); });
 }
 
 // Kernels outside RcLaunchGuard that read scene memory on a caller's stream (the wavefront stages): remember the stream's latest such
@@ -1032,19 +1056,11 @@ void rc_launch_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t src, uint32
 }
 
 void rc_launch_hit_points(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, float* d_points, float* d_normals, hipStream_t stream) {
-    if (n == 0) return;
-    uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cus * 8);
-    hipLaunchKernelGGL(k_hit_points, dim3(blocks), dim3(256), 0, stream, rc_scene_view_static(s), d_rays, d_hits, n, d_points, d_normals);
-    RC_HIP(hipGetLastError());
-    rc_note_stage_launch(s, stream);
+    launch_stage(s, stream, n, k_hit_points, rc_scene_view_static(s), d_rays, d_hits, n, d_points, d_normals);
 }
 
 void rc_launch_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float light[3], float bias, RcRay* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cus * 8);
-    hipLaunchKernelGGL(k_shadow_rays, dim3(blocks), dim3(256), 0, stream, rc_scene_view_static(s), d_rays, d_hits, n, light[0], light[1], light[2], bias, d_out);
-    RC_HIP(hipGetLastError());
-    rc_note_stage_launch(s, stream);
+    launch_stage(s, stream, n, k_shadow_rays, rc_scene_view_static(s), d_rays, d_hits, n, light[0], light[1], light[2], bias, d_out);
 }
 
 // One persistent any_hit launch over the n * n_lights (hit, light) items (ShadowSource / VisibilitySink); natural claim order -- the rays are
@@ -1053,12 +1069,7 @@ void rc_launch_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* 
                                  uint8_t* d_visible, hipStream_t stream) {
     const uint64_t total = n * n_lights;
     if (total == 0) return;
-    check_buffer_range(s);
-    DriverLaunch launch(s, stream, total);
-    if (s->opt.entry_cull < 2) launch.v.entry_cull = 0u;  // any_hit: the rule of rc_launch_trace
-    launch.guard.start();
-    launch.run<true>(ShadowJob{d_rays, d_hits, d_lights, n_lights, bias, d_visible});
-    launch.guard.finish();
+    DriverLaunch(s, stream, total).go<true>(ShadowJob{d_rays, d_hits, d_lights, n_lights, bias, d_visible});
 }
 
 // The soft-shadow pair (SoftShadowParams): the composed stage writes the n * n_lights * samples rays; the driver is one persistent any_hit
@@ -1071,35 +1082,22 @@ void rc_launch_soft_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d
                                 uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
                                 float bias, RcRay* d_out, hipStream_t stream) {
     const uint64_t total = n * n_lights * samples;
-    if (total == 0) return;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((total + 255) / 256, (uint64_t)s->n_cus * 8);
-    hipLaunchKernelGGL(k_soft_shadow_rays, dim3(blocks), dim3(256), 0, stream, rc_scene_view_static(s),
-                       soft_shadow_params(d_rays, d_hits, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias), total, d_out);
-    RC_HIP(hipGetLastError());
-    rc_note_stage_launch(s, stream);
+    launch_stage(s, stream, total, k_soft_shadow_rays, rc_scene_view_static(s),
+                 soft_shadow_params(d_rays, d_hits, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias), total, d_out);
 }
 void rc_launch_soft_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
                                       uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in,
                                       uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream) {
     const uint64_t total = n * n_lights * samples;
     if (total == 0) return;
-    check_buffer_range(s);
-    DriverLaunch launch(s, stream, total);
-    if (s->opt.entry_cull < 2) launch.v.entry_cull = 0u;  // any_hit: the rule of rc_launch_trace
-    launch.guard.start();
-    launch.run<true>(SoftShadowJob{soft_shadow_params(d_rays, d_hits, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias), d_count});
-    launch.guard.finish();
+    DriverLaunch(s, stream, total).go<true>(SoftShadowJob{soft_shadow_params(d_rays, d_hits, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias), d_count});
 }
 
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                            const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n, uint64_t seed, uint32_t bounce, float bias,
                            RcRay* d_out, hipStream_t stream) {
-    if (n == 0) return;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cus * 8);
-    hipLaunchKernelGGL(k_bounce_rays, dim3(blocks), dim3(256), 0, stream, rc_scene_view_static(s), d_rays, d_hits, d_src, d_src_count, wrap ? 1 : 0,
-                       d_path_in, d_path_out, path_base, (uint32_t)n, (uint32_t)seed, (uint32_t)(seed >> 32), 0x424E0000u | bounce, bias, d_out);
-    RC_HIP(hipGetLastError());
-    rc_note_stage_launch(s, stream);
+    launch_stage(s, stream, n, k_bounce_rays, rc_scene_view_static(s), d_rays, d_hits, d_src, d_src_count, wrap ? 1 : 0, d_path_in, d_path_out, path_base,
+                 (uint32_t)n, (uint32_t)seed, (uint32_t)(seed >> 32), 0x424E0000u | bounce, bias, d_out);
 }
 
 void rc_launch_primary_rays(rc_scene* s, const float pos[3], const float right[3], const float up[3], const float forward[3], float half_width,
@@ -1111,9 +1109,7 @@ void rc_launch_primary_rays(rc_scene* s, const float pos[3], const float right[3
     c.half_width = half_width; c.half_height = half_height;
     c.width = width; c.height = height; c.samples = samples; c.jitter = jitter ? 1u : 0u;
     c.k0 = (uint32_t)seed; c.k1 = (uint32_t)(seed >> 32);
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cus * 16);
-    hipLaunchKernelGGL(k_primary_rays, dim3(blocks), dim3(256), 0, stream, c, n, d_out);
-    RC_HIP(hipGetLastError());
+    launch_stage<16, false>(s, stream, n, k_primary_rays, c, n, d_out);  // (reads no scene memory)
 }
 
 // Indices of the rays that hit, ascending, and their number: the compaction step between wavefront stages (the reference's

@@ -569,18 +569,21 @@ __device__ inline RcRay load_ray(const RcRay* rays, uint64_t i) {
     float4 a = q[0], b = q[1];
     return RcRay{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 }
-
+__device__ __forceinline__ void store_ray(RcRay* out, uint64_t i, const RcRay r) {  // (by value: by reference the stage kernels schedule differently)
+    float4* q = reinterpret_cast<float4*>(out + i);
+    q[0] = make_float4(r.ox, r.oy, r.oz, r.tmin);
+    q[1] = make_float4(r.dx, r.dy, r.dz, r.tmax);
+}
+// The placeholder rays (o = 0, d = (0,0,1)).  Macros: a use IS the literal -- as functions or constexpr objects they change the shadow shells' registers.
+#define RC_DUMMY_RAY RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 0.f}   // the reference's placeholder for a slot whose ray missed: t_max = 0 (docs/src/wavefront-renderer.jl:288-333)
+#define RC_DEAD_RAY RcRay{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, -1.f}   // [t_min, t_max] = [0, -1]: misses everything and costs no traversal
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 // Ray source / hit sink of the plain trace entry points: RTRay array in, RTHitResult array out (:2010-2023).
 struct ArraySource {
     const RcRay* rays;
-    __device__ inline RcRay operator()(uint64_t i) const {
-        const float4* q = reinterpret_cast<const float4*>(rays + i);
-        float4 a = q[0], b = q[1];
-        return RcRay{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    }
+    __device__ inline RcRay operator()(uint64_t i) const { return load_ray(rays, i); }
     // Round 6: a wave that has just claimed the range [first, end) touches one dword of every 64-byte line of it (lane L: rays first + 2 L and
     // first + 2 L + 1; 64 lanes = 128 rays = a whole chunk), in the same memory round trip as its first ray loads.  A batch traced for the first
     // time is read from HBM (through cold TLB entries), and a chunk is consumed in 3-4 refills of 20-64 rays -- each of which used to pay that
