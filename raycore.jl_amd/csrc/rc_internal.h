@@ -68,26 +68,14 @@ struct DevBuf {  // owning device buffer, grow-only reuse
 // "Is the last user of this per-stream resource done?" is asked of an event the LIBRARY recorded behind that user, never of the caller's
 // stream handle (hipStreamQuery on a stream another thread is capturing into invalidates the capture, and on a destroyed
 // stream it fails, so an entry keyed by a dead stream was never handed on).
+// The event is the closing event the launch records anyway (its counter slot's t1, which lives as long as the scene), not one of the
+// resource's own: an event record is a packet of its own on the queue, ~3 us between two kernels.  The slot's next
+// launch records t1 again; that launch runs behind this one (same stream, or it waited for t1 first: RcLaunchGuard), so "t1 is done"
+// still implies "this launch is done" -- the answer can only come later than with an event of its own, never earlier.
 struct RcEvent {
-    hipEvent_t e = nullptr;
-    bool recorded = false, owned = false;
-    RcEvent() = default;
-    RcEvent(const RcEvent&) = delete;
-    RcEvent& operator=(const RcEvent&) = delete;
-    RcEvent(RcEvent&& o) noexcept : e(o.e), recorded(o.recorded), owned(o.owned) { o.e = nullptr; o.recorded = o.owned = false; }
-    RcEvent& operator=(RcEvent&& o) noexcept { if (this != &o) { drop(); e = o.e; recorded = o.recorded; owned = o.owned; o.e = nullptr; o.recorded = o.owned = false; } return *this; }
-    ~RcEvent() { drop(); }
-    void drop() { if (e && owned) (void)hipEventDestroy(e); e = nullptr; recorded = owned = false; }
-    void record(hipStream_t st) {  // an event of its own behind the stream's work so far
-        if (e && !owned) drop();
-        if (!e) { if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); e = nullptr; return; } owned = true; }
-        if (hipEventRecord(e, st) == hipSuccess) recorded = true; else (void)hipGetLastError();
-    }
-    // ... or the closing event the launch recorded anyway (its counter slot's t1, which lives as long as the scene): one event record per
-    // launch fewer for each resource -- an event record is a packet of its own on the queue, ~3 us between two kernels.  The slot's next
-    // launch records t1 again; that launch runs behind this one (same stream, or it waited for t1 first: RcLaunchGuard), so "t1 is done"
-    // still implies "this launch is done" -- the answer can only come later than with an event of its own, never earlier.
-    void follow(hipEvent_t closing) { drop(); e = closing; recorded = closing != nullptr; }
+    hipEvent_t e = nullptr;  // borrowed: the scene owns it
+    bool recorded = false;
+    void follow(hipEvent_t closing) { e = closing; recorded = closing != nullptr; }
     bool idle() const {  // never blocks
         if (!recorded) return true;
         const hipError_t q = hipEventQuery(e);

@@ -191,25 +191,20 @@ RcLaunchGuard::RcLaunchGuard(rc_scene* scene, hipStream_t st) : s(scene), stream
     if (s->opt.stats) RC_HIP(hipMemsetAsync(rc_stats_words(s), 0, kStatsWords * sizeof(unsigned long long), stream));
 }
 
-static int rc_event_mode() {  // dev (tools/archive/event_probe.py): RC_EVENT_MODE = 0 product, 1 hipEventDisableSystemFence on t1 too, 2 no t0 event, 3 no events at all (single-stream runs only), 4 system fence on t0 as well (rounds 3-4)
-    static const int mode = [] { const char* e = getenv("RC_EVENT_MODE"); return e ? atoi(e) : 0; }();
-    return mode;
-}
 void RcLaunchGuard::start() {
     if (capturing) return;
     rc_scene::LaunchSlot& ls = s->slots[slot];
     if (!ls.t0) {
         // t0 only marks a time in front of the kernel: nothing is published by it, so it skips the system-scope fence (0.5 % of a back-to-back
         // launch sequence, profiles/r05_launch_fixed_costs.txt); t1 keeps the default -- the host reads pinned words behind it
-        RC_HIP(hipEventCreateWithFlags(&ls.t0, rc_event_mode() == 4 ? hipEventDefault : hipEventDisableSystemFence));
-        RC_HIP(hipEventCreateWithFlags(&ls.t1, rc_event_mode() == 1 ? hipEventDisableSystemFence : hipEventDefault));
+        RC_HIP(hipEventCreateWithFlags(&ls.t0, hipEventDisableSystemFence));
+        RC_HIP(hipEventCreateWithFlags(&ls.t1, hipEventDefault));
     }
-    if (rc_event_mode() < 2) RC_HIP(hipEventRecord(ls.t0, stream));
+    RC_HIP(hipEventRecord(ls.t0, stream));
 }
 
 void RcLaunchGuard::bind() {  // instead of start(): the launch's kernel carries the events itself (launch_variant)
     if (capturing) return;
-    if (rc_event_mode() >= 2) { start(); return; }  // (dev modes measure the event packets)
     rc_scene::LaunchSlot& ls = s->slots[slot];
     if (!ls.t0) {
         RC_HIP(hipEventCreateWithFlags(&ls.t0, hipEventDisableSystemFence));
@@ -222,10 +217,10 @@ void RcLaunchGuard::finish() {
     RC_HIP(hipGetLastError());
     if (capturing) return;  // a captured launch has no events of its own: the graph orders it, and its duration is the replay's business
     rc_scene::LaunchSlot& ls = s->slots[slot];
-    if (rc_event_mode() < 3 && !carried) RC_HIP(hipEventRecord(ls.t1, stream));
-    // the per-stream resources this launch used are busy until here (asked by the next stream that wants to take one over)
-    const bool closed = rc_event_mode() < 3;  // (they follow the launch's closing event instead of recording their own)
-    for (int i = 0; i < n_busy; ++i) { if (closed) busy[i]->follow(ls.t1); else busy[i]->record(stream); }
+    if (!carried) RC_HIP(hipEventRecord(ls.t1, stream));
+    // the per-stream resources this launch used are busy until here (asked by the next stream that wants to take one over): they follow the
+    // launch's closing event instead of recording one of their own
+    for (int i = 0; i < n_busy; ++i) busy[i]->follow(ls.t1);
     ls.stream = stream;
     ls.recorded = true;
     ls.seq = ++s->timing_seq;
@@ -437,17 +432,11 @@ static void launch_variant(RcLaunchGuard& g, int64_t kernel, const TraceArgs& a,
 //   (A first-launch PREDICTOR -- claim order from the number of top-of-tree boxes each chunk's middle ray passes -- was built and measured in
 //   round 4: worth 5-12 % of a 1 M-ray launch, and the small kernels it needs cost as much: profiles/r04_first_launch_predictor.txt.  Not kept.)
 // hist[kHistScale + 4 slot]: [0], [1] = the threshold / the top of the scale the slot's latest recording launch worked with; [2], [3] = the pair its next one will.
-// dev knobs (tools/probes/build_variants.sh): the number of cost classes of the rebuilt order and the share of the chunks the reporting
-// threshold aims at.  Round 5 (tools/probes/order_quality_probe.py, docs/EXPERIMENTS.md): 10 / 16 / 26 / 31 classes order equally well; the
+// The number of cost classes of the rebuilt order and the share of the chunks (per cent) the reporting threshold aims at.  Round 5
+// (tools/probes/order_quality_probe.py, docs/EXPERIMENTS.md): 10 / 16 / 26 / 31 classes order equally well; the
 // share matters -- with 30-70 % of the chunks reporting (rounds 3-4: 10-40 %) the same batches run 3-8 % faster, because the chunks below
 // the threshold are claimed in natural order BEHIND the reported ones and most of a batch's medium-long chunks were among them.
-#ifndef RC_ORDER_CLASSES
-#define RC_ORDER_CLASSES 10
-#endif
-#ifndef RC_ORDER_RAISE_PCT
-#define RC_ORDER_RAISE_PCT 70
-#define RC_ORDER_LOWER_PCT 30
-#endif
+constexpr int kOrderClasses = 10, kOrderRaisePct = 70, kOrderLowerPct = 30;
 // Close repeats (order_select): the largest direction term -- mean over the 64 samples of |dd|^2 / |d|^2 -- at which a launch with the slot's
 // own origins still continues the slot's history.  Jitter inside a pixel gives 4e-8 at 2048^2, 2.4e-7 at 1280 x 800, 2.7e-6 at 256^2 (45
 // degrees); a camera turned in place by 0.15 / 0.2 / 5 degrees 6.7e-6 / 1.2e-5 / 7.3e-3.  tools/probes/close_repeat_predictor.py
@@ -455,7 +444,7 @@ static void launch_variant(RcLaunchGuard& g, int64_t kernel, const TraceArgs& a,
 // longest chunks to the end of the launch as the order learned from another jitter seed of the same view does; from 1.2e-5 on, more.
 constexpr float kCloseDirMax = 6e-6f;
 namespace {
-constexpr int kOrderThreads = 256, kOrderPerThread = 4, kOrderTile = kOrderThreads * kOrderPerThread, kOrderClasses = RC_ORDER_CLASSES, kOrderMaxBlocks = 256;
+constexpr int kOrderThreads = 256, kOrderPerThread = 4, kOrderTile = kOrderThreads * kOrderPerThread, kOrderMaxBlocks = 256;
 constexpr int kOrderPacked = (kOrderClasses + 4) / 5;  // u64 words of 12-bit per-class counters (k_order_scatter)
 static_assert(kOrderClasses + 1 <= 32, "k_order_scatter sums the blocks' counts with 32 threads per block group");
 static_assert(rc_scene::ChunkHistory::kHeaderWords == (uint32_t)kHistHeaderWords, "rc_internal.h repeats the size of a header copy");
@@ -564,8 +553,8 @@ __global__ __launch_bounds__(kOrderThreads) void k_order_scatter(uint32_t* cost_
         uint32_t* scale = hist + kHistScale + 4 * slot;  // the scale of the slot's NEXT recording launch
         const uint32_t thr = scale[0], reported = n_chunks - unreported;
         uint32_t next = thr;
-        if (reported * 100ull > (unsigned long long)n_chunks * RC_ORDER_RAISE_PCT) next += (next >> 2) + 1u;        // more than this share of the chunks reported: raise the bar
-        else if (reported * 100ull < (unsigned long long)n_chunks * RC_ORDER_LOWER_PCT && next > 2u) next -= next >> 2;  // fewer than this: lower it
+        if (reported * 100ull > (unsigned long long)n_chunks * kOrderRaisePct) next += (next >> 2) + 1u;        // more than this share of the chunks reported: raise the bar
+        else if (reported * 100ull < (unsigned long long)n_chunks * kOrderLowerPct && next > 2u) next -= next >> 2;  // fewer than this: lower it
         scale[2] = next;
         scale[3] = mx > next ? mx : next + 8u;  // the longest lifetime just seen scales the next recording's classes
         hist[kHistPending + slot] = 0u;

@@ -355,13 +355,8 @@ struct LaneStackP {
     // slot of the lane's own column, and a pop after a push reads at most the slot just written.  push and pop above test `top < limit` per
     // lane, which the compiler turns into an exec-mask save / restore and a skip branch per site and pass -- for a spill path that is almost
     // never taken.  phased_trace keeps the lanes at or beyond the LDS depth out of its interior loop and serves them with push / pop in a pass
-    // of their own: LDS, the spill area and the status word see the same bytes either way.
-    // -DRC_STACK_BRANCHY (dev, tools/ab_build.sh): push / pop everywhere, the form before docs/EXPERIMENTS.md "stack fast path".
-#if defined(RC_STACK_BRANCHY)
-    static constexpr bool kFast = false;
-#else
-    static constexpr bool kFast = true;
-#endif
+    // of their own: LDS, the spill area and the status word see the same bytes either way.  (Measured against push / pop everywhere:
+    // docs/EXPERIMENTS.md "stack fast path".)
     // `if (do_push) push(v); return keep ? keep_v : pop();` -- the slot above the top is free, so it is written whether or not the lane
     // pushes; LDS operations of a wave complete in order, so a lane that pushes and pops in one pass reads `v` back
     __device__ inline uint32_t push_pop_lds(pos_t& top, bool do_push, uint32_t v, bool keep, uint32_t keep_v) {
@@ -376,13 +371,8 @@ struct LaneStackP {
     // the node, so that its latency overlaps the node fetch's; the overload below then needs no read behind the slab test.  Relies on: every
     // lane the interior loop admits has at least one entry below `top` (the INVALID pushed at refill, or the sentinel pushed at instance
     // entry), so `top - BLOCK` lies in the lane's own column; LDS operations of a wave complete in order, so the peek sees the previous
-    // pass's write.  The slots hold the same bytes as with the late read.
-    // -DRC_STACK_LATE_POP (dev, tools/ab_build.sh): the read behind the write, the form before docs/EXPERIMENTS.md "stack peek".
-#if defined(RC_STACK_LATE_POP)
-    static constexpr bool kPeek = false;
-#else
-    static constexpr bool kPeek = true;
-#endif
+    // pass's write.  The slots hold the same bytes as with the late read.  (Measured against the read behind the write, which shapes with
+    // Shape::kLatePop still take: docs/EXPERIMENTS.md "stack peek".)
     __device__ inline uint32_t peek_lds(pos_t top) const { return *(top - BLOCK); }
     __device__ inline uint32_t push_pop_lds(pos_t& top, bool do_push, uint32_t v, bool keep, uint32_t keep_v, uint32_t old_top) {
         *top = (E)v;
@@ -413,14 +403,10 @@ struct LaneStackP {
     // each in every pass when the compiler is left to it (the form before).  `up` / `down` hold +stride / -stride in two registers the caller
     // keeps across the loop: two independent selects and one three-operand add, two levels deep.  (d = h0 + h1 - 1 from inline constants and
     // one 24-bit multiply-add by the stride in a scalar register needs no vector register, and was measured: a chain of three, a quarter to
-    // a half of this form's gain -- docs/EXPERIMENTS.md "VALU trims".  -DRC_TRIM_MAD builds it.)
+    // a half of this form's gain -- docs/EXPERIMENTS.md "VALU trims".)
     __device__ inline uint32_t push_pop_lds(addr_t& a, bool h0, bool h1, bool first0, uint32_t c0, uint32_t c1, uint32_t old_top, uint32_t up, uint32_t down) {
         *(lds_e*)(uintptr_t)(a + kStrideBytes) = (E)(first0 ? c1 : c0);
-#if defined(RC_TRIM_MAD)   // (`up` = the stride in a scalar register the caller keeps opaque, `down` unused)
-        a = (uint32_t)(__mul24((h0 ? 1 : 0) - (h1 ? 0 : 1), (int)up) + (int)a);
-#else
         a = a + (h0 ? up : 0u) + (h1 ? 0u : down);
-#endif
         return (first0 | (h0 & !h1)) ? c0 : (h1 ? c1 : old_top);
     }
 };
@@ -549,21 +535,6 @@ __device__ inline bool step(RayState& s, const SceneView& a, Stack& st) {
     return s.node != RC_INVALID_NODE;
 }
 
-__device__ inline void write_hit(const RayState& s, const SceneView& a, RcHit* hits, uint64_t ray_index) {
-    uint4 w0, w1;
-    if (s.closest_inst >= 0) {  // :2010-2017
-        const uint4 m3 = *(reinterpret_cast<const uint4*>(a.inst + s.closest_inst) + 3);
-        w0 = make_uint4(1u, __float_as_uint(s.closest_t), m3.y + s.closest_prim - 1u, m3.z);
-        w1 = make_uint4(__float_as_uint(s.hit_u), __float_as_uint(s.hit_v), (uint32_t)s.closest_inst, 0u);
-    } else {  // :2018-2023
-        w0 = make_uint4(0u, 0u, RC_INVALID_NODE, 0u);
-        w1 = make_uint4(0u, 0u, RC_INVALID_NODE, 0u);
-    }
-    uint4* out = reinterpret_cast<uint4*>(hits + ray_index);
-    out[0] = w0;
-    out[1] = w1;
-}
-
 __device__ inline RcRay load_ray(const RcRay* rays, uint64_t i) {
     const float4* q = reinterpret_cast<const float4*>(rays + i);
     float4 a = q[0], b = q[1];
@@ -588,11 +559,7 @@ struct ArraySource {
     // first + 2 L + 1; 64 lanes = 128 rays = a whole chunk), in the same memory round trip as its first ray loads.  A batch traced for the first
     // time is read from HBM (through cold TLB entries), and a chunk is consumed in 3-4 refills of 20-64 rays -- each of which used to pay that
     // round trip; now the later ones find their lines in L2.  The value is never used (the caller only keeps it alive up to the ray loads' wait).
-#ifdef RC_NO_RAY_PREFETCH   // dev: A/B builds (tools/ab_fresh.py)
-    static constexpr bool kPrefetch = false;
-#else
-    static constexpr bool kPrefetch = true;
-#endif
+    static constexpr bool kPrefetch = true;   // (the generated-ray sources of rc_drivers.hip have nothing to prefetch: false)
     __device__ inline uint32_t prefetch(unsigned long long first, unsigned long long end, int lane) const {
         const unsigned long long i = first + 2ull * (unsigned long long)lane;
         return i < end ? *reinterpret_cast<const uint32_t*>(rays + i) : 0u;
@@ -603,11 +570,11 @@ struct HitWriter {
     RcHit* hits;
     __device__ inline void operator()(uint64_t i, bool hit, float t, float u, float v, uint32_t prim, int instance) const {
         uint4 w0, w1;
-        if (hit) {
+        if (hit) {  // :2010-2017
             const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
             w0 = make_uint4(1u, __float_as_uint(t), m3.y + prim - 1u, m3.z);
             w1 = make_uint4(__float_as_uint(u), __float_as_uint(v), (uint32_t)instance, 0u);
-        } else {
+        } else {  // :2018-2023
             w0 = make_uint4(0u, 0u, RC_INVALID_NODE, 0u);
             w1 = make_uint4(0u, 0u, RC_INVALID_NODE, 0u);
         }
@@ -616,6 +583,10 @@ struct HitWriter {
         out[1] = w1;
     }
 };
+// The result of a ray traced with step() (kernels 0 / 1), written the same way.
+__device__ inline void write_hit(const RayState& s, const SceneView& a, RcHit* hits, uint64_t ray_index) {
+    HitWriter{a.inst, hits}(ray_index, s.closest_inst >= 0, s.closest_t, s.hit_u, s.hit_v, s.closest_prim, s.closest_inst);
+}
 
 // ---- persistent waves, phase-structured ("while-while") scheduling: the core of trace kernel 3 and of the drivers ----
 // Run one block of the loop body at a time, for the lanes that need it, in a fixed phase order:
@@ -809,14 +780,10 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
     constexpr int BLOCK = Shape::kBlock;
     constexpr bool STATS = Shape::kStats, TIMELINE = Shape::kTimeline, STACK16 = Shape::kStack16;
     typedef LaneStackP<Shape::kLdsDepth, BLOCK, typename Shape::entry_t> Stack;
-    constexpr bool PEEK = Stack::kPeek && !Shape::kLatePop;
-    // The interior loop keeps the stack position as the integer address of the top entry (LaneStackP::addr_t) wherever it peeks.
-    // -DRC_NO_TRIM_INTERIOR (dev, tools/ab_build.sh): the pointer form, as before docs/EXPERIMENTS.md "VALU trims"
-#if defined(RC_NO_TRIM_INTERIOR)
-    constexpr bool ADDR = false;
-#else
-    constexpr bool ADDR = Stack::kFast && PEEK && !Shape::kPtrStack;
-#endif
+    constexpr bool PEEK = !Shape::kLatePop;
+    // The interior loop keeps the stack position as the integer address of the top entry (LaneStackP::addr_t) wherever it peeks; the
+    // pointer form it replaced (docs/EXPERIMENTS.md "VALU trims") remains for the shapes that ask for it.
+    constexpr bool ADDR = PEEK && !Shape::kPtrStack;
     // node values that are not nodes: the 32-bit INVALID / sentinel of the reference, or their low halves where everything fits 16 bits
     constexpr uint32_t kInv = STACK16 ? 0xFFFFu : RC_INVALID_NODE, kSent = STACK16 ? 0xFFFEu : RC_TOP_LEVEL_SENTINEL;
     const float2* const tl = top.tl;
@@ -886,51 +853,25 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
     // compiler does not know -- it would rebuild both constants with a v_mov in every pass --, and the LDS address of the workgroup's first
     // stack entry (wave-uniform)
     uint32_t step_up = Stack::kStrideBytes, step_down = 0u - Stack::kStrideBytes;
-#if defined(RC_TRIM_MAD)
-    if (ADDR) asm volatile("" : "+s"(step_up));
-#else
     if (ADDR) asm volatile("" : "+v"(step_up), "+v"(step_down));
-#endif
     const uint32_t stacks_addr = (uint32_t)(uintptr_t)(typename Stack::lds_e*)lds_stack;
-#if defined(RC_EXP_VALU_FREE)
-    float exp_free = 1.0f;  // (lives across the whole loop; the volatile asm statements that update it are what keeps it)
-#endif
 
     for (;;) {
-#if defined(RC_AGE_PRIO)  // dev experiment (VERDICT r4 #2a): a wave that carries a ray older than RC_AGE_PRIO interior iterations issues ahead of its SIMD's other waves
-        {
-            const bool old_ray = live && (it_total - start_it) > (uint32_t)RC_AGE_PRIO;
-            if (__ballot(old_ray)) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
         // ---- interior phase: intersect_internal_node (:1807-1832) + push far / descend near / pop (:1946-1960, 1991-1993)
         // One pass over an interior node.  DEEP = false: every participating lane's next free stack slot lies below the LDS depth (the loop
         // below admits no other lane), so push and pop are the branch-free LDS forms; DEEP = true: the general push / pop with the spill path.
         typename Stack::addr_t ta = ADDR ? st.top_addr(sp) : 0u;  // the interior loop's form of `sp`; converted back behind the loop
         auto interior_pass = [&](auto deep_tag) {
             constexpr bool DEEP = decltype(deep_tag)::value;
-#if defined(RC_EXP_VALU)  // dev experiment (tools/probes/build_variants.sh; profiles/r05_bound_probe.txt): RC_EXP_VALU extra slow-class VALU instructions (one dependent chain) per interior pass
-            { float dummy = tmin;
-#pragma unroll
-              for (int k = 0; k < RC_EXP_VALU; ++k) asm volatile("v_max_f32 %0, %0, %1" : "+v"(dummy) : "v"(closest_t));
-              if (dummy == 1.2345e-30f) tmin = dummy; }
-#endif
-#if defined(RC_EXP_NOP)   // ... RC_EXP_NOP x 16 idle cycles in the pass
-#pragma unroll
-            for (int k = 0; k < RC_EXP_NOP; ++k) asm volatile("s_nop 15");
-#endif
             float4 na, nb, nc;
             u2v ch;
             constexpr int PS = Shape::kPlaneNodes;  // plane stride
             // the value a pop in this pass returns unless the pass pushes (LaneStackP::peek_lds), off the chain.  Requested right BEHIND the node
             // fetch: the buffer arm waits for every LDS operation in flight before it issues its loads (they write the registers the plane
             // reads write), so a peek in front of the fetch puts its latency in front of the loads in every pass that has no LDS lane.  The
-            // scheduling barrier keeps the compiler from sinking the read behind the fetch's waits, next to its use.
-            // -DRC_STACK_PEEK_AT_HEAD (dev, tools/ab_build.sh): the peek in front of the fetch (docs/EXPERIMENTS.md "stack peek")
+            // scheduling barrier keeps the compiler from sinking the read behind the fetch's waits, next to its use.  (The peek in front of
+            // the fetch was measured: docs/EXPERIMENTS.md "stack peek".)
             uint32_t old_top = 0u;
-#if defined(RC_STACK_PEEK_AT_HEAD)
-            if (!DEEP && PEEK) old_top = ADDR ? st.peek_lds(ta) : st.peek_lds(sp);
-#endif
             if ((Shape::top == Top::Lds && (cur_inst < 0 || node <= a.blas_k)) || (Shape::top == Top::PartialLds && node <= (cur_inst < 0 ? a.tlas_k : a.blas_k))) {
                 const float2* q = tl + ((node - 1u) + (cur_inst < 0 ? 0u : a.lds_blas_base));
                 const float2 p0 = q[0], p1 = q[PS], p2 = q[2 * PS], p3 = q[3 * PS], p4 = q[4 * PS], p5 = q[5 * PS], p6 = q[6 * PS];
@@ -941,24 +882,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
                 na = buf_f4(nrs1, off); nb = buf_f4(nrs1, off, 16); nc = buf_f4(nrs1, off, 32);
                 ch = __builtin_amdgcn_raw_buffer_load_b64(nrs1, off, 48, 0);
             }
-#if !defined(RC_STACK_PEEK_AT_HEAD)
             if (!DEEP && PEEK) { old_top = ADDR ? st.peek_lds(ta) : st.peek_lds(sp); __builtin_amdgcn_sched_barrier(0); }
-#endif
-#if defined(RC_EXP_VALU_FREE)  // dev experiment (profiles/valu_slot_price.txt): RC_EXP_VALU_FREE extra VALU instructions per interior pass that nothing in the pass reads -- an
-            // accumulator of their own, issued in the shadow of the node fetch: the price of an issue slot, where RC_EXP_VALU's chain prices latency.
-            // Slow class (v_max_f32) by default, -DRC_EXP_VALU_FREE_MUL: the full-rate class (v_mul_f32)
-            {
-#pragma unroll
-                for (int k = 0; k < RC_EXP_VALU_FREE; ++k) {
-#if defined(RC_EXP_VALU_FREE_MUL)
-                    asm volatile("v_mul_f32 %0, %0, %1" : "+v"(exp_free) : "v"(closest_t));
-#else
-                    asm volatile("v_max_f32 %0, %0, %1" : "+v"(exp_free) : "v"(closest_t));
-#endif
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
             // packed node (rc_pack_node): na = child-0 (min.x,min.y,max.x,max.y), nb = child-1 likewise, nc = z of both
             const v2f ixy = {inv.x, inv.y}, oxy = {ox.x, ox.y}, izz = {inv.z, inv.z}, ozz = {ox.z, ox.z};
             const v2f n0xy = v2f{na.x, na.y} * ixy + oxy, f0xy = v2f{na.z, na.w} * ixy + oxy;
@@ -989,14 +913,14 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
         for (;;) {
             RC_MARK("interior_begin");
             const bool shallow = ADDR ? Stack::below_limit(ta, stacks_addr) : sp < st.limit;
-            const bool is_int = node < n_level && (!Stack::kFast || shallow);
-            const unsigned long long m_int = __builtin_amdgcn_ballot_w64(node < n_level) & (Stack::kFast ? __builtin_amdgcn_ballot_w64(shallow) : ~0ull);
+            const bool is_int = node < n_level && shallow;
+            const unsigned long long m_int = __builtin_amdgcn_ballot_w64(node < n_level) & __builtin_amdgcn_ballot_w64(shallow);
             if (m_int == 0ull) break;
             const int n_int = __popcll(m_int);
             it_total += 1u;
             if (STATS) { st_iter[1] += 1; st_lane[1] += is_int ? 1 : 0; }
             if (TIMELINE) { tl_int += 1; if (tl_tx) tl_int_x += 1; }
-            if (is_int) interior_pass(std::integral_constant<bool, !Stack::kFast>());
+            if (is_int) interior_pass(std::false_type());
             RC_MARK("interior_end");
             if (n_int < thr_eff) break;  // too few interior lanes left: serve the waiting ones first
         }
@@ -1004,7 +928,7 @@ __device__ inline void phased_trace(const SceneView& av, const PersistArgs& a, t
         // One vote per outer iteration: is any lane of the wave at or beyond the LDS depth?  If so (rare), those lanes get one interior pass
         // of their own with the general push / pop.  The stack sites of the record and switch phases keep the general forms: their
         // branch-free variants behind this vote measured no gain (docs/EXPERIMENTS.md, "stack fast path").
-        if (Stack::kFast && __builtin_expect(__ballot(!(sp < st.limit)) != 0ull, 0)) {
+        if (__builtin_expect(__ballot(!(sp < st.limit)) != 0ull, 0)) {
             const bool deep = node < n_level && !(sp < st.limit);
             if (__ballot(deep)) {
                 it_total += 1u;

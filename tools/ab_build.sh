@@ -1,6 +1,7 @@
 #!/bin/bash
 # Dev: builds a second copy of the library with extra compiler flags into tools/ab/<name>.so for A/B measurements inside ONE gpurun call
-# (box-to-box differences are larger than most kernel changes).   tools/ab_build.sh noprefetch -DRC_NO_RAY_PREFETCH
+# (box-to-box differences are larger than most kernel changes).   tools/ab_build.sh planes1278 -DRC_LDS_PLANES16=1278
+# With no flags, run from a checkout of the parent commit, it builds the parent's library whole:   tools/ab_build.sh parent
 set -e
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -3,7 +3,7 @@
 (tools/ab_build.sh builds variants into tools/ab/):
 
     python tools/ab_fresh.py                      # the in-tree library
-    python tools/ab_fresh.py tools/ab/noprefetch.so
+    python tools/ab_fresh.py tools/ab/parent.so   # the parent commit's library (tools/ab_build.sh parent, from a checkout of it)
 
 Workloads: C3 4 Mi jittered primaries (the bench headline), C3 1 Mi jittered primaries, C2 1 M grid rays from perturbed view directions, C3 shadow
 rays of jittered primaries (any_hit), and for reference the same-buffer figures (one cache-warm buffer, cost_order 0)."""

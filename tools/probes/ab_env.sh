@@ -1,6 +1,6 @@
 #!/bin/bash
-# dev: one library, several environments (e.g. RC_EVENT_MODE), interleaved on one GPU box:
-#   tools/probes/ab_env.sh "RC_EVENT_MODE=0 RC_EVENT_MODE=2 RC_EVENT_MODE=3" [perf_probe args...]
+# dev: one library, several environments (e.g. RC_ENTRY_CULL), interleaved on one GPU box:
+#   tools/probes/ab_env.sh "RC_ENTRY_CULL=1 RC_ENTRY_CULL=0" [perf_probe args...]
 ES=$1; shift
 for round in 1 2; do
   for e in $ES; do

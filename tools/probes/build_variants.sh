@@ -1,6 +1,6 @@
 #!/bin/bash
-# dev: builds of the library with extra -D flags on rc_traverse.hip (the experiments of rc_traverse_core.h), for A/B runs on one GPU box:
-#   tools/probes/build_variants.sh name1 "-DRC_EXP_VALU=12" name2 "-DRC_EXP_NOP=4" ...   -> tools/probes/libs/<name>.so
+# dev: builds of the library with extra -D flags on rc_traverse.hip (the dev variants of rc_traverse_core.h), for A/B runs on one GPU box:
+#   tools/probes/build_variants.sh name1 "-DRC_LDS_PLANES16=1278" name2 "-DRC_PHASE_MARKERS" ...   -> tools/probes/libs/<name>.so
 set -e
 cd "$(dirname "$0")/../../raycore.jl_amd/csrc"
 FLAGS="--offload-arch=gfx950 -O3 -fno-slp-vectorize -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt -Wno-unused-result"
