@@ -791,6 +791,48 @@ int rc_get_illumination_dirs_device(rc_scene* scene, const float* d_dirs, uint32
                                     uint64_t row_stride, void* stream);
 int rc_generate_ray_grid_dirs_device(rc_scene* scene, const float* d_dirs, uint32_t n_dirs, uint32_t grid, rc_ray* d_rays, void* stream);
 
+/* ---- Ambient occlusion: how open is the hemisphere above every hit?  `samples` cosine-weighted any_hit rays of length max_dist per hit; the
+ * visible fraction count / samples is the cosine-weighted openness of the point (with max_dist = +Inf its sky-view factor, the per-point form
+ * of what rc_get_illumination_device and rc_view_factor_totals answer per triangle).
+ * d_rays / d_hits: the closest-hit stage's n rays and hit records.  d_path_in (may be NULL) / path_base: the path of slot i is
+ * path_base + (d_path_in ? d_path_in[i] : i), exactly as in rc_bounce_rays_device: a compacted, chunked or sharded queue draws the same
+ * samples for the same path.
+ * Sample s of slot i, every expression evaluated left to right in f32 with no contraction:
+ *   (p, nn) = the hit point and flipped geometric normal of slot i (rc_hit_points_device's)
+ *   rnd = Philox4x32-10, counter (lo32 path, hi32 path, s, 0x414F0000 | depth), key = (lo32 seed, hi32 seed)
+ *   u1, u2 = its first two words as 24-bit floats in [0, 1): (word >> 8) * 2^-24, the conversion of rc_bounce_rays_device
+ *   d = the cosine-weighted direction about nn that rc_bounce_rays_device makes from (nn, u1, u2): the same function, not renormalised
+ *   ray(i, s) = origin p + nn * bias, t_min 0, direction d, t_max max_dist.
+ * A sample depends on (seed, path, depth, s) only -- not on n, the slot or `samples`: raising `samples` keeps the earlier ones.
+ *
+ * rc_ambient_occlusion_rays_device, the composed stage: writes n * samples rays, ray(i, s) at slot i * samples + s; a slot whose primary ray
+ * missed gets rc_shadow_rays_device's dummy ray (d = (0,0,1), t_max = 0).  The output feeds rc_trace_any_device unchanged.
+ * rc_ambient_occlusion_device, the fused driver: one persistent any_hit launch over all (hit, sample) items, the rays generated when a lane
+ * takes an item and never stored.  d_count: n u32.  Identity with the composed path, exact, no tolerance:
+ *   d_count[i] += sum over s of (d_hits[i].hit && ray(i, s).t_max > 0 && !any_hit(ray(i, s)).hit),
+ * where ray(i, s) is bit for bit what rc_ambient_occlusion_rays_device writes (the same device function makes both) and any_hit is what
+ * rc_trace_any_device reports for it.  t_max = max_dist > 0 for every slot that hit, so the middle term only excludes the dummy ray of a
+ * missed primary ray, which costs no traversal.  A hit whose frame is NaN (a singular instance transform, say) has a NaN origin or
+ * direction but t_max = max_dist > 0: NO extra gate applies, it is traced and counts as whatever rc_trace_any_device reports for that ray,
+ * the same in both paths.
+ * The call ACCUMULATES into d_count (the convention of rc_soft_shadow_visibility_device): the caller zeroes it, and progressive
+ * accumulation over calls with different `seed` or `depth` is legal.  Each visible sample is one relaxed device-scope u32 atomic add;
+ * integer adds are exact in any order, so the counts are reproducible.  Items are claimed in natural order; the entry cull follows
+ * rc_trace_any_device (off unless option "entry_cull" is 2).
+ * No allocation, copy, event, memset, host synchronisation or scene-owned scratch: re-entrant across streams, and captured on a capturing
+ * stream under the rules of the other driver launches (one capture slot; the stream must have run the call eagerly before).  A stack
+ * overflow is reported by rc_wait.  n == 0 or samples == 0: succeeds, nothing is enqueued.
+ * Errors, all before anything is enqueued: RC_ERR_INVALID_ARGUMENT (NULL scene, checked first and with or without a device; NULL d_rays,
+ * d_hits or output while there is work; n * samples >= 2^32, products that wrap in 64 bits included; samples >= 65536; depth >= 65536;
+ * max_dist not > 0 -- NaN included, +Inf is legal), RC_ERR_NOT_SYNCED (the rules of rc_shadow_visibility_device).
+ * Measured against the composed path in docs/EXPERIMENTS.md, "Ambient occlusion". */
+int rc_ambient_occlusion_rays_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples,
+                                     float max_dist, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
+                                     float bias, rc_ray* d_ao_rays, void* stream);
+int rc_ambient_occlusion_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist,
+                                uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias,
+                                uint32_t* d_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -568,6 +568,25 @@ class TLAS:
                                                      int(samples), int(seed), int(depth), ptr(d_path_in) if d_path_in else None, int(path_base),
                                                      float(bias), ptr(d_count), ptr(stream) if stream else None))
 
+    def ambient_occlusion_rays_device(self, d_rays, d_hits, n, samples, d_ao_rays, max_dist=float("inf"), seed=0, depth=0, bias=1e-3,
+                                      d_path_in=None, path_base=0, stream=None):
+        """The ambient-occlusion rays of all hits x `samples` (rc_ambient_occlusion_rays_device): n * samples RTRay slots, ray (i, s) at
+        i * samples + s -- from hit point + normal * bias in a cosine-weighted direction about the normal, t_max = max_dist -- ready for
+        trace_device(mode='any').  A sample depends on (seed, path, depth, s) only."""
+        check(lib().rc_ambient_occlusion_rays_device(self._h, ptr(d_rays), ptr(d_hits), int(n), int(samples), float(max_dist), int(seed), int(depth),
+                                                     ptr(d_path_in) if d_path_in else None, int(path_base), float(bias), ptr(d_ao_rays),
+                                                     ptr(stream) if stream else None))
+
+    def ambient_occlusion_device(self, d_rays, d_hits, n, samples, d_count, max_dist=float("inf"), seed=0, depth=0, bias=1e-3, d_path_in=None,
+                                 path_base=0, stream=None):
+        """Ambient occlusion in one traversal launch (rc_ambient_occlusion_device): d_count (device pointer, n u32) is ACCUMULATED --
+        count[i] += the samples of hit i's hemisphere that reach max_dist unoccluded, exactly what ambient_occlusion_rays_device +
+        trace_device(mode='any') + the t_max > 0 gate give, without their buffers.  The caller zeroes d_count and divides by `samples`:
+        the cosine-weighted openness of the point, its sky-view factor with max_dist = inf."""
+        check(lib().rc_ambient_occlusion_device(self._h, ptr(d_rays), ptr(d_hits), int(n), int(samples), float(max_dist), int(seed), int(depth),
+                                                ptr(d_path_in) if d_path_in else None, int(path_base), float(bias), ptr(d_count),
+                                                ptr(stream) if stream else None))
+
     def illumination_dirs_device(self, d_dirs, n_dirs, grid, d_counts, row_stride=None, stream=None):
         """get_illumination for n_dirs directions in one call (rc_get_illumination_dirs_device).  d_dirs: device pointer to n_dirs x 3 f32
         (need not be normalised), read WHEN THE KERNELS RUN, like the TLAS root the grids are laid out from: no host copy of the world
@@ -889,6 +908,29 @@ def get_illumination_dirs(accel, viewdirs, grid_size=1000, weights=None):
     rows = counts.cpu().numpy().view(np.uint32)[:d * n].reshape(d, n)
     rows = np.minimum(rows, np.uint32(1 << 24)).astype(np.float32)  # the reference's Float32 sums stop at 2^24
     return rows if w is None else w @ rows.astype(np.float64)
+
+
+def ambient_occlusion(accel, rays, hits, samples, max_dist=float("inf"), seed=0, bias=1e-3):
+    """How open is the hemisphere above every hit?  rays / hits: the RAY_DT rays and the HIT_DT records a closest-hit trace of them
+    returned.  Returns the (n,) uint32 counts of the `samples` cosine-weighted samples per hit that reach max_dist unoccluded (0 where
+    the ray missed): count / samples is the point's openness, its sky-view factor with max_dist = inf.  Upload, one
+    ambient_occlusion_device call, download."""
+    r = _as_rays(rays)
+    h = np.ascontiguousarray(hits)
+    if h.dtype != HIT_DT or h.shape != r.shape:
+        raise ValueError("hits must be a HIT_DT array with one record per ray")
+    import torch
+    t = _owner(accel)
+    n = len(r)
+    dev = f"cuda:{t.device}"
+    torch.cuda.synchronize(t.device)  # (the call runs on the default stream: behind whatever the caller enqueued on streams of its own)
+    d_rays = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_hits = torch.from_numpy(h.view(np.uint8).reshape(-1).copy()).to(dev)
+    counts = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    t.ambient_occlusion_device(d_rays.data_ptr(), d_hits.data_ptr(), n, samples, counts.data_ptr(), max_dist=max_dist, seed=seed, bias=bias)
+    torch.cuda.synchronize(t.device)
+    t.wait_for_gpu()  # (reports a traversal stack overflow)
+    return counts.cpu().numpy().view(np.uint32)[:n].copy()
 
 
 def _vf_out(n, out):

@@ -1681,6 +1681,37 @@ int rc_soft_shadow_visibility_device(rc_scene* s, const rc_ray* d_rays, const rc
     });
 }
 
+// What the two ambient-occlusion calls check before anything is enqueued (0: go on)
+static int ambient_occlusion_args(const char* name, rc_scene* s, const void* d_rays, const void* d_hits, uint64_t n, uint32_t samples, float max_dist,
+                                  uint32_t depth, const void* d_out) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (samples >= 65536u || depth >= 65536u) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": samples and depth must be below 65536");
+    if (!(max_dist > 0.0f)) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": max_dist must be > 0");
+    if (samples && n >= ((1ull << 32) + samples - 1) / samples) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": n * samples must be below 2^32");
+    if (n && samples && (!d_rays || !d_hits || !d_out)) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": NULL argument");
+    return 0;
+}
+int rc_ambient_occlusion_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
+                                     uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, rc_ray* d_ao_rays, void* stream) {
+    if (int e = ambient_occlusion_args("rc_ambient_occlusion_rays_device", s, d_rays, d_hits, n, samples, max_dist, depth, d_ao_rays)) return e;
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        rc_launch_ao_rays(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, samples, max_dist, seed, depth, d_path_in,
+                          path_base, bias, reinterpret_cast<RcRay*>(d_ao_rays), (hipStream_t)stream);
+    });
+}
+int rc_ambient_occlusion_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
+                                uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, uint32_t* d_count, void* stream) {
+    if (int e = ambient_occlusion_args("rc_ambient_occlusion_device", s, d_rays, d_hits, n, samples, max_dist, depth, d_count)) return e;
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        rc_launch_ambient_occlusion(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, samples, max_dist, seed, depth,
+                                    d_path_in, path_base, bias, d_count, (hipStream_t)stream);
+    });
+}
+
 int rc_bounce_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                           const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n_out, uint64_t seed, uint32_t bounce, float bias,
                           rc_ray* d_out, void* stream) {

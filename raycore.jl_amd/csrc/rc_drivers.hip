@@ -715,6 +715,64 @@ __device__ inline float3_ cosine_hemisphere_dir(const float3_ n, float u1, float
     return add3(add3(scale3(bu, dx), scale3(bv, dy)), scale3(n, z));
 }
 
+// ---- ambient occlusion: `samples` cosine-weighted any_hit rays of length max_dist over the hemisphere of every hit ---------------------
+// Sample s of slot i: (p, nn) = hit_frame; (u1, u2) = the first two words of Philox4x32-10(counter = (lo32 path, hi32 path, s,
+// 0x414F0000 | depth), key = seed) through the bounce stage's 24-bit conversion; d = cosine_hemisphere_dir(nn, u1, u2), not renormalised;
+// the ray is o = p + nn * bias, t_min = 0, d, t_max = max_dist.  Every expression left to right, no contraction.  The visible fraction
+// count / samples is the cosine-weighted openness of the hemisphere (the sky-view factor of the point with max_dist = Inf).
+struct AoParams {
+    const RcRay* rays;
+    const RcHit* hits;
+    const uint32_t* path_in;   // path of slot i (nullptr: i), as in k_bounce_rays
+    uint64_t path_base;
+    uint32_t samples, k0, k1, depth;
+    float bias, max_dist;
+};
+// The occlusion ray of sample s of slot i, whose primary ray hit (h = hits[i]): shared by the stage kernel and the fused driver's source, so
+// the two agree bit for bit.
+__device__ inline RcRay ao_ray(const SceneView& v, const AoParams& q, uint32_t i, uint32_t s, const RcRay& r, const RcHit& h) {
+    float3_ p, nn;
+    hit_frame(v, r, h, p, nn);
+    const uint64_t path = q.path_base + (q.path_in ? (uint64_t)q.path_in[i] : (uint64_t)i);
+    uint32_t rnd[4];
+    philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), s, 0x414F0000u | q.depth, q.k0, q.k1, rnd);
+    const float3_ d = cosine_hemisphere_dir(nn, u32_to_unit(rnd[0]), u32_to_unit(rnd[1]));
+    const float3_ o = add3(p, scale3(nn, q.bias));
+    return RcRay{o.x, o.y, o.z, 0.f, d.x, d.y, d.z, q.max_dist};
+}
+// The composed stage: n * samples rays, slot i * samples + s; a slot whose primary ray missed gets k_shadow_rays' dummy ray.  The output
+// feeds rc_trace_any_device unchanged.
+__global__ void k_ao_rays(SceneView v, AoParams q, uint64_t total, RcRay* out) {
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t i = (uint32_t)j / q.samples, s = (uint32_t)j - i * q.samples;  // (total < 2^32)
+        RcRay ar = RC_DUMMY_RAY;
+        const RcHit h = q.hits[i];
+        if (h.hit) ar = ao_ray(v, q, i, s, q.rays[i], h);
+        store_ray(out, j, ar);
+    }
+}
+// The fused driver: work item j = i * samples + s, so the samples of a hit sit in neighbouring lanes and share its records.  A missed
+// primary ray gives the dead ray; t_max = max_dist > 0 for every other item (checked by the caller), so there is no further gate: a hit
+// with a NaN frame traces its NaN ray, as rc_trace_any_device does with the stored one.
+struct AoSource {
+    const SceneView& v;
+    AoParams q;
+    __device__ inline RcRay operator()(uint64_t j) const {
+        const uint32_t i = (uint32_t)j / q.samples, s = (uint32_t)j - i * q.samples;  // (n * samples < 2^32)
+        const RcHit h = q.hits[i];
+        if (!h.hit) return RC_DEAD_RAY;
+        return ao_ray(v, q, i, s, load_ray(q.rays, i), h);
+    }
+    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
+};
+// (VisibilityCountSink with count[j / samples] = slot i: one relaxed agent-scope u32 add per visible sample)
+struct AoJob {
+    AoParams q;
+    uint32_t* count;
+    __device__ inline AoSource source(const SceneView& v) const { return AoSource{v, q}; }  // (v: the kernel's own by-value parameter)
+    __device__ inline VisibilityCountSink sink(const SceneView&) const { return VisibilityCountSink{count, q.samples}; }
+};
+
 // Diffuse bounce: output slot i continues the path of source slot s (s = i, or d_src[i] for i < count, or d_src[i % count] round robin
 // with k = i / count), from hit_point + normal * bias in a cosine-weighted direction about the geometric normal.  The uniforms are
 // Philox4x32-10(counter = (lo32 path, hi32 path, k, 0x424E0000 | bounce), key = seed): a path's bounce does not depend on compaction,
@@ -1091,6 +1149,25 @@ void rc_launch_soft_shadow_visibility(rc_scene* s, const RcRay* d_rays, const Rc
     const uint64_t total = n * n_lights * samples;
     if (total == 0) return;
     DriverLaunch(s, stream, total).go<true>(SoftShadowJob{soft_shadow_params(d_rays, d_hits, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias), d_count});
+}
+
+// The ambient-occlusion pair (AoParams): the composed stage writes the n * samples rays; the driver is one persistent any_hit launch over the
+// same items in natural claim order that ACCUMULATES the visible samples into d_count[i].  total < 2^32 (checked by the caller).
+static AoParams ao_params(const RcRay* d_rays, const RcHit* d_hits, uint32_t samples, float max_dist, uint64_t seed, uint32_t depth,
+                          const uint32_t* d_path_in, uint64_t path_base, float bias) {
+    return AoParams{d_rays, d_hits, d_path_in, path_base, samples, (uint32_t)seed, (uint32_t)(seed >> 32), depth, bias, max_dist};
+}
+void rc_launch_ao_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed, uint32_t depth,
+                       const uint32_t* d_path_in, uint64_t path_base, float bias, RcRay* d_out, hipStream_t stream) {
+    const uint64_t total = n * samples;
+    launch_stage(s, stream, total, k_ao_rays, rc_scene_view_static(s), ao_params(d_rays, d_hits, samples, max_dist, seed, depth, d_path_in, path_base, bias),
+                 total, d_out);
+}
+void rc_launch_ambient_occlusion(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
+                                 uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream) {
+    const uint64_t total = n * samples;
+    if (total == 0) return;
+    DriverLaunch(s, stream, total).go<true>(AoJob{ao_params(d_rays, d_hits, samples, max_dist, seed, depth, d_path_in, path_base, bias), d_count});
 }
 
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,

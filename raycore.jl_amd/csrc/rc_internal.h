@@ -528,6 +528,13 @@ void rc_launch_soft_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d
 void rc_launch_soft_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
                                       uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in,
                                       uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream);
+// Ambient occlusion: `samples` cosine-weighted rays of length max_dist over the hemisphere of every hit (Philox keyed by path, depth, s).  The
+// composed stage writes ray i * samples + s; the driver ACCUMULATES the visible samples into count[i] in one traversal launch.
+// n * samples < 2^32; samples, depth < 2^16; max_dist > 0
+void rc_launch_ao_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed, uint32_t depth,
+                       const uint32_t* d_path_in, uint64_t path_base, float bias, RcRay* d_out, hipStream_t stream);
+void rc_launch_ambient_occlusion(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
+                                 uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream);
 // Diffuse (cosine-weighted) bounce rays, slot-aligned or gathered through d_src / *d_src_count (read on the device); n < 2^32, bounce < 2^16
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                            const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n, uint64_t seed, uint32_t bounce, float bias,

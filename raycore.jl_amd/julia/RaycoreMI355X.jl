@@ -486,6 +486,24 @@ soft_shadow_visibility_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::
                 (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, Ptr{Float32}, Ptr{Float32}, UInt32, UInt32, UInt64, UInt32, Ptr{UInt32}, UInt64,
                  Cfloat, Ptr{UInt32}, Ptr{Cvoid}),
                 a.owner.ptr, d_rays, d_hits, n, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias, d_count, stream))
+"Ambient-occlusion rays of all hits x `samples`: ray `(i, s)` (0-based) at slot `i * samples + s` of `d_out`, from hit point + normal * bias in a cosine-weighted direction about the normal (Philox keyed by path, depth and `s`), `t_max = max_dist`; ready for `trace_device!` with `any = true`."
+ambient_occlusion_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n::Integer, samples::Integer,
+                               d_out::Ptr{RTRay}; max_dist::Float32 = Inf32, seed::UInt64 = UInt64(0), depth::Integer = 0,
+                               bias::Float32 = 1f-3, d_path_in::Ptr{UInt32} = Ptr{UInt32}(C_NULL), path_base::Integer = 0,
+                               stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_ambient_occlusion_rays_device, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, UInt32, Cfloat, UInt64, UInt32, Ptr{UInt32}, UInt64, Cfloat, Ptr{RTRay},
+                 Ptr{Cvoid}),
+                a.owner.ptr, d_rays, d_hits, n, samples, max_dist, seed, depth, d_path_in, path_base, bias, d_out, stream))
+"Ambient occlusion in one traversal launch: `d_count[i]` (0-based, n UInt32, ACCUMULATED: zero it first) += the samples of hit `i`'s hemisphere that reach `max_dist` unoccluded; divide by `samples` for the openness (the sky-view factor with `max_dist = Inf32`)."
+ambient_occlusion_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n::Integer, samples::Integer,
+                          d_count::Ptr{UInt32}; max_dist::Float32 = Inf32, seed::UInt64 = UInt64(0), depth::Integer = 0,
+                          bias::Float32 = 1f-3, d_path_in::Ptr{UInt32} = Ptr{UInt32}(C_NULL), path_base::Integer = 0,
+                          stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_ambient_occlusion_device, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, UInt32, Cfloat, UInt64, UInt32, Ptr{UInt32}, UInt64, Cfloat, Ptr{UInt32},
+                 Ptr{Cvoid}),
+                a.owner.ptr, d_rays, d_hits, n, samples, max_dist, seed, depth, d_path_in, path_base, bias, d_count, stream))
 "Diffuse (cosine-weighted) bounce rays: slot-aligned, or gathered through `d_src` / `d_src_count` (a device count; `wrap` = round robin)."
 bounce_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n_out::Integer, d_out::Ptr{RTRay};
                     seed::UInt64 = UInt64(0), bounce::Integer = 0, bias::Float32 = 1f-3, d_src::Ptr{UInt32} = Ptr{UInt32}(C_NULL),

@@ -8,6 +8,8 @@ accumulation stay with the caller.
 Buffers are torch tensors on the accel's device: ray / hit records are uint8 tensors of 32 bytes per slot (RTRay / RTHitResult, view them
 with RAY_DT / HIT_DT), path ids and counts are int32 tensors holding u32 values.
 """
+import math
+
 import numpy as np
 
 from ._capi import RaycoreError
@@ -31,6 +33,18 @@ def lookat_camera(eye, target, width, height, fov_deg=45.0, up=(0.0, 1.0, 0.0)):
 def _stream(stream):
     import torch
     return stream if stream is not None else torch.cuda.current_stream()
+
+
+def check_ao_arguments(n, ao_samples, ao_distance):
+    """(ao_samples, ao_distance) as (int, float) for a frame of n paths, or ValueError: what rc_ambient_occlusion_device would refuse, said
+    before a device is touched."""
+    if isinstance(ao_samples, bool) or ao_samples != int(ao_samples) or not 0 <= int(ao_samples) < 65536:
+        raise ValueError("ao_samples must be an integer in [0, 65536)")
+    if not float(ao_distance) > 0.0:  # (NaN included; inf is legal)
+        raise ValueError("ao_distance must be > 0 (inf: unbounded)")
+    if int(n) * int(ao_samples) >= 2 ** 32:
+        raise ValueError("width * height * samples * ao_samples must be below 2^32")
+    return int(ao_samples), float(ao_distance)
 
 
 class WavefrontPaths:
@@ -74,7 +88,14 @@ class WavefrontPaths:
     shadow_counts[b] (an int32 tensor holding n * L u32 counts) on the frame's stream and runs one soft_shadow_visibility_device with
     depth=b, d_path_in=path_ids[b] and the frame's seed: count i * L + l is the number of the shadow_samples samples of light l that slot i
     of hits[b] sees, a path's samples do not depend on compaction, and visible[b] is not produced (an empty list).  light_radii with
-    shadow_samples == 1 is refused: one sample is the hard shadow and would ignore the radii."""
+    shadow_samples == 1 is refused: one sample is the hard shadow and would ignore the radii.
+
+    Ambient occlusion: with_ambient_occlusion(ao_samples, ao_distance=inf) after the constructor (which leaves ao_samples = 0; like
+    rebuild_ratio it is not a constructor keyword, for the same reason).  With ao_samples > 0 each depth b, after its shadow stage,
+    zeroes ao_counts[b] (an int32 tensor holding n u32 counts) on the frame's stream and runs one ambient_occlusion_device with
+    max_dist=ao_distance, depth=b, d_path_in=path_ids[b] and the frame's seed and bias: count i is the number of the ao_samples
+    cosine-weighted hemisphere samples of slot i of hits[b] that reach ao_distance unoccluded, and a path's samples do not depend on
+    compaction.  With ao_samples == 0 the frame is what it was: no launch, no buffer, the same traced_rays()."""
 
     def __init__(self, accel, width, height, samples, depth, camera, light=None, seed=0, bias=1e-3, compact=True, dynamic=None, rebuild=False,
                  deform=None, lights=None, fused_shadows=False, shadow_samples=1, light_radii=None):
@@ -125,6 +146,7 @@ class WavefrontPaths:
         self.dynamic = list(dynamic) if dynamic else []
         self.rebuild = "auto" if rebuild == "auto" else bool(rebuild)
         self.rebuild_ratio = 1.5
+        self.ao_samples, self.ao_distance, self.ao_counts = 0, math.inf, []
         self.deform = list(deform) if deform else []
         dev = torch.device("cuda", accel.device)
         rec = lambda: torch.zeros(self.n * 32, dtype=torch.uint8, device=dev)  # noqa: E731
@@ -165,11 +187,26 @@ class WavefrontPaths:
             accel.refit_or_rebuild_device_async(self.rebuild_ratio, stream=torch.cuda.current_stream(dev).cuda_stream)
             torch.cuda.current_stream(dev).synchronize()
 
+    def with_ambient_occlusion(self, ao_samples, ao_distance=math.inf):
+        """Switch the frame's ambient-occlusion stage on (ao_samples > 0) or off (0), before the next run() or capture(); returns self.
+        ValueError for ao_samples outside [0, 65536), an ao_distance that is not > 0, or width*height*samples*ao_samples >= 2^32 -- all
+        before a tensor is made.  A captured frame keeps the stage it was captured with, so it is refused here."""
+        ao_samples, ao_distance = check_ao_arguments(self.n, ao_samples, ao_distance)
+        if self._graph_stream is not None:
+            raise RaycoreError(1, "WavefrontPaths.with_ambient_occlusion: this frame is already captured")
+        import torch
+        dev = torch.device("cuda", self.accel.device)
+        counts = [torch.zeros(self.n, dtype=torch.int32, device=dev) for _ in range(self.depth)] if ao_samples else []
+        torch.cuda.current_stream(dev).synchronize()  # (as in the constructor: a frame may run on another stream than the allocating one)
+        self.ao_samples, self.ao_distance, self.ao_counts = ao_samples, ao_distance, counts
+        self._streams = set()  # the new buffers are recorded on a stream at its next run()
+        return self
+
     def buffers(self):
         fused = self.visible + [self.lights] if self.fused_shadows else []
         if self.shadow_samples > 1:
             fused = fused + self.shadow_counts + [self.light_radii]
-        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + fused + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic] + [t for _, t in self.deform]
+        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + fused + self.ao_counts + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic] + [t for _, t in self.deform]
 
     def run(self, stream=None):
         """Enqueue one frame on `stream` (a torch.cuda.Stream; None = the current stream).  No host synchronisation.  The first frame on
@@ -210,6 +247,12 @@ class WavefrontPaths:
                 a.shadow_rays_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.light, self.shadow_rays[b].data_ptr(),
                                      bias=self.bias, stream=st)
                 a.trace_device(self.shadow_rays[b].data_ptr(), self.shadow_hits[b].data_ptr(), n, mode="any", stream=st)
+            if self.ao_samples > 0:
+                with torch.cuda.stream(s):  # the call accumulates: zero on the frame's stream, whichever stream is current
+                    self.ao_counts[b].zero_()
+                a.ambient_occlusion_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.ao_samples, self.ao_counts[b].data_ptr(),
+                                           max_dist=self.ao_distance, seed=self.seed, depth=b, bias=self.bias,
+                                           d_path_in=self.path_ids[b].data_ptr(), stream=st)
             if b + 1 >= self.depth:
                 break
             src = cnt = None
@@ -242,8 +285,9 @@ class WavefrontPaths:
 
     def traced_rays(self):
         """Ray slots one frame traces: per depth one closest-hit pass (primary or bounce) and one any-hit pass (shadow) over every slot,
-        dead ones included -- with fused_shadows one any-hit item per slot and light, with shadow_samples > 1 per slot, light and sample."""
-        return self.n * (1 + (self.n_lights * self.shadow_samples if self.fused_shadows else 1)) * self.depth
+        dead ones included -- with fused_shadows one any-hit item per slot and light, with shadow_samples > 1 per slot, light and sample;
+        with ao_samples > 0 one more any-hit item per slot and sample."""
+        return self.n * (1 + (self.n_lights * self.shadow_samples if self.fused_shadows else 1)) * self.depth + self.n * self.ao_samples * self.depth
 
 
 def c4_bounce_rays_device(accel, d_rays, d_hits, n_primary, n_rays, d_out, seed=0xC4, stream=None):
