@@ -791,6 +791,29 @@ int rc_get_illumination_dirs_device(rc_scene* scene, const float* d_dirs, uint32
                                     uint64_t row_stride, void* stream);
 int rc_generate_ray_grid_dirs_device(rc_scene* scene, const float* d_dirs, uint32_t n_dirs, uint32_t grid, rc_ray* d_rays, void* stream);
 
+/* ---- View-factor products: the view-factor matrix APPLIED TO A VECTOR, without the matrix: what a radiosity iteration
+ * B <- E + rho .* (M * B) ./ R needs of view_factors (src/kernels.jl:74-104).  With M = the reference's result[src_meta, hit_meta], every counted ray (the rule of :93-97) from
+ * a source with metadata a that hits metadata b adds
+ *     mx [a-1] += x[b-1]        (M  x)[a-1]
+ *     mtx[b-1] += x[a-1]        (M^T x)[b-1]
+ * x: n_prims u32, indexed by metadata - 1 like the totals vectors; mx, mtx: n_prims u64, sums modulo 2^64 -- integer adds, exact in any
+ * order, so every partition of sources x rays gives the same words; either output may be NULL.  Same rays (Philox keyed by seed, ray
+ * index, source primitive) and the same counting rule as rc_view_factors, so the vectors equal that matrix times x exactly, and with
+ * x = 1 they are `emitted` and `received` of rc_view_factor_totals.  x is read only for counted rays, whose metadata are both in 1..N:
+ * metadata 0 or above N never index it.  No N x N array exists anywhere; the call costs the tracing.
+ * _device: rays [ray_begin, ray_end) of the sources with flat primitive indices [src_begin, src_end), clamped to the scene, ACCUMULATED
+ *   into device vectors on the caller's stream; an empty range enqueues nothing.  The argument list is rc_view_factor_totals_device's with
+ *   d_x in front of the outputs, and so are the rules: the hot vector (d_mtx) is counted into private copies and added atomically at the
+ *   end of the launch, scratch is per stream, shards accumulate on one stream or concurrently on several, and the call may be captured
+ *   on a stream that has run it eagerly once, like rc_get_illumination_dirs_device.  It is the shard unit of a multi-process run
+ *   (torch.distributed reduce of 2 N int64).  RC_ERR_INVALID_ARGUMENT for a NULL scene, a NULL d_x or both outputs NULL;
+ *   RC_ERR_NOT_SYNCED as the other *_device queries.
+ * rc_view_factor_products: host arrays, all sources and rays, the outputs OVERWRITTEN.
+ * Register and scratch figures of the three kernel shells and the cost beside the totals call: docs/EXPERIMENTS.md, "View-factor products". */
+int rc_view_factor_products_device(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end,
+                                   uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_x, uint64_t* d_mx, uint64_t* d_mtx, void* stream);
+int rc_view_factor_products(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, const uint32_t* x, uint64_t* out_mx, uint64_t* out_mtx);
+
 /* ---- Ambient occlusion: how open is the hemisphere above every hit?  `samples` cosine-weighted any_hit rays of length max_dist per hit; the
  * visible fraction count / samples is the cosine-weighted openness of the point (with max_dist = +Inf its sky-view factor, the per-point form
  * of what rc_get_illumination_device and rc_view_factor_totals answer per triangle).

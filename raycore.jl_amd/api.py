@@ -596,6 +596,17 @@ class TLAS:
         rs = self.n_primitives() if row_stride is None else int(row_stride)
         check(lib().rc_get_illumination_dirs_device(self._h, ptr(d_dirs), int(n_dirs), int(grid), ptr(d_counts), rs, ptr(stream) if stream else None))
 
+    def view_factor_products_device(self, x_ptr, mx_ptr, mtx_ptr, rays_per_triangle, seed, src=None, rays=None, stream=None):
+        """The view-factor matrix applied to a device vector without the matrix (rc_view_factor_products_device).  x_ptr: N u32 indexed
+        by metadata - 1; mx_ptr / mtx_ptr: N u64 each (either may be None), ACCUMULATED: mx += M x, mtx += M^T x with M what
+        view_factors(accel, rays_per_triangle, seed) returns, modulo 2^64.  src / rays: (begin, end) ranges of flat source primitives and
+        of ray indices (default: all) -- the shards of one job add up to the whole, on one stream or on several."""
+        s0, s1 = (0, 0xFFFFFFFF) if src is None else src
+        r0, r1 = (0, int(rays_per_triangle)) if rays is None else rays
+        check(lib().rc_view_factor_products_device(self._h, int(rays_per_triangle), int(seed), int(s0), int(s1), int(r0), int(r1), ptr(x_ptr),
+                                                   ptr(mx_ptr) if mx_ptr else None, ptr(mtx_ptr) if mtx_ptr else None,
+                                                   ptr(stream) if stream else None))
+
     def ray_grid_dirs_device(self, d_dirs, n_dirs, grid, d_rays, stream=None):
         """The ray grids of n_dirs device-resident directions (rc_generate_ray_grid_dirs_device): n_dirs x grid^2 RTRay records, direction
         d's at d * grid^2 in generate_ray_grid's layout, laid out on the device from the TLAS root as it is when the kernel runs."""
@@ -988,6 +999,154 @@ def view_factor_totals_multi(accels, rays_per_triangle=10000, seed=0):
     handles = (C.c_void_p * len(owners))(*[o._h for o in owners])
     check(lib().rc_view_factor_totals_multi(handles, len(owners), int(rays_per_triangle), int(seed), ptr(received), ptr(emitted)))
     return received, emitted
+
+
+U32_MAX = (1 << 32) - 1
+REFLECTANCE_ONE = 1 << 16  # view_factor_bounces' reflectance is 16.16 fixed point
+
+
+def check_products_x(x, n=None):
+    """x of view_factor_products: a uint32 vector (of length n, once the primitive count is known)."""
+    if not isinstance(x, np.ndarray) or x.dtype != np.uint32 or x.ndim != 1:
+        raise ValueError("x must be a one-dimensional uint32 array with one value per primitive")
+    if n is not None and len(x) != n:
+        raise ValueError(f"x must hold one value per primitive: {len(x)} values for {n} primitives")
+    return np.ascontiguousarray(x)
+
+
+def view_factor_products(accel, x, rays_per_triangle=10000, seed=0):
+    """The view-factor matrix applied to a vector WITHOUT the N x N matrix (rc_view_factor_products): (mx, mtx), uint64 vectors with
+    mx = M @ x and mtx = M.T @ x modulo 2^64, M = view_factors(accel, rays_per_triangle, seed) as a [src_meta - 1, hit_meta - 1] array.
+    x: uint32, length N.  With x = 1 these are view_factor_totals' emitted and received.  Costs the tracing only."""
+    check_products_x(x)
+    t = _owner(accel)
+    n = t.n_primitives()
+    x = check_products_x(x, n)
+    mx, mtx = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    check(lib().rc_view_factor_products(t._h, int(rays_per_triangle), int(seed), ptr(x), ptr(mx), ptr(mtx)))
+    return mx, mtx
+
+
+def _is_tensor(a):
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def _u32_values(a, what, limit=U32_MAX):
+    """A vector of integers in 0..limit as int64: a numpy integer array, or a device int64 / int32 torch tensor (int32: read as the bit
+    patterns of u32 words).  Out of range: ValueError -- for a numpy array before anything touches the device."""
+    if _is_tensor(a):
+        import torch
+        if a.dtype not in (torch.int64, torch.int32) or a.dim() != 1:
+            raise ValueError(f"{what} must be a one-dimensional int64 or int32 tensor (or a numpy integer array)")
+        v = a.to(torch.int64)
+        if a.dtype == torch.int32:
+            v = v & U32_MAX
+        if v.numel() and (int(v.min()) < 0 or int(v.max()) > limit):
+            raise ValueError(f"{what} must lie in 0..{limit}")
+        return v
+    v = np.asarray(a)
+    if v.ndim != 1 or v.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be a one-dimensional integer array")
+    if v.size and (int(v.min()) < 0 or int(v.max()) > limit):
+        raise ValueError(f"{what} must lie in 0..{limit}")
+    return v.astype(np.int64)
+
+
+def check_bounce_arguments(emission, reflectance, bounces, rays_per_triangle):
+    """The arguments of view_factor_bounces, checked before the library is touched: (emission, reflectance) as int64 vectors of equal length."""
+    if isinstance(bounces, bool) or int(bounces) != bounces or bounces < 0:
+        raise ValueError("bounces must be a non-negative integer")
+    if isinstance(rays_per_triangle, bool) or int(rays_per_triangle) != rays_per_triangle or not 1 <= rays_per_triangle < (1 << 31):
+        raise ValueError("rays_per_triangle must be in 1..2^31 - 1: (M x)[i] <= rays_per_triangle * (2^32 - 1) has to fit int64")
+    e = _u32_values(emission, "emission")
+    rho = _u32_values(reflectance, "reflectance", REFLECTANCE_ONE)
+    if len(e) != len(rho):
+        raise ValueError("emission and reflectance must have one value per primitive each")
+    return e, rho
+
+
+def view_factor_bounces(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, stream=None):
+    """`bounces` steps of the radiosity iteration with the reference's sampled view-factor matrix, in integers, on the device:
+
+        x_0 = e,    x_{k+1}[i] = min(2^32 - 1, e[i] + (((M x_k)[i] // R) * rho[i] >> 16))
+
+    M is what view_factors(accel, R, seed) returns, as a [src_meta - 1, hit_meta - 1] array, R = rays_per_triangle: the REFERENCE's matrix,
+    whose rays leave a triangle uniformly over the hemisphere -- view factors as the reference defines them, not cosine-corrected form
+    factors.  The same seed is used every bounce, so this is the iteration with that one matrix, and every step is exact: no float is
+    involved, and the result does not depend on how the device orders its adds.
+    emission: u32 per primitive (indexed by metadata - 1); reflectance: 0..65536, 16.16 fixed point (65536 = 1.0).  Both are numpy integer
+    arrays or device int64 / int32 torch tensors (int32: the bit patterns of u32 words).  Each bounce is zero -> view_factor_products_device
+    -> an elementwise torch update, all on `stream` (a torch stream or a raw handle; default: the current one) with no host wait between
+    bounces; the matrix never exists.  Returns x: a uint32 numpy array for numpy input, else an int64 tensor on the device, ready on `stream`.
+    ValueError for reflectance > 65536, values outside u32, or rays_per_triangle >= 2^31 ((M x)[i] must fit torch's int64)."""
+    e, rho = check_bounce_arguments(emission, reflectance, bounces, rays_per_triangle)
+    import torch
+    t = _owner(accel)
+    n = t.n_primitives()
+    if len(e) != n:
+        raise ValueError(f"emission and reflectance must hold one value per primitive: {len(e)} values for {n} primitives")
+    dev = torch.device("cuda", t.device)
+    on_host = not _is_tensor(e)
+    ts = stream if isinstance(stream, torch.cuda.Stream) else (torch.cuda.ExternalStream(int(stream), device=dev) if stream else torch.cuda.current_stream(dev))
+    with torch.cuda.stream(ts):
+        e, rho = (torch.from_numpy(a).to(dev) if not _is_tensor(a) else a.to(dev) for a in (e, rho))
+        for a in (e, rho):
+            a.record_stream(ts)  # (a caller's tensor, or its int64 copy made on the stream the caller was on)
+        x = e.clone()
+        x32 = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        mx = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        for _ in range(int(bounces)):
+            bounce_step(t, e, rho, x, x32, mx, int(rays_per_triangle), int(seed), ts.cuda_stream)
+    if on_host:
+        ts.synchronize()
+        t.wait_for_gpu()  # (reports a traversal stack overflow)
+        return x.cpu().numpy().astype(np.uint32)
+    return x
+
+
+def bounce_step(t, e, rho, x, x32, mx, rays_per_triangle, seed, stream):
+    """One bounce of view_factor_bounces on the current torch stream, whose raw handle is `stream`: x (int64, values in u32) is replaced by
+    the next iterate; x32 (int32) and mx (int64) are scratch of the same length.  Nothing here waits for the device, so a loop of steps may
+    be captured into a graph (after one eager step)."""
+    import torch
+    n = x.numel()
+    x32[:n].copy_(x.view(torch.int32).view(n, 2)[:, 0])  # the low words: x as u32
+    mx.zero_()
+    t.view_factor_products_device(x32.data_ptr(), mx.data_ptr(), None, rays_per_triangle, seed, stream=stream)
+    nxt = e + ((torch.div(mx[:n], rays_per_triangle, rounding_mode="floor") * rho) >> 16)  # (M x)[i] < 2^63: non-negative in int64
+    x.copy_(nxt.clamp_(max=U32_MAX))
+
+
+def radiosity_scale(emission, reflectance):
+    """The quantisation of radiosity(): (scale, e_q, rho_q) with e_q = floor(e * scale) u32 and rho_q = rint(rho * 65536); scale leaves the
+    headroom 1 / (1 - max rho) of the converged solution below 2^32.  ValueError unless e is finite and >= 0 and rho lies in [0, 1)."""
+    e = np.asarray(emission, dtype=np.float64)
+    rho = np.asarray(reflectance, dtype=np.float64)
+    if e.ndim != 1 or rho.shape != e.shape:
+        raise ValueError("emission and reflectance must be vectors with one value per primitive each")
+    if not np.isfinite(e).all() or (e < 0).any():
+        raise ValueError("emission must be finite and non-negative")
+    if not (np.isfinite(rho).all() and (rho >= 0).all() and (rho < 1).all()):
+        raise ValueError("reflectance must lie in [0, 1)")
+    rho_q = np.rint(rho * REFLECTANCE_ONE).astype(np.int64)
+    top = min(int(rho_q.max()), REFLECTANCE_ONE - 1) / REFLECTANCE_ONE if rho_q.size else 0.0
+    e_max = float(e.max()) if e.size else 0.0
+    scale = U32_MAX * (1.0 - top) / e_max if e_max > 0 else 1.0
+    e_q = np.minimum(np.floor(e * scale), U32_MAX).astype(np.int64)
+    return scale, e_q, rho_q
+
+
+def radiosity(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, stream=None, return_scale=False):
+    """Radiosity by `bounces` steps of B <- E + rho .* (M B) / R in float terms: the convenience on top of view_factor_bounces.
+    M is the REFERENCE's view-factor matrix view_factors(accel, R, seed), sampled with its uniform-hemisphere rays -- view factors as the
+    reference defines them, NOT cosine-corrected form factors.  emission: float array >= 0; reflectance: float array in [0, 1) (ValueError
+    otherwise).  e is quantised to u32 with a scale that leaves the headroom 1 / (1 - max rho) below 2^32, rho to 16.16 fixed point
+    (radiosity_scale), the iteration runs in integers on the device, and the result is scaled back to float64.
+    return_scale: also return the scale (result = integer iterate / scale; one quantisation step is 1 / scale)."""
+    scale, e_q, rho_q = radiosity_scale(emission, reflectance)
+    x = view_factor_bounces(accel, e_q, rho_q, bounces, rays_per_triangle, seed, stream)
+    b = x.astype(np.float64) / scale
+    return (b, scale) if return_scale else b
 
 
 def multi_prepare(accels):

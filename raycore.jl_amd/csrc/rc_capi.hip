@@ -1557,6 +1557,37 @@ int rc_view_factor_totals_device(rc_scene* s, uint32_t rays_per_triangle, uint64
                             reinterpret_cast<unsigned long long*>(d_emitted), (hipStream_t)stream);
     });
 }
+// The view-factor matrix applied to a vector, M x and M^T x, without the matrix (ViewFactorProductsSink, rc_drivers.hip).
+int rc_view_factor_products_device(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin,
+                                   uint32_t ray_end, const uint32_t* d_x, uint64_t* d_mx, uint64_t* d_mtx, void* stream) {
+    if (!s || !d_x || (!d_mx && !d_mtx)) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        rc_launch_vf_products(s, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, d_x, reinterpret_cast<unsigned long long*>(d_mx),
+                              reinterpret_cast<unsigned long long*>(d_mtx), (hipStream_t)stream);
+    });
+}
+// Host arrays: x goes up behind the two zeroed vectors of the scene's staging area, one launch over all sources and rays, the vectors come back.
+int rc_view_factor_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, const uint32_t* x, uint64_t* out_mx, uint64_t* out_mtx) {
+    if (!s || !x || (!out_mx && !out_mtx)) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded([&] {
+        use_device(s);
+        require_synced_host(s);
+        std::lock_guard<std::mutex> one_at_a_time(s->host_call_mu);
+        const uint32_t n = s->n_flat_prims;
+        if (n == 0) return;
+        s->u64_stage.reserve((size_t)2 * n + (n + 1u) / 2u);  // mx[N], mtx[N], then x[N] in u32
+        unsigned long long* d_mx = s->u64_stage.p;
+        uint32_t* d_x = reinterpret_cast<uint32_t*>(d_mx + (size_t)2 * n);
+        RC_HIP(hipMemsetAsync(d_mx, 0, sizeof(unsigned long long) * 2u * n, s->stream));
+        RC_HIP(hipMemcpyAsync(d_x, x, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s->stream));
+        rc_launch_vf_products(s, rays_per_triangle, seed, 0, n, 0, rays_per_triangle, d_x, out_mx ? d_mx : nullptr, out_mtx ? d_mx + n : nullptr, s->stream);
+        if (out_mx) RC_HIP(hipMemcpyAsync(out_mx, d_mx, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, s->stream));
+        if (out_mtx) RC_HIP(hipMemcpyAsync(out_mtx, d_mx + n, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, s->stream));
+        check_status(s, s->stream);
+    });
+}
 int rc_view_factor_totals_multi(rc_scene* const* scenes, int n_scenes, uint32_t rays_per_triangle, uint64_t seed, uint64_t* out_received, uint64_t* out_emitted) {
     if (!scenes || n_scenes < 1 || (!out_received && !out_emitted)) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
     return guarded([&] {

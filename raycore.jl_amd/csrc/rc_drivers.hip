@@ -492,6 +492,67 @@ struct ViewFactorTotalsJob {
 // Keeps the pointer form of the interior loop's stack position in the plain shell: 79 VGPRs, 36 bytes of private segment with the integer form.
 template <>
 struct JobShapeFlags<ViewFactorTotalsJob> { static constexpr unsigned kPlain = ShapePtrStack, kLds = 0u, kPartial = 0u; };
+// The weighted sibling of wave_count: acc[index] += value from every active lane, one atomic per group of equal targets carrying the group's
+// SUM.  Called under phased_trace's `if (fin)`, by a divergent subset of the wave, so it reads no lane it has not just balloted: the leader's
+// index with a readlane, then the group's values one readlane per set bit of the group's ballot, added in scalar registers (u64: 64 values
+// of up to 2^32 - 1 need 38 bits).  A butterfly over all 64 lanes would read registers of lanes that are not executing.
+// (Also built: bit-plane ballots, sum = sum_b 2^b * popcount(ballot(in group && bit b of value)), 32 ballots whatever the group's size --
+// docs/EXPERIMENTS.md, "View-factor products".)
+__device__ inline void wave_add(unsigned long long* acc, uint32_t index, uint32_t value, bool active) {
+    bool pending = active;
+#pragma unroll 1
+    for (int r = 0; r < 4; ++r) {
+        const unsigned long long act = __ballot(pending);
+        if (!act) return;
+        const int leader = __ffsll((long long)act) - 1;
+        const uint32_t target = (uint32_t)__builtin_amdgcn_readlane((int)index, leader);
+        const bool same = pending && index == target;
+        const unsigned long long grp = __ballot(same);
+        unsigned long long sum = 0;
+#pragma unroll 1
+        for (unsigned long long m = grp; m; m &= m - 1ull) sum += (uint32_t)__builtin_amdgcn_readlane((int)value, __ffsll((long long)m) - 1);
+        if ((int)(threadIdx.x & 63u) == leader) atomicAdd(acc + index, sum);
+        pending = pending && !same;
+        if (__popcll(grp) == 1) break;  // a group of one: the targets are probably all different, stop looking for duplicates
+    }
+    if (pending) atomicAdd(acc + index, (unsigned long long)value);
+}
+// The view-factor matrix applied to a vector without the matrix (rc_view_factor_products*): with M = the reference's
+// result[src_meta, hit_meta] (:93-97), every counted ray from metadata a that hits metadata b adds x[b - 1] to mx[a - 1] = (M x)[a - 1] and
+// x[a - 1] to mtx[b - 1] = (M^T x)[b - 1], in u64 modulo 2^64 -- exact in any order, so any partition of sources x rays gives the same
+// words.  Same source, same rays, same counting rule as ViewFactorTotalsSink, whose vectors these are for x = 1.  x is read for counted rays
+// only: both metadata are in 1..N then.  mtx is the hot vector and goes through the copy histogram like `received`; mx is per source and
+// nearly wave-uniform in its target like `emitted`, but its lanes add different values (wave_add).
+struct ViewFactorProductsSink {
+    const RcInstRec* inst;
+    const RcPrim* prims;
+    uint32_t n_prims, src_begin, n_ray;
+    const uint32_t* x;
+    unsigned long long* mtx;  // one histogram of scratch words (zeroed by the launcher), or nullptr
+    CopyHist h;
+    unsigned long long* mx;   // [n_prims] or nullptr
+    __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
+        bool counted = false;
+        uint32_t to_meta = 1, src_meta = 1;
+        if (hit) {
+            const uint32_t src = src_begin + (uint32_t)(w / n_ray);
+            const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
+            to_meta = prims[m3.y + prim - 1u].meta; src_meta = prims[src].meta;
+            counted = to_meta != src_meta && src_meta >= 1 && src_meta <= n_prims && to_meta >= 1 && to_meta <= n_prims;
+        }
+        if (mtx) wave_add(mtx + h.base(h.copy()), h.slot(to_meta - 1u), counted ? x[src_meta - 1u] : 0u, counted);
+        if (mx) wave_add(mx, src_meta - 1u, counted ? x[to_meta - 1u] : 0u, counted);
+    }
+};
+struct ViewFactorProductsJob {
+    uint32_t k0, k1, src_begin, ray_begin, n_ray;
+    const uint32_t* x;
+    unsigned long long* mtx;
+    CopyHist h;
+    unsigned long long* mx;
+    __device__ inline ViewFactorSource source(const SceneView& v) const { return ViewFactorSource{v.prims, nullptr, k0, k1, src_begin, ray_begin, n_ray}; }
+    __device__ inline ViewFactorProductsSink sink(const SceneView& v) const { return ViewFactorProductsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, x, mtx, h, mx}; }
+};
 struct ViewFactorJob {
     uint32_t k0, k1, src_begin, ray_begin, n_ray;
     uint32_t* matrix;
@@ -1080,6 +1141,22 @@ void rc_launch_vf_totals(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
     unsigned long long* scratch = d_received ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
     launch.go<false>(ViewFactorTotalsJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, scratch, h, d_emitted}, Nothing(),
                      [&] { if (d_received) rc_hist_fold(stream, scratch, h, np, FoldAddU64{{}, d_received}); });
+}
+
+// The products (M x, M^T x) of the same shard with the device vector d_x (n_prims u32), ACCUMULATED into d_mx / d_mtx (n_prims u64 each, device;
+// either may be nullptr).  The launch of rc_launch_vf_totals with ViewFactorProductsJob: d_mtx takes `received`'s copy histogram and fold.
+void rc_launch_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin,
+                           uint32_t ray_end, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx, hipStream_t stream) {
+    if (src_end > s->n_flat_prims) src_end = s->n_flat_prims;
+    if (ray_end > rays_per_triangle) ray_end = rays_per_triangle;
+    if (src_begin >= src_end || ray_begin >= ray_end || (!d_mx && !d_mtx)) return;
+    const uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
+    DriverLaunch launch(s, stream, total);
+    const uint32_t np = s->n_flat_prims;
+    const CopyHist h = CopyHist::of(np);
+    unsigned long long* scratch = d_mtx ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
+    launch.go<false>(ViewFactorProductsJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, d_x, scratch, h, d_mx}, Nothing(),
+                     [&] { if (d_mtx) rc_hist_fold(stream, scratch, h, np, FoldAddU64{{}, d_mtx}); });
 }
 
 // Kernels outside RcLaunchGuard that read scene memory on a caller's stream (the wavefront stages): remember the stream's latest such

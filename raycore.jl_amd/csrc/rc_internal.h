@@ -503,6 +503,8 @@ void rc_vf_source_range(rc_scene* s, uint32_t row_begin, uint32_t row_end, uint3
 // rc_multi.hip
 void rc_launch_vf_totals(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin,
                          uint32_t ray_end, unsigned long long* d_received, unsigned long long* d_emitted, hipStream_t stream);
+void rc_launch_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin,
+                           uint32_t ray_end, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx, hipStream_t stream);
 void rc_multi_prepare_impl(rc_scene* const* scenes, int n_scenes, float out_ms[4]);
 int rc_multi_ranks_impl(rc_scene* const* scenes, int n_scenes);
 void rc_view_factor_totals_multi_impl(rc_scene* const* scenes, int n_scenes, uint32_t rays_per_triangle, uint64_t seed, uint64_t* out_received, uint64_t* out_emitted);

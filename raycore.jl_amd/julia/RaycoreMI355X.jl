@@ -307,6 +307,27 @@ view_factor_totals_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, seed
                            ray_end::Integer, d_received::Ptr{UInt64}, d_emitted::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_view_factor_totals_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
                 a.owner.ptr, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, d_received, d_emitted, stream))
+"""
+    view_factor_products(accel, x::Vector{UInt32}; rays_per_triangle, seed) -> (mx::Vector{UInt64}, mtx::Vector{UInt64})
+
+The view-factor matrix applied to a vector without the N x N matrix: with `M = view_factors(accel; rays_per_triangle, seed)`,
+`mx == M * x` and `mtx == M' * x` in UInt64 arithmetic (modulo 2^64), what a radiosity iteration `B <- E + rho .* (M * B) ./ R` needs of
+the matrix.  `x` has one value per primitive, indexed by metadata.  With `x = ones` these are `emitted` and `received` of
+`view_factor_totals`.  Costs the tracing only.
+"""
+function view_factor_products(a::MI355XStaticTLAS, x::Vector{UInt32}; rays_per_triangle = 10000, seed::UInt64 = rand(UInt64))
+    n = counts(a.owner)[4]
+    length(x) == n || throw(ArgumentError("x must hold one value per primitive"))
+    mx, mtx = Vector{UInt64}(undef, n), Vector{UInt64}(undef, n)
+    check(ccall((:rc_view_factor_products, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}), a.owner.ptr, rays_per_triangle, seed, x, mx, mtx))
+    return mx, mtx
+end
+"One shard of the products (sources [src_begin, src_end) x rays [ray_begin, ray_end)) with the device vector `d_x` (N UInt32), ACCUMULATED
+into device vectors of N UInt64 each (either may be C_NULL): the unit of a multi-process run, and of a device-resident bounce iteration."
+view_factor_products_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, seed::UInt64, src_begin::Integer, src_end::Integer, ray_begin::Integer,
+                             ray_end::Integer, d_x::Ptr{UInt32}, d_mx::Ptr{UInt64}, d_mtx::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_view_factor_products_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
+                a.owner.ptr, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, d_x, d_mx, d_mtx, stream))
 "Rows [row_begin, row_end) (0-based, end exclusive) of the matrix into `out` (column-major, any leading dimension >= N): the unit of a
 multi-process run, where every process maps the same shared-memory matrix (`Mmap.mmap` of a file in /dev/shm) and fills its own rows."
 function view_factors_rows!(out::AbstractMatrix{UInt32}, a::MI355XStaticTLAS, row_begin::Integer, row_end::Integer; rays_per_triangle = 10000, seed::UInt64)
