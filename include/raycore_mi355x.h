@@ -814,6 +814,43 @@ int rc_view_factor_products_device(rc_scene* scene, uint32_t rays_per_triangle, 
                                    uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_x, uint64_t* d_mx, uint64_t* d_mtx, void* stream);
 int rc_view_factor_products(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, const uint32_t* x, uint64_t* out_mx, uint64_t* out_mtx);
 
+/* ---- Sparse view-factor matrix: the matrix of view_factors (src/kernels.jl:74-104) ITSELF, as CSR, built once on the device.  A source
+ * shoots rays_per_triangle rays, so a row of M = the reference's result[src_meta, hit_meta] has at most min(R, N) non-zeros: the dense N x N
+ * form is the wrong container (4 TB at 1 Mi triangles; the CSR at R = 256 holds at most 256 Mi entries).  Same rays (Philox keyed by seed,
+ * ray index, source primitive) and the same counting rule (:93-97) as rc_view_factors, so the integers are that matrix's.
+ * The call OVERWRITES its outputs with rows [row_begin, row_end) of M (row r <=> metadata r + 1; row_end is clamped to N) in canonical CSR:
+ *   d_row_ptr: rows + 1 u64, d_row_ptr[0] = 0, d_row_ptr[rows] = *d_nnz; entries k in [d_row_ptr[r], d_row_ptr[r + 1]) belong to row
+ *   row_begin + r; d_cols[k] (0-based column = hit metadata - 1) strictly ascending within a row; d_vals[k] >= 1 -- no explicit zeros.
+ * The arrays are therefore a function of (scene, rays_per_triangle, seed, row range) alone: neither the scratch size (option
+ * "vf_sparse_scratch_bytes", default 256 MiB: the job is cut into chunks of WHOLE rows whose rays x 8 bytes fit it; a single larger row gets
+ * a chunk of its own) nor the shape of any kernel changes a word.  Sources with metadata 0 or above N have no row; sources that share a
+ * metadata share a row.  Rows are independent: the blocks of a partition of [0, N) concatenate (each block's d_row_ptr starts at 0) -- row
+ * blocks are the shard unit of a multi-device build.
+ * Capacity (the idiom of rc_collide_instances, without a host read): *d_nnz and ALL of d_row_ptr are always the true values; entries at
+ * positions < capacity are the correct first entries; nothing is written at or beyond capacity; d_cols / d_vals may be NULL when capacity
+ * is 0 -- the counting call.
+ * _device: everything on the caller's stream, no host wait between the steps (trace of one u64 key per ray, radix sort, run-length
+ *   encoding, append; an exclusive scan of the row counts at the end); scratch is per stream, two streams may build at once.  NOT
+ *   capturable: RC_ERR_NOT_SYNCED on a stream that is being captured.  RC_ERR_INVALID_ARGUMENT for a NULL scene, d_row_ptr or d_nnz, NULL
+ *   d_cols / d_vals with capacity > 0, or a row whose sources x rays_per_triangle reaches 2^32.
+ * rc_view_factors_sparse: host arrays, all rows; returns RC_OK and reports *out_nnz, which the caller compares with capacity.
+ *
+ * rc_view_factor_sparse_products_device: the products of a CSR block with a vector, the step of a radiosity iteration once the matrix of
+ * view_factors (src/kernels.jl:74-104) is held sparse.  For block rows r in [0, n_rows) and entries k of row r it ACCUMULATES, modulo 2^64,
+ *     d_mx [row_offset + r] += d_vals[k] * d_x[d_cols[k]]
+ *     d_mtx[d_cols[k]]      += d_vals[k] * d_x[row_offset + r]
+ * either output may be NULL.  With the CSR of the same (rays_per_triangle, seed) the sums equal rc_view_factor_products_device's words bit
+ * for bit -- at the cost of reading nnz x 8 bytes instead of tracing N x R rays again.  Row-parallel, the row bounds are read from
+ * d_row_ptr on the device: capturable, and no host wait is needed behind the build.  The arrays are NOT validated: d_cols[k] < the length
+ * of d_x / d_mtx is the caller's contract.  RC_ERR_INVALID_ARGUMENT for a NULL scene, d_row_ptr or d_x, or both outputs NULL.
+ * Measured build, product and break-even figures: docs/EXPERIMENTS.md, "Sparse view-factor matrix". */
+int rc_view_factors_sparse_device(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, uint32_t row_begin, uint32_t row_end,
+                                  uint64_t* d_row_ptr, uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, uint64_t* d_nnz, void* stream);
+int rc_view_factors_sparse(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, uint64_t* out_row_ptr, uint32_t* out_cols,
+                           uint32_t* out_vals, uint64_t capacity, uint64_t* out_nnz);
+int rc_view_factor_sparse_products_device(rc_scene* scene, uint32_t n_rows, uint32_t row_offset, const uint64_t* d_row_ptr, const uint32_t* d_cols,
+                                          const uint32_t* d_vals, const uint32_t* d_x, uint64_t* d_mx, uint64_t* d_mtx, void* stream);
+
 /* ---- Ambient occlusion: how open is the hemisphere above every hit?  `samples` cosine-weighted any_hit rays of length max_dist per hit; the
  * visible fraction count / samples is the cosine-weighted openness of the point (with max_dist = +Inf its sky-view factor, the per-point form
  * of what rc_get_illumination_device and rc_view_factor_totals answer per triangle).

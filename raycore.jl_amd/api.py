@@ -607,6 +607,24 @@ class TLAS:
                                                    ptr(mx_ptr) if mx_ptr else None, ptr(mtx_ptr) if mtx_ptr else None,
                                                    ptr(stream) if stream else None))
 
+    def view_factors_sparse_device(self, row_ptr_ptr, cols_ptr, vals_ptr, capacity, nnz_ptr, rays_per_triangle, seed, rows=None, stream=None):
+        """Rows `rows` = (begin, end) (default: all; end is clamped to N) of the view-factor matrix in canonical CSR on the device
+        (rc_view_factors_sparse_device), OVERWRITTEN: row_ptr_ptr: rows + 1 u64 starting at 0; cols_ptr / vals_ptr: `capacity` u32 each
+        (None with capacity 0: the counting call); nnz_ptr: one u64.  nnz and row_ptr are always the true values, entries below
+        `capacity` the correct first ones, nothing is written at or beyond it.  Everything runs on `stream`; not capturable."""
+        r0, r1 = (0, 0xFFFFFFFF) if rows is None else rows
+        check(lib().rc_view_factors_sparse_device(self._h, int(rays_per_triangle), int(seed), int(r0), int(r1), ptr(row_ptr_ptr),
+                                                  ptr(cols_ptr) if cols_ptr else None, ptr(vals_ptr) if vals_ptr else None, int(capacity),
+                                                  ptr(nnz_ptr), ptr(stream) if stream else None))
+
+    def view_factor_sparse_products_device(self, n_rows, row_ptr_ptr, cols_ptr, vals_ptr, x_ptr, mx_ptr, mtx_ptr, row_offset=0, stream=None):
+        """The products of a device CSR block with a device vector (rc_view_factor_sparse_products_device), ACCUMULATED modulo 2^64:
+        mx[row_offset + r] += sum_k vals[k] x[cols[k]], mtx[cols[k]] += vals[k] x[row_offset + r]; mx_ptr / mtx_ptr: u64 vectors, either
+        may be None.  Nothing is read on the host: capturable, and needs no wait behind the build.  The arrays are not validated."""
+        check(lib().rc_view_factor_sparse_products_device(self._h, int(n_rows), int(row_offset), ptr(row_ptr_ptr), ptr(cols_ptr) if cols_ptr else None,
+                                                          ptr(vals_ptr) if vals_ptr else None, ptr(x_ptr), ptr(mx_ptr) if mx_ptr else None,
+                                                          ptr(mtx_ptr) if mtx_ptr else None, ptr(stream) if stream else None))
+
     def ray_grid_dirs_device(self, d_dirs, n_dirs, grid, d_rays, stream=None):
         """The ray grids of n_dirs device-resident directions (rc_generate_ray_grid_dirs_device): n_dirs x grid^2 RTRay records, direction
         d's at d * grid^2 in generate_ray_grid's layout, laid out on the device from the TLAS root as it is when the kernel runs."""
@@ -1031,6 +1049,146 @@ def _is_tensor(a):
     return type(a).__module__.split(".")[0] == "torch"
 
 
+def check_csr(row_ptr, cols, vals, n_cols=None):
+    """The arrays of a CSR block, checked on the host before any library call: (row_ptr uint64, cols uint32, vals uint32), contiguous.
+    row_ptr starts at 0, never decreases and ends at len(cols) == len(vals); with n_cols every column index is below it.  ValueError otherwise."""
+    for a, dt, what in ((row_ptr, np.uint64, "row_ptr"), (cols, np.uint32, "cols"), (vals, np.uint32, "vals")):
+        if not isinstance(a, np.ndarray) or a.dtype != dt or a.ndim != 1:
+            raise ValueError(f"{what} must be a one-dimensional {np.dtype(dt).name} array")
+    if len(row_ptr) < 1 or int(row_ptr[0]) != 0:
+        raise ValueError("row_ptr must hold rows + 1 offsets and start at 0")
+    if len(cols) != len(vals) or int(row_ptr[-1]) != len(cols):
+        raise ValueError(f"row_ptr must end at the number of entries: row_ptr[-1] = {int(row_ptr[-1])}, {len(cols)} cols, {len(vals)} vals")
+    if len(row_ptr) > 1 and (row_ptr[1:] < row_ptr[:-1]).any():
+        raise ValueError("row_ptr must not decrease")
+    if n_cols is not None and len(cols) and int(cols.max()) >= n_cols:
+        raise ValueError(f"cols must lie below {n_cols}: the largest is {int(cols.max())}")
+    return np.ascontiguousarray(row_ptr), np.ascontiguousarray(cols), np.ascontiguousarray(vals)
+
+
+class SparseViewFactors(tuple):
+    """A block of rows of the view-factor matrix in CSR: unpacks as (row_ptr uint64, cols uint32, vals uint32) -- the argument order of
+    scipy.sparse.csr_matrix((vals, cols, row_ptr), shape=(len(row_ptr) - 1, n)) -- and remembers what the products need: `accel` (its
+    owner runs the kernels), `n` (columns = length of x), `row_offset` (the matrix row of the block's first row), `rays_per_triangle` and
+    `seed` it was traced with (None for a handmade matrix), `nnz` (the true count: larger than len(cols) after a build whose capacity was
+    too small).  view_factors_sparse returns one whose arrays are ALSO still on the device (device_arrays()); one made from numpy arrays
+    is uploaded on first use."""
+
+    def __new__(cls, row_ptr, cols, vals, accel, n, row_offset=0, rays_per_triangle=None, seed=None, nnz=None, device=None):
+        self = super().__new__(cls, (row_ptr, cols, vals))
+        self.accel, self.n, self.row_offset, self.rays_per_triangle, self.seed = accel, int(n), int(row_offset), rays_per_triangle, seed
+        self.nnz = int(len(cols) if nnz is None else nnz)
+        self._device = device
+        return self
+
+    @classmethod
+    def from_arrays(cls, accel, row_ptr, cols, vals, n=None, row_offset=0, rays_per_triangle=None, seed=None):
+        """A CSR block from host arrays (checked: check_csr).  n: the number of columns (default: row_offset + rows, a square matrix)."""
+        if isinstance(row_offset, bool) or int(row_offset) != row_offset or row_offset < 0:
+            raise ValueError("row_offset must be a non-negative integer")
+        rows = len(row_ptr) - 1 if isinstance(row_ptr, np.ndarray) else 0
+        n = row_offset + rows if n is None else n
+        if isinstance(n, bool) or int(n) != n or n < row_offset + rows or n >= 1 << 32:
+            raise ValueError("n must be an integer with row_offset + rows <= n < 2^32")
+        return cls(*check_csr(row_ptr, cols, vals, n), accel, n, row_offset, rays_per_triangle, seed)
+
+    @property
+    def n_rows(self):
+        return len(self[0]) - 1
+
+    def device_arrays(self):
+        """(row_ptr int64, cols int32, vals int32) torch tensors on the accel's device holding the bit patterns of the unsigned words."""
+        if self._device is None:
+            import torch
+            dev = torch.device("cuda", _owner(self.accel).device)
+            self._device = tuple(torch.from_numpy(a.view(s)).to(dev) for a, s in zip(self, (np.int64, np.int32, np.int32)))
+        return self._device
+
+
+def check_sparse_arguments(rays_per_triangle, seed, rows, capacity):
+    """The arguments of view_factors_sparse, checked before the library is touched."""
+    if isinstance(rays_per_triangle, bool) or int(rays_per_triangle) != rays_per_triangle or not 1 <= rays_per_triangle < (1 << 32):
+        raise ValueError("rays_per_triangle must be an integer in 1..2^32 - 1")
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= seed < (1 << 64):
+        raise ValueError("seed must be an integer in 0..2^64 - 1")
+    if rows is not None:
+        if not isinstance(rows, (tuple, list)) or len(rows) != 2 or any(isinstance(r, bool) or int(r) != r for r in rows) or not 0 <= rows[0] <= rows[1] < (1 << 32):
+            raise ValueError("rows must be (begin, end) with 0 <= begin <= end < 2^32")
+    if capacity is not None and (isinstance(capacity, bool) or int(capacity) != capacity or capacity < 0):
+        raise ValueError("capacity must be None or a non-negative integer")
+
+
+def view_factors_sparse(accel, rays_per_triangle=10000, seed=0, rows=None, capacity=None):
+    """The view-factor matrix itself, SPARSE (rc_view_factors_sparse_device): (row_ptr uint64, cols uint32, vals uint32), the canonical CSR
+    of rows `rows` = (begin, end) (default: all; end is clamped to N) of M = view_factors(accel, rays_per_triangle, seed) as a
+    [src_meta - 1, hit_meta - 1] array -- columns strictly ascending within a row, every value >= 1, row_ptr starting at 0.  The triple is
+    in the argument order of scipy.sparse.csr_matrix((vals, cols, row_ptr), shape=(rows, N)); scipy is not needed here.  A row has at most
+    min(rays_per_triangle, N) entries, so the result has at most rows x rays_per_triangle of them where the dense matrix has N^2 words.
+    capacity=None: a counting call, then a filling call of exactly that size.  With a capacity, one call: the first min(nnz, capacity)
+    entries are returned and `.nnz` of the result is the true count (row_ptr is always the true one).
+    The result is a SparseViewFactors: the arrays stay on the device as well, for view_factor_sparse_products and view_factor_bounces."""
+    check_sparse_arguments(rays_per_triangle, seed, rows, capacity)
+    import torch
+    t = _owner(accel)
+    n = t.n_primitives()
+    r0, r1 = (0, n) if rows is None else (min(int(rows[0]), n), min(int(rows[1]), n))
+    dev = torch.device("cuda", t.device)
+    st = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        head = torch.zeros(r1 - r0 + 2, dtype=torch.int64, device=dev)  # row_ptr[rows + 1], then nnz
+        nnz_ptr = head.data_ptr() + 8 * (r1 - r0 + 1)
+        if capacity is None:
+            t.view_factors_sparse_device(head.data_ptr(), None, None, 0, nnz_ptr, rays_per_triangle, seed, (r0, r1), st.cuda_stream)
+            capacity = int(head[-1].item())
+        entries = torch.zeros((2, max(int(capacity), 1)), dtype=torch.int32, device=dev)
+        t.view_factors_sparse_device(head.data_ptr(), entries[0].data_ptr() if capacity else None, entries[1].data_ptr() if capacity else None,
+                                     int(capacity), nnz_ptr, rays_per_triangle, seed, (r0, r1), st.cuda_stream)
+        st.synchronize()
+        t.wait_for_gpu()  # (reports a traversal stack overflow)
+        nnz = int(head[-1].item())
+        filled = min(nnz, int(capacity))
+        d_row_ptr, d_cols, d_vals = head[:r1 - r0 + 1], entries[0, :filled], entries[1, :filled]
+        host = (d_row_ptr.cpu().numpy().view(np.uint64), d_cols.cpu().numpy().view(np.uint32), d_vals.cpu().numpy().view(np.uint32))
+    return SparseViewFactors(*host, t, n, r0, int(rays_per_triangle), int(seed), nnz, (d_row_ptr, d_cols, d_vals))
+
+
+def view_factor_sparse_products(csr, x):
+    """(mx, mtx) = (M x, M^T x) modulo 2^64 for a CSR block `csr` (a SparseViewFactors: view_factors_sparse's result or
+    SparseViewFactors.from_arrays) and x: uint32, one value per column -- uint64 vectors of the same length, zero outside the block's rows
+    (mx) .  One memory-bound pass over the entries (rc_view_factor_sparse_products_device) where view_factor_products traces every ray
+    again; with the CSR of the same rays_per_triangle and seed the words are equal.  The arrays and x are checked before the library is called."""
+    if not isinstance(csr, SparseViewFactors):
+        raise ValueError("csr must be a SparseViewFactors (view_factors_sparse's result, or SparseViewFactors.from_arrays)")
+    check_products_x(x)
+    if csr.nnz != len(csr[1]):
+        raise ValueError(f"the matrix is truncated: {len(csr[1])} of {csr.nnz} entries (build it with a larger capacity)")
+    check_csr(*csr, csr.n)
+    x = check_products_x(x, csr.n)
+    import torch
+    t = _owner(csr.accel)
+    dev = torch.device("cuda", t.device)
+    st = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        row_ptr, cols, vals = csr.device_arrays()
+        d_x = torch.from_numpy(x.view(np.int32)).to(dev)
+        out = torch.zeros((2, max(csr.n, 1)), dtype=torch.int64, device=dev)
+        t.view_factor_sparse_products_device(csr.n_rows, row_ptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), d_x.data_ptr(), out[0].data_ptr(),
+                                             out[1].data_ptr(), csr.row_offset, st.cuda_stream)
+        st.synchronize()
+        got = out.cpu().numpy().view(np.uint64)
+    return got[0, :csr.n].copy(), got[1, :csr.n].copy()
+
+
+def check_bounce_matrix(matrix):
+    """The matrix of view_factor_bounces: all rows of a traced matrix, complete."""
+    if matrix.rays_per_triangle is None or matrix.seed is None:
+        raise ValueError("the matrix must come from view_factors_sparse: the bounce divides by its rays_per_triangle")
+    if matrix.row_offset != 0 or matrix.n_rows != matrix.n:
+        raise ValueError(f"the matrix must hold all rows: it holds {matrix.n_rows} from row {matrix.row_offset} of {matrix.n}")
+    if matrix.nnz != len(matrix[1]):
+        raise ValueError(f"the matrix is truncated: {len(matrix[1])} of {matrix.nnz} entries (build it with a larger capacity)")
+
+
 def _u32_values(a, what, limit=U32_MAX):
     """A vector of integers in 0..limit as int64: a numpy integer array, or a device int64 / int32 torch tensor (int32: read as the bit
     patterns of u32 words).  Out of range: ValueError -- for a numpy array before anything touches the device."""
@@ -1078,11 +1236,20 @@ def view_factor_bounces(accel, emission, reflectance, bounces, rays_per_triangle
     arrays or device int64 / int32 torch tensors (int32: the bit patterns of u32 words).  Each bounce is zero -> view_factor_products_device
     -> an elementwise torch update, all on `stream` (a torch stream or a raw handle; default: the current one) with no host wait between
     bounces; the matrix never exists.  Returns x: a uint32 numpy array for numpy input, else an int64 tensor on the device, ready on `stream`.
-    ValueError for reflectance > 65536, values outside u32, or rays_per_triangle >= 2^31 ((M x)[i] must fit torch's int64)."""
+    ValueError for reflectance > 65536, values outside u32, or rays_per_triangle >= 2^31 ((M x)[i] must fit torch's int64).
+    `accel` may be the MATRIX instead: a SparseViewFactors holding all rows (view_factors_sparse(accel, R, seed)).  Then nothing is traced:
+    each bounce is zero -> view_factor_sparse_products_device (mx only) -> the same update, with the matrix's own accel, rays_per_triangle and
+    seed (the two keyword arguments are not read), and the result is word for word the retraced one."""
+    matrix = accel if isinstance(accel, SparseViewFactors) else None
+    if matrix is not None:
+        check_bounce_matrix(matrix)
+        accel, rays_per_triangle, seed = matrix.accel, matrix.rays_per_triangle, matrix.seed
     e, rho = check_bounce_arguments(emission, reflectance, bounces, rays_per_triangle)
+    if matrix is not None and len(e) != matrix.n:
+        raise ValueError(f"emission and reflectance must hold one value per primitive: {len(e)} values for {matrix.n} primitives")
     import torch
     t = _owner(accel)
-    n = t.n_primitives()
+    n = t.n_primitives() if matrix is None else matrix.n
     if len(e) != n:
         raise ValueError(f"emission and reflectance must hold one value per primitive: {len(e)} values for {n} primitives")
     dev = torch.device("cuda", t.device)
@@ -1096,7 +1263,10 @@ def view_factor_bounces(accel, emission, reflectance, bounces, rays_per_triangle
         x32 = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         mx = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
         for _ in range(int(bounces)):
-            bounce_step(t, e, rho, x, x32, mx, int(rays_per_triangle), int(seed), ts.cuda_stream)
+            if matrix is None:
+                bounce_step(t, e, rho, x, x32, mx, int(rays_per_triangle), int(seed), ts.cuda_stream)
+            else:
+                bounce_step_sparse(matrix, e, rho, x, x32, mx, ts.cuda_stream)
     if on_host:
         ts.synchronize()
         t.wait_for_gpu()  # (reports a traversal stack overflow)
@@ -1114,6 +1284,20 @@ def bounce_step(t, e, rho, x, x32, mx, rays_per_triangle, seed, stream):
     mx.zero_()
     t.view_factor_products_device(x32.data_ptr(), mx.data_ptr(), None, rays_per_triangle, seed, stream=stream)
     nxt = e + ((torch.div(mx[:n], rays_per_triangle, rounding_mode="floor") * rho) >> 16)  # (M x)[i] < 2^63: non-negative in int64
+    x.copy_(nxt.clamp_(max=U32_MAX))
+
+
+def bounce_step_sparse(matrix, e, rho, x, x32, mx, stream):
+    """bounce_step with the matrix held sparse on the device (a SparseViewFactors with all rows): the same zero -> M x -> update, the product
+    being one pass over the entries.  Nothing waits for the device or reads it on the host, so the step may be captured at once."""
+    import torch
+    n = x.numel()
+    row_ptr, cols, vals = matrix.device_arrays()
+    x32[:n].copy_(x.view(torch.int32).view(n, 2)[:, 0])
+    mx.zero_()
+    _owner(matrix.accel).view_factor_sparse_products_device(n, row_ptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), x32.data_ptr(), mx.data_ptr(), None,
+                                                           0, stream)
+    nxt = e + ((torch.div(mx[:n], matrix.rays_per_triangle, rounding_mode="floor") * rho) >> 16)
     x.copy_(nxt.clamp_(max=U32_MAX))
 
 
@@ -1136,15 +1320,19 @@ def radiosity_scale(emission, reflectance):
     return scale, e_q, rho_q
 
 
-def radiosity(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, stream=None, return_scale=False):
+def radiosity(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, stream=None, return_scale=False, matrix=None):
     """Radiosity by `bounces` steps of B <- E + rho .* (M B) / R in float terms: the convenience on top of view_factor_bounces.
     M is the REFERENCE's view-factor matrix view_factors(accel, R, seed), sampled with its uniform-hemisphere rays -- view factors as the
     reference defines them, NOT cosine-corrected form factors.  emission: float array >= 0; reflectance: float array in [0, 1) (ValueError
     otherwise).  e is quantised to u32 with a scale that leaves the headroom 1 / (1 - max rho) below 2^32, rho to 16.16 fixed point
     (radiosity_scale), the iteration runs in integers on the device, and the result is scaled back to float64.
-    return_scale: also return the scale (result = integer iterate / scale; one quantisation step is 1 / scale)."""
+    return_scale: also return the scale (result = integer iterate / scale; one quantisation step is 1 / scale).
+    matrix: the SparseViewFactors of view_factors_sparse(accel, rays_per_triangle, seed) -- the bounces then apply it instead of tracing
+    (view_factor_bounces); the result is the same."""
     scale, e_q, rho_q = radiosity_scale(emission, reflectance)
-    x = view_factor_bounces(accel, e_q, rho_q, bounces, rays_per_triangle, seed, stream)
+    if matrix is not None and not isinstance(matrix, SparseViewFactors):
+        raise ValueError("matrix must be a SparseViewFactors (view_factors_sparse's result)")
+    x = view_factor_bounces(accel if matrix is None else matrix, e_q, rho_q, bounces, rays_per_triangle, seed, stream)
     b = x.astype(np.float64) / scale
     return (b, scale) if return_scale else b
 

@@ -1372,6 +1372,7 @@ int rc_set_option(rc_scene* s, const char* name, int64_t value) {
     }
     else if (k == "vf_chunk_bytes") s->opt.vf_chunk_bytes = value < 4096 ? 4096 : (value > (int64_t(4) << 30) ? (int64_t(4) << 30) : value);
     else if (k == "illum_scratch_bytes") s->opt.illum_scratch_bytes = value < 1 ? 1 : (value > (int64_t(4) << 30) ? (int64_t(4) << 30) : value);  // (a launch always gets one direction's worth)
+    else if (k == "vf_sparse_scratch_bytes") s->opt.vf_sparse_scratch_bytes = value < 8 ? 8 : (value > (int64_t(16) << 30) ? (int64_t(16) << 30) : value);  // (a chunk always gets one whole row)
     else if (k == "timeline_ptr") s->opt.timeline_ptr = value;  // dev instrumentation: the caller owns the buffer and its size (8 x u64 per wave of the launch)
     else if (k == "debug_set_overflow") {  // test hook: raise the sticky stack-overflow word as a kernel would (no LBVH is deep enough to do it for real)
         const char* hooks = getenv("RC_ENABLE_DEBUG_HOOKS");  // not part of the product's interface: only a process that asks for the hooks gets them
@@ -1445,6 +1446,7 @@ int rc_get_option(rc_scene* s, const char* name, int64_t* value) {
     }
     else if (k == "vf_chunk_bytes") *value = s->opt.vf_chunk_bytes;
     else if (k == "illum_scratch_bytes") *value = s->opt.illum_scratch_bytes;
+    else if (k == "vf_sparse_scratch_bytes") *value = s->opt.vf_sparse_scratch_bytes;
     else if (k == "blas_top_k") *value = s->blas_top_k;
     else if (k == "tlas_top_k") *value = s->tlas_top_k;
     else if (k.rfind("stat", 0) == 0 && ((k.size() == 5 && ((k[4] >= '0' && k[4] <= '9') || (k[4] >= 'a' && k[4] <= 'f'))) ||
@@ -1586,6 +1588,62 @@ int rc_view_factor_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t se
         if (out_mx) RC_HIP(hipMemcpyAsync(out_mx, d_mx, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, s->stream));
         if (out_mtx) RC_HIP(hipMemcpyAsync(out_mtx, d_mx + n, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, s->stream));
         check_status(s, s->stream);
+    });
+}
+// The view-factor matrix itself, sparse: rows [row_begin, row_end) in canonical CSR on the device (rc_launch_vf_sparse, rc_drivers.hip).
+// The build sorts, so it refuses a stream that is being captured -- before anything is enqueued, whether or not the source order is fresh.
+int rc_view_factors_sparse_device(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t row_begin, uint32_t row_end, uint64_t* d_row_ptr,
+                                  uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, uint64_t* d_nnz, void* stream) {
+    if (!s || !d_row_ptr || !d_nnz || (capacity && (!d_cols || !d_vals))) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (stream && hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive)
+            throw RcError(RC_ERR_NOT_SYNCED, "rc_view_factors_sparse_device: the matrix cannot be built while the stream is being captured (the build sorts and sizes its scratch on the host) -- build it before the capture; rc_view_factor_sparse_products_device may be captured");
+        (void)hipGetLastError();
+        rc_ensure_vf_order(s, (hipStream_t)stream);
+        rc_launch_vf_sparse(s, rays_per_triangle, seed, row_begin, row_end, reinterpret_cast<unsigned long long*>(d_row_ptr), d_cols, d_vals, capacity,
+                            reinterpret_cast<unsigned long long*>(d_nnz), (hipStream_t)stream);
+    });
+}
+// Host arrays, all rows: device arrays of the caller's capacity for the length of the call, the first min(nnz, capacity) entries come back.
+int rc_view_factors_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint64_t* out_row_ptr, uint32_t* out_cols, uint32_t* out_vals,
+                           uint64_t capacity, uint64_t* out_nnz) {
+    if (!s || !out_row_ptr || !out_nnz || (capacity && (!out_cols || !out_vals))) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded([&] {
+        use_device(s);
+        require_synced_host(s);
+        std::lock_guard<std::mutex> one_at_a_time(s->host_call_mu);
+        const uint32_t n = s->n_flat_prims;
+        DevBuf<unsigned long long> ptr;  // row_ptr[n + 1], then nnz
+        DevBuf<uint32_t> entries;        // cols[capacity], vals[capacity]
+        ptr.reserve((size_t)n + 2u);
+        if (capacity) entries.reserve((size_t)2 * capacity);
+        rc_ensure_vf_order(s, s->stream);
+        rc_launch_vf_sparse(s, rays_per_triangle, seed, 0, n, ptr.p, entries.p, capacity ? entries.p + capacity : nullptr, capacity, ptr.p + n + 1u, s->stream);
+        unsigned long long nnz = 0;
+        RC_HIP(hipMemcpyAsync(out_row_ptr, ptr.p, sizeof(uint64_t) * ((size_t)n + 1u), hipMemcpyDeviceToHost, s->stream));
+        RC_HIP(hipMemcpyAsync(&nnz, ptr.p + n + 1u, sizeof(nnz), hipMemcpyDeviceToHost, s->stream));
+        RC_HIP(hipStreamSynchronize(s->stream));
+        *out_nnz = nnz;
+        const size_t filled = (size_t)std::min<unsigned long long>(nnz, capacity);
+        if (filled) {
+            RC_HIP(hipMemcpyAsync(out_cols, entries.p, sizeof(uint32_t) * filled, hipMemcpyDeviceToHost, s->stream));
+            RC_HIP(hipMemcpyAsync(out_vals, entries.p + capacity, sizeof(uint32_t) * filled, hipMemcpyDeviceToHost, s->stream));
+        }
+        check_status(s, s->stream);
+        RC_HIP(hipStreamSynchronize(s->stream));
+    });
+}
+// mx += M x, mtx += M^T x for a CSR block on the device (k_vf_sparse_products): the arrays are the caller's contract, nothing is validated.
+int rc_view_factor_sparse_products_device(rc_scene* s, uint32_t n_rows, uint32_t row_offset, const uint64_t* d_row_ptr, const uint32_t* d_cols,
+                                          const uint32_t* d_vals, const uint32_t* d_x, uint64_t* d_mx, uint64_t* d_mtx, void* stream) {
+    if (!s || !d_row_ptr || !d_x || (!d_mx && !d_mtx)) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded([&] {
+        use_device(s);
+        rc_launch_vf_sparse_products(s, n_rows, row_offset, reinterpret_cast<const unsigned long long*>(d_row_ptr), d_cols, d_vals, d_x,
+                                     reinterpret_cast<unsigned long long*>(d_mx), reinterpret_cast<unsigned long long*>(d_mtx), (hipStream_t)stream);
     });
 }
 int rc_view_factor_totals_multi(rc_scene* const* scenes, int n_scenes, uint32_t rays_per_triangle, uint64_t seed, uint64_t* out_received, uint64_t* out_emitted) {

@@ -565,6 +565,101 @@ struct ViewFactorJob {
     }
 };
 
+// The sparse view-factor matrix (rc_view_factors_sparse*): the same job once more, but the matrix itself is kept, as CSR.  A chunk of whole
+// rows is traced with the sources in metadata order; work item w stores ONE u64 key at pairs[w] -- (row - the chunk's first row) << col_bits
+// | col for a counted ray (the rule of :93-97), `sentinel` = 1 << (row_bits + col_bits), which sorts behind every key, for any other ray.
+// One plain store per finished ray at an index below the launch's item count, no atomics: the keys are sorted and run-length encoded
+// afterwards (rc_launch_vf_sparse), so the arrays do not depend on which wave traced what.
+struct ViewFactorPairsSink {
+    const RcInstRec* inst;
+    const RcPrim* prims;
+    const uint32_t* order;
+    uint32_t n_prims, src_begin, n_ray, row0, col_bits;
+    unsigned long long sentinel;
+    unsigned long long* pairs;
+    __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
+        unsigned long long key = sentinel;
+        if (hit) {
+            const uint32_t src = order[src_begin + (uint32_t)(w / n_ray)];
+            const uint32_t to_meta = hit_meta(inst, prims, instance, prim), src_meta = prims[src].meta;
+            if (vf_counted(to_meta, src_meta, n_prims)) key = ((unsigned long long)(src_meta - 1u - row0) << col_bits) | (to_meta - 1u);
+        }
+        pairs[w] = key;
+    }
+};
+struct ViewFactorPairsJob {
+    uint32_t k0, k1, src_begin, n_ray, row0, col_bits;
+    unsigned long long sentinel;
+    unsigned long long* pairs;
+    const uint32_t* order;
+    __device__ inline ViewFactorSource source(const SceneView& v) const { return ViewFactorSource{v.prims, order, k0, k1, src_begin, 0u, n_ray}; }
+    __device__ inline ViewFactorPairsSink sink(const SceneView& v) const {
+        return ViewFactorPairsSink{v.inst, v.prims, order, v.n_prims, src_begin, n_ray, row0, col_bits, sentinel, pairs};
+    }
+};
+// Appends one chunk's compressed keys to the CSR arrays.  unique / lengths / n_runs: the run-length encoding of the chunk's SORTED keys, on
+// the device; the sentinel's run, if there is one, is the last and is dropped.  Entry i goes to position *nnz_in + i of cols / vals unless
+// that is at or beyond `capacity`; the row's count (row_count, indexed from the job's first row; `row0` = the chunk's first row in it) grows
+// by one per entry -- consecutive entries of a row are consecutive lanes, so a wave adds once per row it touches --; *nnz_out = *nnz_in +
+// entries.  nnz_in and nnz_out are different words: every workgroup reads the one, the first writes the other.  The grid is sized by the
+// chunk's rays, an upper bound of its entries that the host knows.
+__global__ __launch_bounds__(256) void k_vf_sparse_append(const unsigned long long* unique, const uint32_t* lengths, const uint32_t* n_runs,
+                                                          unsigned long long sentinel, uint32_t col_bits, uint32_t row0,
+                                                          const unsigned long long* nnz_in, unsigned long long* nnz_out, uint32_t* cols,
+                                                          uint32_t* vals, unsigned long long capacity, unsigned long long* row_count) {
+    const uint32_t runs = *n_runs;
+    const uint32_t entries = runs - ((runs && unique[runs - 1u] == sentinel) ? 1u : 0u);
+    const unsigned long long base = *nnz_in;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t i0 = (uint64_t)blockIdx.x * 256u; i0 < entries; i0 += (uint64_t)gridDim.x * 256u) {  // (uniform per workgroup: every lane reaches the ballot)
+        const uint64_t i = i0 + threadIdx.x;
+        const bool active = i < entries;
+        const unsigned long long key = active ? unique[i] : 0ull;
+        const uint32_t row = (uint32_t)(key >> col_bits);
+        if (active && base + i < capacity) {
+            cols[base + i] = (uint32_t)(key & ((1ull << col_bits) - 1ull));
+            vals[base + i] = lengths[i];
+        }
+        const uint32_t before = __shfl_up(row, 1);
+        const bool first = active && (lane == 0u || before != row);
+        const unsigned long long ends = __ballot(first || !active);  // where a group of equal rows ends: at the next first lane, or at the first idle one
+        if (first) {
+            const unsigned long long behind = ends & ~((2ull << lane) - 1ull);
+            const uint32_t n = (behind ? (uint32_t)__ffsll((long long)behind) - 1u : 64u) - lane;
+            atomicAdd(row_count + row0 + row, (unsigned long long)n);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *nnz_out = base + entries;
+}
+// The products of a CSR block with a vector (rc_view_factor_sparse_products_device): one wave per row, the lanes stride the row's entries
+// with coalesced loads of cols / vals and gather x.  mx[row_offset + r] += sum_k vals[k] * x[cols[k]]: a u64 butterfly over the wave and one
+// atomic per row (atomic, so that row blocks on several streams may share a vector).  mtx[cols[k]] += vals[k] * x[row_offset + r]: one u64
+// atomic per entry -- a row's columns are all different, so there is nothing to combine inside a wave.  All sums modulo 2^64.  The row
+// bounds come from row_ptr on the device: the grid depends on n_rows alone.
+// (Also built: 16 lanes per row, four rows per wave -- equal at rows of some 40 entries, 1.24 x and 1.44 x slower at the rows of the reduced
+// and the full C5: docs/EXPERIMENTS.md, "Sparse view-factor matrix".)
+__global__ __launch_bounds__(256) void k_vf_sparse_products(uint32_t n_rows, uint32_t row_offset, const unsigned long long* row_ptr, const uint32_t* cols,
+                                                            const uint32_t* vals, const uint32_t* x, unsigned long long* mx, unsigned long long* mtx) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t r = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); r < n_rows; r += n_waves) {
+        const unsigned long long begin = row_ptr[r], end = row_ptr[r + 1u];
+        const unsigned long long xr = mtx ? x[row_offset + r] : 0u;
+        unsigned long long sum = 0;
+        for (unsigned long long k = begin + lane; k < end; k += 64u) {
+            const uint32_t c = cols[k];
+            const unsigned long long v = vals[k];
+            if (mx) sum += v * x[c];
+            if (xr) atomicAdd(mtx + c, v * xr);
+        }
+        if (mx) {
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
+            if (lane == 0u && sum) atomicAdd(mx + row_offset + r, sum);
+        }
+    }
+}
+
 __global__ void k_meta_keys(const RcPrim* prims, uint32_t n, uint32_t* keys, uint32_t* vals) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { keys[i] = prims[i].meta; vals[i] = i; }
@@ -1157,6 +1252,121 @@ void rc_launch_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t see
     unsigned long long* scratch = d_mtx ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
     launch.go<false>(ViewFactorProductsJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, d_x, scratch, h, d_mx}, Nothing(),
                      [&] { if (d_mtx) rc_hist_fold(stream, scratch, h, np, FoldAddU64{{}, d_mtx}); });
+}
+
+// Rows [row_begin, row_end) of the view-factor matrix in canonical CSR (rc_view_factors_sparse_device), all on `stream`, no host wait.
+// The sources are addressed in metadata order (the caller has called rc_ensure_vf_order): a range of rows is a contiguous range of source
+// positions, and metadata 0 or above N lie outside every range.  The job is cut HERE, on the host, into chunks of WHOLE rows whose rays x 8
+// bytes fit option "vf_sparse_scratch_bytes" (a single row above it gets a chunk of its own).  Per chunk: the trace stores one key per ray
+// (ViewFactorPairsJob); a radix sort over the bits that can vary -- ceil(log2 rows of the chunk) + ceil(log2 N) + the sentinel's --; a
+// run-length encoding whose run count stays on the device; k_vf_sparse_append.  The chunks are whole rows in ascending order, so what they
+// append is the sorted result.  d_row_ptr holds the rows' COUNTS until an exclusive scan behind the last chunk turns them into offsets.
+// The running nnz alternates between *d_nnz and d_row_ptr[rows] (which no count uses), so that the append kernel reads one word and
+// writes another; the last chunk writes *d_nnz.  Every word that crosses a chunk boundary lives in the caller's arrays: the scratch is
+// the stream's (rc_totals_scratch), sized once for the largest chunk, and holds nothing between two launches.
+namespace {
+struct SparseChunk { uint32_t row0, row1, pos0, pos1; };
+uint32_t ceil_log2(uint64_t n) { uint32_t b = 0; while (b < 64u && (1ull << b) < n) ++b; return b; }
+size_t round16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+}  // namespace
+void rc_launch_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t row_begin, uint32_t row_end, unsigned long long* d_row_ptr,
+                         uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, unsigned long long* d_nnz, hipStream_t stream) {
+    const uint32_t np = s->n_flat_prims, R = rays_per_triangle;
+    if (row_end > np) row_end = np;
+    if (row_begin > row_end) row_begin = row_end;
+    const uint32_t rows = row_end - row_begin;
+    // the plan: chunks of whole rows
+    std::vector<SparseChunk> chunks;
+    const uint64_t max_items = std::max<uint64_t>((uint64_t)s->opt.vf_sparse_scratch_bytes / 8u, 1u);
+    uint64_t most_items = 0;
+    if (rows && R) {
+        uint32_t p0 = 0, p1 = 0;
+        rc_vf_source_range(s, row_begin, row_end, p0, p1);
+        const std::vector<uint32_t>& m = s->vf_meta_sorted;
+        for (uint32_t i = p0; i < p1;) {
+            SparseChunk c{m[i] - 1u, 0u, i, i};
+            while (i < p1) {
+                uint32_t j = i;
+                while (j < p1 && m[j] == m[i]) ++j;  // the sources of one row
+                if (((uint64_t)(j - i) * R) >> 32) throw RcError(1, "rc_view_factors_sparse: one row's sources x rays_per_triangle reaches 2^32");
+                if (i != c.pos0 && (uint64_t)(j - c.pos0) * R > max_items) break;
+                c.row1 = m[i];
+                i = j;
+            }
+            c.pos1 = i;
+            most_items = std::max<uint64_t>(most_items, (uint64_t)(c.pos1 - c.pos0) * R);
+            chunks.push_back(c);
+        }
+    }
+    const uint32_t col_bits = ceil_log2(np);
+    RC_HIP(hipMemsetAsync(d_row_ptr, 0, sizeof(unsigned long long) * ((size_t)rows + 1u), stream));
+    RC_HIP(hipMemsetAsync(d_nnz, 0, sizeof(unsigned long long), stream));
+    if (chunks.empty()) return;
+    // the scratch of one chunk, sized for the largest: keys, sorted keys (the unique keys then overwrite the unsorted ones), run lengths,
+    // the run count, the scanned row pointers, and the primitives' own temporary storage
+    size_t tmp_bytes = 1;
+    for (const SparseChunk& c : chunks) {
+        const uint64_t items = (uint64_t)(c.pos1 - c.pos0) * R;
+        const int end_bit = (int)(ceil_log2(c.row1 - c.row0) + col_bits + 1u);
+        if (end_bit > 64) throw RcError(1, "rc_view_factors_sparse: a chunk's (row, column) keys need more than 64 bits");
+        size_t b = 0;
+        RC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, b, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, items, 0, end_bit, stream));
+        tmp_bytes = std::max(tmp_bytes, b);
+        b = 0;
+        RC_HIP(::rocprim::run_length_encode(nullptr, b, (const unsigned long long*)nullptr, (unsigned int)items, (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, stream));
+        tmp_bytes = std::max(tmp_bytes, b);
+    }
+    {
+        size_t b = 0;
+        RC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)(rows + 1u), stream));
+        tmp_bytes = std::max(tmp_bytes, b);
+    }
+    const size_t key_bytes = round16(sizeof(unsigned long long) * most_items), len_bytes = round16(sizeof(uint32_t) * most_items),
+                 ptr_bytes = round16(sizeof(unsigned long long) * ((size_t)rows + 1u));
+    const size_t total_bytes = 2u * key_bytes + len_bytes + 16u + ptr_bytes + round16(tmp_bytes);
+    unsigned long long* const running[2] = {d_nnz, d_row_ptr + rows};
+    const size_t n_chunks = chunks.size();
+    for (size_t ci = 0; ci < n_chunks; ++ci) {
+        const SparseChunk& c = chunks[ci];
+        const uint64_t items = (uint64_t)(c.pos1 - c.pos0) * R;
+        const uint32_t row_bits = ceil_log2(c.row1 - c.row0);
+        const unsigned long long sentinel = 1ull << (row_bits + col_bits);
+        DriverLaunch launch(s, stream, items);
+        unsigned char* base = reinterpret_cast<unsigned char*>(rc_totals_scratch(launch.guard, total_bytes / 8u));
+        unsigned long long* keys = reinterpret_cast<unsigned long long*>(base);
+        unsigned long long* sorted = reinterpret_cast<unsigned long long*>(base + key_bytes);
+        uint32_t* lengths = reinterpret_cast<uint32_t*>(base + 2u * key_bytes);
+        uint32_t* n_runs = reinterpret_cast<uint32_t*>(base + 2u * key_bytes + len_bytes);
+        unsigned long long* scanned = reinterpret_cast<unsigned long long*>(base + 2u * key_bytes + len_bytes + 16u);
+        void* tmp = base + 2u * key_bytes + len_bytes + 16u + ptr_bytes;
+        launch.go<false>(
+            ViewFactorPairsJob{(uint32_t)seed, (uint32_t)(seed >> 32), c.pos0, R, c.row0, col_bits, sentinel, keys, s->vf_order.p}, Nothing(), [&] {
+                size_t b = tmp_bytes;
+                RC_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, b, (const unsigned long long*)keys, sorted, items, 0, (int)(row_bits + col_bits + 1u), stream));
+                b = tmp_bytes;
+                RC_HIP(::rocprim::run_length_encode(tmp, b, (const unsigned long long*)sorted, (unsigned int)items, keys, lengths, n_runs, stream));
+                const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + 255u) / 256u, (uint64_t)std::max(s->n_cus, 1) * 8u);
+                hipLaunchKernelGGL(k_vf_sparse_append, dim3(blocks), dim3(256), 0, stream, (const unsigned long long*)keys, (const uint32_t*)lengths,
+                                   (const uint32_t*)n_runs, sentinel, col_bits, c.row0 - row_begin, (const unsigned long long*)running[(n_chunks - ci) & 1u],
+                                   running[(n_chunks - ci - 1u) & 1u], d_cols, d_vals, (unsigned long long)capacity, d_row_ptr);
+                RC_HIP(hipGetLastError());
+                if (ci + 1u == n_chunks) {  // counts -> offsets
+                    b = tmp_bytes;
+                    RC_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, b, (const unsigned long long*)d_row_ptr, scanned, (int)(rows + 1u), stream));
+                    RC_HIP(hipMemcpyAsync(d_row_ptr, scanned, sizeof(unsigned long long) * ((size_t)rows + 1u), hipMemcpyDeviceToDevice, stream));
+                }
+            });
+    }
+}
+
+// mx += M x, mtx += M^T x for rows [row_offset, row_offset + n_rows) of a CSR block (k_vf_sparse_products): nothing is read on the host, so
+// the call may be captured and needs no wait behind the build.  Four rows per workgroup; at most 64 workgroups per CU, the rest by stride.
+void rc_launch_vf_sparse_products(rc_scene* s, uint32_t n_rows, uint32_t row_offset, const unsigned long long* d_row_ptr, const uint32_t* d_cols,
+                                  const uint32_t* d_vals, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx, hipStream_t stream) {
+    if (n_rows == 0 || (!d_mx && !d_mtx)) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_rows + 3u) / 4u, (uint64_t)std::max(s->n_cus, 1) * 64u);
+    hipLaunchKernelGGL(k_vf_sparse_products, dim3(blocks), dim3(256), 0, stream, n_rows, row_offset, d_row_ptr, d_cols, d_vals, d_x, d_mx, d_mtx);
+    RC_HIP(hipGetLastError());
 }
 
 // Kernels outside RcLaunchGuard that read scene memory on a caller's stream (the wavefront stages): remember the stream's latest such

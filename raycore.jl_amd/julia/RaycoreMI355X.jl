@@ -328,6 +328,36 @@ view_factor_products_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, se
                              ray_end::Integer, d_x::Ptr{UInt32}, d_mx::Ptr{UInt64}, d_mtx::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_view_factor_products_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
                 a.owner.ptr, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, d_x, d_mx, d_mtx, stream))
+"""
+    view_factors_sparse(accel; rays_per_triangle, seed) -> (row_ptr::Vector{UInt64}, cols::Vector{UInt32}, vals::Vector{UInt32})
+
+The matrix of `view_factors(accel; rays_per_triangle, seed)` itself, as canonical CSR with 0-based offsets and columns: the entries
+`row_ptr[r] + 1 : row_ptr[r + 1]` belong to source metadata `r`, `cols` (hit metadata - 1) ascend strictly within a row, every value is
+at least 1.  `SparseArrays.SparseMatrixCSC(N, N, row_ptr .+ 1, cols .+ 1, vals)` is its TRANSPOSE (CSC of the transpose = CSR).  A counting
+call sizes the arrays, a second call fills them; the dense N x N matrix never exists.
+"""
+function view_factors_sparse(a::MI355XStaticTLAS; rays_per_triangle = 10000, seed::UInt64 = rand(UInt64))
+    n = counts(a.owner)[4]
+    row_ptr, nnz = Vector{UInt64}(undef, n + 1), Ref{UInt64}(0)
+    check(ccall((:rc_view_factors_sparse, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, Ptr{UInt64}, Ptr{UInt32}, Ptr{UInt32}, UInt64, Ptr{UInt64}),
+                a.owner.ptr, rays_per_triangle, seed, row_ptr, C_NULL, C_NULL, 0, nnz))
+    cols, vals = Vector{UInt32}(undef, nnz[]), Vector{UInt32}(undef, nnz[])
+    check(ccall((:rc_view_factors_sparse, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, Ptr{UInt64}, Ptr{UInt32}, Ptr{UInt32}, UInt64, Ptr{UInt64}),
+                a.owner.ptr, rays_per_triangle, seed, row_ptr, cols, vals, length(cols), nnz))
+    return row_ptr, cols, vals
+end
+"Rows [row_begin, row_end) of the sparse matrix into device arrays on `stream` (`d_row_ptr`: rows + 1 UInt64 from 0; `d_cols`, `d_vals`:
+`capacity` UInt32 each, C_NULL with capacity 0 to count; `d_nnz`: one UInt64, always the true count): the unit of a multi-device build."
+view_factors_sparse_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, seed::UInt64, row_begin::Integer, row_end::Integer, d_row_ptr::Ptr{UInt64},
+                            d_cols::Ptr{UInt32}, d_vals::Ptr{UInt32}, capacity::Integer, d_nnz::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_view_factors_sparse_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, Ptr{UInt64}, Ptr{UInt32}, Ptr{UInt32}, UInt64, Ptr{UInt64}, Ptr{Cvoid}),
+                a.owner.ptr, rays_per_triangle, seed, row_begin, row_end, d_row_ptr, d_cols, d_vals, capacity, d_nnz, stream))
+"`d_mx[row_offset + r] += sum_k d_vals[k] * d_x[d_cols[k]]` and `d_mtx[d_cols[k]] += d_vals[k] * d_x[row_offset + r]` (UInt64, modulo 2^64;
+either output may be C_NULL) for the `n_rows` rows of a device CSR block: the bounce of a radiosity iteration without tracing.  Capturable."
+view_factor_sparse_products_device!(a::MI355XStaticTLAS, n_rows::Integer, row_offset::Integer, d_row_ptr::Ptr{UInt64}, d_cols::Ptr{UInt32}, d_vals::Ptr{UInt32},
+                                    d_x::Ptr{UInt32}, d_mx::Ptr{UInt64}, d_mtx::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_view_factor_sparse_products_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt32, Ptr{UInt64}, Ptr{UInt32}, Ptr{UInt32}, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
+                a.owner.ptr, n_rows, row_offset, d_row_ptr, d_cols, d_vals, d_x, d_mx, d_mtx, stream))
 "Rows [row_begin, row_end) (0-based, end exclusive) of the matrix into `out` (column-major, any leading dimension >= N): the unit of a
 multi-process run, where every process maps the same shared-memory matrix (`Mmap.mmap` of a file in /dev/shm) and fills its own rows."
 function view_factors_rows!(out::AbstractMatrix{UInt32}, a::MI355XStaticTLAS, row_begin::Integer, row_end::Integer; rays_per_triangle = 10000, seed::UInt64)
