@@ -851,6 +851,39 @@ int rc_view_factors_sparse(rc_scene* scene, uint32_t rays_per_triangle, uint64_t
 int rc_view_factor_sparse_products_device(rc_scene* scene, uint32_t n_rows, uint32_t row_offset, const uint64_t* d_row_ptr, const uint32_t* d_cols,
                                           const uint32_t* d_vals, const uint32_t* d_x, uint64_t* d_mx, uint64_t* d_mtx, void* stream);
 
+/* ---- Final gather: how much of a per-triangle solution arrives at every hit point?  The step between the analysis half (a u32 per
+ * primitive indexed by metadata - 1: rc_view_factor_products_device's x, a radiosity iterate) and the per-hit half: the hemisphere samples of
+ * rc_ambient_occlusion_device (declared below), traced for the CLOSEST hit -- closest_hit, src/instanced-bvh.jl:1902-2024 -- and the field
+ * summed over what they hit.  The samples are cosine-weighted (cosine_sample_hemisphere, src/math.jl:1-21), so sum / samples is the
+ * cosine-weighted mean of x over the hemisphere: the irradiance in x's units when x is a Lambertian radiosity.
+ * d_rays, d_hits, n, samples, max_dist, seed, depth, d_path_in, path_base, bias: rc_ambient_occlusion_device's, and ray(i, s) is bit for
+ * bit the ray rc_ambient_occlusion_rays_device writes at slot i * samples + s (the same device function makes both); there is no ray stage
+ * of its own.  d_x: n_primitives u32, indexed by metadata - 1, read WHEN THE KERNEL RUNS and for counted samples only: a captured call
+ * follows a solution that changes between replays.  d_sum: n u64.  d_open: n u32, may be NULL.  miss_value: what a sample that escapes
+ * adds (the sky's radiance in x's units; 0: no sky).
+ * Identity with the composed path, exact, no tolerance, N = the scene's primitive count:
+ *   d_sum[i]  += sum over s of  live(i,s) && H.hit && 1 <= m <= N ? x[m-1]  :  live(i,s) && !H.hit ? miss_value : 0
+ *   d_open[i] += sum over s of  live(i,s) && !H.hit
+ * where live(i,s) = d_hits[i].hit && ray(i,s).t_max > 0, H is what rc_trace_closest_device reports for ray(i,s), and m is the metadata of
+ * the primitive H names.  A hit whose metadata lies outside 1..N adds nothing (the rule of get_illumination, src/kernels.jl:123).  Sums are
+ * modulo 2^64: integer adds, exact in any order, so the words do not depend on scheduling, kernel shape or sharding.
+ * Two consequences: d_open equals what rc_ambient_occlusion_device adds to d_count for the same arguments -- on these rays (t_min = 0)
+ * closest_hit and any_hit agree on whether there is a hit --; and a hit whose frame is NaN gets NO extra gate, as there: its NaN ray is
+ * traced and counts as whatever rc_trace_closest_device reports for it, the same in both paths.
+ * The call ACCUMULATES into d_sum and d_open: the caller zeroes them, and accumulation over calls with different `seed` or `depth` is
+ * legal.  Items are claimed in natural order; the entry cull follows rc_trace_closest_device.
+ * No allocation, copy, event, memset, host synchronisation or scene-owned scratch: re-entrant across streams, and captured on a capturing
+ * stream under the rules of the other driver launches (one capture slot; the stream must have run the call eagerly before).  A stack
+ * overflow is reported by rc_wait.  n == 0 or samples == 0: succeeds, nothing is enqueued.
+ * Errors, all before anything is enqueued and in rc_ambient_occlusion_device's order: RC_ERR_INVALID_ARGUMENT (NULL scene, checked first
+ * and with or without a device; samples >= 65536; depth >= 65536; max_dist not > 0 -- NaN included, +Inf is legal; n * samples >= 2^32,
+ * products that wrap in 64 bits included; NULL d_rays, d_hits, d_sum or d_x while there is work), RC_ERR_NOT_SYNCED (the rules of
+ * rc_shadow_visibility_device).
+ * Measured against the composed path in docs/EXPERIMENTS.md, "Final gather". */
+int rc_final_gather_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist,
+                           uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias,
+                           const uint32_t* d_x, uint32_t miss_value, uint64_t* d_sum, uint32_t* d_open, void* stream);
+
 /* ---- Ambient occlusion: how open is the hemisphere above every hit?  `samples` cosine-weighted any_hit rays of length max_dist per hit; the
  * visible fraction count / samples is the cosine-weighted openness of the point (with max_dist = +Inf its sky-view factor, the per-point form
  * of what rc_get_illumination_device and rc_view_factor_totals answer per triangle).

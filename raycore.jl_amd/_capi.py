@@ -145,6 +145,7 @@ SYMBOLS = [
     ("rc_generate_ray_grid_dirs_device", _int, [_vp, _vp, _u32, _u32, _vp, _vp]),
     ("rc_ambient_occlusion_rays_device", _int, [_vp, _vp, _vp, _u64, _u32, C.c_float, _u64, _u32, _vp, _u64, C.c_float, _vp, _vp]),
     ("rc_ambient_occlusion_device", _int, [_vp, _vp, _vp, _u64, _u32, C.c_float, _u64, _u32, _vp, _u64, C.c_float, _vp, _vp]),
+    ("rc_final_gather_device", _int, [_vp, _vp, _vp, _u64, _u32, C.c_float, _u64, _u32, _vp, _u64, C.c_float, _vp, _u32, _vp, _vp, _vp]),
 ]
 
 _lib = None

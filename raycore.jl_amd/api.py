@@ -587,6 +587,17 @@ class TLAS:
                                                 ptr(d_path_in) if d_path_in else None, int(path_base), float(bias), ptr(d_count),
                                                 ptr(stream) if stream else None))
 
+    def final_gather_device(self, d_rays, d_hits, n, samples, d_x, d_sum, d_open=None, miss_value=0, max_dist=float("inf"), seed=0, depth=0,
+                            bias=1e-3, d_path_in=None, path_base=0, stream=None):
+        """The final gather in one traversal launch (rc_final_gather_device): ambient_occlusion_device's samples traced for the CLOSEST hit.
+        d_sum (device pointer, n u64) is ACCUMULATED -- sum[i] += x[meta - 1] of what each sample of hit i's hemisphere hits first
+        (metadata outside 1..n_primitives: nothing), miss_value for a sample that reaches max_dist --, and d_open (n u32, may be None) with
+        the samples that escape: ambient_occlusion_device's counts.  d_x: device pointer to n_primitives u32, read when the kernel runs.
+        The caller zeroes the outputs; sum / samples is the cosine-weighted mean of x over the hemisphere."""
+        check(lib().rc_final_gather_device(self._h, ptr(d_rays), ptr(d_hits), int(n), int(samples), float(max_dist), int(seed), int(depth),
+                                           ptr(d_path_in) if d_path_in else None, int(path_base), float(bias), ptr(d_x), int(miss_value), ptr(d_sum),
+                                           ptr(d_open) if d_open else None, ptr(stream) if stream else None))
+
     def illumination_dirs_device(self, d_dirs, n_dirs, grid, d_counts, row_stride=None, stream=None):
         """get_illumination for n_dirs directions in one call (rc_get_illumination_dirs_device).  d_dirs: device pointer to n_dirs x 3 f32
         (need not be normalised), read WHEN THE KERNELS RUN, like the TLAS root the grids are laid out from: no host copy of the world
@@ -960,6 +971,79 @@ def ambient_occlusion(accel, rays, hits, samples, max_dist=float("inf"), seed=0,
     torch.cuda.synchronize(t.device)
     t.wait_for_gpu()  # (reports a traversal stack overflow)
     return counts.cpu().numpy().view(np.uint32)[:n].copy()
+
+
+def _gather_inputs(rays, hits, samples, max_dist, miss_value):
+    """(rays, hits, samples, max_dist, miss_value) of final_gather, checked without a device: ValueError for what
+    rc_final_gather_device would refuse, and for a miss_value that is no u32."""
+    from .wavefront import check_gather_arguments
+    r = _as_rays(rays)
+    h = np.ascontiguousarray(hits)
+    if h.dtype != HIT_DT or h.shape != r.shape:
+        raise ValueError("hits must be a HIT_DT array with one record per ray")
+    return (r, h) + check_gather_arguments(len(r), samples, max_dist, miss_value)
+
+
+def final_gather(accel, rays, hits, x, samples, max_dist=float("inf"), miss_value=0, seed=0, bias=1e-3):
+    """The final gather: how much of a per-primitive field arrives at every hit?  rays / hits: the RAY_DT rays and the HIT_DT records a
+    closest-hit trace of them returned; x: uint32, one value per primitive, indexed by metadata - 1 (view_factor_bounces' result, say).
+    Returns (sums, open): sums (n,) uint64 -- x summed over what the `samples` cosine-weighted samples of each hit's hemisphere hit
+    first (metadata outside 1..N adds nothing), miss_value for every sample that reaches max_dist --, and open (n,) uint32, the samples
+    that escape: ambient_occlusion()'s counts.  sums / samples is the cosine-weighted mean of x over the hemisphere.  Upload, one
+    final_gather_device call, download."""
+    r, h, samples, max_dist, miss_value = _gather_inputs(rays, hits, samples, max_dist, miss_value)
+    check_products_x(x)
+    import torch
+    t = _owner(accel)
+    x = check_products_x(x, t.n_primitives())
+    n = len(r)
+    dev = f"cuda:{t.device}"
+    torch.cuda.synchronize(t.device)  # (the call runs on the default stream: behind whatever the caller enqueued on streams of its own)
+    d_rays = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_hits = torch.from_numpy(h.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_x = torch.from_numpy(x.view(np.int32).copy()).to(dev)
+    sums = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    opened = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    t.final_gather_device(d_rays.data_ptr(), d_hits.data_ptr(), n, samples, d_x.data_ptr(), sums.data_ptr(), opened.data_ptr(), miss_value=miss_value,
+                          max_dist=max_dist, seed=seed, bias=bias)
+    torch.cuda.synchronize(t.device)
+    t.wait_for_gpu()  # (reports a traversal stack overflow)
+    return sums.cpu().numpy().view(np.uint64)[:n].copy(), opened.cpu().numpy().view(np.uint32)[:n].copy()
+
+
+def irradiance_scale(b, sky=0.0):
+    """The quantisation of irradiance(): (scale, b_q, sky_q) with ONE scale for the field and the sky, scale = (2^32 - 1) / max(max b, sky)
+    (1 when both are zero), b_q = floor(b * scale) as uint32 and sky_q = floor(sky * scale) -- floor, as radiosity_scale quantises
+    emission.  ValueError unless b is a vector of finite values >= 0 and sky is finite and >= 0."""
+    b = np.asarray(b, dtype=np.float64)
+    sky = float(sky)
+    if b.ndim != 1:
+        raise ValueError("b must be a vector with one value per primitive")
+    if not np.isfinite(b).all() or (b < 0).any():
+        raise ValueError("b must be finite and non-negative")
+    if not np.isfinite(sky) or sky < 0:
+        raise ValueError("sky must be finite and non-negative")
+    top = max(float(b.max()) if b.size else 0.0, sky)
+    scale = U32_MAX / top if top > 0 else 1.0
+    b_q = np.minimum(np.floor(b * scale), U32_MAX).astype(np.uint32)
+    return scale, b_q, int(min(np.floor(sky * scale), U32_MAX))
+
+
+def irradiance(accel, rays, hits, b, samples, sky=0.0, max_dist=float("inf"), seed=0, bias=1e-3, return_open=False):
+    """The cosine-weighted mean of the per-primitive field b over the hemisphere above every hit, float64 (n,): the mean over `samples`
+    cosine-weighted directions of b at whatever each direction hits first, `sky` for a direction that reaches max_dist.  When b is a
+    Lambertian radiosity (radiosity()'s result) this is the IRRADIANCE at the point in b's units, sky being the sky's radiosity; multiply
+    by the local reflectance for the reflected radiosity.  0 where the ray missed.
+    b (float, >= 0, one value per primitive, indexed by metadata - 1) and sky are quantised with one scale, scale = (2^32 - 1) /
+    max(max b, sky), with floor (irradiance_scale); the sums are exact integers (final_gather) and the result is sums / (samples * scale).
+    One quantisation step is 1 / scale = max(max b, sky) / (2^32 - 1): every sample's value is at most one step below its float value,
+    and so is their mean.  return_open: also return final_gather's open counts (ambient_occlusion()'s).  samples must be >= 1."""
+    scale, b_q, sky_q = irradiance_scale(b, sky)
+    if isinstance(samples, bool) or samples != int(samples) or int(samples) < 1:
+        raise ValueError("samples must be an integer in [1, 65536)")
+    sums, opened = final_gather(accel, rays, hits, b_q, samples, max_dist=max_dist, miss_value=sky_q, seed=seed, bias=bias)
+    e = sums.astype(np.float64) / (int(samples) * scale)
+    return (e, opened) if return_open else e
 
 
 def _vf_out(n, out):

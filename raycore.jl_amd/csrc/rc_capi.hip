@@ -1800,6 +1800,19 @@ int rc_ambient_occlusion_device(rc_scene* s, const rc_ray* d_rays, const rc_hit*
                                     d_path_in, path_base, bias, d_count, (hipStream_t)stream);
     });
 }
+int rc_final_gather_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
+                           uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, const uint32_t* d_x, uint32_t miss_value,
+                           uint64_t* d_sum, uint32_t* d_open, void* stream) {
+    // (d_sum takes the place of the ambient-occlusion output in the shared checks; d_open may be NULL)
+    if (int e = ambient_occlusion_args("rc_final_gather_device", s, d_rays, d_hits, n, samples, max_dist, depth, d_sum)) return e;
+    if (n && samples && !d_x) return fail(RC_ERR_INVALID_ARGUMENT, "rc_final_gather_device: NULL argument");
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        rc_launch_final_gather(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, samples, max_dist, seed, depth, d_path_in,
+                               path_base, bias, d_x, miss_value, d_sum, d_open, (hipStream_t)stream);
+    });
+}
 
 int rc_bounce_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                           const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n_out, uint64_t seed, uint32_t bounce, float bias,

@@ -929,6 +929,49 @@ struct AoJob {
     __device__ inline VisibilityCountSink sink(const SceneView&) const { return VisibilityCountSink{count, q.samples}; }
 };
 
+// ---- final gather: the sum of a per-primitive field x over the closest hits of the same hemisphere samples ------------------------------
+// AoSource's items and rays unchanged (item j = i * samples + s, ao_ray()), traced for the CLOSEST hit.  Per finished item, i = j / samples:
+//   a hit whose metadata m (hit_meta) lies in 1..n_prims:   sum[i] += x[m - 1]
+//   a hit with metadata outside 1..n_prims:                 nothing (get_illumination's rule, src/kernels.jl:123)
+//   no hit and t > 0 (VisibilityCountSink's rule: a live ray that reached max_dist):   sum[i] += miss_value, open[i] += 1 (open may be null)
+//   a dead item (t = -1: the primary ray missed):           nothing
+// u64 adds are exact in any order, so sum does not depend on scheduling, shell or shard.  x is read when the kernel runs, for counted
+// samples only.  The samples of a slot sit in neighbouring lanes -- wave_add's good case: one atomic per slot and wave carrying the group's
+// sum.  (Also built and measured: one plain u64 atomic per counted lane, within 2 % either way -- docs/EXPERIMENTS.md, "Final gather".)
+struct GatherSink {
+    const RcInstRec* inst;
+    const RcPrim* prims;
+    uint32_t n_prims;
+    const uint32_t* x;
+    uint32_t miss_value, samples;
+    unsigned long long* sum;
+    uint32_t* open;
+    __device__ inline void operator()(uint64_t j, bool hit, float t, float, float, uint32_t prim, int instance) const {
+        const uint32_t i = (uint32_t)j / samples;
+        bool counted = false;
+        uint32_t value = 0;
+        if (hit) {
+            const uint32_t m = hit_meta(inst, prims, instance, prim);
+            counted = m >= 1 && m <= n_prims;
+            if (counted) value = x[m - 1u];
+        } else if (t > 0.0f) {
+            counted = true;
+            value = miss_value;
+            if (open) __hip_atomic_fetch_add(open + i, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        wave_add(sum, i, value, counted);
+    }
+};
+struct GatherJob {
+    AoParams q;
+    const uint32_t* x;
+    uint32_t miss_value;
+    unsigned long long* sum;
+    uint32_t* open;
+    __device__ inline AoSource source(const SceneView& v) const { return AoSource{v, q}; }  // (v: the kernel's own by-value parameter)
+    __device__ inline GatherSink sink(const SceneView& v) const { return GatherSink{v.inst, v.prims, v.n_prims, x, miss_value, q.samples, sum, open}; }
+};
+
 // Diffuse bounce: output slot i continues the path of source slot s (s = i, or d_src[i] for i < count, or d_src[i % count] round robin
 // with k = i / count), from hit_point + normal * bias in a cosine-weighted direction about the geometric normal.  The uniforms are
 // Philox4x32-10(counter = (lo32 path, hi32 path, k, 0x424E0000 | bounce), key = seed): a path's bounce does not depend on compaction,
@@ -1455,6 +1498,16 @@ void rc_launch_ambient_occlusion(rc_scene* s, const RcRay* d_rays, const RcHit* 
     const uint64_t total = n * samples;
     if (total == 0) return;
     DriverLaunch(s, stream, total).go<true>(AoJob{ao_params(d_rays, d_hits, samples, max_dist, seed, depth, d_path_in, path_base, bias), d_count});
+}
+// The final gather: the same items and rays in one persistent CLOSEST-hit launch in natural claim order that ACCUMULATES x at the hit
+// primitives' metadata (miss_value for an escaped sample) into d_sum[i] and the escaped samples into d_open[i] (may be null).
+void rc_launch_final_gather(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
+                            uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, const uint32_t* d_x, uint32_t miss_value,
+                            uint64_t* d_sum, uint32_t* d_open, hipStream_t stream) {
+    const uint64_t total = n * samples;
+    if (total == 0) return;
+    DriverLaunch(s, stream, total).go<false>(GatherJob{ao_params(d_rays, d_hits, samples, max_dist, seed, depth, d_path_in, path_base, bias), d_x, miss_value,
+                                                       reinterpret_cast<unsigned long long*>(d_sum), d_open});
 }
 
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,

@@ -543,6 +543,11 @@ void rc_launch_ao_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, ui
                        const uint32_t* d_path_in, uint64_t path_base, float bias, RcRay* d_out, hipStream_t stream);
 void rc_launch_ambient_occlusion(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
                                  uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream);
+// Final gather: the ambient-occlusion driver's items and rays traced for the closest hit; ACCUMULATES x[meta - 1] of every sample's hit
+// (miss_value for a sample that escapes) into sum[i] (u64) and the escaped samples into open[i] (may be null).  Same limits; d_x: n_prims u32
+void rc_launch_final_gather(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
+                            uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, const uint32_t* d_x, uint32_t miss_value,
+                            uint64_t* d_sum, uint32_t* d_open, hipStream_t stream);
 // Diffuse (cosine-weighted) bounce rays, slot-aligned or gathered through d_src / *d_src_count (read on the device); n < 2^32, bounce < 2^16
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                            const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n, uint64_t seed, uint32_t bounce, float bias,

@@ -555,6 +555,16 @@ ambient_occlusion_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{R
                 (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, UInt32, Cfloat, UInt64, UInt32, Ptr{UInt32}, UInt64, Cfloat, Ptr{UInt32},
                  Ptr{Cvoid}),
                 a.owner.ptr, d_rays, d_hits, n, samples, max_dist, seed, depth, d_path_in, path_base, bias, d_count, stream))
+"Final gather in one traversal launch: the samples of `ambient_occlusion_device!` traced for the closest hit. `d_sum[i]` (0-based, n UInt64, ACCUMULATED: zero it first) += `d_x[meta - 1]` of what each sample of hit `i`'s hemisphere hits first (metadata outside 1..N: nothing), `miss_value` for a sample that reaches `max_dist`; `d_open[i]` (n UInt32, may be `C_NULL`) += the samples that escape. `d_x`: one UInt32 per primitive, read when the kernel runs. Divide by `samples` for the cosine-weighted mean of `x` over the hemisphere."
+final_gather_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n::Integer, samples::Integer,
+                     d_x::Ptr{UInt32}, d_sum::Ptr{UInt64}; d_open::Ptr{UInt32} = Ptr{UInt32}(C_NULL), miss_value::Integer = 0,
+                     max_dist::Float32 = Inf32, seed::UInt64 = UInt64(0), depth::Integer = 0, bias::Float32 = 1f-3,
+                     d_path_in::Ptr{UInt32} = Ptr{UInt32}(C_NULL), path_base::Integer = 0, stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_final_gather_device, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, UInt32, Cfloat, UInt64, UInt32, Ptr{UInt32}, UInt64, Cfloat, Ptr{UInt32},
+                 UInt32, Ptr{UInt64}, Ptr{UInt32}, Ptr{Cvoid}),
+                a.owner.ptr, d_rays, d_hits, n, samples, max_dist, seed, depth, d_path_in, path_base, bias, d_x, miss_value, d_sum, d_open,
+                stream))
 "Diffuse (cosine-weighted) bounce rays: slot-aligned, or gathered through `d_src` / `d_src_count` (a device count; `wrap` = round robin)."
 bounce_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n_out::Integer, d_out::Ptr{RTRay};
                     seed::UInt64 = UInt64(0), bounce::Integer = 0, bias::Float32 = 1f-3, d_src::Ptr{UInt32} = Ptr{UInt32}(C_NULL),

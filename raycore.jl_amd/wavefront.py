@@ -47,6 +47,20 @@ def check_ao_arguments(n, ao_samples, ao_distance):
     return int(ao_samples), float(ao_distance)
 
 
+def check_gather_arguments(n, samples, distance, miss_value):
+    """(samples, distance, miss_value) as (int, float, int) for a frame of n paths, or ValueError: what rc_final_gather_device would
+    refuse -- and a miss_value that is no u32 --, said before a device is touched."""
+    if isinstance(samples, bool) or samples != int(samples) or not 0 <= int(samples) < 65536:
+        raise ValueError("samples must be an integer in [0, 65536)")
+    if not float(distance) > 0.0:  # (NaN included; inf is legal)
+        raise ValueError("distance must be > 0 (inf: unbounded)")
+    if isinstance(miss_value, bool) or miss_value != int(miss_value) or not 0 <= int(miss_value) < 2 ** 32:
+        raise ValueError("miss_value must be an integer in [0, 2^32)")
+    if int(n) * int(samples) >= 2 ** 32:
+        raise ValueError("the number of hits times samples must be below 2^32")
+    return int(samples), float(distance), int(miss_value)
+
+
 class WavefrontPaths:
     """Owns the device buffers of a `depth`-deep path frame of width*height*samples paths on `accel` (a synced TLAS) and enqueues it.
 
@@ -95,7 +109,15 @@ class WavefrontPaths:
     zeroes ao_counts[b] (an int32 tensor holding n u32 counts) on the frame's stream and runs one ambient_occlusion_device with
     max_dist=ao_distance, depth=b, d_path_in=path_ids[b] and the frame's seed and bias: count i is the number of the ao_samples
     cosine-weighted hemisphere samples of slot i of hits[b] that reach ao_distance unoccluded, and a path's samples do not depend on
-    compaction.  With ao_samples == 0 the frame is what it was: no launch, no buffer, the same traced_rays()."""
+    compaction.  With ao_samples == 0 the frame is what it was: no launch, no buffer, the same traced_rays().
+
+    Final gather: with_final_gather(x, samples, distance=inf, miss_value=0) after the constructor, like the ambient-occlusion switch.  x is
+    an int32 tensor on the accel's device holding one u32 per primitive (indexed by metadata - 1: a radiosity iterate, say), held by
+    reference and read by every frame when its kernels run.  With samples > 0 each depth b, after the ambient-occlusion stage, zeroes
+    gather_sums[b] (int64, n) and gather_open[b] (int32, n) on the frame's stream and runs one final_gather_device with
+    max_dist=distance, depth=b, d_path_in=path_ids[b] and the frame's seed and bias: sum i is x summed over what the `samples` hemisphere
+    samples of slot i of hits[b] hit first (miss_value for one that escapes), open i the samples that escape -- the ambient-occlusion
+    stage's rays, so with equal samples and distance gather_open[b] equals ao_counts[b].  With samples == 0 the frame is what it was."""
 
     def __init__(self, accel, width, height, samples, depth, camera, light=None, seed=0, bias=1e-3, compact=True, dynamic=None, rebuild=False,
                  deform=None, lights=None, fused_shadows=False, shadow_samples=1, light_radii=None):
@@ -147,6 +169,7 @@ class WavefrontPaths:
         self.rebuild = "auto" if rebuild == "auto" else bool(rebuild)
         self.rebuild_ratio = 1.5
         self.ao_samples, self.ao_distance, self.ao_counts = 0, math.inf, []
+        self.gather_samples, self.gather_distance, self.gather_miss, self.gather_x, self.gather_sums, self.gather_open = 0, math.inf, 0, None, [], []
         self.deform = list(deform) if deform else []
         dev = torch.device("cuda", accel.device)
         rec = lambda: torch.zeros(self.n * 32, dtype=torch.uint8, device=dev)  # noqa: E731
@@ -202,11 +225,35 @@ class WavefrontPaths:
         self._streams = set()  # the new buffers are recorded on a stream at its next run()
         return self
 
+    def with_final_gather(self, x, samples, distance=math.inf, miss_value=0):
+        """Switch the frame's final-gather stage on (samples > 0) or off (0), before the next run() or capture(); returns self.  x: an
+        int32 tensor of n_primitives words on the accel's device (u32 values, indexed by metadata - 1), kept by reference and read each
+        frame.  ValueError for samples outside [0, 65536), a distance that is not > 0, a miss_value that is no u32,
+        width*height*samples*samples >= 2^32 or an x of another kind -- all before a tensor is made.  A captured frame keeps the stage it
+        was captured with, so it is refused here."""
+        samples, distance, miss_value = check_gather_arguments(self.n, samples, distance, miss_value)
+        if self._graph_stream is not None:
+            raise RaycoreError(1, "WavefrontPaths.with_final_gather: this frame is already captured")
+        import torch
+        dev = torch.device("cuda", self.accel.device)
+        if samples:
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.int32 or x.dim() != 1 or x.device != dev or not x.is_contiguous():
+                raise ValueError("x must be a contiguous one-dimensional int32 tensor on the accel's device")
+            if x.numel() != self.accel.n_primitives():
+                raise ValueError(f"x must hold one value per primitive: {x.numel()} values for {self.accel.n_primitives()} primitives")
+        sums = [torch.zeros(self.n, dtype=torch.int64, device=dev) for _ in range(self.depth)] if samples else []
+        opened = [torch.zeros(self.n, dtype=torch.int32, device=dev) for _ in range(self.depth)] if samples else []
+        torch.cuda.current_stream(dev).synchronize()  # (as in the constructor: a frame may run on another stream than the allocating one)
+        self.gather_samples, self.gather_distance, self.gather_miss = samples, distance, miss_value
+        self.gather_x, self.gather_sums, self.gather_open = (x if samples else None), sums, opened
+        self._streams = set()  # the new buffers are recorded on a stream at its next run()
+        return self
+
     def buffers(self):
         fused = self.visible + [self.lights] if self.fused_shadows else []
         if self.shadow_samples > 1:
             fused = fused + self.shadow_counts + [self.light_radii]
-        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + fused + self.ao_counts + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic] + [t for _, t in self.deform]
+        return self.rays + self.hits + self.shadow_rays + self.shadow_hits + fused + self.ao_counts + self.gather_sums + self.gather_open + ([self.gather_x] if self.gather_samples else []) + self.path_ids + [self.indices, self.count] + [t for _, t in self.dynamic] + [t for _, t in self.deform]
 
     def run(self, stream=None):
         """Enqueue one frame on `stream` (a torch.cuda.Stream; None = the current stream).  No host synchronisation.  The first frame on
@@ -253,6 +300,14 @@ class WavefrontPaths:
                 a.ambient_occlusion_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.ao_samples, self.ao_counts[b].data_ptr(),
                                            max_dist=self.ao_distance, seed=self.seed, depth=b, bias=self.bias,
                                            d_path_in=self.path_ids[b].data_ptr(), stream=st)
+            if self.gather_samples > 0:
+                with torch.cuda.stream(s):  # the call accumulates: zero on the frame's stream, whichever stream is current
+                    self.gather_sums[b].zero_()
+                    self.gather_open[b].zero_()
+                a.final_gather_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.gather_samples, self.gather_x.data_ptr(),
+                                      self.gather_sums[b].data_ptr(), self.gather_open[b].data_ptr(), miss_value=self.gather_miss,
+                                      max_dist=self.gather_distance, seed=self.seed, depth=b, bias=self.bias,
+                                      d_path_in=self.path_ids[b].data_ptr(), stream=st)
             if b + 1 >= self.depth:
                 break
             src = cnt = None
@@ -286,8 +341,9 @@ class WavefrontPaths:
     def traced_rays(self):
         """Ray slots one frame traces: per depth one closest-hit pass (primary or bounce) and one any-hit pass (shadow) over every slot,
         dead ones included -- with fused_shadows one any-hit item per slot and light, with shadow_samples > 1 per slot, light and sample;
-        with ao_samples > 0 one more any-hit item per slot and sample."""
-        return self.n * (1 + (self.n_lights * self.shadow_samples if self.fused_shadows else 1)) * self.depth + self.n * self.ao_samples * self.depth
+        with ao_samples > 0 one more any-hit item per slot and sample, with the final gather one more closest-hit item per slot and sample."""
+        return (self.n * (1 + (self.n_lights * self.shadow_samples if self.fused_shadows else 1)) * self.depth + self.n * self.ao_samples * self.depth
+                + self.n * self.gather_samples * self.depth)
 
 
 def c4_bounce_rays_device(accel, d_rays, d_hits, n_primary, n_rays, d_out, seed=0xC4, stream=None):
