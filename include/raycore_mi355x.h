@@ -851,6 +851,59 @@ int rc_view_factors_sparse(rc_scene* scene, uint32_t rays_per_triangle, uint64_t
 int rc_view_factor_sparse_products_device(rc_scene* scene, uint32_t n_rows, uint32_t row_offset, const uint64_t* d_row_ptr, const uint32_t* d_cols,
                                           const uint32_t* d_vals, const uint32_t* d_x, uint64_t* d_mx, uint64_t* d_mtx, void* stream);
 
+/* ---- Illumination from point sources: get_illumination (src/kernels.jl:112-124) for lamps at a FINITE position.  The reference's
+ * get_illumination and rc_get_illumination_dirs_device shoot an orthographic grid -- a source at infinity, the sun or a sky sector.  These
+ * two calls extend that driver to sources inside the scene: a jittered, stratified, equal-area set of grid^2 rays from each source, the
+ * closest hit, and one count per source and primitive.
+ * WHAT A COUNT MEANS.  For an ISOTROPIC source, d_counts[k][j] / grid^2 is the fraction of the lamp's flux that arrives at the primitives
+ * with metadata j + 1: their visible solid angle over 4 pi.  The 1 / r^2 and cosine factors come out of the shooting, in integers; there is
+ * no float in the kernel.  For a LAMBERTIAN emitter (a ceiling panel, a window patch) the same count under cosine-weighted shooting is the
+ * form factor from the emitter to those primitives; weights @ counts / grid^2 with each lamp's flux as its weight is the received flux per
+ * primitive -- the `emission` of a radiosity solve, up to the caller's reflectance and area.
+ * A SOURCE is one rc_ray record in DEVICE memory, read WHEN THE KERNEL RUNS: o = the lamp's position, d = its axis, t_min and t_max copied
+ * unchanged into every ray it emits (t_max: the lamp's range).  d.x == 0 && d.y == 0 && d.z == 0 (either sign of zero): isotropic;
+ * anything else: Lambertian about d / sqrt(dot(d, d)).
+ * Source k (0-based in the call) shoots grid^2 rays, cell = a * grid + b with a, b in [0, grid); every expression f32, one operation at a
+ * time, left to right, IEEE divide and square root, no contraction:
+ *   rnd = Philox4x32-10, counter (cell, first_source + k, 0, 0x50530000), key = (lo32 seed, hi32 seed)
+ *   xi1, xi2 = its first two words as 24-bit floats in [0, 1): (word >> 8) * 2^-24, the conversion of rc_bounce_rays_device
+ *   u1 = ((float)a + xi1) / (float)grid, u2 = ((float)b + xi2) / (float)grid     (u may round to exactly 1; both mappings are defined there)
+ *   isotropic:  z = 1 - 2 * u1;  s = sqrtf(fmaxf(0, 1 - z * z));  phi = (2 * 3.1415927f) * u2;  (sin, cos) of (double)phi by the f64
+ *               kernels of the view-factor sampler, each rounded once to f32;  dir = (s * cos, s * sin, z), not renormalised
+ *   Lambertian: dir = the cosine-weighted direction about the normalised axis that rc_bounce_rays_device makes from (axis, u1, u2): the
+ *               same function, not renormalised
+ *   ray(k, cell) = origin o, t_min, direction dir, t_max.
+ * first_source only offsets the Philox counter: a set of sources split over several calls, groups, streams or devices gives the rows of
+ * the one-call result.  A source with non-finite fields gives whatever the composed path below gives for it.
+ *
+ * rc_point_source_rays_device, the composed stage: writes n_sources x grid^2 rays, ray(k, cell) at k * grid^2 + cell.  One kernel, no
+ * scratch.  The output feeds rc_trace_closest_device unchanged.
+ * rc_get_illumination_points_device, the fused driver.  WORK-ITEM LAYOUT: item i = k * grid^2 + cell; the ray is generated when a lane takes
+ * the item -- bit for bit the stage's, the same device function makes both -- and never stored.  Items are claimed in natural order.
+ *   d_counts[k * row_stride + (meta - 1)] += the number of rays of source k whose closest hit has metadata `meta`; metadata outside
+ *   1..n_prims is dropped (src/kernels.jl:123).  row_stride >= n_prims, in u32 words; words of a row beyond n_prims are not touched.
+ *   d_escaped[k] += the number of rays of source k that hit nothing.  n_sources u32; may be NULL, and then the kernel has no code for it.
+ * Both outputs ACCUMULATE with u32 atomics, exact in any order: the caller zeroes them, and calls on several streams may share them.  Per
+ * source: row sum + escaped + dropped = grid^2.
+ * The sources are traced in groups of G consecutive ones, one persistent launch per group behind one memset and in front of one fold; G is
+ * the largest count with G * grid^2 < 2^32 whose private histogram copies (G * 512 * ceil(n_prims / 8) bytes; with d_escaped n_prims + 64
+ * in place of n_prims: a source's escapes are counted in 64 more entries of each copy, not on the one word d_escaped[k]) fit option
+ * "illum_scratch_bytes" (at least one source's worth is always used); the group's first index is added to first_source.
+ * The option changes no result.  There is no parameter kernel in front and nothing is read on the host.
+ * Scene state, capture rules and scratch ownership are those of rc_get_illumination_dirs_device: legal on a capturing stream that has run
+ * the call eagerly once (one capture slot per group), and behind rc_refit_device_async, rc_rebuild_tlas_device_async or
+ * rc_update_geometry_device_async on the same stream with no host wait.  A replay reads the CURRENT d_sources: lamps that move between
+ * replays just work.  n_sources == 0, grid == 0 or an empty scene: success, nothing enqueued.
+ * Errors, all before anything is enqueued and with the outputs untouched: RC_ERR_INVALID_ARGUMENT (NULL scene; NULL d_sources, d_counts or
+ * d_rays while n_sources and grid are non-zero; grid >= 65536; row_stride < n_prims; first_source + n_sources > 2^32), RC_ERR_NOT_SYNCED
+ * (as for rc_get_illumination_dirs_device).  A stack overflow is reported by rc_wait.
+ * Register and scratch figures of the new kernel shells and the comparison with the composed path:
+ * docs/EXPERIMENTS.md, "Illumination from point sources". */
+int rc_point_source_rays_device(rc_scene* scene, const rc_ray* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed,
+                                uint32_t first_source, rc_ray* d_rays, void* stream);
+int rc_get_illumination_points_device(rc_scene* scene, const rc_ray* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed,
+                                      uint32_t first_source, uint32_t* d_counts, uint64_t row_stride, uint32_t* d_escaped, void* stream);
+
 /* ---- Final gather: how much of a per-triangle solution arrives at every hit point?  The step between the analysis half (a u32 per
  * primitive indexed by metadata - 1: rc_view_factor_products_device's x, a radiosity iterate) and the per-hit half: the hemisphere samples of
  * rc_ambient_occlusion_device (declared below), traced for the CLOSEST hit -- closest_hit, src/instanced-bvh.jl:1902-2024 -- and the field

@@ -8,7 +8,7 @@ from . import wavefront  # noqa: F401  (torch is imported when a frame is built)
 from ._capi import HIT_DT, LIB_PATH, RAY_DT, SYMBOLS, TRIANGLE_DT, RaycoreError, lib  # noqa: F401
 from .api import (BLAS4, CONTACT_DT, CollisionResult, ContactPair, collide_instances, collide_instances_any, EMPTY_TRIANGLE, RAYHIT_DT, INVALID_HANDLE, any_hit4, build_blas4, closest_hit4, Bounds3, Ray, RayHit, StaticTLAS, TLAS, TLAS_from_items,  # noqa: F401
                   TLAS_from_meshes, TLASHandle, Triangle, adapt, any_hit, closest_hit, generate_ray_grid,
-                  get_centroid, get_illumination, get_illumination_dirs, hits_from_grid, typed_hit_metadata, mat4_to_mat3x4, sync, trace_rays, view_factors, view_factors_multi, view_factor_totals, view_factor_totals_multi, multi_prepare, trace_multi, get_illumination_multi,
+                  get_centroid, get_illumination, get_illumination_dirs, get_illumination_points, point_sources, hits_from_grid, typed_hit_metadata, mat4_to_mat3x4, sync, trace_rays, view_factors, view_factors_multi, view_factor_totals, view_factor_totals_multi, multi_prepare, trace_multi, get_illumination_multi,
                   world_bound, expand_faceviews, ambient_occlusion, final_gather, irradiance, irradiance_scale, view_factor_products, view_factor_bounces, radiosity, radiosity_scale,
                   view_factors_sparse, view_factor_sparse_products, SparseViewFactors)
 

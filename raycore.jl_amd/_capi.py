@@ -146,6 +146,8 @@ SYMBOLS = [
     ("rc_ambient_occlusion_rays_device", _int, [_vp, _vp, _vp, _u64, _u32, C.c_float, _u64, _u32, _vp, _u64, C.c_float, _vp, _vp]),
     ("rc_ambient_occlusion_device", _int, [_vp, _vp, _vp, _u64, _u32, C.c_float, _u64, _u32, _vp, _u64, C.c_float, _vp, _vp]),
     ("rc_final_gather_device", _int, [_vp, _vp, _vp, _u64, _u32, C.c_float, _u64, _u32, _vp, _u64, C.c_float, _vp, _u32, _vp, _vp, _vp]),
+    ("rc_point_source_rays_device", _int, [_vp, _vp, _u32, _u32, _u64, _u32, _vp, _vp]),
+    ("rc_get_illumination_points_device", _int, [_vp, _vp, _u32, _u32, _u64, _u32, _vp, _u64, _vp, _vp]),
 ]
 
 _lib = None

@@ -607,6 +607,24 @@ class TLAS:
         rs = self.n_primitives() if row_stride is None else int(row_stride)
         check(lib().rc_get_illumination_dirs_device(self._h, ptr(d_dirs), int(n_dirs), int(grid), ptr(d_counts), rs, ptr(stream) if stream else None))
 
+    def point_source_rays_device(self, d_sources, n_sources, grid, d_rays, seed=0, first_source=0, stream=None):
+        """The rays of n_sources device-resident point sources (rc_point_source_rays_device): n_sources x grid^2 RTRay records, source
+        k's at k * grid^2 in cell order.  d_sources: device pointer to n_sources RTRay records (o = position, d = axis -- zero: isotropic,
+        else Lambertian about it --, t_min / t_max copied into every ray), read when the kernel runs."""
+        check(lib().rc_point_source_rays_device(self._h, ptr(d_sources), int(n_sources), int(grid), int(seed), int(first_source), ptr(d_rays),
+                                                ptr(stream) if stream else None))
+
+    def illumination_points_device(self, d_sources, n_sources, grid, d_counts, row_stride=None, d_escaped=None, seed=0, first_source=0, stream=None):
+        """get_illumination for n_sources POINT sources in one call (rc_get_illumination_points_device): grid^2 stratified rays per
+        source, the rays of point_source_rays_device bit for bit.  d_counts: device pointer to n_sources rows of `row_stride` (default:
+        the primitive count) u32, ACCUMULATED: d_counts[k * row_stride + meta - 1] += the hits of source k; d_escaped (n_sources u32, may
+        be None) += the rays of source k that hit nothing.  d_sources is read WHEN THE KERNEL RUNS: the call follows the asynchronous
+        updates without a host wait, may be captured, and a replay follows lamps that moved.  first_source offsets the random-number
+        counter only: sources [a, b) of a set with first_source = a give rows [a, b) of the one-call result."""
+        rs = self.n_primitives() if row_stride is None else int(row_stride)
+        check(lib().rc_get_illumination_points_device(self._h, ptr(d_sources), int(n_sources), int(grid), int(seed), int(first_source), ptr(d_counts), rs,
+                                                      ptr(d_escaped) if d_escaped else None, ptr(stream) if stream else None))
+
     def view_factor_products_device(self, x_ptr, mx_ptr, mtx_ptr, rays_per_triangle, seed, src=None, rays=None, stream=None):
         """The view-factor matrix applied to a device vector without the matrix (rc_view_factor_products_device).  x_ptr: N u32 indexed
         by metadata - 1; mx_ptr / mtx_ptr: N u64 each (either may be None), ACCUMULATED: mx += M x, mtx += M^T x with M what
@@ -948,6 +966,74 @@ def get_illumination_dirs(accel, viewdirs, grid_size=1000, weights=None):
     rows = counts.cpu().numpy().view(np.uint32)[:d * n].reshape(d, n)
     rows = np.minimum(rows, np.uint32(1 << 24)).astype(np.float32)  # the reference's Float32 sums stop at 2^24
     return rows if w is None else w @ rows.astype(np.float64)
+
+
+def point_sources(points, axes=None, max_dist=float("inf"), t_min=0.0):
+    """The RAY_DT source records of get_illumination_points / illumination_points_device: o = points[k], d = axes[k] (zero or no axes:
+    isotropic; anything else: a Lambertian emitter about it), t_min, t_max = max_dist (a scalar or one per source).  ValueError for shapes
+    that do not fit, positions or axes that are not finite, a max_dist that is not > 0 (inf is legal) or a t_min that is not finite."""
+    p = np.ascontiguousarray(points, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("points must be a (S, 3) array of positions")
+    if not np.isfinite(p).all():
+        raise ValueError("points must be finite")
+    s = p.shape[0]
+    a = np.zeros((s, 3), np.float32)
+    if axes is not None:
+        a = np.ascontiguousarray(axes, dtype=np.float32)
+        if a.shape != (s, 3):
+            raise ValueError("axes must be a (S, 3) array, one axis per point (zero: isotropic)")
+        if not np.isfinite(a).all():
+            raise ValueError("axes must be finite")
+    reach = np.asarray(max_dist, dtype=np.float32)
+    if reach.shape not in ((), (s,)):
+        raise ValueError("max_dist must be a scalar or hold one value per point")
+    if not (reach > 0).all():
+        raise ValueError("max_dist must be > 0 (inf: no limit)")
+    near = np.asarray(t_min, dtype=np.float32)
+    if near.shape not in ((), (s,)) or not np.isfinite(near).all():
+        raise ValueError("t_min must be a finite scalar or hold one finite value per point")
+    src = np.zeros(s, RAY_DT)
+    src["o"], src["d"], src["tmin"], src["tmax"] = p, a, near, reach
+    return src
+
+
+def get_illumination_points(accel, points, grid_size=256, axes=None, max_dist=float("inf"), weights=None, seed=0, return_escaped=False):
+    """get_illumination (src/kernels.jl:112-124) for S POINT sources inside the scene -- lamps, heaters, antennas -- in one call: every
+    source shoots grid_size^2 jittered, stratified, equal-area rays, and the closest hits are counted per source and primitive.  Returns
+    the (S, N) uint32 counts.  For an isotropic source (no axis, or a zero one) counts[k, j] / grid_size^2 is the fraction of the lamp's
+    flux that arrives at the primitives with metadata j + 1, their visible solid angle over 4 pi; with axes[k] != 0 source k is a
+    Lambertian emitter about that axis and the fraction is its form factor to them.  max_dist: the lamps' range, a scalar or one per
+    source.  With `weights` (length S, each lamp's flux) the float64 N-vector weights @ counts / grid_size^2 instead, formed on the host
+    -- the convention of get_illumination_dirs --: the received flux per primitive, the `emission` of radiosity() up to reflectance and
+    area.  return_escaped: also the (S,) uint32 counts of rays that hit nothing."""
+    src = point_sources(points, axes, max_dist)
+    s = len(src)
+    if isinstance(grid_size, bool) or not isinstance(grid_size, (int, np.integer)) or not 0 <= int(grid_size) < 65536:
+        raise ValueError("grid_size must be an integer in 0..65535")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64):
+        raise ValueError("seed must be an integer in 0..2^64 - 1")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (s,):
+            raise ValueError("weights must hold one value per point")
+        if int(grid_size) == 0:
+            raise ValueError("weights need a grid_size above 0")
+    import torch
+    t = _owner(accel)
+    n = t.n_primitives()
+    dev = f"cuda:{t.device}"
+    torch.cuda.synchronize(t.device)  # (the call runs on the default stream: behind whatever the caller enqueued on streams of its own)
+    d_src = torch.from_numpy(src.view(np.uint8).reshape(-1).copy()).to(dev) if s else None
+    counts = torch.zeros(max(s * n, 1), dtype=torch.int32, device=dev)
+    escaped = torch.zeros(max(s, 1), dtype=torch.int32, device=dev)
+    t.illumination_points_device(d_src.data_ptr() if s else None, s, int(grid_size), counts.data_ptr(), n, escaped.data_ptr(), seed=int(seed))
+    torch.cuda.synchronize(t.device)
+    t.wait_for_gpu()  # (reports a traversal stack overflow, like the host-buffer get_illumination)
+    rows = counts.cpu().numpy().view(np.uint32)[:s * n].reshape(s, n).copy()
+    out = rows if w is None else (w @ rows.astype(np.float64)) / (float(int(grid_size)) ** 2)
+    return (out, escaped.cpu().numpy().view(np.uint32)[:s].copy()) if return_escaped else out
 
 
 def ambient_occlusion(accel, rays, hits, samples, max_dist=float("inf"), seed=0, bias=1e-3):

@@ -1923,4 +1923,34 @@ int rc_generate_ray_grid_dirs_device(rc_scene* s, const float* d_dirs, uint32_t 
     });
 }
 
+// What the two point-source calls check before anything is enqueued (0: go on)
+static int points_args(const char* name, rc_scene* s, const rc_ray* d_sources, uint32_t n_sources, uint32_t grid, uint32_t first_source, const void* d_out) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (n_sources && grid && (!d_sources || !d_out)) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": NULL argument");
+    if (grid >= 65536u) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": grid * grid must be below 2^32");
+    if ((uint64_t)first_source + n_sources > (1ull << 32)) return fail(RC_ERR_INVALID_ARGUMENT, std::string(name) + ": first_source + n_sources must not pass 2^32");
+    return 0;
+}
+int rc_point_source_rays_device(rc_scene* s, const rc_ray* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed, uint32_t first_source,
+                                rc_ray* d_rays, void* stream) {
+    if (int e = points_args("rc_point_source_rays_device", s, d_sources, n_sources, grid, first_source, d_rays)) return e;
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        if (s->n_tlas_nodes == 0) return;  // an empty scene: nothing enqueued
+        rc_launch_point_source_rays(s, reinterpret_cast<const RcRay*>(d_sources), n_sources, grid, seed, first_source, reinterpret_cast<RcRay*>(d_rays), (hipStream_t)stream);
+    });
+}
+int rc_get_illumination_points_device(rc_scene* s, const rc_ray* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed, uint32_t first_source,
+                                      uint32_t* d_counts, uint64_t row_stride, uint32_t* d_escaped, void* stream) {
+    if (int e = points_args("rc_get_illumination_points_device", s, d_sources, n_sources, grid, first_source, d_counts)) return e;
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        if (n_sources && grid && row_stride < s->n_flat_prims) throw RcError(RC_ERR_INVALID_ARGUMENT, "rc_get_illumination_points_device: row_stride is smaller than the number of primitives");
+        if (s->n_tlas_nodes == 0) return;  // an empty scene: nothing enqueued
+        rc_launch_illumination_points(s, reinterpret_cast<const RcRay*>(d_sources), n_sources, grid, seed, first_source, d_counts, row_stride, d_escaped, (hipStream_t)stream);
+    });
+}
+
 }  // extern "C"

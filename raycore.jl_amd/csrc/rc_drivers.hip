@@ -972,6 +972,117 @@ struct GatherJob {
     __device__ inline GatherSink sink(const SceneView& v) const { return GatherSink{v.inst, v.prims, v.n_prims, x, miss_value, q.samples, sum, open}; }
 };
 
+// ---- illumination from point sources: get_illumination (src/kernels.jl:112-124) for lamps at a finite position ---------------------------
+// A source is one RcRay record in device memory: o = the lamp's position, d = its axis, t_min / t_max copied unchanged into every ray it
+// emits (t_max: the lamp's range).  d.x == 0 && d.y == 0 && d.z == 0 (either sign of zero): ISOTROPIC; anything else: LAMBERTIAN about
+// normalize3(d).  Source k (0-based in the call) shoots grid^2 jittered, stratified, equal-area rays, cell = a * grid + b, a, b in [0, grid):
+//   rnd = Philox4x32-10(counter = (cell, first_source + k, 0, 0x50530000), key = (lo32 seed, hi32 seed))
+//   xi1 = u32_to_unit(rnd[0]), xi2 = u32_to_unit(rnd[1])
+//   u1 = ((float)a + xi1) / (float)grid, u2 = ((float)b + xi2) / (float)grid      (f32, one operation at a time, IEEE divide; u may
+//                                                                                   round to exactly 1: both mappings are defined there)
+//   isotropic:  z = 1 - 2 * u1;  s = sqrtf(fmaxf(0, 1 - z * z));  phi = (2 * 3.1415927f) * u2;  (sin, cos) = sincos_f64((double)phi), each
+//               rounded once to f32;  dir = (s * cos, s * sin, z), not renormalised
+//   Lambertian: dir = cosine_hemisphere_dir(normalize3(d), u1, u2)
+//   ray = {o, t_min, dir, t_max}
+// every expression left to right, no contraction.  first_source only offsets the Philox counter: the sources of one set, split over
+// calls, groups, streams or devices, give the rows of the one-call result.  A source with non-finite fields gives whatever these
+// expressions give for it, in the stage and in the driver alike.  Shared by the stage kernel and the fused driver's source, so the two
+// agree bit for bit.
+__device__ inline RcRay point_source_ray(const RcRay* sources, uint32_t first_source, uint32_t k, uint32_t cell, uint32_t grid, uint32_t k0, uint32_t k1) {
+    const RcRay src = load_ray(sources, k);
+    const uint32_t a = cell / grid, b = cell - a * grid;
+    uint32_t rnd[4];
+    philox4x32_10(cell, first_source + k, 0u, 0x50530000u, k0, k1, rnd);
+    const float u1 = ((float)a + u32_to_unit(rnd[0])) / (float)grid, u2 = ((float)b + u32_to_unit(rnd[1])) / (float)grid;
+    float3_ d;
+    if (src.dx == 0.0f && src.dy == 0.0f && src.dz == 0.0f) {
+        const float z = 1.0f - 2.0f * u1;
+        const float sn = __builtin_sqrtf(fmaxf(0.0f, 1.0f - z * z));
+        const float phi = (2.0f * 3.1415927f) * u2;
+        double sp, cp;
+        sincos_f64((double)phi, sp, cp);
+        d = mk3(sn * (float)cp, sn * (float)sp, z);
+    } else
+        d = cosine_hemisphere_dir(normalize3(mk3(src.dx, src.dy, src.dz)), u1, u2);
+    return RcRay{src.ox, src.oy, src.oz, src.tmin, d.x, d.y, d.z, src.tmax};
+}
+// The composed stage: n_sources * grid^2 rays, source k's from k * grid^2 on, in cell order.  One kernel, no scratch.
+__global__ void k_point_source_rays(const RcRay* sources, uint32_t first_source, uint32_t grid, uint32_t k0, uint32_t k1, uint64_t total, RcRay* out) {
+    const uint64_t cells = (uint64_t)grid * grid;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = i / cells;
+        store_ray(out, i, point_source_ray(sources, first_source, (uint32_t)k, (uint32_t)(i - k * cells), grid, k0, k1));
+    }
+}
+// The fused driver for a GROUP of sources in one launch: work item i = k_local * grid^2 + cell (items = G * grid^2 < 2^32: both divide in
+// 32 bits).  The source record is read HERE, when the kernel runs: a captured launch follows lamps that move between replays, and there
+// is no parameter kernel in front.
+struct PointSource {
+    const RcRay* sources;  // the group's first source
+    uint32_t first_source, cells, grid, k0, k1;
+    __device__ inline RcRay operator()(uint64_t i) const {
+        const uint32_t k = (uint32_t)i / cells, cell = (uint32_t)i - k * cells;
+        return point_source_ray(sources, first_source, k, cell, grid, k0, k1);
+    }
+    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
+};
+// DirsHistogramSink (row = the source of the group) that also counts the rays that hit nothing.  A source's escapes are ONE counter, and
+// about half of a lamp's rays escape: counted straight into d_escaped[k] with one wave-aggregated atomic per wave and source (the way the
+// totals driver counts `emitted`, whose targets change from wave to wave) the whole call ran at the rate of that word -- 3.4 to 3.7 times
+// the composed path's time at 16 and 64 sources (docs/EXPERIMENTS.md, "Illumination from point sources").  So the escapes are histogram
+// entries like the hits: the copies are laid out for n_prims + kEscapeSlots indices, an escaping ray counts on index n_prims + (a slot chosen
+// per WAVE, so that a wave's lanes still combine), in its workgroup's copy, and k_escaped_fold adds a source's 16 x 64 words into
+// d_escaped[k].  A finished ray is a counted hit, an escape or neither: one wave_count for both kinds.
+constexpr uint32_t kEscapeSlots = 64;
+struct PointEscapeSink {
+    const RcInstRec* inst;
+    const RcPrim* prims;
+    uint32_t n_prims;
+    uint32_t* scratch;  // one histogram of n_prims + kEscapeSlots indices per source of the group, zeroed by the launcher
+    CopyHist h;
+    uint32_t cells;
+    __device__ inline void operator()(uint64_t i, bool hit, float, float, float, uint32_t prim, int instance) const {
+        uint32_t j = n_prims + ((((blockIdx.x >> 4) * (blockDim.x >> 6)) + (threadIdx.x >> 6)) & (kEscapeSlots - 1u));
+        bool counted = !hit;
+        if (hit) {
+            const uint32_t meta = hit_meta(inst, prims, instance, prim);
+            counted = meta >= 1 && meta <= n_prims;  // metadata outside 1..N is dropped (src/kernels.jl:123)
+            j = meta - 1u;
+        }
+        const unsigned long long copy = (unsigned long long)((uint32_t)i / cells) * kHistCopies + h.copy();
+        wave_count(scratch, counted ? h.base(copy) + h.slot(j) : 0ull, counted);
+    }
+};
+// One thread per (source of the group, escape slot): the sum over the copies, added to the caller's word.
+__global__ void k_escaped_fold(const uint32_t* scratch, CopyHist h, uint32_t n_prims, uint32_t n_rows, uint32_t* escaped) {
+    const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    if (t >= (uint64_t)n_rows * kEscapeSlots) return;
+    const uint32_t k = (uint32_t)(t / kEscapeSlots), j = n_prims + (uint32_t)(t % kEscapeSlots);
+    const uint32_t* base = scratch + k * h.words();
+    uint32_t sum = 0;
+    for (uint32_t c = 0; c < kHistCopies; ++c) sum += base[(size_t)c * 8u * h.n8 + (j & 7u) * h.n8 + (j >> 3)];
+    if (sum) atomicAdd(escaped + k, sum);
+}
+// ESCAPED = false (d_escaped is NULL): the sink IS DirsHistogramSink, not a branch per ray.
+template <bool ESCAPED>
+struct PointIlluminationJobT {
+    const RcRay* sources;
+    uint32_t first_source, cells, grid, k0, k1;
+    uint32_t* scratch;
+    CopyHist h;  // ESCAPED: of n_prims + kEscapeSlots indices
+    __device__ inline PointSource source(const SceneView&) const { return PointSource{sources, first_source, cells, grid, k0, k1}; }
+    template <bool E = ESCAPED>
+    __device__ inline typename std::enable_if<E, PointEscapeSink>::type sink(const SceneView& v) const { return PointEscapeSink{v.inst, v.prims, v.n_prims, scratch, h, cells}; }
+    template <bool E = ESCAPED>
+    __device__ inline typename std::enable_if<!E, DirsHistogramSink>::type sink(const SceneView& v) const { return DirsHistogramSink{v.inst, v.prims, v.n_prims, scratch, h, cells}; }
+};
+// Keeps the late pop in the partial shell of the job that counts escapes: with the peeked stack top it has an 8-byte private segment (80
+// VGPRs either way).  The five other shells of the two jobs have none with the default flags.
+template <>
+struct JobShapeFlags<PointIlluminationJobT<true>> { static constexpr unsigned kPlain = 0u, kLds = 0u, kPartial = ShapeLatePop; };
+typedef PointIlluminationJobT<true> PointIlluminationJob;
+typedef PointIlluminationJobT<false> PointIlluminationCountsJob;
+
 // Diffuse bounce: output slot i continues the path of source slot s (s = i, or d_src[i] for i < count, or d_src[i % count] round robin
 // with k = i / count), from hit_point + normal * bias in a cosine-weighted direction about the geometric normal.  The uniforms are
 // Philox4x32-10(counter = (lo32 path, hi32 path, k, 0x424E0000 | bounce), key = seed): a path's bounce does not depend on compaction,
@@ -1212,6 +1323,47 @@ void rc_launch_illumination_dirs(rc_scene* s, const float* d_dirs, uint32_t n_di
         launch.go<false>(IlluminationDirsJob{scratch.params, (uint32_t)cells, scratch.hist, h}, Nothing(),
                          [&] { rc_hist_fold(stream, scratch.hist, h, np, FoldAddU32Rows{nd, d_counts + (uint64_t)d0 * row_stride, row_stride}); });
     }
+}
+
+// n_sources x grid^2 rays of device-resident point sources (k_point_source_rays): reads no scene memory.
+void rc_launch_point_source_rays(rc_scene* s, const RcRay* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed, uint32_t first_source,
+                                 RcRay* d_rays, hipStream_t stream) {
+    const uint64_t total = (uint64_t)n_sources * grid * grid;
+    launch_stage<8, false>(s, stream, total, k_point_source_rays, d_sources, first_source, grid, (uint32_t)seed, (uint32_t)(seed >> 32), total, d_rays);
+}
+
+// get_illumination for n_sources device-resident POINT sources, ACCUMULATED into d_counts[k * row_stride + (meta - 1)] (u32) and, unless
+// it is null, the rays that hit nothing into d_escaped[k].  The sources are traced in groups of G consecutive ones like the directions of
+// rc_launch_illumination_dirs, under the same rule for G (G * grid^2 < 2^32, histogram copies within option "illum_scratch_bytes", at least
+// one source's worth).  Per group: one memset, one persistent launch (PointIlluminationJob), one fold; the group's first index is added to
+// first_source for the Philox counter, so the grouping changes no result.  Nothing is read on the host and there is no kernel in front:
+// the source records are read by the traversal kernel itself.  grid^2 < 2^32 and first_source + n_sources <= 2^32 (checked by the caller).
+template <bool ESCAPED>
+static void launch_illumination_points(rc_scene* s, const RcRay* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed, uint32_t first_source,
+                                       uint32_t* d_counts, uint64_t row_stride, uint32_t* d_escaped, hipStream_t stream) {
+    const uint32_t np = s->n_flat_prims;
+    const CopyHist h = CopyHist::of(ESCAPED ? np + kEscapeSlots : np);  // (the escapes are kEscapeSlots more indices of every copy: PointEscapeSink)
+    const uint64_t cells = (uint64_t)grid * grid;
+    const uint64_t source_bytes = sizeof(uint32_t) * h.words();
+    const uint64_t group = std::min<uint64_t>(n_sources, std::min<uint64_t>(((1ull << 32) - 1u) / cells, std::max<uint64_t>((uint64_t)s->opt.illum_scratch_bytes / source_bytes, 1)));
+    for (uint32_t k0 = 0; k0 < n_sources; k0 += (uint32_t)group) {
+        const uint32_t nk = (uint32_t)std::min<uint64_t>(group, n_sources - k0);
+        DriverLaunch launch(s, stream, nk * cells);
+        uint32_t* scratch = rc_hist_scratch<uint32_t>(launch.guard, h, nk).hist;
+        launch.go<false>(PointIlluminationJobT<ESCAPED>{d_sources + k0, first_source + k0, (uint32_t)cells, grid, (uint32_t)seed, (uint32_t)(seed >> 32), scratch, h},
+                         Nothing(), [&] {
+                             rc_hist_fold(stream, scratch, h, np, FoldAddU32Rows{nk, d_counts + (uint64_t)k0 * row_stride, row_stride});
+                             if (ESCAPED)
+                                 hipLaunchKernelGGL(k_escaped_fold, dim3((uint32_t)(((uint64_t)nk * kEscapeSlots + 255u) / 256u)), dim3(256), 0, stream,
+                                                    (const uint32_t*)scratch, h, np, nk, d_escaped + k0);
+                         });
+    }
+}
+void rc_launch_illumination_points(rc_scene* s, const RcRay* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed, uint32_t first_source,
+                                   uint32_t* d_counts, uint64_t row_stride, uint32_t* d_escaped, hipStream_t stream) {
+    if (n_sources == 0 || grid == 0 || s->n_flat_prims == 0) return;
+    if (d_escaped) launch_illumination_points<true>(s, d_sources, n_sources, grid, seed, first_source, d_counts, row_stride, d_escaped, stream);
+    else launch_illumination_points<false>(s, d_sources, n_sources, grid, seed, first_source, d_counts, row_stride, nullptr, stream);
 }
 
 // RC_VF_SOURCES_BY_METADATA: the flat primitives' indices sorted by (metadata, index) -- and the sorted metadata themselves on the host --

@@ -431,6 +431,13 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
 // the same for n_dirs device-resident directions, laid out on the device from the TLAS root: no host copy of the world bound is read; grid^2 < 2^32
 void rc_launch_ray_grid_dirs(rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, RcRay* d_rays, hipStream_t stream);
 void rc_launch_illumination_dirs(rc_scene* s, const float* d_dirs, uint32_t n_dirs, uint32_t grid, uint32_t* d_counts, uint64_t row_stride, hipStream_t stream);
+// get_illumination for device-resident POINT sources (one RcRay record each: position, axis -- zero: isotropic, else Lambertian --, t_min, t_max),
+// grid^2 stratified rays per source keyed by (seed, first_source + k, cell): the ray stage, and the fused driver that ACCUMULATES
+// d_counts[k * row_stride + meta - 1] and d_escaped[k] (may be null).  grid^2 < 2^32, first_source + n_sources <= 2^32
+void rc_launch_point_source_rays(rc_scene* s, const RcRay* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed, uint32_t first_source,
+                                 RcRay* d_rays, hipStream_t stream);
+void rc_launch_illumination_points(rc_scene* s, const RcRay* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed, uint32_t first_source,
+                                   uint32_t* d_counts, uint64_t row_stride, uint32_t* d_escaped, hipStream_t stream);
 void rc_launch_view_factors(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end,
                             uint32_t ray_begin, uint32_t ray_end, uint32_t* d_matrix, uint64_t row_stride,
                             uint64_t col_stride, uint32_t row_offset, uint32_t flags, hipStream_t stream);

@@ -488,6 +488,56 @@ function get_illumination_dirs(a::MI355XStaticTLAS, viewdirs::AbstractVector; gr
     return weights === nothing ? out : Float64.(out) * Float64[weights...]
 end
 
+"The rays of `n_sources` device-resident POINT sources: n_sources x grid^2 RTRay records, source `k`'s (0-based) from `k * grid^2` on in
+ cell order.  A source is one RTRay record: `o` = the lamp's position, `d` = its axis (zero: isotropic, anything else: a Lambertian
+ emitter about it), `t_min` / `t_max` copied into every ray it emits.  Read when the kernel runs."
+point_source_rays_device!(a::MI355XStaticTLAS, d_sources::Ptr{RTRay}, n_sources::Integer, grid_size::Integer, d_rays::Ptr{RTRay};
+                          seed::UInt64 = UInt64(0), first_source::Integer = 0, stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_point_source_rays_device, LIB), Cint, (Ptr{Cvoid}, Ptr{RTRay}, UInt32, UInt32, UInt64, UInt32, Ptr{RTRay}, Ptr{Cvoid}),
+                a.owner.ptr, d_sources, n_sources, grid_size, seed, first_source, d_rays, stream))
+"get_illumination for `n_sources` POINT sources in one call: grid^2 jittered, stratified, equal-area rays per source, the rays of
+ `point_source_rays_device!` bit for bit.  `d_counts[k * row_stride + meta - 1]` (0-based, UInt32, ACCUMULATED: zero it first) += the
+ hits of source `k`; `d_escaped[k]` (UInt32, may be `C_NULL`) += its rays that hit nothing.  `d_sources` is read when the kernel runs: no
+ host wait behind the asynchronous updates, capturable, and a replay follows lamps that moved.  `first_source` only offsets the
+ random-number counter: sources [a, b) of a set with `first_source = a` give rows [a, b) of the one-call result."
+illumination_points_device!(a::MI355XStaticTLAS, d_sources::Ptr{RTRay}, n_sources::Integer, grid_size::Integer, d_counts::Ptr{UInt32},
+                            row_stride::Integer = counts(a.owner)[4]; d_escaped::Ptr{UInt32} = Ptr{UInt32}(C_NULL), seed::UInt64 = UInt64(0),
+                            first_source::Integer = 0, stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_get_illumination_points_device, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{RTRay}, UInt32, UInt32, UInt64, UInt32, Ptr{UInt32}, UInt64, Ptr{UInt32}, Ptr{Cvoid}),
+                a.owner.ptr, d_sources, n_sources, grid_size, seed, first_source, d_counts, row_stride, d_escaped, stream))
+"get_illumination (src/kernels.jl:112-124) for point sources inside the scene: an N x S Matrix{UInt32} whose column `k` counts, per
+ primitive metadata, the closest hits of the grid_size^2 rays of the lamp at `points[k]`.  `axes[k]` zero (or no axes): isotropic, and
+ count / grid_size^2 is the visible solid angle over 4 pi; anything else: a Lambertian emitter about it, and the fraction is its form
+ factor.  `max_dist`: the lamps' range.  With `weights` (each lamp's flux) the length-N Float64 vector `counts * weights / grid_size^2`,
+ formed on the host; `return_escaped`: also the per-source counts of rays that hit nothing."
+function get_illumination_points(a::MI355XStaticTLAS, points::AbstractVector; grid_size = 256, axes = nothing, max_dist = Inf32,
+                                 weights = nothing, seed::UInt64 = UInt64(0), return_escaped::Bool = false)
+    ns, np = length(points), Int(counts(a.owner)[4])
+    all(p -> length(p) == 3, points) || error("every point needs three components")
+    axes === nothing || (length(axes) == ns && all(v -> length(v) == 3, axes)) || error("axes must hold one three-component axis per point")
+    weights === nothing || length(weights) == ns || error("weights must hold one value per point")
+    0 <= grid_size < 65536 || error("grid_size must lie in 0..65535")
+    max_dist > 0 || error("max_dist must be > 0")
+    src = RTRay[RTRay(points[k][1], points[k][2], points[k][3], 0f0,
+                      axes === nothing ? 0f0 : axes[k][1], axes === nothing ? 0f0 : axes[k][2], axes === nothing ? 0f0 : axes[k][3],
+                      Float32(max_dist)) for k in 1:ns]
+    rows, escaped = zeros(UInt32, np, ns), zeros(UInt32, ns)
+    if ns > 0 && np > 0 && grid_size > 0
+        d_src, d_counts, d_escaped = device_alloc(sizeof(src)), device_alloc(sizeof(rows)), device_alloc(sizeof(escaped))
+        device_upload!(d_src, src)
+        device_zero!(d_counts, sizeof(rows))
+        device_zero!(d_escaped, sizeof(escaped))
+        illumination_points_device!(a, Ptr{RTRay}(d_src), ns, grid_size, Ptr{UInt32}(d_counts), np; d_escaped = Ptr{UInt32}(d_escaped), seed = seed)
+        Raycore.wait_for_gpu!(a.owner)
+        device_download!(vec(rows), d_counts)
+        device_download!(escaped, d_escaped)
+        device_free(d_src); device_free(d_counts); device_free(d_escaped)
+    end
+    out = weights === nothing ? rows : Float64.(rows) * Float64[weights...] / Float64(grid_size)^2
+    return return_escaped ? (out, escaped) : out
+end
+
 "One shard of view_factors! (src/kernels.jl:80-104): source primitives [src_begin, src_end) x rays [ray_begin, ray_end), counts
  ACCUMULATED into d_matrix at row * row_stride + col * col_stride (row = src_meta - 1, or the source's sorted position - row_offset
  when by_primitive); the multi-GPU drivers (one process per GPU, RCCL) are built on this entry point."
