@@ -814,6 +814,53 @@ int rc_view_factor_products_device(rc_scene* scene, uint32_t rays_per_triangle, 
                                    uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_x, uint64_t* d_mx, uint64_t* d_mtx, void* stream);
 int rc_view_factor_products(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, const uint32_t* x, uint64_t* out_mx, uint64_t* out_mtx);
 
+/* ---- Form factors between surface groups: the view-factor job (src/kernels.jl:74-104) with a choice of SAMPLING, counted per GROUP of
+ * primitives -- a wall, a sphere, a thermal zone -- with a WEIGHT per source primitive.  The reference shoots its rays uniformly over the
+ * hemisphere (random_hemisphere_uniform, src/kernels.jl:92); a Lambertian surface exchanges energy with a cosine weighting, so the
+ * reference's matrix is not a form-factor matrix: between opposite walls of the unit cube it gives 0.11 where the form factor is 0.1998.
+ * THE SAMPLED RAY of (source primitive, ray index): the Philox4x32-10 draw of rc_view_factor_rays_device -- counter (ray_idx, src_prim, 0,
+ * 0), key = seed -> r1, r2, xi1, xi2 -- and, in BOTH samplings, its point on the triangle and its origin pt + normal * 0.01f.
+ *   RC_VF_SAMPLING_UNIFORM: the direction of rc_view_factor_rays_device, bit for bit (the same device function).
+ *   RC_VF_SAMPLING_COSINE:  d = the cosine-weighted direction about the triangle's unit normal that rc_bounce_rays_device makes from
+ *     (normal, xi1, xi2) -- the same function, applied to the third and fourth Philox words, not renormalised.  t_min = 0, t_max = inf.
+ * rc_view_factor_sampled_rays_device, the composed stage: writes rays [ray_begin, ray_begin + n_rays) of one source primitive, the sibling
+ * of rc_view_factor_rays_device.  RC_ERR_INVALID_ARGUMENT for a NULL scene or d_rays, sampling > 1, or src_prim out of range.
+ * rc_view_factor_groups_device, the fused driver.  Work item w -> flat source primitive src_begin + w / n_ray, ray ray_begin + w % n_ray,
+ * traced for the closest hit.  THE RULE, word for word:
+ *   N = number of flat primitives. a = the source's metadata, b = the hit's. ga = groups[a-1], gb = groups[b-1]. wa = weights ? weights[a-1] : 1.
+ *   A source whose a is outside 1..N, or whose ga >= G, contributes nothing.
+ *   Miss: escaped[ga] += wa, if escaped is given.
+ *   Hit with b in 1..N, b != a and gb < G: matrix[ga * G + gb] += wa.  (The reference's rule hit_idx != tri_idx, src/kernels.jl:96, is kept.)
+ *   Any other hit adds nothing.
+ *   All sums are u64 modulo 2^64: exact in any order, so any partition of sources x rays gives the same words.
+ * d_groups, d_weights: N u32 each, indexed by metadata - 1, read WHEN THE KERNEL RUNS and for metadata in 1..N only; d_weights may be NULL.
+ * d_matrix: G * G u64, row = source group; d_escaped: G u64, or NULL.  A group value >= G (0xFFFFFFFF, say) excludes a primitive as a
+ * source and as a target.
+ * THE IDENTITY.  With RC_VF_SAMPLING_UNIFORM the result is an exact function of the reference's matrix M = result[src_meta, hit_meta] of
+ * rc_view_factors for the same (rays_per_triangle, seed):  matrix = P diag(w) M P^T  with P[g, i] = (groups[i] == g), in integers; with
+ * identity groups and no weights it IS that matrix (u32 widened), and its row and column sums are rc_view_factor_totals' vectors.  In both
+ * samplings the words equal what rc_view_factor_sampled_rays_device -> rc_trace_closest_device -> the rule above give.  With
+ * RC_VF_SAMPLING_COSINE and weights proportional to the primitives' areas, matrix[A, B] / (R * sum of the weights of A) estimates the form
+ * factor F_AB = sum_{i in A} A_i F_iB / A_A.
+ * Both outputs ACCUMULATE: the caller zeroes them.  Rays [ray_begin, ray_end) of the sources with flat primitive indices [src_begin,
+ * src_end), clamped to the scene like rc_view_factor_totals_device's; an empty range enqueues nothing; shards accumulate on one stream
+ * or concurrently on several.  With a handful of groups every wave adds onto a few dozen words, so the kernel counts into private copies
+ * of the G * G (+ G) words and adds them to the outputs atomically at the end of the launch when the copies (128 * 8 * ceil((G * G + G) / 8)
+ * bytes) fit 256 MiB (G <= 1447 with escapes), and straight onto the outputs otherwise.  Both paths give the same words.
+ * Scratch is per stream; nothing is read on the host, and the call may be captured on a stream that has run it eagerly once, like
+ * rc_view_factor_products_device; a replay reads the CURRENT d_groups and d_weights.  Legal behind rc_update_geometry_device_async on the
+ * same stream with no host wait.
+ * RC_ERR_INVALID_ARGUMENT for a NULL scene, d_groups or d_matrix, for sampling > 1, and for n_groups outside 1..65535 (the kernel indexes
+ * G * G + G words in 32 bits); RC_ERR_NOT_SYNCED as the other *_device queries.
+ * Register and scratch figures of the kernel shells and the measurements: docs/EXPERIMENTS.md, "Form factors between surface groups". */
+#define RC_VF_SAMPLING_UNIFORM 0u   /* the reference's rays, src/kernels.jl:92 */
+#define RC_VF_SAMPLING_COSINE  1u   /* Lambertian: form factors */
+int rc_view_factor_sampled_rays_device(rc_scene* scene, uint64_t seed, uint32_t sampling, uint32_t src_prim, uint32_t ray_begin,
+                                       uint32_t n_rays, rc_ray* d_rays, void* stream);
+int rc_view_factor_groups_device(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t src_begin,
+                                 uint32_t src_end, uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups,
+                                 const uint32_t* d_weights, uint64_t* d_matrix, uint64_t* d_escaped, void* stream);
+
 /* ---- Sparse view-factor matrix: the matrix of view_factors (src/kernels.jl:74-104) ITSELF, as CSR, built once on the device.  A source
  * shoots rays_per_triangle rays, so a row of M = the reference's result[src_meta, hit_meta] has at most min(R, N) non-zeros: the dense N x N
  * form is the wrong container (4 TB at 1 Mi triangles; the CSR at R = 256 holds at most 256 Mi entries).  Same rays (Philox keyed by seed,

@@ -93,6 +93,8 @@ SYMBOLS = [
     ("rc_view_factor_totals_multi", _int, [C.POINTER(_vp), _int, _u32, _u64, _vp, _vp]),
     ("rc_view_factor_products_device", _int, [_vp, _u32, _u64, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     ("rc_view_factor_products", _int, [_vp, _u32, _u64, _vp, _vp, _vp]),
+    ("rc_view_factor_sampled_rays_device", _int, [_vp, _u64, _u32, _u32, _u32, _u32, _vp, _vp]),
+    ("rc_view_factor_groups_device", _int, [_vp, _u32, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     ("rc_view_factors_sparse_device", _int, [_vp, _u32, _u64, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp]),
     ("rc_view_factors_sparse", _int, [_vp, _u32, _u64, _vp, _vp, _vp, _u64, _vp]),
     ("rc_view_factor_sparse_products_device", _int, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

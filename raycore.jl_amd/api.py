@@ -636,6 +636,27 @@ class TLAS:
                                                    ptr(mx_ptr) if mx_ptr else None, ptr(mtx_ptr) if mtx_ptr else None,
                                                    ptr(stream) if stream else None))
 
+    def view_factor_sampled_rays_device(self, d_rays, src_prim, n_rays, seed=0, sampling="uniform", ray_begin=0, stream=None):
+        """The sampled view-factor rays of one flat source primitive (rc_view_factor_sampled_rays_device): n_rays RTRay records for ray
+        indices ray_begin.. .  sampling "uniform": the reference's rays, bit for bit view_factor_rays_device's; "cosine": the same
+        origins with cosine-weighted directions about the triangle's normal -- the rays of form factors."""
+        check(lib().rc_view_factor_sampled_rays_device(self._h, int(seed), vf_sampling(sampling), int(src_prim), int(ray_begin), int(n_rays), ptr(d_rays),
+                                                       ptr(stream) if stream else None))
+
+    def view_factor_groups_device(self, groups_ptr, n_groups, matrix_ptr, rays_per_triangle, seed, sampling="uniform", weights_ptr=None,
+                                  escaped_ptr=None, src=None, rays=None, stream=None):
+        """Weighted counts between GROUPS of primitives (rc_view_factor_groups_device).  groups_ptr / weights_ptr (may be None: weight 1):
+        N u32 each, indexed by metadata - 1, read when the kernel runs; matrix_ptr: n_groups x n_groups u64, row = source group;
+        escaped_ptr: n_groups u64 or None.  Both outputs are ACCUMULATED: a ray from metadata a (group ga, weight wa) that hits metadata
+        b != a of group gb adds wa to matrix[ga, gb], one that hits nothing adds wa to escaped[ga]; a group >= n_groups excludes the
+        primitive.  src / rays: (begin, end) ranges of flat source primitives and of ray indices (default: all) -- the shards of one
+        job add up to the whole, on one stream or on several."""
+        s0, s1 = (0, 0xFFFFFFFF) if src is None else src
+        r0, r1 = (0, int(rays_per_triangle)) if rays is None else rays
+        check(lib().rc_view_factor_groups_device(self._h, int(rays_per_triangle), int(seed), vf_sampling(sampling), int(s0), int(s1), int(r0), int(r1),
+                                                 ptr(groups_ptr), int(n_groups), ptr(weights_ptr) if weights_ptr else None, ptr(matrix_ptr),
+                                                 ptr(escaped_ptr) if escaped_ptr else None, ptr(stream) if stream else None))
+
     def view_factors_sparse_device(self, row_ptr_ptr, cols_ptr, vals_ptr, capacity, nnz_ptr, rays_per_triangle, seed, rows=None, stream=None):
         """Rows `rows` = (begin, end) (default: all; end is clamped to N) of the view-factor matrix in canonical CSR on the device
         (rc_view_factors_sparse_device), OVERWRITTEN: row_ptr_ptr: rows + 1 u64 starting at 0; cols_ptr / vals_ptr: `capacity` u32 each
@@ -1215,6 +1236,137 @@ def view_factor_products(accel, x, rays_per_triangle=10000, seed=0):
     return mx, mtx
 
 
+VF_SAMPLING = {"uniform": 0, "cosine": 1}  # RC_VF_SAMPLING_UNIFORM (the reference's rays) / RC_VF_SAMPLING_COSINE (Lambertian: form factors)
+MAX_VF_GROUPS = 65535
+VF_NO_GROUP = U32_MAX  # a group value that excludes a primitive whatever n_groups is
+
+
+def vf_sampling(sampling):
+    """The RC_VF_SAMPLING_* word of "uniform" / "cosine" (or of 0 / 1).  ValueError for anything else."""
+    if isinstance(sampling, str) and sampling in VF_SAMPLING:
+        return VF_SAMPLING[sampling]
+    if not isinstance(sampling, (bool, str)) and isinstance(sampling, (int, np.integer)) and int(sampling) in (0, 1):
+        return int(sampling)
+    raise ValueError(f"sampling must be 'uniform' or 'cosine', not {sampling!r}")
+
+
+def _u32_vector(a, what):
+    """A one-dimensional array of integers in 0..2^32 - 1 as contiguous uint32.  ValueError otherwise."""
+    a = np.asarray(a)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be a one-dimensional integer array with one value per primitive")
+    if a.size and (int(a.min()) < 0 or int(a.max()) > U32_MAX):
+        raise ValueError(f"{what} must lie in 0..2^32 - 1")
+    return np.ascontiguousarray(a.astype(np.uint32))
+
+
+def check_groups_arguments(groups, weights, rays_per_triangle, seed, sampling, n_groups):
+    """The arguments of view_factor_groups, checked before any device is touched: (groups u32, weights u32 or None, sampling word, G)."""
+    g = _u32_vector(groups, "groups")
+    w = None if weights is None else _u32_vector(weights, "weights")
+    if w is not None and len(w) != len(g):
+        raise ValueError(f"groups and weights must hold one value per primitive each: {len(g)} groups, {len(w)} weights")
+    if isinstance(rays_per_triangle, bool) or not isinstance(rays_per_triangle, (int, np.integer)) or not 0 <= int(rays_per_triangle) <= U32_MAX:
+        raise ValueError("rays_per_triangle must be an integer in 0..2^32 - 1")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64):
+        raise ValueError("seed must be an integer in 0..2^64 - 1")
+    word = vf_sampling(sampling)
+    if n_groups is None:
+        named = g[g < VF_NO_GROUP]
+        n_groups = int(named.max()) + 1 if named.size else 0
+    if isinstance(n_groups, bool) or not isinstance(n_groups, (int, np.integer)) or not 1 <= int(n_groups) <= MAX_VF_GROUPS:
+        raise ValueError(f"n_groups must be an integer in 1..{MAX_VF_GROUPS} (the default is the largest group below 2^32 - 1, plus one)")
+    return g, w, word, int(n_groups)
+
+
+def view_factor_groups(accel, groups, rays_per_triangle=10000, seed=0, weights=None, sampling="uniform", n_groups=None, return_escaped=False):
+    """Weighted view-factor counts between GROUPS of primitives -- walls, bodies, thermal zones -- without the N x N matrix
+    (rc_view_factor_groups_device): the (G, G) uint64 array [source group, hit group].  groups[i] is the 0-based group of the primitives
+    with metadata i + 1 (length N; a value >= n_groups, 2^32 - 1 say, leaves them out as sources and as targets); weights[i] (uint32,
+    default 1) is what each of their rays adds.  Every primitive shoots rays_per_triangle rays: sampling "uniform" shoots the
+    reference's (then the result is P diag(w) M P^T of M = view_factors(accel, rays_per_triangle, seed), exactly), "cosine" shoots
+    them cosine-weighted about the normal, as a Lambertian surface emits: the counts of FORM factors (form_factors()).  A ray that hits
+    its own source's metadata is not counted (the reference's rule); one that hits nothing is counted in `escaped` ((G,) uint64,
+    returned too with return_escaped).  n_groups defaults to the largest group below 2^32 - 1, plus one.  Upload, one call, download.
+    ValueError for wrong lengths, values outside u32, an unknown sampling or n_groups outside 1..65535."""
+    g, w, word, G = check_groups_arguments(groups, weights, rays_per_triangle, seed, sampling, n_groups)
+    import torch
+    t = _owner(accel)
+    n = t.n_primitives()
+    if len(g) != n:
+        raise ValueError(f"groups must hold one value per primitive: {len(g)} values for {n} primitives")
+    dev = f"cuda:{t.device}"
+    torch.cuda.synchronize(t.device)  # (the call runs on the default stream: behind whatever the caller enqueued on streams of its own)
+    d_g = torch.from_numpy(g.view(np.int32)).to(dev) if n else None
+    d_w = torch.from_numpy(w.view(np.int32)).to(dev) if (w is not None and n) else None
+    out = torch.zeros(G * G + G, dtype=torch.int64, device=dev)
+    if n:
+        t.view_factor_groups_device(d_g.data_ptr(), G, out.data_ptr(), int(rays_per_triangle), int(seed), word, d_w.data_ptr() if d_w is not None else None,
+                                    out.data_ptr() + 8 * G * G)
+    torch.cuda.synchronize(t.device)
+    t.wait_for_gpu()  # (reports a traversal stack overflow)
+    words = out.cpu().numpy().view(np.uint64)
+    matrix, escaped = words[:G * G].reshape(G, G).copy(), words[G * G:].copy()
+    return (matrix, escaped) if return_escaped else matrix
+
+
+def form_factor_weights(areas, rays_per_triangle):
+    """Integer ray weights proportional to the primitives' areas, for view_factor_groups: w = floor(areas * s) as uint32, with s the
+    largest scale for which every w <= 2^32 - 1 and rays_per_triangle * sum(w) < 2^63 (the u64 sums of a group then never wrap, and fit
+    an int64).  Pure numpy.  ValueError unless areas is a vector of finite values >= 0 with a positive one, and rays_per_triangle an
+    integer in 1..2^32 - 1."""
+    a = np.asarray(areas, dtype=np.float64)
+    if a.ndim != 1 or not np.isfinite(a).all() or (a < 0).any() or not (a > 0).any():
+        raise ValueError("areas must be a vector of finite, non-negative values, at least one of them positive")
+    if isinstance(rays_per_triangle, bool) or not isinstance(rays_per_triangle, (int, np.integer)) or not 1 <= int(rays_per_triangle) <= U32_MAX:
+        raise ValueError("rays_per_triangle must be an integer in 1..2^32 - 1")
+    R = int(rays_per_triangle)
+    s = min(U32_MAX / float(a.max()), float(1 << 63) / (R * float(a.sum())))
+    while True:
+        w = np.minimum(np.floor(a * s), float(U32_MAX)).astype(np.uint64)
+        if R * int(w.sum(dtype=np.uint64)) < (1 << 63):  # (sum(w) <= N * 2^32 < 2^64: the u64 sum itself does not wrap)
+            return w.astype(np.uint32)
+        s = np.nextafter(s, 0.0)  # the float quotient rounded up: one step down restores the bound
+
+
+def primitive_areas(accel):
+    """The areas of the scene's primitives as float64, indexed by metadata - 1 (the order of groups and weights), from the exported
+    primitives: |cross(v1 - v0, v2 - v0)| / 2 in float64.  ValueError unless the metadata are a permutation of 1..N (the view-factor
+    convention, src/kernels.jl:85)."""
+    prims = _owner(accel)._prims()
+    n = len(prims)
+    meta = prims["meta"].astype(np.int64)
+    if not np.array_equal(np.sort(meta), np.arange(1, n + 1)):
+        raise ValueError("primitive_areas needs metadata that are a permutation of 1..N")
+    v = prims["v"].astype(np.float64)
+    out = np.empty(n, np.float64)
+    out[meta - 1] = 0.5 * np.linalg.norm(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]), axis=1)
+    return out
+
+
+def form_factors_from_counts(matrix, escaped, groups, weights, rays_per_triangle):
+    """The float arithmetic of form_factors on view_factor_groups' integers: F[A, B] = matrix[A, B] / (R * sum_{i in A} w_i) and escaped[A]
+    likewise, float64; a group without weight gets zeros.  The denominators are formed in Python integers."""
+    matrix, escaped = np.asarray(matrix, np.uint64), np.asarray(escaped, np.uint64)
+    G = len(escaped)
+    g, w = np.asarray(groups, np.int64), np.asarray(weights, np.uint64)
+    denom = np.array([int(rays_per_triangle) * int(w[g == A].sum(dtype=np.uint64)) for A in range(G)], dtype=np.float64)
+    safe = np.where(denom > 0, denom, 1.0)
+    return matrix.astype(np.float64) / safe[:, None], escaped.astype(np.float64) / safe
+
+
+def form_factors(accel, groups, rays_per_triangle=10000, seed=0, n_groups=None):
+    """Form factors between groups of primitives: (F, escaped), float64, F[A, B] = the fraction of the energy a Lambertian surface A emits
+    that arrives at surface B first, escaped[A] the fraction that leaves the scene.  Cosine sampling with area weights:
+    F_AB = sum_{i in A} A_i F_iB / A_A is estimated by view_factor_groups(..., weights=form_factor_weights(primitive_areas(accel), R),
+    sampling="cosine") over R * sum_{i in A} w_i.  Rays between two primitives of the SAME metadata are not counted; rows sum to at most 1.
+    groups: as in view_factor_groups.  A G x G radiosity solve on F is one numpy line: B = solve(I - diag(rho) F, E)."""
+    check_groups_arguments(groups, None, rays_per_triangle, seed, "cosine", n_groups)
+    w = form_factor_weights(primitive_areas(accel), rays_per_triangle)
+    matrix, escaped = view_factor_groups(accel, groups, rays_per_triangle, seed, weights=w, sampling="cosine", n_groups=n_groups, return_escaped=True)
+    return form_factors_from_counts(matrix, escaped, groups, w, rays_per_triangle)
+
+
 def _is_tensor(a):
     return type(a).__module__.split(".")[0] == "torch"
 
@@ -1400,7 +1552,7 @@ def view_factor_bounces(accel, emission, reflectance, bounces, rays_per_triangle
 
     M is what view_factors(accel, R, seed) returns, as a [src_meta - 1, hit_meta - 1] array, R = rays_per_triangle: the REFERENCE's matrix,
     whose rays leave a triangle uniformly over the hemisphere -- view factors as the reference defines them, not cosine-corrected form
-    factors.  The same seed is used every bounce, so this is the iteration with that one matrix, and every step is exact: no float is
+    factors (form_factors() gives those, cosine-sampled and area-weighted, between groups of primitives).  The same seed is used every bounce, so this is the iteration with that one matrix, and every step is exact: no float is
     involved, and the result does not depend on how the device orders its adds.
     emission: u32 per primitive (indexed by metadata - 1); reflectance: 0..65536, 16.16 fixed point (65536 = 1.0).  Both are numpy integer
     arrays or device int64 / int32 torch tensors (int32: the bit patterns of u32 words).  Each bounce is zero -> view_factor_products_device
@@ -1493,7 +1645,8 @@ def radiosity_scale(emission, reflectance):
 def radiosity(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, stream=None, return_scale=False, matrix=None):
     """Radiosity by `bounces` steps of B <- E + rho .* (M B) / R in float terms: the convenience on top of view_factor_bounces.
     M is the REFERENCE's view-factor matrix view_factors(accel, R, seed), sampled with its uniform-hemisphere rays -- view factors as the
-    reference defines them, NOT cosine-corrected form factors.  emission: float array >= 0; reflectance: float array in [0, 1) (ValueError
+    reference defines them, NOT cosine-corrected form factors (for those, at the level of groups of primitives, see form_factors(): a
+    G x G solve on its matrix is one numpy line).  emission: float array >= 0; reflectance: float array in [0, 1) (ValueError
     otherwise).  e is quantised to u32 with a scale that leaves the headroom 1 / (1 - max rho) below 2^32, rho to 16.16 fixed point
     (radiosity_scale), the iteration runs in integers on the device, and the result is scaled back to float64.
     return_scale: also return the scale (result = integer iterate / scale; one quantisation step is 1 / scale).

@@ -1570,6 +1570,20 @@ int rc_view_factor_products_device(rc_scene* s, uint32_t rays_per_triangle, uint
                               reinterpret_cast<unsigned long long*>(d_mtx), (hipStream_t)stream);
     });
 }
+// The G x G matrix of weighted counts between groups of primitives, with a choice of sampling (ViewFactorGroupsSink, rc_drivers.hip).
+int rc_view_factor_groups_device(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t src_begin, uint32_t src_end,
+                                 uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
+                                 uint64_t* d_matrix, uint64_t* d_escaped, void* stream) {
+    if (!s || !d_groups || !d_matrix) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (sampling > RC_VF_SAMPLING_COSINE) return fail(RC_ERR_INVALID_ARGUMENT, "rc_view_factor_groups_device: sampling must be RC_VF_SAMPLING_UNIFORM or RC_VF_SAMPLING_COSINE");
+    if (n_groups < 1 || n_groups > 65535) return fail(RC_ERR_INVALID_ARGUMENT, "rc_view_factor_groups_device: n_groups must lie in 1..65535");
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        rc_launch_vf_groups(s, rays_per_triangle, seed, sampling, src_begin, src_end, ray_begin, ray_end, d_groups, n_groups, d_weights,
+                            reinterpret_cast<unsigned long long*>(d_matrix), reinterpret_cast<unsigned long long*>(d_escaped), (hipStream_t)stream);
+    });
+}
 // Host arrays: x goes up behind the two zeroed vectors of the scene's staging area, one launch over all sources and rays, the vectors come back.
 int rc_view_factor_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, const uint32_t* x, uint64_t* out_mx, uint64_t* out_mtx) {
     if (!s || !x || (!out_mx && !out_mtx)) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -1703,6 +1717,18 @@ int rc_view_factor_rays_device(rc_scene* s, uint64_t seed, uint32_t src_prim, ui
         require_synced(s);
         if (src_prim >= s->n_flat_prims) throw RcError(RC_ERR_INVALID_ARGUMENT, "src_prim out of range");
         rc_launch_view_factor_rays(s, seed, src_prim, ray_begin, n_rays, reinterpret_cast<RcRay*>(d_rays), (hipStream_t)stream);
+    });
+}
+
+int rc_view_factor_sampled_rays_device(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t src_prim, uint32_t ray_begin, uint32_t n_rays, rc_ray* d_rays,
+                                       void* stream) {
+    if (!s || !d_rays) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (sampling > RC_VF_SAMPLING_COSINE) return fail(RC_ERR_INVALID_ARGUMENT, "rc_view_factor_sampled_rays_device: sampling must be RC_VF_SAMPLING_UNIFORM or RC_VF_SAMPLING_COSINE");
+    return guarded([&] {
+        use_device(s);
+        require_synced(s);
+        if (src_prim >= s->n_flat_prims) throw RcError(RC_ERR_INVALID_ARGUMENT, "src_prim out of range");
+        rc_launch_view_factor_sampled_rays(s, seed, sampling, src_prim, ray_begin, n_rays, reinterpret_cast<RcRay*>(d_rays), (hipStream_t)stream);
     });
 }
 

@@ -1083,6 +1083,110 @@ struct JobShapeFlags<PointIlluminationJobT<true>> { static constexpr unsigned kP
 typedef PointIlluminationJobT<true> PointIlluminationJob;
 typedef PointIlluminationJobT<false> PointIlluminationCountsJob;
 
+// ---- form factors between surface groups: the view-factor job with a choice of sampling, counted per GROUP of primitives ------------------
+// The sampled view-factor ray of (source primitive, ray index): view_factor_ray()'s Philox draw -- counter (ray_idx, src, 0, 0), key = seed
+// -> r1, r2, xi1, xi2 -- and its point on the triangle and origin pt + normal * 0.01f in both samplings.  COSINE = false: view_factor_ray()
+// itself, the reference's uniform hemisphere (src/kernels.jl:92).  COSINE = true: d = cosine_hemisphere_dir(normal, xi1, xi2), the function
+// of the bounce, AO and point-source stages applied to the triangle's unit normal with the third and fourth Philox words, not renormalised:
+// the direction density of a Lambertian surface, so the counts are FORM factors.  t_min = 0, t_max = inf.  The sampling is a template
+// parameter: the cosine path carries no f64 acos, the uniform path no disk mapping.
+template <bool COSINE>
+__device__ inline RcRay view_factor_sampled_ray(const RcPrim& tri, uint32_t src, uint32_t ray_idx, uint32_t k0, uint32_t k1) {
+    if (!COSINE) return view_factor_ray(tri, src, ray_idx, k0, k1);
+    float3_ p1 = mk3(tri.v[0], tri.v[1], tri.v[2]), p2 = mk3(tri.v[3], tri.v[4], tri.v[5]), p3 = mk3(tri.v[6], tri.v[7], tri.v[8]);
+    float3_ normal = normalize3(cross3(sub3(p2, p1), sub3(p3, p1)));
+    uint32_t rnd[4];
+    philox4x32_10(ray_idx, src, 0u, 0u, k0, k1, rnd);
+    float r1 = u32_to_unit(rnd[0]), r2 = u32_to_unit(rnd[1]), xi1 = u32_to_unit(rnd[2]), xi2 = u32_to_unit(rnd[3]);
+    float sqrt_r1 = __builtin_sqrtf(r1);
+    float wu = 1.0f - sqrt_r1, wv = sqrt_r1 * (1.0f - r2), ww = sqrt_r1 * r2;
+    float3_ pt = add3(add3(scale3(p1, wu), scale3(p2, wv)), scale3(p3, ww));
+    float3_ o = add3(pt, scale3(normal, 0.01f));
+    float3_ d = cosine_hemisphere_dir(normal, xi1, xi2);
+    return RcRay{o.x, o.y, o.z, 0.0f, d.x, d.y, d.z, INFINITY};
+}
+// The composed stage, the sibling of k_view_factor_rays: the rays [ray_begin, ray_begin + n_ray) of one source primitive.
+template <bool COSINE>
+__global__ void k_view_factor_sampled_rays(SceneView v, uint32_t k0, uint32_t k1, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_ray) out[i] = view_factor_sampled_ray<COSINE>(v.prims[src], src, ray_begin + i, k0, k1);
+}
+// Work item w -> flat source primitive src_begin + w / n_ray, ray ray_begin + w % n_ray: ViewFactorSource's split without the metadata order.
+template <bool COSINE>
+struct ViewFactorSampledSource {
+    const RcPrim* prims;
+    uint32_t k0, k1, src_begin, ray_begin, n_ray;
+    __device__ inline RcRay operator()(uint64_t w) const {
+        const uint32_t src = src_begin + (uint32_t)(w / n_ray), ray_idx = ray_begin + (uint32_t)(w % n_ray);
+        return view_factor_sampled_ray<COSINE>(prims[src], src, ray_idx, k0, k1);
+    }
+    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
+};
+// The counting rule, N = the flat primitive count, G = n_groups: a = the source's metadata, b = the hit's (hit_meta), ga = groups[a - 1],
+// gb = groups[b - 1], wa = weights ? weights[a - 1] : 1.  A source whose a is outside 1..N or whose ga >= G contributes nothing.  A miss:
+// escaped[ga] += wa, if escaped is given.  A hit with b in 1..N, b != a (the reference's hit_idx != tri_idx, src/kernels.jl:96) and gb < G:
+// matrix[ga * G + gb] += wa.  Any other hit adds nothing.  u64 adds modulo 2^64: exact in any order, so any partition of sources x rays
+// gives the same words.  groups and weights are read for metadata in 1..N only.
+// With a handful of groups every wave of the launch adds onto a few dozen words -- the case CopyHist exists for: when the launcher hands
+// out scratch (h.n8 != 0), a ray counts on index ga * G + gb, or G * G + ga for an escape, of its workgroup's private copy -- one wave_add
+// for both kinds, a finished ray is one or the other -- and k_hist_fold (FoldAddU64Groups) adds the copies into the caller's arrays.
+// Without scratch the same sums go straight onto `matrix` and `escaped`.  Indices stay below 2^32: G <= 65535, G * G + G <= 65535 * 65536.
+struct ViewFactorGroupsSink {
+    const RcInstRec* inst;
+    const RcPrim* prims;
+    uint32_t n_prims, src_begin, n_ray, n_groups;
+    const uint32_t* groups;
+    const uint32_t* weights;      // or nullptr: every source weighs 1
+    unsigned long long* matrix;   // h.n8 != 0: the launch's copy histogram (zeroed by the launcher); else the caller's G x G words
+    unsigned long long* escaped;  // h.n8 != 0: non-null when escapes are counted (into the copies); else the caller's G words or nullptr
+    CopyHist h;                   // of G * G (+ G) indices, or {0}: no copies
+    __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
+        const uint32_t a = prims[src_begin + (uint32_t)(w / n_ray)].meta;
+        bool counted = false, escape = false;
+        uint32_t j = 0, wa = 0;
+        if (a >= 1 && a <= n_prims) {
+            const uint32_t ga = groups[a - 1u];
+            if (ga < n_groups) {
+                if (hit) {
+                    const uint32_t b = hit_meta(inst, prims, instance, prim);
+                    if (b >= 1 && b <= n_prims && b != a) {
+                        const uint32_t gb = groups[b - 1u];
+                        if (gb < n_groups) { counted = true; j = ga * n_groups + gb; }
+                    }
+                } else if (escaped) { counted = true; escape = true; j = ga; }
+                if (counted) wa = weights ? weights[a - 1u] : 1u;
+            }
+        }
+        if (h.n8) {  // (uniform over the launch: every finishing lane reaches the same wave_add)
+            if (escape) j += n_groups * n_groups;
+            wave_add(matrix + h.base(h.copy()), counted ? h.slot(j) : 0u, wa, counted);
+        } else {
+            wave_add(matrix, j, wa, counted && !escape);
+            if (escaped) wave_add(escaped, j, wa, escape);
+        }
+    }
+};
+// The fold of the groups job's copies: index j < n_matrix = G * G is a matrix word, the G behind them are the escapes.
+struct FoldAddU64Groups : FoldOneRow {
+    unsigned long long* matrix;
+    unsigned long long* escaped;
+    uint32_t n_matrix;
+    __device__ inline void add(uint32_t, uint32_t j, unsigned long long sum) const { atomicAdd(j < n_matrix ? matrix + j : escaped + (j - n_matrix), sum); }
+};
+template <bool COSINE>
+struct ViewFactorGroupsJob {
+    uint32_t k0, k1, src_begin, ray_begin, n_ray, n_groups;
+    const uint32_t* groups;
+    const uint32_t* weights;
+    unsigned long long* matrix;
+    unsigned long long* escaped;
+    CopyHist h;
+    __device__ inline ViewFactorSampledSource<COSINE> source(const SceneView& v) const { return ViewFactorSampledSource<COSINE>{v.prims, k0, k1, src_begin, ray_begin, n_ray}; }
+    __device__ inline ViewFactorGroupsSink sink(const SceneView& v) const {
+        return ViewFactorGroupsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, n_groups, groups, weights, matrix, escaped, h};
+    }
+};
+
 // Diffuse bounce: output slot i continues the path of source slot s (s = i, or d_src[i] for i < count, or d_src[i % count] round robin
 // with k = i / count), from hit_point + normal * bias in a cosine-weighted direction about the geometric normal.  The uniforms are
 // Philox4x32-10(counter = (lo32 path, hi32 path, k, 0x424E0000 | bounce), key = seed): a path's bounce does not depend on compaction,
@@ -1449,6 +1553,38 @@ void rc_launch_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t see
                      [&] { if (d_mtx) rc_hist_fold(stream, scratch, h, np, FoldAddU64{{}, d_mtx}); });
 }
 
+// The G x G matrix of weighted counts between groups of primitives (rc_view_factor_groups_device): the shard of rc_launch_vf_totals with
+// ViewFactorGroupsJob, ACCUMULATED into d_matrix (G * G u64, row = source group) and d_escaped (G u64, may be nullptr).  The kernel counts
+// into kHistCopies private copies of the G * G (+ G) words when they fit kVfGroupsCopyBytes and k_hist_fold adds them; otherwise it adds
+// straight onto the caller's words.  The bound is 256 MiB (G <= 1447 with escapes): the copies cost about 0.45 ms per GiB to zero and fold,
+// and stop paying at about 32 MiB for a 5.5 M-ray job and at about 2 GiB for a 205 M-ray one (docs/EXPERIMENTS.md, "Form factors between
+// surface groups").  Both paths give the same words.  d_groups, d_weights and the scene are read when the kernel runs.  1 <= G <= 65535
+// (checked by the caller): wave_add indexes in 32 bits.
+constexpr unsigned long long kVfGroupsCopyBytes = 256ull << 20;
+template <bool COSINE>
+static void launch_vf_groups(rc_scene* s, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups,
+                             uint32_t n_groups, const uint32_t* d_weights, unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream) {
+    const uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
+    DriverLaunch launch(s, stream, total);
+    const uint32_t gg = n_groups * n_groups, n = gg + (d_escaped ? n_groups : 0u);
+    CopyHist h = CopyHist::of(n);
+    const bool copies = sizeof(unsigned long long) * h.words() <= kVfGroupsCopyBytes;
+    unsigned long long* scratch = copies ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
+    if (!copies) h = CopyHist{0u};
+    launch.go<false>(ViewFactorGroupsJob<COSINE>{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, n_groups, d_groups, d_weights,
+                                                 copies ? scratch : d_matrix, d_escaped, h},
+                     Nothing(), [&] { if (copies) rc_hist_fold(stream, scratch, h, n, FoldAddU64Groups{{}, d_matrix, d_escaped, gg}); });
+}
+void rc_launch_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t src_begin, uint32_t src_end,
+                         uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
+                         unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream) {
+    if (src_end > s->n_flat_prims) src_end = s->n_flat_prims;
+    if (ray_end > rays_per_triangle) ray_end = rays_per_triangle;
+    if (src_begin >= src_end || ray_begin >= ray_end) return;
+    if (sampling) launch_vf_groups<true>(s, seed, src_begin, src_end, ray_begin, ray_end, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream);
+    else launch_vf_groups<false>(s, seed, src_begin, src_end, ray_begin, ray_end, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream);
+}
+
 // Rows [row_begin, row_end) of the view-factor matrix in canonical CSR (rc_view_factors_sparse_device), all on `stream`, no host wait.
 // The sources are addressed in metadata order (the caller has called rc_ensure_vf_order): a range of rows is a contiguous range of source
 // positions, and metadata 0 or above N lie outside every range.  The job is cut HERE, on the host, into chunks of WHOLE rows whose rays x 8
@@ -1591,6 +1727,17 @@ void rc_launch_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t src, uint32
     if (n_ray == 0) return;
     SceneView v = rc_scene_view_static(s);
     hipLaunchKernelGGL(k_view_factor_rays, dim3((n_ray + 255) / 256), dim3(256), 0, stream, v, (uint32_t)seed, (uint32_t)(seed >> 32), src, ray_begin, n_ray, d_out);
+    RC_HIP(hipGetLastError());
+    rc_note_stage_launch(s, stream);
+}
+
+void rc_launch_view_factor_sampled_rays(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out,
+                                        hipStream_t stream) {
+    if (n_ray == 0) return;
+    SceneView v = rc_scene_view_static(s);
+    const dim3 grid((n_ray + 255) / 256);
+    if (sampling) hipLaunchKernelGGL(k_view_factor_sampled_rays<true>, grid, dim3(256), 0, stream, v, (uint32_t)seed, (uint32_t)(seed >> 32), src, ray_begin, n_ray, d_out);
+    else hipLaunchKernelGGL(k_view_factor_sampled_rays<false>, grid, dim3(256), 0, stream, v, (uint32_t)seed, (uint32_t)(seed >> 32), src, ray_begin, n_ray, d_out);
     RC_HIP(hipGetLastError());
     rc_note_stage_launch(s, stream);
 }

@@ -518,6 +518,13 @@ void rc_launch_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
                          uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, unsigned long long* d_nnz, hipStream_t stream);
 void rc_launch_vf_sparse_products(rc_scene* s, uint32_t n_rows, uint32_t row_offset, const unsigned long long* d_row_ptr, const uint32_t* d_cols,
                                   const uint32_t* d_vals, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx, hipStream_t stream);
+// Form factors between surface groups (rc_drivers.hip): the sampled view-factor rays (sampling 0 = the reference's uniform hemisphere, 1 = cosine)
+// of one source primitive, and the G x G matrix of weighted counts between groups of primitives, ACCUMULATED in u64.
+void rc_launch_view_factor_sampled_rays(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out,
+                                        hipStream_t stream);
+void rc_launch_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t src_begin, uint32_t src_end,
+                         uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
+                         unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream);
 void rc_multi_prepare_impl(rc_scene* const* scenes, int n_scenes, float out_ms[4]);
 int rc_multi_ranks_impl(rc_scene* const* scenes, int n_scenes);
 void rc_view_factor_totals_multi_impl(rc_scene* const* scenes, int n_scenes, uint32_t rays_per_triangle, uint64_t seed, uint64_t* out_received, uint64_t* out_emitted);

@@ -328,6 +328,23 @@ view_factor_products_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, se
                              ray_end::Integer, d_x::Ptr{UInt32}, d_mx::Ptr{UInt64}, d_mtx::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_view_factor_products_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
                 a.owner.ptr, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, d_x, d_mx, d_mtx, stream))
+const VF_SAMPLING_UNIFORM = UInt32(0)  # the reference's rays (src/kernels.jl:92)
+const VF_SAMPLING_COSINE = UInt32(1)   # Lambertian: form factors
+"The sampled view-factor rays of one source primitive: `sampling = VF_SAMPLING_UNIFORM` gives `view_factor_rays_device!`'s rays bit for bit,
+`VF_SAMPLING_COSINE` the same origins with cosine-weighted directions about the triangle's normal."
+view_factor_sampled_rays_device!(a::MI355XStaticTLAS, seed::UInt64, sampling::Integer, src_prim::Integer, ray_begin::Integer, n_rays::Integer,
+                                 d_rays::Ptr{RTRay}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_view_factor_sampled_rays_device, LIB), Cint, (Ptr{Cvoid}, UInt64, UInt32, UInt32, UInt32, UInt32, Ptr{RTRay}, Ptr{Cvoid}),
+                a.owner.ptr, seed, sampling, src_prim, ray_begin, n_rays, d_rays, stream))
+"One shard (sources [src_begin, src_end) x rays [ray_begin, ray_end)) of the weighted counts between GROUPS of primitives, ACCUMULATED into
+`d_matrix` (G x G UInt64, row = source group, row-major) and `d_escaped` (G UInt64, may be C_NULL).  `d_groups` / `d_weights` (may be C_NULL):
+N UInt32 each, indexed by metadata - 1, 0-based group numbers; a group >= G excludes the primitive.  With `VF_SAMPLING_COSINE` and weights
+proportional to the areas, `matrix[A, B] / (R * sum of A's weights)` estimates the form factor from group A to group B."
+view_factor_groups_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, seed::UInt64, sampling::Integer, src_begin::Integer, src_end::Integer,
+                           ray_begin::Integer, ray_end::Integer, d_groups::Ptr{UInt32}, n_groups::Integer, d_weights::Ptr{UInt32},
+                           d_matrix::Ptr{UInt64}, d_escaped::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_view_factor_groups_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, UInt32, Ptr{UInt32}, UInt32, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
+                a.owner.ptr, rays_per_triangle, seed, sampling, src_begin, src_end, ray_begin, ray_end, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream))
 """
     view_factors_sparse(accel; rays_per_triangle, seed) -> (row_ptr::Vector{UInt64}, cols::Vector{UInt32}, vals::Vector{UInt32})
 
