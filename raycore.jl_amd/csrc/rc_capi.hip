@@ -1716,7 +1716,7 @@ int rc_view_factor_rays_device(rc_scene* s, uint64_t seed, uint32_t src_prim, ui
         use_device(s);
         require_synced(s);
         if (src_prim >= s->n_flat_prims) throw RcError(RC_ERR_INVALID_ARGUMENT, "src_prim out of range");
-        rc_launch_view_factor_rays(s, seed, src_prim, ray_begin, n_rays, reinterpret_cast<RcRay*>(d_rays), (hipStream_t)stream);
+        rc_launch_view_factor_rays(s, seed, RC_VF_SAMPLING_UNIFORM, src_prim, ray_begin, n_rays, reinterpret_cast<RcRay*>(d_rays), (hipStream_t)stream);
     });
 }
 
@@ -1728,7 +1728,7 @@ int rc_view_factor_sampled_rays_device(rc_scene* s, uint64_t seed, uint32_t samp
         use_device(s);
         require_synced(s);
         if (src_prim >= s->n_flat_prims) throw RcError(RC_ERR_INVALID_ARGUMENT, "src_prim out of range");
-        rc_launch_view_factor_sampled_rays(s, seed, sampling, src_prim, ray_begin, n_rays, reinterpret_cast<RcRay*>(d_rays), (hipStream_t)stream);
+        rc_launch_view_factor_rays(s, seed, sampling, src_prim, ray_begin, n_rays, reinterpret_cast<RcRay*>(d_rays), (hipStream_t)stream);
     });
 }
 
@@ -1743,10 +1743,11 @@ int rc_hit_points_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits
 
 int rc_shadow_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float light[3], float bias, rc_ray* d_shadow_rays, void* stream) {
     if (!s || !d_rays || !d_hits || !light || !d_shadow_rays) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    const ShadowParams q{reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), nullptr, 1u, bias};
     return guarded([&] {
         use_device(s);
         require_synced(s);
-        rc_launch_shadow_rays(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, light, bias, reinterpret_cast<RcRay*>(d_shadow_rays), (hipStream_t)stream);
+        rc_launch_shadow_rays(s, q, light, n, reinterpret_cast<RcRay*>(d_shadow_rays), (hipStream_t)stream);
     });
 }
 
@@ -1755,10 +1756,11 @@ int rc_shadow_visibility_device(rc_scene* s, const rc_ray* d_rays, const rc_hit*
     if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
     if (n && n_lights && (!d_rays || !d_hits || !d_lights || !d_visible)) return fail(RC_ERR_INVALID_ARGUMENT, "rc_shadow_visibility_device: NULL argument");
     if (n_lights && n >= ((1ull << 32) + n_lights - 1) / n_lights) return fail(RC_ERR_INVALID_ARGUMENT, "rc_shadow_visibility_device: n * n_lights must be below 2^32");
+    const ShadowParams q{reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), d_lights, n_lights, bias};
     return guarded([&] {
         use_device(s);
         require_synced(s);
-        rc_launch_shadow_visibility(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, d_lights, n_lights, bias, d_visible, (hipStream_t)stream);
+        rc_launch_shadow_visibility(s, q, n, d_visible, (hipStream_t)stream);
     });
 }
 
@@ -1777,22 +1779,22 @@ int rc_soft_shadow_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* 
                                uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
                                float bias, rc_ray* d_shadow_rays, void* stream) {
     if (int e = soft_shadow_args("rc_soft_shadow_rays_device", s, d_rays, d_hits, n, d_lights, d_radii, n_lights, samples, depth, d_shadow_rays)) return e;
+    const SoftShadowParams q{reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), d_lights, d_radii, d_path_in, path_base, n_lights, samples, rc_philox_key(seed), depth, bias};
     return guarded([&] {
         use_device(s);
         require_synced(s);
-        rc_launch_soft_shadow_rays(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, d_lights, d_radii, n_lights, samples,
-                                   seed, depth, d_path_in, path_base, bias, reinterpret_cast<RcRay*>(d_shadow_rays), (hipStream_t)stream);
+        rc_launch_soft_shadow_rays(s, q, n, reinterpret_cast<RcRay*>(d_shadow_rays), (hipStream_t)stream);
     });
 }
 int rc_soft_shadow_visibility_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
                                      uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
                                      float bias, uint32_t* d_count, void* stream) {
     if (int e = soft_shadow_args("rc_soft_shadow_visibility_device", s, d_rays, d_hits, n, d_lights, d_radii, n_lights, samples, depth, d_count)) return e;
+    const SoftShadowParams q{reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), d_lights, d_radii, d_path_in, path_base, n_lights, samples, rc_philox_key(seed), depth, bias};
     return guarded([&] {
         use_device(s);
         require_synced(s);
-        rc_launch_soft_shadow_visibility(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, d_lights, d_radii, n_lights,
-                                         samples, seed, depth, d_path_in, path_base, bias, d_count, (hipStream_t)stream);
+        rc_launch_soft_shadow_visibility(s, q, n, d_count, (hipStream_t)stream);
     });
 }
 
@@ -1809,21 +1811,21 @@ static int ambient_occlusion_args(const char* name, rc_scene* s, const void* d_r
 int rc_ambient_occlusion_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
                                      uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, rc_ray* d_ao_rays, void* stream) {
     if (int e = ambient_occlusion_args("rc_ambient_occlusion_rays_device", s, d_rays, d_hits, n, samples, max_dist, depth, d_ao_rays)) return e;
+    const AoParams q{reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), d_path_in, path_base, samples, rc_philox_key(seed), depth, bias, max_dist};
     return guarded([&] {
         use_device(s);
         require_synced(s);
-        rc_launch_ao_rays(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, samples, max_dist, seed, depth, d_path_in,
-                          path_base, bias, reinterpret_cast<RcRay*>(d_ao_rays), (hipStream_t)stream);
+        rc_launch_ao_rays(s, q, n, reinterpret_cast<RcRay*>(d_ao_rays), (hipStream_t)stream);
     });
 }
 int rc_ambient_occlusion_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
                                 uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, uint32_t* d_count, void* stream) {
     if (int e = ambient_occlusion_args("rc_ambient_occlusion_device", s, d_rays, d_hits, n, samples, max_dist, depth, d_count)) return e;
+    const AoParams q{reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), d_path_in, path_base, samples, rc_philox_key(seed), depth, bias, max_dist};
     return guarded([&] {
         use_device(s);
         require_synced(s);
-        rc_launch_ambient_occlusion(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, samples, max_dist, seed, depth,
-                                    d_path_in, path_base, bias, d_count, (hipStream_t)stream);
+        rc_launch_ambient_occlusion(s, q, n, d_count, (hipStream_t)stream);
     });
 }
 int rc_final_gather_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
@@ -1832,11 +1834,11 @@ int rc_final_gather_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hi
     // (d_sum takes the place of the ambient-occlusion output in the shared checks; d_open may be NULL)
     if (int e = ambient_occlusion_args("rc_final_gather_device", s, d_rays, d_hits, n, samples, max_dist, depth, d_sum)) return e;
     if (n && samples && !d_x) return fail(RC_ERR_INVALID_ARGUMENT, "rc_final_gather_device: NULL argument");
+    const AoParams q{reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), d_path_in, path_base, samples, rc_philox_key(seed), depth, bias, max_dist};
     return guarded([&] {
         use_device(s);
         require_synced(s);
-        rc_launch_final_gather(s, reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), n, samples, max_dist, seed, depth, d_path_in,
-                               path_base, bias, d_x, miss_value, d_sum, d_open, (hipStream_t)stream);
+        rc_launch_final_gather(s, q, n, d_x, miss_value, d_sum, d_open, (hipStream_t)stream);
     });
 }
 

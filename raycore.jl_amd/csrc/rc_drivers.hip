@@ -390,54 +390,84 @@ __device__ inline void orthogonal_basis(const float3_ normal, float3_& bu, float
     bu = normalize3(cross3(bv, n));
 }
 
-// The ray view_factors! shoots for (source primitive, ray index) (:83-92 + src/math.jl:125-174)
-__device__ inline RcRay view_factor_ray(const RcPrim& tri, uint32_t src, uint32_t ray_idx, uint32_t k0, uint32_t k1) {
+__device__ inline float3_ cosine_hemisphere_dir(const float3_ n, float u1, float u2);  // (below, with the stages that shoot cosine-weighted rays)
+// The ray of (source primitive, ray index) in the view-factor family (:83-92 + src/math.jl:125-174): the Philox draw -- counter (ray_idx, src,
+// 0, 0), key = seed -> r1, r2, xi1, xi2 --, the point on the triangle and the origin pt + normal * 0.01f are the same in both samplings.
+// COSINE = false: view_factors!'s own ray, the reference's uniform hemisphere (src/kernels.jl:92).  COSINE = true: d =
+// cosine_hemisphere_dir(normal, xi1, xi2), the function of the bounce, AO and point-source stages applied to the triangle's unit normal
+// with the third and fourth Philox words, not renormalised: the direction density of a Lambertian surface, so the counts are FORM
+// factors.  t_min = 0, t_max = inf.  The sampling is a template parameter: the cosine path carries no f64 acos, the uniform path no disk mapping.
+template <bool COSINE>
+__device__ inline RcRay view_factor_ray(const RcPrim& tri, uint32_t src, uint32_t ray_idx, RcPhiloxKey key) {
     float3_ p1 = mk3(tri.v[0], tri.v[1], tri.v[2]), p2 = mk3(tri.v[3], tri.v[4], tri.v[5]), p3 = mk3(tri.v[6], tri.v[7], tri.v[8]);
     float3_ normal = normalize3(cross3(sub3(p2, p1), sub3(p3, p1)));  // GB.orthogonal_vector + normalize (:86-87)
-    float3_ bu, bv;
-    orthogonal_basis(normal, bu, bv);
     uint32_t rnd[4];
-    philox4x32_10(ray_idx, src, 0u, 0u, k0, k1, rnd);
+    philox4x32_10(ray_idx, src, 0u, 0u, key.k0, key.k1, rnd);
     float r1 = u32_to_unit(rnd[0]), r2 = u32_to_unit(rnd[1]), xi1 = u32_to_unit(rnd[2]), xi2 = u32_to_unit(rnd[3]);
     // random_triangle_point (src/math.jl:158-174)
     float sqrt_r1 = __builtin_sqrtf(r1);
     float wu = 1.0f - sqrt_r1, wv = sqrt_r1 * (1.0f - r2), ww = sqrt_r1 * r2;
     float3_ pt = add3(add3(scale3(p1, wu), scale3(p2, wv)), scale3(p3, ww));
     float3_ o = add3(pt, scale3(normal, 0.01f));  // :91
-    // random_hemisphere_uniform (src/math.jl:125-141)
-    float theta = (float)acos_f64((double)xi1);
-    float phi = (2.0f * 3.1415927f) * xi2;
-    double st, ct, sp, cp;
-    sincos_f64((double)theta, st, ct);
-    sincos_f64((double)phi, sp, cp);
-    float sin_t = (float)st, cos_t = (float)ct, sin_p = (float)sp, cos_p = (float)cp;
-    float xl = sin_t * cos_p, yl = sin_t * sin_p, zl = cos_t;
-    float3_ d = add3(add3(scale3(bu, xl), scale3(bv, yl)), scale3(normal, zl));
+    float3_ d;
+    if (COSINE)
+        d = cosine_hemisphere_dir(normal, xi1, xi2);
+    else {  // random_hemisphere_uniform (src/math.jl:125-141)
+        float3_ bu, bv;
+        orthogonal_basis(normal, bu, bv);
+        float theta = (float)acos_f64((double)xi1);
+        float phi = (2.0f * 3.1415927f) * xi2;
+        double st, ct, sp, cp;
+        sincos_f64((double)theta, st, ct);
+        sincos_f64((double)phi, sp, cp);
+        float sin_t = (float)st, cos_t = (float)ct, sin_p = (float)sp, cos_p = (float)cp;
+        float xl = sin_t * cos_p, yl = sin_t * sin_p, zl = cos_t;
+        d = add3(add3(scale3(bu, xl), scale3(bv, yl)), scale3(normal, zl));
+    }
     return RcRay{o.x, o.y, o.z, 0.0f, d.x, d.y, d.z, INFINITY};
 }
 
+// A shard of the view-factor family's work: rays [ray_begin, ray_begin + n_ray) of the sources at positions src_begin.. (vf_shard() makes
+// it on the host).  Work item w is source position src_begin + w / n_ray, ray ray_begin + w % n_ray.
+struct VfShard {
+    RcPhiloxKey key;
+    uint32_t src_begin, ray_begin, n_ray;
+};
 // view_factors! (:80-104): work item = (source primitive, ray); result[src_meta, hit_meta] += 1 when the hit
 // primitive's metadata differs.  One u32 atomic per counted ray.  Runs on the persistent phased traversal core.
+template <bool COSINE>
 struct ViewFactorSource {
     const RcPrim* prims;
     const uint32_t* order;  // RC_VF_SOURCES_BY_METADATA: source position -> flat primitive index, else nullptr (position = index)
-    uint32_t k0, k1, src_begin, ray_begin, n_ray;
+    VfShard sh;
     __device__ inline RcRay operator()(uint64_t w) const {
-        const uint32_t pos = src_begin + (uint32_t)(w / n_ray), ray_idx = ray_begin + (uint32_t)(w % n_ray);
+        const uint32_t pos = sh.src_begin + (uint32_t)(w / sh.n_ray), ray_idx = sh.ray_begin + (uint32_t)(w % sh.n_ray);
         const uint32_t src = order ? order[pos] : pos;
-        return view_factor_ray(prims[src], src, ray_idx, k0, k1);  // Philox is keyed by the PRIMITIVE index: the rays do not depend on the addressing
+        return view_factor_ray<COSINE>(prims[src], src, ray_idx, sh.key);  // Philox is keyed by the PRIMITIVE index: the rays do not depend on the addressing
     }
     static constexpr bool kPrefetch = false;
 };
-// The counting rule of view_factors! (:93-97): the hit primitive's metadata differs from the source's, and both are in 1..N.
-__device__ __forceinline__ bool vf_counted(uint32_t hit_meta, uint32_t src_meta, uint32_t n_prims) {
-    return hit_meta != src_meta && src_meta >= 1 && src_meta <= n_prims && hit_meta >= 1 && hit_meta <= n_prims;
+// The (source, hit) pair of a finished item and the counting rule of view_factors! (:93-97): the hit primitive's metadata differs from the
+// source's, and both are in 1..N.  The source is decoded for every item (the groups job counts a miss on its source's group), the hit
+// (hit_meta) for a hit only.  `v` is the kernel's own by-value SceneView parameter: the sinks that call this keep a REFERENCE to it
+// (Job::sink(v) in k_driver*), which lives as long as the kernel runs -- a sink made anywhere else must be given a view that outlives it.
+struct VfPair {
+    uint32_t pos, src, src_meta, to_meta;
+    bool counted;
+};
+__device__ __forceinline__ VfPair vf_pair(const SceneView& v, const uint32_t* order, const VfShard& sh, uint64_t w, bool hit, uint32_t prim, int instance) {
+    VfPair p;
+    p.pos = sh.src_begin + (uint32_t)(w / sh.n_ray);
+    p.src = order ? order[p.pos] : p.pos;
+    p.to_meta = hit ? hit_meta(v.inst, v.prims, instance, prim) : 0u;  // (the hit's load first: in the other order the matrix job's shells change)
+    p.src_meta = v.prims[p.src].meta;
+    p.counted = hit && p.to_meta != p.src_meta && p.src_meta >= 1 && p.src_meta <= v.n_prims && p.to_meta >= 1 && p.to_meta <= v.n_prims;
+    return p;
 }
 struct ViewFactorSink {
-    const RcInstRec* inst;
-    const RcPrim* prims;
+    const SceneView& v;
     const uint32_t* order;
-    uint32_t n_prims, src_begin, n_ray;
+    VfShard sh;
     uint32_t* matrix;
     uint64_t row_stride, col_stride;
     uint32_t row_offset, flags;
@@ -445,12 +475,10 @@ struct ViewFactorSink {
         bool counted = false;
         unsigned long long index = 0;
         if (hit) {
-            const uint32_t pos = src_begin + (uint32_t)(w / n_ray);
-            const uint32_t src = order ? order[pos] : pos;
-            const uint32_t to_meta = hit_meta(inst, prims, instance, prim), src_meta = prims[src].meta;
-            counted = vf_counted(to_meta, src_meta, n_prims);
-            const uint32_t row = (flags & 4u) ? src_meta - 1 : ((flags & 2u) ? pos : ((flags & 1u) ? src : src_meta - 1));
-            if (counted) index = (uint64_t)(row - row_offset) * row_stride + (uint64_t)(to_meta - 1) * col_stride;
+            const VfPair p = vf_pair(v, order, sh, w, true, prim, instance);
+            counted = p.counted;
+            const uint32_t row = (flags & 4u) ? p.src_meta - 1 : ((flags & 2u) ? p.pos : ((flags & 1u) ? p.src : p.src_meta - 1));
+            if (counted) index = (uint64_t)(row - row_offset) * row_stride + (uint64_t)(p.to_meta - 1) * col_stride;
         }
         wave_count(matrix, index, counted);
     }
@@ -462,32 +490,25 @@ struct ViewFactorSink {
 // `received` is the hot vector -- most rays of a closed scene end on a few large triangles --, so the kernel counts it into a copy histogram
 // of u64 words (CopyHist), and k_hist_fold adds the copies into the caller's vector afterwards.
 struct ViewFactorTotalsSink {
-    const RcInstRec* inst;
-    const RcPrim* prims;
-    uint32_t n_prims, src_begin, n_ray;
+    const SceneView& v;
+    VfShard sh;
     unsigned long long* received;  // one histogram of scratch counters (zeroed by the launcher), or nullptr
     CopyHist h;
     unsigned long long* emitted;   // [n_prims] or nullptr: per source, nearly wave-uniform -- one atomic per group (wave_count)
     __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
-        bool counted = false;
-        uint32_t to_meta = 1, src_meta = 1;
-        if (hit) {  // hit_meta() and vf_counted(), written out: through either helper the three shells of this job come out differently
-            const uint32_t src = src_begin + (uint32_t)(w / n_ray);
-            const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
-            to_meta = prims[m3.y + prim - 1u].meta; src_meta = prims[src].meta;
-            counted = to_meta != src_meta && src_meta >= 1 && src_meta <= n_prims && to_meta >= 1 && to_meta <= n_prims;
-        }
-        if (received) wave_count(received + h.base(h.copy()), (unsigned long long)h.slot(to_meta - 1u), counted);
-        if (emitted) wave_count(emitted, (unsigned long long)(src_meta - 1u), counted);
+        VfPair p{0u, 0u, 1u, 1u, false};
+        if (hit) p = vf_pair(v, nullptr, sh, w, true, prim, instance);
+        if (received) wave_count(received + h.base(h.copy()), (unsigned long long)h.slot(p.to_meta - 1u), p.counted);
+        if (emitted) wave_count(emitted, (unsigned long long)(p.src_meta - 1u), p.counted);
     }
 };
 struct ViewFactorTotalsJob {
-    uint32_t k0, k1, src_begin, ray_begin, n_ray;
+    VfShard sh;
     unsigned long long* received;
     CopyHist h;
     unsigned long long* emitted;
-    __device__ inline ViewFactorSource source(const SceneView& v) const { return ViewFactorSource{v.prims, nullptr, k0, k1, src_begin, ray_begin, n_ray}; }
-    __device__ inline ViewFactorTotalsSink sink(const SceneView& v) const { return ViewFactorTotalsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, received, h, emitted}; }
+    __device__ inline ViewFactorSource<false> source(const SceneView& v) const { return ViewFactorSource<false>{v.prims, nullptr, sh}; }
+    __device__ inline ViewFactorTotalsSink sink(const SceneView& v) const { return ViewFactorTotalsSink{v, sh, received, h, emitted}; }
 };
 // Keeps the pointer form of the interior loop's stack position in the plain shell: 79 VGPRs, 36 bytes of private segment with the integer form.
 template <>
@@ -534,6 +555,9 @@ struct ViewFactorProductsSink {
     __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
         bool counted = false;
         uint32_t to_meta = 1, src_meta = 1;
+        // vf_pair(), written out on fields of the sink's own: through the helper (and a SceneView reference) the three shells of this job change,
+        // and the default shell then timed 0.048 ms slower on the reduced C5 where the parent's own runs spread 0.041 (docs/EXPERIMENTS.md,
+        // "Drivers: the view-factor, hit-sample and row-group jobs written once", and profiles/drivers_write_once_ab.txt).  This form compiles to the code it had before.
         if (hit) {
             const uint32_t src = src_begin + (uint32_t)(w / n_ray);
             const uint4 m3 = *(reinterpret_cast<const uint4*>(inst + instance) + 3);
@@ -545,24 +569,22 @@ struct ViewFactorProductsSink {
     }
 };
 struct ViewFactorProductsJob {
-    uint32_t k0, k1, src_begin, ray_begin, n_ray;
+    VfShard sh;
     const uint32_t* x;
     unsigned long long* mtx;
     CopyHist h;
     unsigned long long* mx;
-    __device__ inline ViewFactorSource source(const SceneView& v) const { return ViewFactorSource{v.prims, nullptr, k0, k1, src_begin, ray_begin, n_ray}; }
-    __device__ inline ViewFactorProductsSink sink(const SceneView& v) const { return ViewFactorProductsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, x, mtx, h, mx}; }
+    __device__ inline ViewFactorSource<false> source(const SceneView& v) const { return ViewFactorSource<false>{v.prims, nullptr, sh}; }
+    __device__ inline ViewFactorProductsSink sink(const SceneView& v) const { return ViewFactorProductsSink{v.inst, v.prims, v.n_prims, sh.src_begin, sh.n_ray, x, mtx, h, mx}; }
 };
 struct ViewFactorJob {
-    uint32_t k0, k1, src_begin, ray_begin, n_ray;
+    VfShard sh;
     uint32_t* matrix;
     uint64_t row_stride, col_stride;
     uint32_t row_offset, flags;
     const uint32_t* order;
-    __device__ inline ViewFactorSource source(const SceneView& v) const { return ViewFactorSource{v.prims, order, k0, k1, src_begin, ray_begin, n_ray}; }
-    __device__ inline ViewFactorSink sink(const SceneView& v) const {
-        return ViewFactorSink{v.inst, v.prims, order, v.n_prims, src_begin, n_ray, matrix, row_stride, col_stride, row_offset, flags};
-    }
+    __device__ inline ViewFactorSource<false> source(const SceneView& v) const { return ViewFactorSource<false>{v.prims, order, sh}; }
+    __device__ inline ViewFactorSink sink(const SceneView& v) const { return ViewFactorSink{v, order, sh, matrix, row_stride, col_stride, row_offset, flags}; }
 };
 
 // The sparse view-factor matrix (rc_view_factors_sparse*): the same job once more, but the matrix itself is kept, as CSR.  A chunk of whole
@@ -571,31 +593,29 @@ struct ViewFactorJob {
 // One plain store per finished ray at an index below the launch's item count, no atomics: the keys are sorted and run-length encoded
 // afterwards (rc_launch_vf_sparse), so the arrays do not depend on which wave traced what.
 struct ViewFactorPairsSink {
-    const RcInstRec* inst;
-    const RcPrim* prims;
+    const SceneView& v;
     const uint32_t* order;
-    uint32_t n_prims, src_begin, n_ray, row0, col_bits;
+    VfShard sh;
+    uint32_t row0, col_bits;
     unsigned long long sentinel;
     unsigned long long* pairs;
     __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
         unsigned long long key = sentinel;
         if (hit) {
-            const uint32_t src = order[src_begin + (uint32_t)(w / n_ray)];
-            const uint32_t to_meta = hit_meta(inst, prims, instance, prim), src_meta = prims[src].meta;
-            if (vf_counted(to_meta, src_meta, n_prims)) key = ((unsigned long long)(src_meta - 1u - row0) << col_bits) | (to_meta - 1u);
+            const VfPair p = vf_pair(v, order, sh, w, true, prim, instance);
+            if (p.counted) key = ((unsigned long long)(p.src_meta - 1u - row0) << col_bits) | (p.to_meta - 1u);
         }
         pairs[w] = key;
     }
 };
 struct ViewFactorPairsJob {
-    uint32_t k0, k1, src_begin, n_ray, row0, col_bits;
+    VfShard sh;  // (whole rows: ray_begin = 0)
+    uint32_t row0, col_bits;
     unsigned long long sentinel;
     unsigned long long* pairs;
     const uint32_t* order;
-    __device__ inline ViewFactorSource source(const SceneView& v) const { return ViewFactorSource{v.prims, order, k0, k1, src_begin, 0u, n_ray}; }
-    __device__ inline ViewFactorPairsSink sink(const SceneView& v) const {
-        return ViewFactorPairsSink{v.inst, v.prims, order, v.n_prims, src_begin, n_ray, row0, col_bits, sentinel, pairs};
-    }
+    __device__ inline ViewFactorSource<false> source(const SceneView& v) const { return ViewFactorSource<false>{v.prims, order, sh}; }
+    __device__ inline ViewFactorPairsSink sink(const SceneView& v) const { return ViewFactorPairsSink{v, order, sh, row0, col_bits, sentinel, pairs}; }
 };
 // Appends one chunk's compressed keys to the CSR arrays.  unique / lengths / n_runs: the run-length encoding of the chunk's SORTED keys, on
 // the device; the sentinel's run, if there is one, is the last and is dropped.  Entry i goes to position *nnz_in + i of cols / vals unless
@@ -665,9 +685,11 @@ __global__ void k_meta_keys(const RcPrim* prims, uint32_t n, uint32_t* keys, uin
     if (i < n) { keys[i] = prims[i].meta; vals[i] = i; }
 }
 
-__global__ void k_view_factor_rays(SceneView v, uint32_t k0, uint32_t k1, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* out) {
+// The composed stage: the rays [ray_begin, ray_begin + n_ray) of one source primitive.
+template <bool COSINE>
+__global__ void k_view_factor_rays(SceneView v, RcPhiloxKey key, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* out) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_ray) out[i] = view_factor_ray(v.prims[src], src, ray_begin + i, k0, k1);
+    if (i < n_ray) out[i] = view_factor_ray<COSINE>(v.prims[src], src, ray_begin + i, key);
 }
 
 // ---- wavefront stages adjacent to the trace (docs/src/wavefront-renderer.jl:296-333) ---------
@@ -710,37 +732,62 @@ __device__ inline RcRay shadow_ray(const SceneView& v, const RcRay& r, const RcH
     hit_frame(v, r, h, p, nn);
     return shadow_ray_from(p, nn, light, bias);
 }
-__global__ void k_shadow_rays(SceneView v, const RcRay* rays, const RcHit* hits, uint64_t n, float lx, float ly, float lz, float bias, RcRay* out) {
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        RcRay s = RC_DUMMY_RAY;
-        const RcHit h = hits[i];
-        if (h.hit) s = shadow_ray(v, rays[i], h, mk3(lx, ly, lz), bias);
-        store_ray(out, i, s);
+
+// ---- the hit-sample family: work items are (hit slot, sub-item), the ray of an item is made from the slot's primary ray and hit ----------
+// An item description (ShadowItems, SoftShadowItems, AoItems) holds the family's parameters `q` and gives slot(j), the hit slot of item j;
+// ray(v, j, i, r, h), the ray of item j of slot i whose primary ray r hit (h); and kGate, whether an item whose ray has a t_max that is
+// not > 0 is dead.  One description serves the composed stage and the fused driver's source, so the two agree bit for bit.
+// The composed stage: slot j of the output belongs to item j; an item whose primary ray missed gets the reference's dummy ray.  The output
+// feeds rc_trace_any_device unchanged (which applies the t_max gate to the stored ray itself).  total < 2^32.
+template <class Items>
+__global__ void k_hit_item_rays(SceneView v, Items it, uint64_t total, RcRay* out) {
+    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t i = it.slot((uint32_t)j);
+        RcRay r = RC_DUMMY_RAY;
+        const RcHit h = it.q.hits[i];
+        if (h.hit) r = it.ray(v, (uint32_t)j, i, it.q.rays[i], h);
+        store_ray(out, j, r);
     }
+}
+// The fused driver's source: the ray is made when a lane is refilled and never stored, so only the kernel can apply the gate of
+// test_shadow_rays! (:353-358), `ray.t_max > 0 ? !any_hit(...) : false`: an item whose primary ray missed, or (kGate) whose ray has a t_max
+// that is not > 0 (0: the light sits on the shadow origin; NaN: a NaN t or normal out of a singular instance), gets the dead ray.
+template <class Items>
+struct HitItemSource {
+    const SceneView& v;
+    Items it;
+    __device__ inline RcRay operator()(uint64_t j) const {
+        const uint32_t i = it.slot((uint32_t)j);
+        const RcHit h = it.q.hits[i];
+        if (!h.hit) return RC_DEAD_RAY;
+        const RcRay r = it.ray(v, (uint32_t)j, i, load_ray(it.q.rays, i), h);
+        return (!Items::kGate || r.tmax > 0.0f) ? r : RC_DEAD_RAY;
+    }
+    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
+};
+
+// The Philox draw of a path-keyed sample: path = path_base + (path_in ? path_in[i] : i) fills the first two counter words, the caller's
+// c2 and c3 the others.  Returns the path.
+__device__ inline uint64_t path_philox(uint64_t path_base, const uint32_t* path_in, uint32_t i, uint32_t c2, uint32_t c3, RcPhiloxKey key, uint32_t rnd[4]) {
+    const uint64_t path = path_base + (path_in ? (uint64_t)path_in[i] : (uint64_t)i);
+    philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), c2, c3, key.k0, key.k1, rnd);
+    return path;
 }
 
 // generate_shadow_rays! + test_shadow_rays! for all hits x all lights (:279-362) fused on the persistent phased traversal core: work item
 // j = i * n_lights + l is hit i seen from light l (the reference's slot (idx-1)*NLights + light_idx), so neighbouring lanes share a hit's
-// records.  The shadow ray is made when a lane is refilled and never stored; a finished any_hit writes the one byte the shading reads.
-// test_shadow_rays! (:353-358) is `ray.t_max > 0 ? !any_hit(...) : false`: an item whose primary ray missed, or whose shadow ray has a t_max
-// that is not > 0 (0: the light sits on the shadow origin; NaN: a NaN t or normal out of a singular instance), gets the dead ray and the
-// byte 0.  The ray is never stored, so only the kernel can apply that gate.
-struct ShadowSource {
-    const SceneView& v;
-    const RcRay* rays;
-    const RcHit* hits;
-    const float* lights;  // n_lights x 3, read here: a captured launch follows lights that move between replays
-    uint32_t n_lights;
-    float bias;
-    __device__ inline RcRay operator()(uint64_t j) const {
-        const uint32_t i = (uint32_t)j / n_lights, l = (uint32_t)j - i * n_lights;  // (n * n_lights < 2^32)
-        const RcHit h = hits[i];
-        if (!h.hit) return RC_DEAD_RAY;
-        const float* lp = lights + 3u * (size_t)l;
-        const RcRay s = shadow_ray(v, load_ray(rays, i), h, mk3(lp[0], lp[1], lp[2]), bias);
-        return s.tmax > 0.0f ? s : RC_DEAD_RAY;
+// records; a finished any_hit writes the one byte the shading reads, 0 for a dead item.  STAGE: generate_shadow_rays! for ONE point light
+// given by value (`light`; q.lights is null and q.n_lights 1), item j = slot j.
+template <bool STAGE>
+struct ShadowItems {
+    ShadowParams q;
+    float light[3];
+    static constexpr bool kGate = true;
+    __device__ inline uint32_t slot(uint32_t j) const { return STAGE ? j : j / q.n_lights; }  // (n * n_lights < 2^32)
+    __device__ inline RcRay ray(const SceneView& v, uint32_t j, uint32_t i, const RcRay& r, const RcHit& h) const {
+        const float* lp = STAGE ? light : q.lights + 3u * (size_t)(j - i * q.n_lights);  // q.lights is read here: a captured launch follows lights that move between replays
+        return shadow_ray(v, r, h, mk3(lp[0], lp[1], lp[2]), q.bias);
     }
-    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
 };
 struct VisibilitySink {
     uint8_t* visible;
@@ -750,15 +797,11 @@ struct VisibilitySink {
         visible[j] = (!hit && t > 0.0f) ? 1u : 0u;
     }
 };
-// The job's kernel argument (k_driver*): today's parameters in their order, and the Source / Sink they become next to the kernel's SceneView.
+// The job's kernel argument (k_driver*): its parameters, and the Source / Sink they become next to the kernel's SceneView.
 struct ShadowJob {
-    const RcRay* rays;
-    const RcHit* hits;
-    const float* lights;
-    uint32_t n_lights;
-    float bias;
+    ShadowParams q;
     uint8_t* visible;
-    __device__ inline ShadowSource source(const SceneView& v) const { return ShadowSource{v, rays, hits, lights, n_lights, bias}; }  // (v: the kernel's own by-value parameter)
+    __device__ inline HitItemSource<ShadowItems<false>> source(const SceneView& v) const { return {v, {q, {}}}; }  // (v: the kernel's own by-value parameter)
     __device__ inline VisibilitySink sink(const SceneView&) const { return VisibilitySink{visible}; }
 };
 
@@ -773,66 +816,33 @@ struct ShadowJob {
 // every expression left to right, no contraction.  The ray toward the target is shadow_ray_from()'s, the body of shadow_ray(): origin = the biased hit point, t_max = the
 // distance to the target (the wavefront renderer's convention, not the tutorial's t_max = Inf followed by hit_dist >= shadow_dist: a
 // first-found any_hit beyond the light would otherwise decide visibility).
-struct SoftShadowParams {
-    const RcRay* rays;
-    const RcHit* hits;
-    const float* lights;       // n_lights x 3, read when the kernel runs
-    const float* radii;        // n_lights, likewise
-    const uint32_t* path_in;   // path of slot i (nullptr: i), as in k_bounce_rays
-    uint64_t path_base;
-    uint32_t n_lights, samples, k0, k1, depth;
-    float bias;
-};
-// The shadow ray of sample s of light l seen from slot i, whose primary ray hit (h = hits[i]): shared by the stage kernel and the fused
-// driver's source, so the two agree bit for bit.
-__device__ inline RcRay soft_shadow_ray(const SceneView& v, const SoftShadowParams& q, uint32_t i, uint32_t l, uint32_t s, const RcRay& r, const RcHit& h) {
-    const float* lp = q.lights + 3u * (size_t)l;
-    const float3_ light = mk3(lp[0], lp[1], lp[2]);
-    float3_ target = light;
-    float3_ p, nn;
-    hit_frame(v, r, h, p, nn);  // once: the target's light_dir and the ray's origin come from the same frame
-    if (q.samples > 1u) {
-        const float3_ lv = sub3(light, p);
-        const float ld = __builtin_sqrtf(dot3(lv, lv));
-        const float3_ light_dir = mk3((lv.x / ld), (lv.y / ld), (lv.z / ld));
-        const uint64_t path = q.path_base + (q.path_in ? (uint64_t)q.path_in[i] : (uint64_t)i);
-        uint32_t rnd[4];
-        philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), s | (q.depth << 16), 0x53460000u | l, q.k0, q.k1, rnd);
-        const float radius = q.radii[l];
-        float3_ off = mk3((u32_to_unit(rnd[0]) * 2.0f - 1.0f) * radius, (u32_to_unit(rnd[1]) * 2.0f - 1.0f) * radius, (u32_to_unit(rnd[2]) * 2.0f - 1.0f) * radius);
-        off = sub3(off, scale3(light_dir, dot3(off, light_dir)));
-        target = add3(light, off);
-    }
-    return shadow_ray_from(p, nn, target, q.bias);
-}
-// The composed stage: n * n_lights * samples rays, slot (i * n_lights + l) * samples + s; a slot whose primary ray missed gets k_shadow_rays'
-// dummy ray.  The output feeds rc_trace_any_device unchanged.
-__global__ void k_soft_shadow_rays(SceneView v, SoftShadowParams q, uint64_t total, RcRay* out) {
-    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t il = (uint32_t)j / q.samples, s = (uint32_t)j - il * q.samples;  // (total < 2^32)
-        const uint32_t i = il / q.n_lights, l = il - i * q.n_lights;
-        RcRay sr = RC_DUMMY_RAY;
-        const RcHit h = q.hits[i];
-        if (h.hit) sr = soft_shadow_ray(v, q, i, l, s, q.rays[i], h);
-        store_ray(out, j, sr);
-    }
-}
-// The fused driver: work item j = (i * n_lights + l) * samples + s, so the samples of a (hit, light) pair and the lights of a hit sit in
-// neighbouring lanes and share the hit's records.  ShadowSource's gate: a missed primary ray or a t_max that is not > 0 gives the dead ray.
-struct SoftShadowSource {
-    const SceneView& v;
+// Work item j = (i * n_lights + l) * samples + s (SoftShadowParams, rc_internal.h), so the samples of a (hit, light) pair and the lights
+// of a hit sit in neighbouring lanes and share the hit's records.  ShadowItems' gate.
+struct SoftShadowItems {
     SoftShadowParams q;
-    __device__ inline RcRay operator()(uint64_t j) const {
-        // (the stage kernel's split and ShadowSource's gate, written out: through a shared function -- the item returned as a struct or through
-        // references, the gate by reference or by value -- this job's three shells come out of the compiler differently)
-        const uint32_t il = (uint32_t)j / q.samples, s = (uint32_t)j - il * q.samples;  // (n * n_lights * samples < 2^32)
-        const uint32_t i = il / q.n_lights, l = il - i * q.n_lights;
-        const RcHit h = q.hits[i];
-        if (!h.hit) return RC_DEAD_RAY;
-        const RcRay sr = soft_shadow_ray(v, q, i, l, s, load_ray(q.rays, i), h);
-        return sr.tmax > 0.0f ? sr : RC_DEAD_RAY;
+    static constexpr bool kGate = true;
+    __device__ inline uint32_t slot(uint32_t j) const { return j / q.samples / q.n_lights; }  // (n * n_lights * samples < 2^32)
+    // The shadow ray of sample s of light l seen from slot i
+    __device__ inline RcRay ray(const SceneView& v, uint32_t j, uint32_t i, const RcRay& r, const RcHit& h) const {
+        const uint32_t il = j / q.samples, s = j - il * q.samples, l = il - i * q.n_lights;
+        const float* lp = q.lights + 3u * (size_t)l;
+        const float3_ light = mk3(lp[0], lp[1], lp[2]);
+        float3_ target = light;
+        float3_ p, nn;
+        hit_frame(v, r, h, p, nn);  // once: the target's light_dir and the ray's origin come from the same frame
+        if (q.samples > 1u) {
+            const float3_ lv = sub3(light, p);
+            const float ld = __builtin_sqrtf(dot3(lv, lv));
+            const float3_ light_dir = mk3((lv.x / ld), (lv.y / ld), (lv.z / ld));
+            uint32_t rnd[4];
+            path_philox(q.path_base, q.path_in, i, s | (q.depth << 16), 0x53460000u | l, q.key, rnd);
+            const float radius = q.radii[l];
+            float3_ off = mk3((u32_to_unit(rnd[0]) * 2.0f - 1.0f) * radius, (u32_to_unit(rnd[1]) * 2.0f - 1.0f) * radius, (u32_to_unit(rnd[2]) * 2.0f - 1.0f) * radius);
+            off = sub3(off, scale3(light_dir, dot3(off, light_dir)));
+            target = add3(light, off);
+        }
+        return shadow_ray_from(p, nn, target, q.bias);
     }
-    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
 };
 // count[i * n_lights + l] += 1 for a visible sample (VisibilitySink's rule: a miss that comes back with a t_max > 0).  One relaxed
 // agent-scope u32 add per visible sample: integer adds are exact in any order, so the counts are reproducible; shadowed, gated and
@@ -847,7 +857,7 @@ struct VisibilityCountSink {
 struct SoftShadowJob {
     SoftShadowParams q;
     uint32_t* count;
-    __device__ inline SoftShadowSource source(const SceneView& v) const { return SoftShadowSource{v, q}; }  // (v: the kernel's own by-value parameter)
+    __device__ inline HitItemSource<SoftShadowItems> source(const SceneView& v) const { return {v, {q}}; }  // (v: the kernel's own by-value parameter)
     __device__ inline VisibilityCountSink sink(const SceneView&) const { return VisibilityCountSink{count, q.samples}; }
 };
 
@@ -876,61 +886,38 @@ __device__ inline float3_ cosine_hemisphere_dir(const float3_ n, float u1, float
 // 0x414F0000 | depth), key = seed) through the bounce stage's 24-bit conversion; d = cosine_hemisphere_dir(nn, u1, u2), not renormalised;
 // the ray is o = p + nn * bias, t_min = 0, d, t_max = max_dist.  Every expression left to right, no contraction.  The visible fraction
 // count / samples is the cosine-weighted openness of the hemisphere (the sky-view factor of the point with max_dist = Inf).
-struct AoParams {
-    const RcRay* rays;
-    const RcHit* hits;
-    const uint32_t* path_in;   // path of slot i (nullptr: i), as in k_bounce_rays
-    uint64_t path_base;
-    uint32_t samples, k0, k1, depth;
-    float bias, max_dist;
-};
-// The occlusion ray of sample s of slot i, whose primary ray hit (h = hits[i]): shared by the stage kernel and the fused driver's source, so
-// the two agree bit for bit.
-__device__ inline RcRay ao_ray(const SceneView& v, const AoParams& q, uint32_t i, uint32_t s, const RcRay& r, const RcHit& h) {
-    float3_ p, nn;
-    hit_frame(v, r, h, p, nn);
-    const uint64_t path = q.path_base + (q.path_in ? (uint64_t)q.path_in[i] : (uint64_t)i);
-    uint32_t rnd[4];
-    philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), s, 0x414F0000u | q.depth, q.k0, q.k1, rnd);
+// The cosine-weighted ray off a hit's frame (p, nn): o = p + nn * bias, d = cosine_hemisphere_dir(nn, u1, u2) from the first two Philox
+// words through the 24-bit conversion, [0, t_max].  Shared by the ambient-occlusion items and the bounce stage.
+__device__ inline RcRay cosine_ray(const float3_ p, const float3_ nn, float bias, const uint32_t rnd[4], float t_max) {
     const float3_ d = cosine_hemisphere_dir(nn, u32_to_unit(rnd[0]), u32_to_unit(rnd[1]));
-    const float3_ o = add3(p, scale3(nn, q.bias));
-    return RcRay{o.x, o.y, o.z, 0.f, d.x, d.y, d.z, q.max_dist};
+    const float3_ o = add3(p, scale3(nn, bias));
+    return RcRay{o.x, o.y, o.z, 0.f, d.x, d.y, d.z, t_max};
 }
-// The composed stage: n * samples rays, slot i * samples + s; a slot whose primary ray missed gets k_shadow_rays' dummy ray.  The output
-// feeds rc_trace_any_device unchanged.
-__global__ void k_ao_rays(SceneView v, AoParams q, uint64_t total, RcRay* out) {
-    for (uint64_t j = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; j < total; j += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t i = (uint32_t)j / q.samples, s = (uint32_t)j - i * q.samples;  // (total < 2^32)
-        RcRay ar = RC_DUMMY_RAY;
-        const RcHit h = q.hits[i];
-        if (h.hit) ar = ao_ray(v, q, i, s, q.rays[i], h);
-        store_ray(out, j, ar);
-    }
-}
-// The fused driver: work item j = i * samples + s, so the samples of a hit sit in neighbouring lanes and share its records.  A missed
-// primary ray gives the dead ray; t_max = max_dist > 0 for every other item (checked by the caller), so there is no further gate: a hit
-// with a NaN frame traces its NaN ray, as rc_trace_any_device does with the stored one.
-struct AoSource {
-    const SceneView& v;
+// Work item j = i * samples + s (AoParams, rc_internal.h), so the samples of a hit sit in neighbouring lanes and share its records.  A
+// missed primary ray gives the dead ray; t_max = max_dist > 0 for every other item (checked by the caller), so there is no further gate: a
+// hit with a NaN frame traces its NaN ray, as rc_trace_any_device does with the stored one.
+struct AoItems {
     AoParams q;
-    __device__ inline RcRay operator()(uint64_t j) const {
-        const uint32_t i = (uint32_t)j / q.samples, s = (uint32_t)j - i * q.samples;  // (n * samples < 2^32)
-        const RcHit h = q.hits[i];
-        if (!h.hit) return RC_DEAD_RAY;
-        return ao_ray(v, q, i, s, load_ray(q.rays, i), h);
+    static constexpr bool kGate = false;
+    __device__ inline uint32_t slot(uint32_t j) const { return j / q.samples; }  // (n * samples < 2^32)
+    __device__ inline RcRay ray(const SceneView& v, uint32_t j, uint32_t i, const RcRay& r, const RcHit& h) const {
+        float3_ p, nn;
+        hit_frame(v, r, h, p, nn);
+        uint32_t rnd[4];
+        path_philox(q.path_base, q.path_in, i, j - i * q.samples, 0x414F0000u | q.depth, q.key, rnd);
+        return cosine_ray(p, nn, q.bias, rnd, q.max_dist);
     }
-    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
 };
 // (VisibilityCountSink with count[j / samples] = slot i: one relaxed agent-scope u32 add per visible sample)
 struct AoJob {
     AoParams q;
     uint32_t* count;
-    __device__ inline AoSource source(const SceneView& v) const { return AoSource{v, q}; }  // (v: the kernel's own by-value parameter)
+    __device__ inline HitItemSource<AoItems> source(const SceneView& v) const { return {v, {q}}; }  // (v: the kernel's own by-value parameter)
     __device__ inline VisibilityCountSink sink(const SceneView&) const { return VisibilityCountSink{count, q.samples}; }
 };
 
 // ---- final gather: the sum of a per-primitive field x over the closest hits of the same hemisphere samples ------------------------------
-// AoSource's items and rays unchanged (item j = i * samples + s, ao_ray()), traced for the CLOSEST hit.  Per finished item, i = j / samples:
+// AoItems' items and rays unchanged (item j = i * samples + s), traced for the CLOSEST hit.  Per finished item, i = j / samples:
 //   a hit whose metadata m (hit_meta) lies in 1..n_prims:   sum[i] += x[m - 1]
 //   a hit with metadata outside 1..n_prims:                 nothing (get_illumination's rule, src/kernels.jl:123)
 //   no hit and t > 0 (VisibilityCountSink's rule: a live ray that reached max_dist):   sum[i] += miss_value, open[i] += 1 (open may be null)
@@ -968,7 +955,7 @@ struct GatherJob {
     uint32_t miss_value;
     unsigned long long* sum;
     uint32_t* open;
-    __device__ inline AoSource source(const SceneView& v) const { return AoSource{v, q}; }  // (v: the kernel's own by-value parameter)
+    __device__ inline HitItemSource<AoItems> source(const SceneView& v) const { return {v, {q}}; }  // (v: the kernel's own by-value parameter)
     __device__ inline GatherSink sink(const SceneView& v) const { return GatherSink{v.inst, v.prims, v.n_prims, x, miss_value, q.samples, sum, open}; }
 };
 
@@ -988,11 +975,11 @@ struct GatherJob {
 // calls, groups, streams or devices, give the rows of the one-call result.  A source with non-finite fields gives whatever these
 // expressions give for it, in the stage and in the driver alike.  Shared by the stage kernel and the fused driver's source, so the two
 // agree bit for bit.
-__device__ inline RcRay point_source_ray(const RcRay* sources, uint32_t first_source, uint32_t k, uint32_t cell, uint32_t grid, uint32_t k0, uint32_t k1) {
+__device__ inline RcRay point_source_ray(const RcRay* sources, uint32_t first_source, uint32_t k, uint32_t cell, uint32_t grid, RcPhiloxKey key) {
     const RcRay src = load_ray(sources, k);
     const uint32_t a = cell / grid, b = cell - a * grid;
     uint32_t rnd[4];
-    philox4x32_10(cell, first_source + k, 0u, 0x50530000u, k0, k1, rnd);
+    philox4x32_10(cell, first_source + k, 0u, 0x50530000u, key.k0, key.k1, rnd);
     const float u1 = ((float)a + u32_to_unit(rnd[0])) / (float)grid, u2 = ((float)b + u32_to_unit(rnd[1])) / (float)grid;
     float3_ d;
     if (src.dx == 0.0f && src.dy == 0.0f && src.dz == 0.0f) {
@@ -1011,7 +998,7 @@ __global__ void k_point_source_rays(const RcRay* sources, uint32_t first_source,
     const uint64_t cells = (uint64_t)grid * grid;
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t k = i / cells;
-        store_ray(out, i, point_source_ray(sources, first_source, (uint32_t)k, (uint32_t)(i - k * cells), grid, k0, k1));
+        store_ray(out, i, point_source_ray(sources, first_source, (uint32_t)k, (uint32_t)(i - k * cells), grid, RcPhiloxKey{k0, k1}));
     }
 }
 // The fused driver for a GROUP of sources in one launch: work item i = k_local * grid^2 + cell (items = G * grid^2 < 2^32: both divide in
@@ -1019,10 +1006,11 @@ __global__ void k_point_source_rays(const RcRay* sources, uint32_t first_source,
 // is no parameter kernel in front.
 struct PointSource {
     const RcRay* sources;  // the group's first source
-    uint32_t first_source, cells, grid, k0, k1;
+    uint32_t first_source, cells, grid;
+    RcPhiloxKey key;
     __device__ inline RcRay operator()(uint64_t i) const {
         const uint32_t k = (uint32_t)i / cells, cell = (uint32_t)i - k * cells;
-        return point_source_ray(sources, first_source, k, cell, grid, k0, k1);
+        return point_source_ray(sources, first_source, k, cell, grid, key);
     }
     static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
 };
@@ -1031,8 +1019,8 @@ struct PointSource {
 // totals driver counts `emitted`, whose targets change from wave to wave) the whole call ran at the rate of that word -- 3.4 to 3.7 times
 // the composed path's time at 16 and 64 sources (docs/EXPERIMENTS.md, "Illumination from point sources").  So the escapes are histogram
 // entries like the hits: the copies are laid out for n_prims + kEscapeSlots indices, an escaping ray counts on index n_prims + (a slot chosen
-// per WAVE, so that a wave's lanes still combine), in its workgroup's copy, and k_escaped_fold adds a source's 16 x 64 words into
-// d_escaped[k].  A finished ray is a counted hit, an escape or neither: one wave_count for both kinds.
+// per WAVE, so that a wave's lanes still combine), in its workgroup's copy, and k_hist_fold (FoldAddU32RowsEscaped) adds a source's 16 x 64 words
+// into d_escaped[k].  A finished ray is a counted hit, an escape or neither: one wave_count for both kinds.
 constexpr uint32_t kEscapeSlots = 64;
 struct PointEscapeSink {
     const RcInstRec* inst;
@@ -1053,24 +1041,24 @@ struct PointEscapeSink {
         wave_count(scratch, counted ? h.base(copy) + h.slot(j) : 0ull, counted);
     }
 };
-// One thread per (source of the group, escape slot): the sum over the copies, added to the caller's word.
-__global__ void k_escaped_fold(const uint32_t* scratch, CopyHist h, uint32_t n_prims, uint32_t n_rows, uint32_t* escaped) {
-    const uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    if (t >= (uint64_t)n_rows * kEscapeSlots) return;
-    const uint32_t k = (uint32_t)(t / kEscapeSlots), j = n_prims + (uint32_t)(t % kEscapeSlots);
-    const uint32_t* base = scratch + k * h.words();
-    uint32_t sum = 0;
-    for (uint32_t c = 0; c < kHistCopies; ++c) sum += base[(size_t)c * 8u * h.n8 + (j & 7u) * h.n8 + (j >> 3)];
-    if (sum) atomicAdd(escaped + k, sum);
-}
+// The fold of the job that counts escapes, over n_prims + kEscapeSlots indices per source: the escape slots' sums go to escaped[k].
+struct FoldAddU32RowsEscaped : FoldAddU32Rows {
+    uint32_t n_prims;
+    uint32_t* escaped;
+    __device__ inline void add(uint32_t d, uint32_t j, uint32_t sum) const {
+        if (j < n_prims) FoldAddU32Rows::add(d, j, sum);
+        else atomicAdd(escaped + d, sum);
+    }
+};
 // ESCAPED = false (d_escaped is NULL): the sink IS DirsHistogramSink, not a branch per ray.
 template <bool ESCAPED>
 struct PointIlluminationJobT {
     const RcRay* sources;
-    uint32_t first_source, cells, grid, k0, k1;
+    uint32_t first_source, cells, grid;
+    RcPhiloxKey key;
     uint32_t* scratch;
     CopyHist h;  // ESCAPED: of n_prims + kEscapeSlots indices
-    __device__ inline PointSource source(const SceneView&) const { return PointSource{sources, first_source, cells, grid, k0, k1}; }
+    __device__ inline PointSource source(const SceneView&) const { return PointSource{sources, first_source, cells, grid, key}; }
     template <bool E = ESCAPED>
     __device__ inline typename std::enable_if<E, PointEscapeSink>::type sink(const SceneView& v) const { return PointEscapeSink{v.inst, v.prims, v.n_prims, scratch, h, cells}; }
     template <bool E = ESCAPED>
@@ -1083,45 +1071,7 @@ struct JobShapeFlags<PointIlluminationJobT<true>> { static constexpr unsigned kP
 typedef PointIlluminationJobT<true> PointIlluminationJob;
 typedef PointIlluminationJobT<false> PointIlluminationCountsJob;
 
-// ---- form factors between surface groups: the view-factor job with a choice of sampling, counted per GROUP of primitives ------------------
-// The sampled view-factor ray of (source primitive, ray index): view_factor_ray()'s Philox draw -- counter (ray_idx, src, 0, 0), key = seed
-// -> r1, r2, xi1, xi2 -- and its point on the triangle and origin pt + normal * 0.01f in both samplings.  COSINE = false: view_factor_ray()
-// itself, the reference's uniform hemisphere (src/kernels.jl:92).  COSINE = true: d = cosine_hemisphere_dir(normal, xi1, xi2), the function
-// of the bounce, AO and point-source stages applied to the triangle's unit normal with the third and fourth Philox words, not renormalised:
-// the direction density of a Lambertian surface, so the counts are FORM factors.  t_min = 0, t_max = inf.  The sampling is a template
-// parameter: the cosine path carries no f64 acos, the uniform path no disk mapping.
-template <bool COSINE>
-__device__ inline RcRay view_factor_sampled_ray(const RcPrim& tri, uint32_t src, uint32_t ray_idx, uint32_t k0, uint32_t k1) {
-    if (!COSINE) return view_factor_ray(tri, src, ray_idx, k0, k1);
-    float3_ p1 = mk3(tri.v[0], tri.v[1], tri.v[2]), p2 = mk3(tri.v[3], tri.v[4], tri.v[5]), p3 = mk3(tri.v[6], tri.v[7], tri.v[8]);
-    float3_ normal = normalize3(cross3(sub3(p2, p1), sub3(p3, p1)));
-    uint32_t rnd[4];
-    philox4x32_10(ray_idx, src, 0u, 0u, k0, k1, rnd);
-    float r1 = u32_to_unit(rnd[0]), r2 = u32_to_unit(rnd[1]), xi1 = u32_to_unit(rnd[2]), xi2 = u32_to_unit(rnd[3]);
-    float sqrt_r1 = __builtin_sqrtf(r1);
-    float wu = 1.0f - sqrt_r1, wv = sqrt_r1 * (1.0f - r2), ww = sqrt_r1 * r2;
-    float3_ pt = add3(add3(scale3(p1, wu), scale3(p2, wv)), scale3(p3, ww));
-    float3_ o = add3(pt, scale3(normal, 0.01f));
-    float3_ d = cosine_hemisphere_dir(normal, xi1, xi2);
-    return RcRay{o.x, o.y, o.z, 0.0f, d.x, d.y, d.z, INFINITY};
-}
-// The composed stage, the sibling of k_view_factor_rays: the rays [ray_begin, ray_begin + n_ray) of one source primitive.
-template <bool COSINE>
-__global__ void k_view_factor_sampled_rays(SceneView v, uint32_t k0, uint32_t k1, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_ray) out[i] = view_factor_sampled_ray<COSINE>(v.prims[src], src, ray_begin + i, k0, k1);
-}
-// Work item w -> flat source primitive src_begin + w / n_ray, ray ray_begin + w % n_ray: ViewFactorSource's split without the metadata order.
-template <bool COSINE>
-struct ViewFactorSampledSource {
-    const RcPrim* prims;
-    uint32_t k0, k1, src_begin, ray_begin, n_ray;
-    __device__ inline RcRay operator()(uint64_t w) const {
-        const uint32_t src = src_begin + (uint32_t)(w / n_ray), ray_idx = ray_begin + (uint32_t)(w % n_ray);
-        return view_factor_sampled_ray<COSINE>(prims[src], src, ray_idx, k0, k1);
-    }
-    static constexpr bool kPrefetch = false;  // rays are generated, nothing to read ahead
-};
+// ---- form factors between surface groups: the view-factor job with a choice of sampling (view_factor_ray<COSINE>), counted per GROUP of primitives ----
 // The counting rule, N = the flat primitive count, G = n_groups: a = the source's metadata, b = the hit's (hit_meta), ga = groups[a - 1],
 // gb = groups[b - 1], wa = weights ? weights[a - 1] : 1.  A source whose a is outside 1..N or whose ga >= G contributes nothing.  A miss:
 // escaped[ga] += wa, if escaped is given.  A hit with b in 1..N, b != a (the reference's hit_idx != tri_idx, src/kernels.jl:96) and gb < G:
@@ -1132,28 +1082,26 @@ struct ViewFactorSampledSource {
 // for both kinds, a finished ray is one or the other -- and k_hist_fold (FoldAddU64Groups) adds the copies into the caller's arrays.
 // Without scratch the same sums go straight onto `matrix` and `escaped`.  Indices stay below 2^32: G <= 65535, G * G + G <= 65535 * 65536.
 struct ViewFactorGroupsSink {
-    const RcInstRec* inst;
-    const RcPrim* prims;
-    uint32_t n_prims, src_begin, n_ray, n_groups;
+    const SceneView& v;
+    VfShard sh;
+    uint32_t n_groups;
     const uint32_t* groups;
     const uint32_t* weights;      // or nullptr: every source weighs 1
     unsigned long long* matrix;   // h.n8 != 0: the launch's copy histogram (zeroed by the launcher); else the caller's G x G words
     unsigned long long* escaped;  // h.n8 != 0: non-null when escapes are counted (into the copies); else the caller's G words or nullptr
     CopyHist h;                   // of G * G (+ G) indices, or {0}: no copies
     __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
-        const uint32_t a = prims[src_begin + (uint32_t)(w / n_ray)].meta;
+        const VfPair p = vf_pair(v, nullptr, sh, w, hit, prim, instance);
+        const uint32_t a = p.src_meta;
         bool counted = false, escape = false;
         uint32_t j = 0, wa = 0;
-        if (a >= 1 && a <= n_prims) {
+        if (a >= 1 && a <= v.n_prims) {
             const uint32_t ga = groups[a - 1u];
             if (ga < n_groups) {
-                if (hit) {
-                    const uint32_t b = hit_meta(inst, prims, instance, prim);
-                    if (b >= 1 && b <= n_prims && b != a) {
-                        const uint32_t gb = groups[b - 1u];
-                        if (gb < n_groups) { counted = true; j = ga * n_groups + gb; }
-                    }
-                } else if (escaped) { counted = true; escape = true; j = ga; }
+                if (p.counted) {
+                    const uint32_t gb = groups[p.to_meta - 1u];
+                    if (gb < n_groups) { counted = true; j = ga * n_groups + gb; }
+                } else if (!hit && escaped) { counted = true; escape = true; j = ga; }
                 if (counted) wa = weights ? weights[a - 1u] : 1u;
             }
         }
@@ -1175,16 +1123,15 @@ struct FoldAddU64Groups : FoldOneRow {
 };
 template <bool COSINE>
 struct ViewFactorGroupsJob {
-    uint32_t k0, k1, src_begin, ray_begin, n_ray, n_groups;
+    VfShard sh;
+    uint32_t n_groups;
     const uint32_t* groups;
     const uint32_t* weights;
     unsigned long long* matrix;
     unsigned long long* escaped;
     CopyHist h;
-    __device__ inline ViewFactorSampledSource<COSINE> source(const SceneView& v) const { return ViewFactorSampledSource<COSINE>{v.prims, k0, k1, src_begin, ray_begin, n_ray}; }
-    __device__ inline ViewFactorGroupsSink sink(const SceneView& v) const {
-        return ViewFactorGroupsSink{v.inst, v.prims, v.n_prims, src_begin, n_ray, n_groups, groups, weights, matrix, escaped, h};
-    }
+    __device__ inline ViewFactorSource<COSINE> source(const SceneView& v) const { return ViewFactorSource<COSINE>{v.prims, nullptr, sh}; }
+    __device__ inline ViewFactorGroupsSink sink(const SceneView& v) const { return ViewFactorGroupsSink{v, sh, n_groups, groups, weights, matrix, escaped, h}; }
 };
 
 // Diffuse bounce: output slot i continues the path of source slot s (s = i, or d_src[i] for i < count, or d_src[i % count] round robin
@@ -1209,15 +1156,11 @@ __global__ void k_bounce_rays(SceneView v, const RcRay* rays, const RcHit* hits,
         if (live) {
             const RcHit h = hits[s];
             if (h.hit) {
-                const uint64_t path = path_base + (path_in ? (uint64_t)path_in[s] : (uint64_t)s);
-                path_id = (uint32_t)path;
                 float3_ p, nn;
                 hit_frame(v, rays[s], h, p, nn);
-                const float3_ o = add3(p, scale3(nn, bias));
                 uint32_t rnd[4];
-                philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), k, tag, k0, k1, rnd);
-                const float3_ d = cosine_hemisphere_dir(nn, u32_to_unit(rnd[0]), u32_to_unit(rnd[1]));
-                b = RcRay{o.x, o.y, o.z, 0.f, d.x, d.y, d.z, INFINITY};
+                path_id = (uint32_t)path_philox(path_base, path_in, s, k, tag, RcPhiloxKey{k0, k1}, rnd);
+                b = cosine_ray(p, nn, bias, rnd, INFINITY);
             }
         }
         store_ray(out, i, b);
@@ -1232,7 +1175,7 @@ struct CameraParams {
     float pos[3], right[3], up[3], forward[3];
     float half_width, half_height;
     uint32_t width, height, samples, jitter;
-    uint32_t k0, k1;
+    RcPhiloxKey key;
 };
 __global__ void k_primary_rays(CameraParams c, uint64_t n, RcRay* out) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -1241,7 +1184,7 @@ __global__ void k_primary_rays(CameraParams c, uint64_t n, RcRay* out) {
         float j1 = 0.5f, j2 = 0.5f;
         if (c.jitter) {
             uint32_t rnd[4];
-            philox4x32_10((uint32_t)i, (uint32_t)(i >> 32), 0u, 0x50524159u, c.k0, c.k1, rnd);
+            philox4x32_10((uint32_t)i, (uint32_t)(i >> 32), 0u, 0x50524159u, c.key.k0, c.key.k1, rnd);
             j1 = u32_to_unit(rnd[0]); j2 = u32_to_unit(rnd[1]);
         }
         const float u = 2.0f * ((float)x - 0.5f + j1) / (float)c.width - 1.0f;
@@ -1381,6 +1324,24 @@ struct DriverLaunch {
         guard.finish();
     }
 };
+// The row-grouped illumination calls trace their n_rows rows (directions, point sources) of `cells` rays in groups of G consecutive ones,
+// one persistent launch per group; G is the largest count with G * cells < 2^32 (the sources divide in 32 bits) whose private histogram
+// copies (h: of one row) fit option "illum_scratch_bytes" (at least one row's worth).  each(first, count) per group.
+template <class Each>
+void for_row_groups(rc_scene* s, uint32_t n_rows, uint64_t cells, CopyHist h, Each each) {
+    const uint64_t row_bytes = sizeof(uint32_t) * h.words();
+    const uint64_t group = std::min<uint64_t>(n_rows, std::min<uint64_t>(((1ull << 32) - 1u) / cells, std::max<uint64_t>((uint64_t)s->opt.illum_scratch_bytes / row_bytes, 1)));
+    for (uint32_t r0 = 0; r0 < n_rows; r0 += (uint32_t)group) each(r0, (uint32_t)std::min<uint64_t>(group, n_rows - r0));
+}
+// The shard of a view-factor call: the rays [ray_begin, ray_end) below rays_per_triangle of the source positions [src_begin, src_end) below
+// the flat primitive count.  Returns its item count, 0 for an empty shard.
+uint64_t vf_shard(const rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin, uint32_t ray_end, VfShard& sh) {
+    src_end = std::min(src_end, s->n_flat_prims);
+    ray_end = std::min(ray_end, rays_per_triangle);
+    if (src_begin >= src_end || ray_begin >= ray_end) return 0;
+    sh = VfShard{rc_philox_key(seed), src_begin, ray_begin, ray_end - ray_begin};
+    return (uint64_t)(src_end - src_begin) * sh.n_ray;
+}
 }  // namespace
 
 void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, uint64_t ray_begin, uint64_t ray_end,
@@ -1406,9 +1367,8 @@ void rc_launch_illumination(rc_scene* s, const float viewdir[3], uint32_t grid, 
 }
 
 // get_illumination for n_dirs device-resident directions, ACCUMULATED into d_counts[d * row_stride + (meta - 1)] (u32).  The directions are
-// traced in groups of G consecutive ones, one persistent launch per group (IlluminationDirsJob); G is the largest count with
-// G * grid^2 < 2^32 (the source divides in 32 bits) whose private histogram copies fit option "illum_scratch_bytes" (at least one
-// direction's worth).  Per group: the copies are zeroed, k_grid_params lays the group's grids out from d_dirs and the TLAS root AS THEY
+// traced in groups (for_row_groups), one persistent launch per group (IlluminationDirsJob).  Per group: the copies are zeroed,
+// k_grid_params lays the group's grids out from d_dirs and the TLAS root AS THEY
 // ARE WHEN IT RUNS -- nothing here reads the host copy of the world bound, so the call follows an asynchronous refit or rebuild without a
 // host wait and may be captured --, the launch counts, the fold adds.  Items are claimed in natural order: the plan is fixed at call time,
 // the rays are not known before the kernels run.  grid^2 < 2^32 (checked by the caller).
@@ -1417,29 +1377,27 @@ void rc_launch_illumination_dirs(rc_scene* s, const float* d_dirs, uint32_t n_di
     const CopyHist h = CopyHist::of(np);
     const uint64_t cells = (uint64_t)grid * grid;
     if (n_dirs == 0 || cells == 0 || np == 0) return;
-    const uint64_t dir_bytes = sizeof(uint32_t) * h.words();
-    const uint64_t group = std::min<uint64_t>(n_dirs, std::min<uint64_t>(((1ull << 32) - 1u) / cells, std::max<uint64_t>((uint64_t)s->opt.illum_scratch_bytes / dir_bytes, 1)));
-    for (uint32_t d0 = 0; d0 < n_dirs; d0 += (uint32_t)group) {
-        const uint32_t nd = (uint32_t)std::min<uint64_t>(group, n_dirs - d0);
+    for_row_groups(s, n_dirs, cells, h, [&](uint32_t d0, uint32_t nd) {
         DriverLaunch launch(s, stream, nd * cells);
         const HistScratch<uint32_t> scratch = rc_hist_scratch<uint32_t>(launch.guard, h, nd, nd);  // the group's grids sit behind its histograms
         hipLaunchKernelGGL(k_grid_params, dim3((nd + 63u) / 64u), dim3(64), 0, stream, s->tlas_nodes.p, s->n_tlas_nodes, d_dirs + 3u * (size_t)d0, nd, grid, scratch.params);
         launch.go<false>(IlluminationDirsJob{scratch.params, (uint32_t)cells, scratch.hist, h}, Nothing(),
                          [&] { rc_hist_fold(stream, scratch.hist, h, np, FoldAddU32Rows{nd, d_counts + (uint64_t)d0 * row_stride, row_stride}); });
-    }
+    });
 }
 
 // n_sources x grid^2 rays of device-resident point sources (k_point_source_rays): reads no scene memory.
 void rc_launch_point_source_rays(rc_scene* s, const RcRay* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed, uint32_t first_source,
                                  RcRay* d_rays, hipStream_t stream) {
     const uint64_t total = (uint64_t)n_sources * grid * grid;
-    launch_stage<8, false>(s, stream, total, k_point_source_rays, d_sources, first_source, grid, (uint32_t)seed, (uint32_t)(seed >> 32), total, d_rays);
+    const RcPhiloxKey key = rc_philox_key(seed);
+    launch_stage<8, false>(s, stream, total, k_point_source_rays, d_sources, first_source, grid, key.k0, key.k1, total, d_rays);
 }
 
 // get_illumination for n_sources device-resident POINT sources, ACCUMULATED into d_counts[k * row_stride + (meta - 1)] (u32) and, unless
 // it is null, the rays that hit nothing into d_escaped[k].  The sources are traced in groups of G consecutive ones like the directions of
-// rc_launch_illumination_dirs, under the same rule for G (G * grid^2 < 2^32, histogram copies within option "illum_scratch_bytes", at least
-// one source's worth).  Per group: one memset, one persistent launch (PointIlluminationJob), one fold; the group's first index is added to
+// rc_launch_illumination_dirs (for_row_groups).  Per group: one memset, one persistent launch (PointIlluminationJob), one fold; the
+// group's first index is added to
 // first_source for the Philox counter, so the grouping changes no result.  Nothing is read on the host and there is no kernel in front:
 // the source records are read by the traversal kernel itself.  grid^2 < 2^32 and first_source + n_sources <= 2^32 (checked by the caller).
 template <bool ESCAPED>
@@ -1448,20 +1406,15 @@ static void launch_illumination_points(rc_scene* s, const RcRay* d_sources, uint
     const uint32_t np = s->n_flat_prims;
     const CopyHist h = CopyHist::of(ESCAPED ? np + kEscapeSlots : np);  // (the escapes are kEscapeSlots more indices of every copy: PointEscapeSink)
     const uint64_t cells = (uint64_t)grid * grid;
-    const uint64_t source_bytes = sizeof(uint32_t) * h.words();
-    const uint64_t group = std::min<uint64_t>(n_sources, std::min<uint64_t>(((1ull << 32) - 1u) / cells, std::max<uint64_t>((uint64_t)s->opt.illum_scratch_bytes / source_bytes, 1)));
-    for (uint32_t k0 = 0; k0 < n_sources; k0 += (uint32_t)group) {
-        const uint32_t nk = (uint32_t)std::min<uint64_t>(group, n_sources - k0);
+    for_row_groups(s, n_sources, cells, h, [&](uint32_t k0, uint32_t nk) {
         DriverLaunch launch(s, stream, nk * cells);
         uint32_t* scratch = rc_hist_scratch<uint32_t>(launch.guard, h, nk).hist;
-        launch.go<false>(PointIlluminationJobT<ESCAPED>{d_sources + k0, first_source + k0, (uint32_t)cells, grid, (uint32_t)seed, (uint32_t)(seed >> 32), scratch, h},
-                         Nothing(), [&] {
-                             rc_hist_fold(stream, scratch, h, np, FoldAddU32Rows{nk, d_counts + (uint64_t)k0 * row_stride, row_stride});
-                             if (ESCAPED)
-                                 hipLaunchKernelGGL(k_escaped_fold, dim3((uint32_t)(((uint64_t)nk * kEscapeSlots + 255u) / 256u)), dim3(256), 0, stream,
-                                                    (const uint32_t*)scratch, h, np, nk, d_escaped + k0);
-                         });
-    }
+        const FoldAddU32Rows rows{nk, d_counts + (uint64_t)k0 * row_stride, row_stride};
+        launch.go<false>(PointIlluminationJobT<ESCAPED>{d_sources + k0, first_source + k0, (uint32_t)cells, grid, rc_philox_key(seed), scratch, h}, Nothing(), [&] {
+            if (ESCAPED) rc_hist_fold(stream, scratch, h, np + kEscapeSlots, FoldAddU32RowsEscaped{rows, np, d_escaped + k0});
+            else rc_hist_fold(stream, scratch, h, np, rows);
+        });
+    });
 }
 void rc_launch_illumination_points(rc_scene* s, const RcRay* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed, uint32_t first_source,
                                    uint32_t* d_counts, uint64_t row_stride, uint32_t* d_escaped, hipStream_t stream) {
@@ -1512,28 +1465,26 @@ void rc_vf_source_range(rc_scene* s, uint32_t row_begin, uint32_t row_end, uint3
 void rc_launch_view_factors(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end,
                             uint32_t ray_begin, uint32_t ray_end, uint32_t* d_matrix, uint64_t row_stride, uint64_t col_stride,
                             uint32_t row_offset, uint32_t flags, hipStream_t stream) {
-    if (src_end > s->n_flat_prims) src_end = s->n_flat_prims;
-    if (ray_end > rays_per_triangle) ray_end = rays_per_triangle;
-    if (src_begin >= src_end || ray_begin >= ray_end) return;
-    uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
+    VfShard sh;
+    const uint64_t total = vf_shard(s, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, sh);
+    if (!total) return;
     const uint32_t* order = (flags & 2u) ? s->vf_order.p : nullptr;  // RC_VF_SOURCES_BY_METADATA: the caller has called rc_ensure_vf_order, once per job
-    DriverLaunch(s, stream, total).go<false>(ViewFactorJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, d_matrix, row_stride, col_stride, row_offset, flags, order});
+    DriverLaunch(s, stream, total).go<false>(ViewFactorJob{sh, d_matrix, row_stride, col_stride, row_offset, flags, order});
 }
 
 // Totals of rays [ray_begin, ray_end) of the sources with flat indices [src_begin, src_end), ACCUMULATED into d_received / d_emitted
 // (n_prims u64 each, device; either may be nullptr).
 void rc_launch_vf_totals(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin,
                          uint32_t ray_end, unsigned long long* d_received, unsigned long long* d_emitted, hipStream_t stream) {
-    if (src_end > s->n_flat_prims) src_end = s->n_flat_prims;
-    if (ray_end > rays_per_triangle) ray_end = rays_per_triangle;
-    if (src_begin >= src_end || ray_begin >= ray_end || (!d_received && !d_emitted)) return;
-    const uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
+    VfShard sh;
+    const uint64_t total = vf_shard(s, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, sh);
+    if (!total || (!d_received && !d_emitted)) return;
     DriverLaunch launch(s, stream, total);
     const uint32_t np = s->n_flat_prims;
     const CopyHist h = CopyHist::of(np);
     // the private copies of the hot vector (see ViewFactorTotalsSink): one scratch area per stream, launches on one stream are ordered
     unsigned long long* scratch = d_received ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
-    launch.go<false>(ViewFactorTotalsJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, scratch, h, d_emitted}, Nothing(),
+    launch.go<false>(ViewFactorTotalsJob{sh, scratch, h, d_emitted}, Nothing(),
                      [&] { if (d_received) rc_hist_fold(stream, scratch, h, np, FoldAddU64{{}, d_received}); });
 }
 
@@ -1541,15 +1492,14 @@ void rc_launch_vf_totals(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
 // either may be nullptr).  The launch of rc_launch_vf_totals with ViewFactorProductsJob: d_mtx takes `received`'s copy histogram and fold.
 void rc_launch_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin,
                            uint32_t ray_end, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx, hipStream_t stream) {
-    if (src_end > s->n_flat_prims) src_end = s->n_flat_prims;
-    if (ray_end > rays_per_triangle) ray_end = rays_per_triangle;
-    if (src_begin >= src_end || ray_begin >= ray_end || (!d_mx && !d_mtx)) return;
-    const uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
+    VfShard sh;
+    const uint64_t total = vf_shard(s, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, sh);
+    if (!total || (!d_mx && !d_mtx)) return;
     DriverLaunch launch(s, stream, total);
     const uint32_t np = s->n_flat_prims;
     const CopyHist h = CopyHist::of(np);
     unsigned long long* scratch = d_mtx ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
-    launch.go<false>(ViewFactorProductsJob{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, d_x, scratch, h, d_mx}, Nothing(),
+    launch.go<false>(ViewFactorProductsJob{sh, d_x, scratch, h, d_mx}, Nothing(),
                      [&] { if (d_mtx) rc_hist_fold(stream, scratch, h, np, FoldAddU64{{}, d_mtx}); });
 }
 
@@ -1562,27 +1512,24 @@ void rc_launch_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t see
 // (checked by the caller): wave_add indexes in 32 bits.
 constexpr unsigned long long kVfGroupsCopyBytes = 256ull << 20;
 template <bool COSINE>
-static void launch_vf_groups(rc_scene* s, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups,
-                             uint32_t n_groups, const uint32_t* d_weights, unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream) {
-    const uint64_t total = (uint64_t)(src_end - src_begin) * (ray_end - ray_begin);
+static void launch_vf_groups(rc_scene* s, const VfShard& sh, uint64_t total, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
+                             unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream) {
     DriverLaunch launch(s, stream, total);
     const uint32_t gg = n_groups * n_groups, n = gg + (d_escaped ? n_groups : 0u);
     CopyHist h = CopyHist::of(n);
     const bool copies = sizeof(unsigned long long) * h.words() <= kVfGroupsCopyBytes;
     unsigned long long* scratch = copies ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
     if (!copies) h = CopyHist{0u};
-    launch.go<false>(ViewFactorGroupsJob<COSINE>{(uint32_t)seed, (uint32_t)(seed >> 32), src_begin, ray_begin, ray_end - ray_begin, n_groups, d_groups, d_weights,
-                                                 copies ? scratch : d_matrix, d_escaped, h},
-                     Nothing(), [&] { if (copies) rc_hist_fold(stream, scratch, h, n, FoldAddU64Groups{{}, d_matrix, d_escaped, gg}); });
+    launch.go<false>(ViewFactorGroupsJob<COSINE>{sh, n_groups, d_groups, d_weights, copies ? scratch : d_matrix, d_escaped, h}, Nothing(),
+                     [&] { if (copies) rc_hist_fold(stream, scratch, h, n, FoldAddU64Groups{{}, d_matrix, d_escaped, gg}); });
 }
 void rc_launch_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t src_begin, uint32_t src_end,
                          uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
                          unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream) {
-    if (src_end > s->n_flat_prims) src_end = s->n_flat_prims;
-    if (ray_end > rays_per_triangle) ray_end = rays_per_triangle;
-    if (src_begin >= src_end || ray_begin >= ray_end) return;
-    if (sampling) launch_vf_groups<true>(s, seed, src_begin, src_end, ray_begin, ray_end, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream);
-    else launch_vf_groups<false>(s, seed, src_begin, src_end, ray_begin, ray_end, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream);
+    VfShard sh;
+    const uint64_t total = vf_shard(s, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, sh);
+    if (!total) return;
+    (sampling ? launch_vf_groups<true> : launch_vf_groups<false>)(s, sh, total, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream);
 }
 
 // Rows [row_begin, row_end) of the view-factor matrix in canonical CSR (rc_view_factors_sparse_device), all on `stream`, no host wait.
@@ -1659,7 +1606,8 @@ void rc_launch_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
     const size_t n_chunks = chunks.size();
     for (size_t ci = 0; ci < n_chunks; ++ci) {
         const SparseChunk& c = chunks[ci];
-        const uint64_t items = (uint64_t)(c.pos1 - c.pos0) * R;
+        VfShard sh;
+        const uint64_t items = vf_shard(s, R, seed, c.pos0, c.pos1, 0u, R, sh);  // (whole rows of a non-empty chunk: never 0)
         const uint32_t row_bits = ceil_log2(c.row1 - c.row0);
         const unsigned long long sentinel = 1ull << (row_bits + col_bits);
         DriverLaunch launch(s, stream, items);
@@ -1671,7 +1619,7 @@ void rc_launch_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
         unsigned long long* scanned = reinterpret_cast<unsigned long long*>(base + 2u * key_bytes + len_bytes + 16u);
         void* tmp = base + 2u * key_bytes + len_bytes + 16u + ptr_bytes;
         launch.go<false>(
-            ViewFactorPairsJob{(uint32_t)seed, (uint32_t)(seed >> 32), c.pos0, R, c.row0, col_bits, sentinel, keys, s->vf_order.p}, Nothing(), [&] {
+            ViewFactorPairsJob{sh, c.row0, col_bits, sentinel, keys, s->vf_order.p}, Nothing(), [&] {
                 size_t b = tmp_bytes;
                 RC_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, b, (const unsigned long long*)keys, sorted, items, 0, (int)(row_bits + col_bits + 1u), stream));
                 b = tmp_bytes;
@@ -1723,21 +1671,11 @@ void rc_note_stage_launch(rc_scene* s, hipStream_t stream) {
     RC_HIP(hipEventRecord(it->second, stream));
 }
 
-void rc_launch_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out, hipStream_t stream) {
+// The rays [ray_begin, ray_begin + n_ray) of one source primitive (sampling 0 = the reference's uniform hemisphere, 1 = cosine)
+void rc_launch_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out, hipStream_t stream) {
     if (n_ray == 0) return;
-    SceneView v = rc_scene_view_static(s);
-    hipLaunchKernelGGL(k_view_factor_rays, dim3((n_ray + 255) / 256), dim3(256), 0, stream, v, (uint32_t)seed, (uint32_t)(seed >> 32), src, ray_begin, n_ray, d_out);
-    RC_HIP(hipGetLastError());
-    rc_note_stage_launch(s, stream);
-}
-
-void rc_launch_view_factor_sampled_rays(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out,
-                                        hipStream_t stream) {
-    if (n_ray == 0) return;
-    SceneView v = rc_scene_view_static(s);
-    const dim3 grid((n_ray + 255) / 256);
-    if (sampling) hipLaunchKernelGGL(k_view_factor_sampled_rays<true>, grid, dim3(256), 0, stream, v, (uint32_t)seed, (uint32_t)(seed >> 32), src, ray_begin, n_ray, d_out);
-    else hipLaunchKernelGGL(k_view_factor_sampled_rays<false>, grid, dim3(256), 0, stream, v, (uint32_t)seed, (uint32_t)(seed >> 32), src, ray_begin, n_ray, d_out);
+    hipLaunchKernelGGL(sampling ? k_view_factor_rays<true> : k_view_factor_rays<false>, dim3((n_ray + 255) / 256), dim3(256), 0, stream, rc_scene_view_static(s),
+                       rc_philox_key(seed), src, ray_begin, n_ray, d_out);
     RC_HIP(hipGetLastError());
     rc_note_stage_launch(s, stream);
 }
@@ -1746,74 +1684,43 @@ void rc_launch_hit_points(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits,
     launch_stage(s, stream, n, k_hit_points, rc_scene_view_static(s), d_rays, d_hits, n, d_points, d_normals);
 }
 
-void rc_launch_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float light[3], float bias, RcRay* d_out, hipStream_t stream) {
-    launch_stage(s, stream, n, k_shadow_rays, rc_scene_view_static(s), d_rays, d_hits, n, light[0], light[1], light[2], bias, d_out);
+// The hit-sample family (ShadowParams, SoftShadowParams, AoParams: rc_internal.h).  A composed stage writes one ray per item; a driver is
+// one persistent launch over the same items in natural claim order -- the rays are generated, there is no batch to recognise.  Every item
+// count is below 2^32 (checked by the caller).
+void rc_launch_shadow_rays(rc_scene* s, const ShadowParams& q, const float light[3], uint64_t n, RcRay* d_out, hipStream_t stream) {
+    launch_stage(s, stream, n, k_hit_item_rays<ShadowItems<true>>, rc_scene_view_static(s), ShadowItems<true>{q, {light[0], light[1], light[2]}}, n, d_out);
 }
-
-// One persistent any_hit launch over the n * n_lights (hit, light) items (ShadowSource / VisibilitySink); natural claim order -- the rays are
-// generated, there is no batch to recognise.  n * n_lights < 2^32 (checked by the caller).
-void rc_launch_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, uint32_t n_lights, float bias,
-                                 uint8_t* d_visible, hipStream_t stream) {
-    const uint64_t total = n * n_lights;
-    if (total == 0) return;
-    DriverLaunch(s, stream, total).go<true>(ShadowJob{d_rays, d_hits, d_lights, n_lights, bias, d_visible});
+void rc_launch_shadow_visibility(rc_scene* s, const ShadowParams& q, uint64_t n, uint8_t* d_visible, hipStream_t stream) {
+    if (n * q.n_lights) DriverLaunch(s, stream, n * q.n_lights).go<true>(ShadowJob{q, d_visible});
 }
-
-// The soft-shadow pair (SoftShadowParams): the composed stage writes the n * n_lights * samples rays; the driver is one persistent any_hit
-// launch over the same items in natural claim order that ACCUMULATES the visible samples into d_count.  total < 2^32 (checked by the caller).
-static SoftShadowParams soft_shadow_params(const RcRay* d_rays, const RcHit* d_hits, const float* d_lights, const float* d_radii, uint32_t n_lights,
-                                           uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias) {
-    return SoftShadowParams{d_rays, d_hits, d_lights, d_radii, d_path_in, path_base, n_lights, samples, (uint32_t)seed, (uint32_t)(seed >> 32), depth, bias};
+void rc_launch_soft_shadow_rays(rc_scene* s, const SoftShadowParams& q, uint64_t n, RcRay* d_out, hipStream_t stream) {
+    const uint64_t total = n * q.n_lights * q.samples;
+    launch_stage(s, stream, total, k_hit_item_rays<SoftShadowItems>, rc_scene_view_static(s), SoftShadowItems{q}, total, d_out);
 }
-void rc_launch_soft_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
-                                uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
-                                float bias, RcRay* d_out, hipStream_t stream) {
-    const uint64_t total = n * n_lights * samples;
-    launch_stage(s, stream, total, k_soft_shadow_rays, rc_scene_view_static(s),
-                 soft_shadow_params(d_rays, d_hits, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias), total, d_out);
+// ACCUMULATES the visible samples into d_count[i * n_lights + l]
+void rc_launch_soft_shadow_visibility(rc_scene* s, const SoftShadowParams& q, uint64_t n, uint32_t* d_count, hipStream_t stream) {
+    const uint64_t total = n * q.n_lights * q.samples;
+    if (total) DriverLaunch(s, stream, total).go<true>(SoftShadowJob{q, d_count});
 }
-void rc_launch_soft_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
-                                      uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in,
-                                      uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream) {
-    const uint64_t total = n * n_lights * samples;
-    if (total == 0) return;
-    DriverLaunch(s, stream, total).go<true>(SoftShadowJob{soft_shadow_params(d_rays, d_hits, d_lights, d_radii, n_lights, samples, seed, depth, d_path_in, path_base, bias), d_count});
+void rc_launch_ao_rays(rc_scene* s, const AoParams& q, uint64_t n, RcRay* d_out, hipStream_t stream) {
+    launch_stage(s, stream, n * q.samples, k_hit_item_rays<AoItems>, rc_scene_view_static(s), AoItems{q}, n * q.samples, d_out);
 }
-
-// The ambient-occlusion pair (AoParams): the composed stage writes the n * samples rays; the driver is one persistent any_hit launch over the
-// same items in natural claim order that ACCUMULATES the visible samples into d_count[i].  total < 2^32 (checked by the caller).
-static AoParams ao_params(const RcRay* d_rays, const RcHit* d_hits, uint32_t samples, float max_dist, uint64_t seed, uint32_t depth,
-                          const uint32_t* d_path_in, uint64_t path_base, float bias) {
-    return AoParams{d_rays, d_hits, d_path_in, path_base, samples, (uint32_t)seed, (uint32_t)(seed >> 32), depth, bias, max_dist};
+// ACCUMULATES the visible samples into d_count[i]
+void rc_launch_ambient_occlusion(rc_scene* s, const AoParams& q, uint64_t n, uint32_t* d_count, hipStream_t stream) {
+    if (n * q.samples) DriverLaunch(s, stream, n * q.samples).go<true>(AoJob{q, d_count});
 }
-void rc_launch_ao_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed, uint32_t depth,
-                       const uint32_t* d_path_in, uint64_t path_base, float bias, RcRay* d_out, hipStream_t stream) {
-    const uint64_t total = n * samples;
-    launch_stage(s, stream, total, k_ao_rays, rc_scene_view_static(s), ao_params(d_rays, d_hits, samples, max_dist, seed, depth, d_path_in, path_base, bias),
-                 total, d_out);
-}
-void rc_launch_ambient_occlusion(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
-                                 uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream) {
-    const uint64_t total = n * samples;
-    if (total == 0) return;
-    DriverLaunch(s, stream, total).go<true>(AoJob{ao_params(d_rays, d_hits, samples, max_dist, seed, depth, d_path_in, path_base, bias), d_count});
-}
-// The final gather: the same items and rays in one persistent CLOSEST-hit launch in natural claim order that ACCUMULATES x at the hit
-// primitives' metadata (miss_value for an escaped sample) into d_sum[i] and the escaped samples into d_open[i] (may be null).
-void rc_launch_final_gather(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
-                            uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, const uint32_t* d_x, uint32_t miss_value,
-                            uint64_t* d_sum, uint32_t* d_open, hipStream_t stream) {
-    const uint64_t total = n * samples;
-    if (total == 0) return;
-    DriverLaunch(s, stream, total).go<false>(GatherJob{ao_params(d_rays, d_hits, samples, max_dist, seed, depth, d_path_in, path_base, bias), d_x, miss_value,
-                                                       reinterpret_cast<unsigned long long*>(d_sum), d_open});
+// The final gather: the same items and rays in one persistent CLOSEST-hit launch that ACCUMULATES x at the hit primitives' metadata
+// (miss_value for an escaped sample) into d_sum[i] and the escaped samples into d_open[i] (may be null).
+void rc_launch_final_gather(rc_scene* s, const AoParams& q, uint64_t n, const uint32_t* d_x, uint32_t miss_value, uint64_t* d_sum, uint32_t* d_open, hipStream_t stream) {
+    if (n * q.samples) DriverLaunch(s, stream, n * q.samples).go<false>(GatherJob{q, d_x, miss_value, reinterpret_cast<unsigned long long*>(d_sum), d_open});
 }
 
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                            const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n, uint64_t seed, uint32_t bounce, float bias,
                            RcRay* d_out, hipStream_t stream) {
+    const RcPhiloxKey key = rc_philox_key(seed);
     launch_stage(s, stream, n, k_bounce_rays, rc_scene_view_static(s), d_rays, d_hits, d_src, d_src_count, wrap ? 1 : 0, d_path_in, d_path_out, path_base,
-                 (uint32_t)n, (uint32_t)seed, (uint32_t)(seed >> 32), 0x424E0000u | bounce, bias, d_out);
+                 (uint32_t)n, key.k0, key.k1, 0x424E0000u | bounce, bias, d_out);
 }
 
 void rc_launch_primary_rays(rc_scene* s, const float pos[3], const float right[3], const float up[3], const float forward[3], float half_width,
@@ -1824,7 +1731,7 @@ void rc_launch_primary_rays(rc_scene* s, const float pos[3], const float right[3
     for (int k = 0; k < 3; ++k) { c.pos[k] = pos[k]; c.right[k] = right[k]; c.up[k] = up[k]; c.forward[k] = forward[k]; }
     c.half_width = half_width; c.half_height = half_height;
     c.width = width; c.height = height; c.samples = samples; c.jitter = jitter ? 1u : 0u;
-    c.k0 = (uint32_t)seed; c.k1 = (uint32_t)(seed >> 32);
+    c.key = rc_philox_key(seed);
     launch_stage<16, false>(s, stream, n, k_primary_rays, c, n, d_out);  // (reads no scene memory)
 }
 

@@ -520,8 +520,7 @@ void rc_launch_vf_sparse_products(rc_scene* s, uint32_t n_rows, uint32_t row_off
                                   const uint32_t* d_vals, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx, hipStream_t stream);
 // Form factors between surface groups (rc_drivers.hip): the sampled view-factor rays (sampling 0 = the reference's uniform hemisphere, 1 = cosine)
 // of one source primitive, and the G x G matrix of weighted counts between groups of primitives, ACCUMULATED in u64.
-void rc_launch_view_factor_sampled_rays(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out,
-                                        hipStream_t stream);
+void rc_launch_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out, hipStream_t stream);
 void rc_launch_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t src_begin, uint32_t src_end,
                          uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
                          unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream);
@@ -535,33 +534,58 @@ struct rc_hit;
 void rc_trace_multi_impl(rc_scene* const* scenes, int n_scenes, const rc_ray* rays, rc_hit* hits, uint64_t n, int any);
 void rc_illumination_multi_impl(rc_scene* const* scenes, int n_scenes, const float viewdir[3], uint32_t grid, float* out);
 void rc_trace_host_impl(rc_scene* s, const rc_ray* rays, rc_hit* hits, uint64_t n, int any);  // rc_capi.hip: one scene's host-buffer batch (throws)
-void rc_launch_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t src, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out, hipStream_t stream);
 void rc_launch_hit_points(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, float* d_points, float* d_normals, hipStream_t stream);
-void rc_launch_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float light[3], float bias, RcRay* d_out, hipStream_t stream);
+// The two words of a Philox4x32 key, from the 64-bit seed of a call
+struct RcPhiloxKey { uint32_t k0, k1; };
+inline RcPhiloxKey rc_philox_key(uint64_t seed) { return RcPhiloxKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+// The hit-sample family (rc_drivers.hip): what a call gives beside its output, as the kernels take it.  rc_capi.hip fills one per call,
+// behind its argument checks; all pointers are device memory, read when the kernel runs.
+struct ShadowParams {
+    const RcRay* rays;
+    const RcHit* hits;
+    const float* lights;  // n_lights x 3 (the composed stage takes its one light by value instead: nullptr, n_lights = 1)
+    uint32_t n_lights;
+    float bias;
+};
+struct SoftShadowParams {
+    const RcRay* rays;
+    const RcHit* hits;
+    const float* lights;       // n_lights x 3
+    const float* radii;        // n_lights
+    const uint32_t* path_in;   // path of slot i (nullptr: i), as in the bounce stage
+    uint64_t path_base;
+    uint32_t n_lights, samples;
+    RcPhiloxKey key;
+    uint32_t depth;
+    float bias;
+};
+struct AoParams {
+    const RcRay* rays;
+    const RcHit* hits;
+    const uint32_t* path_in;   // path of slot i (nullptr: i), as in the bounce stage
+    uint64_t path_base;
+    uint32_t samples;
+    RcPhiloxKey key;
+    uint32_t depth;
+    float bias, max_dist;
+};
+// generate_shadow_rays! for one point light (`light`, host memory, passed on by value): slot i of d_out belongs to ray i
+void rc_launch_shadow_rays(rc_scene* s, const ShadowParams& q, const float light[3], uint64_t n, RcRay* d_out, hipStream_t stream);
 // visible[i * n_lights + l] = hit i is lit by light l: shadow-ray generation and any_hit for all hits x all lights in one traversal launch; n * n_lights < 2^32
-void rc_launch_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, uint32_t n_lights, float bias,
-                                 uint8_t* d_visible, hipStream_t stream);
+void rc_launch_shadow_visibility(rc_scene* s, const ShadowParams& q, uint64_t n, uint8_t* d_visible, hipStream_t stream);
 // Soft shadows: `samples` rays per (hit, light) toward Philox-sampled points of an area light.  The composed stage writes ray
 // (i * n_lights + l) * samples + s; the driver ACCUMULATES the visible samples into count[i * n_lights + l] in one traversal launch.
 // n * n_lights * samples < 2^32; n_lights, samples, depth < 2^16
-void rc_launch_soft_shadow_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
-                                uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base,
-                                float bias, RcRay* d_out, hipStream_t stream);
-void rc_launch_soft_shadow_visibility(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, const float* d_lights, const float* d_radii,
-                                      uint32_t n_lights, uint32_t samples, uint64_t seed, uint32_t depth, const uint32_t* d_path_in,
-                                      uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream);
+void rc_launch_soft_shadow_rays(rc_scene* s, const SoftShadowParams& q, uint64_t n, RcRay* d_out, hipStream_t stream);
+void rc_launch_soft_shadow_visibility(rc_scene* s, const SoftShadowParams& q, uint64_t n, uint32_t* d_count, hipStream_t stream);
 // Ambient occlusion: `samples` cosine-weighted rays of length max_dist over the hemisphere of every hit (Philox keyed by path, depth, s).  The
 // composed stage writes ray i * samples + s; the driver ACCUMULATES the visible samples into count[i] in one traversal launch.
 // n * samples < 2^32; samples, depth < 2^16; max_dist > 0
-void rc_launch_ao_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed, uint32_t depth,
-                       const uint32_t* d_path_in, uint64_t path_base, float bias, RcRay* d_out, hipStream_t stream);
-void rc_launch_ambient_occlusion(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
-                                 uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, uint32_t* d_count, hipStream_t stream);
+void rc_launch_ao_rays(rc_scene* s, const AoParams& q, uint64_t n, RcRay* d_out, hipStream_t stream);
+void rc_launch_ambient_occlusion(rc_scene* s, const AoParams& q, uint64_t n, uint32_t* d_count, hipStream_t stream);
 // Final gather: the ambient-occlusion driver's items and rays traced for the closest hit; ACCUMULATES x[meta - 1] of every sample's hit
 // (miss_value for a sample that escapes) into sum[i] (u64) and the escaped samples into open[i] (may be null).  Same limits; d_x: n_prims u32
-void rc_launch_final_gather(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
-                            uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, const uint32_t* d_x, uint32_t miss_value,
-                            uint64_t* d_sum, uint32_t* d_open, hipStream_t stream);
+void rc_launch_final_gather(rc_scene* s, const AoParams& q, uint64_t n, const uint32_t* d_x, uint32_t miss_value, uint64_t* d_sum, uint32_t* d_open, hipStream_t stream);
 // Diffuse (cosine-weighted) bounce rays, slot-aligned or gathered through d_src / *d_src_count (read on the device); n < 2^32, bounce < 2^16
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                            const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n, uint64_t seed, uint32_t bounce, float bias,

@@ -54,7 +54,7 @@ def demangle(names):
     if not tool or not names:
         return {n: n for n in names}
     res = subprocess.run([tool], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return {n: re.sub(r"\(anonymous namespace\)::", "", r)[:240] for n, r in zip(names, res)}  # (library kernels have names of several kB)
+    return {n: re.sub(r"\(anonymous namespace\)::", "", r)[:128] for n, r in zip(names, res)}  # (library kernels have names of several kB; the project's own fit)
 
 
 def figures(meta):
