@@ -1185,8 +1185,8 @@ void rc_expand_mesh(rc_scene* s, const float* d_verts, const uint32_t* d_indices
 }
 
 void rc_ensure_flat_attrs(rc_scene* s) {
-    if (s->flat_attrs_valid) return;
-    if (s->captured_deform)  // (the graph baked "no attribute array" in: its replays would leave the one built here stale)
+    if (s->state.flat_attrs_current()) return;
+    if (s->state.deform_captured())  // (the graph baked "no attribute array" in: its replays would leave the one built here stale)
         throw RcError(6, "shading attributes cannot be built while a graph that captured a geometry update may live: use rc_shading_attributes_device once before the capture, or release the graph (\"release_captures\")");
     rc_wait_async_mutations(s);  // (an asynchronous geometry update on a caller's stream may still be writing the primitives read below)
     s->flat_attrs.reserve(15 * (size_t)(s->n_flat_prims ? s->n_flat_prims : 1));
@@ -1198,7 +1198,7 @@ void rc_ensure_flat_attrs(rc_scene* s) {
     }
     RC_HIP(hipGetLastError());
     RC_HIP(hipStreamSynchronize(s->stream));  // later launches may run on a caller's stream
-    s->flat_attrs_valid = true;
+    s->state.flat_attrs_built();
 }
 
 static hipStream_t rc_utility_stream() {
@@ -1283,8 +1283,7 @@ void rc_build_tlas(rc_scene* s) {
         tn += s->blas[i].n_nodes; tp += s->blas[i].n_prims;
     }
     s->n_flat_nodes = tn; s->n_flat_prims = tp;
-    s->flat_attrs_valid = false;
-    s->vf_order_valid = false;
+    s->state.tlas_build_begun();
     s->flat_nodes.reserve((size_t)tn + 2 * (size_t)n + 1);  // + room for the TLAS copy behind the BLAS nodes
     s->flat_prims.reserve(tp ? tp : 1);
     s->d_descs.reserve(nb ? nb : 1);
@@ -1345,14 +1344,9 @@ void rc_build_tlas(rc_scene* s) {
     RC_HIP(hipMemsetAsync(s->blas_cull_bits.p, 0, sizeof(uint32_t) * (nb ? nb : 1), s->stream));
     if (nb && tp) hipLaunchKernelGGL(k_cull_radius, dim3(grid_for(tp)), dim3(kBlock), 0, s->stream, s->flat_prims.p, tp, s->d_descs.p, nb, s->blas_cull_bits.p);
     s->n_static_instances = n;
-    s->captured_update = false;
-    s->captured_refit = false;  // (a graph that captured a refit of the old arrays is dead: its addresses are gone)
-    s->captured_deform = false;
-    s->blas_bounds_stale = false;  // (rc_sync refreshed the host copies before this rebuild read them)
     for (auto& b : s->blas) b.root_on_device = false;
-    s->quality_armed = false;
+    s->state.tlas_built(n == 0);
     if (n == 0) {  // :969-977
-        s->bound_stale = false;
         s->n_tlas_nodes = 0;
         for (int k = 0; k < 3; ++k) { s->root_min[k] = INFINITY; s->root_max[k] = -INFINITY; }
         RC_HIP(hipStreamSynchronize(s->stream));
@@ -1378,7 +1372,7 @@ void rc_build_tlas(rc_scene* s) {
     per_instance_pass(s, s->stream, n, true, false);
     tlas_chain(s, s->stream, scene_bufs(s, n, grid_for(n), s->tlas_ranges), n);
     read_root_aabb(s, s->tlas_nodes.p, true, s->root_min, s->root_max);
-    s->bound_stale = false;
+    s->state.world_bound_read();
 }
 
 // refit_tlas! (src/instanced-bvh.jl:2197-2222): new transforms -> leaf AABBs -> bottom-up refit, in place
@@ -1389,13 +1383,13 @@ void rc_refit_tlas(rc_scene* s, bool from_device, bool recompute_inverse) {
     if (n == 0) return;
     if (from_device) {
         if (recompute_inverse) hipLaunchKernelGGL(k_update_inverses, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->d_instances.p, n);
-        s->host_instances_stale = true;
+        s->state.refit_from_device_begun();
     } else {
         RC_HIP(hipMemcpyAsync(s->d_instances.p, s->instances.data(), sizeof(RcInstanceDesc) * n, hipMemcpyHostToDevice, s->stream));
     }
     refit_chain(s, s->stream, scene_bufs(s, n, grid_for(n), s->tlas_ranges), n, true);
     read_root_aabb(s, s->tlas_nodes.p, true, s->root_min, s->root_max);
-    s->bound_stale = false;
+    s->state.world_bound_read();
 }
 
 // ---- the asynchronous update: everything on the caller's stream, nothing read back ------------------------------------------------------
@@ -1405,9 +1399,9 @@ static bool stream_capturing(hipStream_t st) {
     return cs == hipStreamCaptureStatusActive;
 }
 static void note_async_mutation(rc_scene* s, hipStream_t st) {
-    if (stream_capturing(st)) return;  // (replays are the caller's to wait for)
-    s->async_stream = st;
-    s->async_pending = true;
+    const bool capturing = stream_capturing(st);
+    if (!capturing) s->async_stream = st;
+    s->state.async_noted(capturing);
 }
 
 void rc_update_instances_async(rc_scene* s, uint32_t first, uint32_t m, const float* d_xforms, hipStream_t st) {
@@ -1417,7 +1411,7 @@ void rc_update_instances_async(rc_scene* s, uint32_t first, uint32_t m, const fl
                        (const uint32_t*)s->d_blas_nprims.p, (const uint32_t*)s->blas_cull_bits.p, (const uint32_t*)s->inst_leaf.p, s->inst_recs.p,
                        s->inst_cull.p, s->tlas_nodes.p, n);
     RC_HIP(hipGetLastError());
-    if (stream_capturing(st)) s->captured_update = true;
+    s->state.instances_updated_async(stream_capturing(st));
     note_async_mutation(s, st);
 }
 
@@ -1429,9 +1423,7 @@ void rc_refit_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
     if (n == 0) return;
     refit_chain(s, st, rebuild_bufs(s), n, per_instance);
     RC_HIP(hipGetLastError());
-    s->host_instances_stale = true;
-    s->bound_stale = true;
-    if (stream_capturing(st)) s->captured_refit = true;  // every replay moves the root box again: the host copy is never trusted while the graph may live
+    s->state.tlas_committed_async(stream_capturing(st));
     note_async_mutation(s, st);
 }
 
@@ -1470,9 +1462,7 @@ static void rebuild_launch(rc_scene* s, hipStream_t st, uint32_t n, int mode, do
 }
 static void after_async_commit(rc_scene* s, hipStream_t st) {
     RC_HIP(hipGetLastError());
-    s->host_instances_stale = true;
-    s->bound_stale = true;
-    if (stream_capturing(st)) s->captured_refit = true;  // (replays move the root box, as a captured refit's do)
+    s->state.tlas_committed_async(stream_capturing(st));
     note_async_mutation(s, st);
 }
 void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
@@ -1480,7 +1470,7 @@ void rc_rebuild_tlas_async(rc_scene* s, bool per_instance, hipStream_t st) {
     if (n == 0) return;
     if (s->rebuild.n != n) throw RcError(4, "rebuild scratch does not match the instance count");  // (reserved by every rebuilding rc_sync)
     if (per_instance) per_instance_pass(s, st, n, true, false);
-    rebuild_launch(s, st, n, s->quality_armed ? (int)kRecord : -1, 0.0);  // (armed: the baseline follows explicit rebuilds)
+    rebuild_launch(s, st, n, s->state.quality_is_armed() ? (int)kRecord : -1, 0.0);  // (armed: the baseline follows explicit rebuilds)
     after_async_commit(s, st);
 }
 
@@ -1491,11 +1481,11 @@ void rc_refit_or_rebuild_tlas_async(rc_scene* s, bool per_instance, double ratio
     const uint32_t n = (uint32_t)s->instances.size();
     if (n == 0) return;
     if (s->rebuild.n != n) throw RcError(4, "rebuild scratch does not match the instance count");
-    if (!s->quality_armed && stream_capturing(st))
+    if (!s->state.quality_is_armed() && stream_capturing(st))
         throw RcError(6, "the first rc_refit_or_rebuild_tlas_device_async after a rebuilding rc_sync records the tree's baseline cost and must run eagerly: call it once before capturing it");
     refit_chain(s, st, rebuild_bufs(s), n, per_instance);
-    rebuild_launch(s, st, n, s->quality_armed ? (int)kDecide : (int)kArm, ratio);
-    s->quality_armed = true;
+    rebuild_launch(s, st, n, s->state.quality_is_armed() ? (int)kDecide : (int)kArm, ratio);
+    s->state.quality_armed_now();
     after_async_commit(s, st);
 }
 
@@ -1504,7 +1494,7 @@ void rc_tlas_cost_async(rc_scene* s, double* d_cost, hipStream_t st) {
     if (n == 0) return;
     cost_pass(s, st, n, 1, d_cost, 0.0, kCostOnly, nullptr);
     RC_HIP(hipGetLastError());
-    if (!s->async_pending || s->async_stream == st) note_async_mutation(s, st);  // no mutation, but rc_scene_destroy waits for it like one (a flag, no event; with work pending on another stream that stream stays the one waited for: the header's LIFETIME note)
+    if (!s->state.async_work_pending() || s->async_stream == st) note_async_mutation(s, st);  // no mutation, but rc_scene_destroy waits for it like one (a flag, no event; with work pending on another stream that stream stays the one waited for: the header's LIFETIME note)
 }
 
 void rc_tlas_quality_read(rc_scene* s, RcTlasQuality* out) {
@@ -1517,7 +1507,7 @@ void rc_tlas_quality_read(rc_scene* s, RcTlasQuality* out) {
 // Host wait for the EAGER asynchronous updates and refits enqueued so far.  Replays of a graph that captured them are the caller's to
 // wait for (a graph can be launched on any stream): the readers below then re-read what the device holds.
 void rc_wait_async_mutations(rc_scene* s) {
-    if (!s->async_pending) return;
+    if (!s->state.async_work_pending()) return;
     RC_HIP(hipSetDevice(s->device));
     if (stream_capturing(s->async_stream))
         throw RcError(6, "the scene was updated asynchronously on a stream that is now being captured: its host-side state (world bound, instance mirror) is stale and cannot be refreshed during the capture");
@@ -1525,14 +1515,14 @@ void rc_wait_async_mutations(rc_scene* s) {
         (void)hipGetLastError();
         RC_HIP(hipDeviceSynchronize());
     }
-    s->async_pending = false;
+    s->state.async_waited();
 }
 
 void rc_ensure_world_bound(rc_scene* s, hipStream_t for_stream) {
-    if (!s->bound_stale && !s->captured_refit) return;
+    if (!s->state.world_bound_needs_read()) return;
     std::lock_guard<std::mutex> lk(s->launch_mu);  // queries are re-entrant: one of them refreshes, the others find it done (callers take no launch guard before this)
-    if (!s->bound_stale && !s->captured_refit) return;
-    if (s->n_tlas_nodes == 0) { s->bound_stale = false; return; }
+    if (!s->state.world_bound_needs_read()) return;
+    if (s->n_tlas_nodes == 0) { s->state.world_bound_read(); return; }
     if (for_stream && stream_capturing(for_stream))
         throw RcError(6, "stale world bound: the scene was refitted asynchronously (rc_refit_device_async) and this call lays its rays out from the world bound, which cannot be read back while the stream is being captured -- call rc_world_bound before the capture");
     RC_HIP(hipSetDevice(s->device));
@@ -1540,7 +1530,7 @@ void rc_ensure_world_bound(rc_scene* s, hipStream_t for_stream) {
     RcNode root;
     rc_copy_now(&root, s->tlas_nodes.p, sizeof(RcNode), hipMemcpyDeviceToHost);
     host_root_aabb(root, true, s->root_min, s->root_max);
-    s->bound_stale = false;
+    s->state.world_bound_read();
 }
 
 // ---- update!(tlas, handle, new_geometry) (src/instanced-bvh.jl:808-857) on the caller's stream: build_blas (:1376-1443) from a device soup,
@@ -1706,7 +1696,7 @@ void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_ver
     c.blas_nodes = b.nodes.p; c.flat_nodes = s->flat_nodes.p + hd.nodes_offset;
     c.blas_prims = b.prims.p; c.flat_prims = s->flat_prims.p + hd.primitives_offset;
     c.src_face = mesh ? b.src_face.p : nullptr;
-    c.flat_attrs = s->flat_attrs_valid ? s->flat_attrs.p + 15 * (size_t)hd.primitives_offset : nullptr;
+    c.flat_attrs = s->state.flat_attrs_current() ? s->flat_attrs.p + 15 * (size_t)hd.primitives_offset : nullptr;
     c.normals = b.has_attrs ? (d_mesh_normals ? d_mesh_normals : b.m_normals.p) : nullptr;
     c.uvs = b.has_uvs ? b.m_uvs.p : nullptr;
     c.indices = b.m_indices.p;
@@ -1723,8 +1713,7 @@ void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_ver
                        s->blas_cull_bits.p, (const uint32_t*)s->inst_leaf.p, s->inst_recs.p, s->inst_cull.p, s->tlas_nodes.p, ni);
     RC_HIP(hipGetLastError());
     b.root_on_device = true;
-    s->blas_bounds_stale = true;
-    if (capturing) s->captured_deform = true;
+    s->state.geometry_updated_async(capturing);
     note_async_mutation(s, st);
 }
 
@@ -1732,9 +1721,9 @@ void rc_update_geometry_async(rc_scene* s, uint32_t blas_idx, const float* d_ver
 // the geometries that were updated in place since, after a host wait for the eager updates.  While a graph that captured one may live, on
 // every use.
 void rc_ensure_blas_bounds(rc_scene* s) {
-    if (!s->blas_bounds_stale && !s->captured_deform) return;
+    if (!s->state.blas_bounds_need_read()) return;
     std::lock_guard<std::mutex> lk(s->launch_mu);  // exports are re-entrant: one of them refreshes, the others find it done (rc_ensure_world_bound)
-    if (!s->blas_bounds_stale && !s->captured_deform) return;
+    if (!s->state.blas_bounds_need_read()) return;
     RC_HIP(hipSetDevice(s->device));
     rc_wait_async_mutations(s);
     const size_t nb = std::min(s->descs.size(), s->blas.size());
@@ -1745,7 +1734,7 @@ void rc_ensure_blas_bounds(rc_scene* s) {
         if (!b.root_on_device) continue;  // (a geometry replaced on the host since holds the newer box)
         memcpy(b.root_min, dev[i].root_min, 12); memcpy(b.root_max, dev[i].root_max, 12);
         memcpy(s->descs[i].root_min, dev[i].root_min, 12); memcpy(s->descs[i].root_max, dev[i].root_max, 12);
-        if (!s->captured_deform) b.root_on_device = false;
+        if (!s->state.deform_captured()) b.root_on_device = false;
     }
-    s->blas_bounds_stale = false;
+    s->state.blas_bounds_read();
 }

@@ -124,29 +124,23 @@ void compact_instances(rc_scene* s) {
 // The host mirror of tlas.instances is authoritative except after a device-side rewrite (rc_refit_device): pull it back
 // before anything reads or edits it.
 void sync_host_instances(rc_scene* s) {
-    // (captured_update: replays of a graph rewrite the descriptors at times the host does not see, so the mirror is pulled on every use --
-    // unless it holds edits of its own that the next rc_sync has yet to upload)
-    if (!s->host_instances_stale && !(s->captured_update && s->has_static && !s->mirror_edited)) return;
+    if (!s->state.mirror_needs_pull()) return;
     RC_HIP(hipSetDevice(s->device));
     rc_wait_async_mutations(s);
     RC_HIP(hipStreamSynchronize(s->stream));
     if (!s->instances.empty())
         rc_copy_now(s->instances.data(), s->d_instances.p, sizeof(RcInstanceDesc) * s->instances.size(), hipMemcpyDeviceToHost);
-    s->host_instances_stale = false;  // (device_dirty stays: a read of the mirror is no mutation, the update still waits for its refit)
+    s->state.mirror_pulled();
 }
 
 void require_synced(rc_scene* s) {
-    if (!s->has_static || s->dirty || s->transforms_dirty)
+    if (!s->state.synced())
         throw RcError(RC_ERR_NOT_SYNCED, "scene has pending mutations: call rc_sync before tracing (Adapt.adapt does this per dispatch)");
 }
 // The asynchronous device-side mutations write the arrays where the last rc_sync put them: nothing the host holds may be pending.
 void require_device_resident(rc_scene* s, const char* message) {
-    if (!s->has_static || s->dirty || s->mirror_edited) throw RcError(RC_ERR_NOT_SYNCED, message);
+    if (!s->state.device_resident()) throw RcError(RC_ERR_NOT_SYNCED, message);
 }
-// A device-side update was enqueued: the DEVICE descriptors are newer than the mirror and than the last refit (rc_internal.h)
-void note_device_update(rc_scene* s) { s->host_instances_stale = s->device_dirty = s->transforms_dirty = true; }
-// A device-side refit / rebuild was enqueued: it commits the updates so far
-void note_device_commit(rc_scene* s) { s->device_dirty = s->transforms_dirty = false; }
 // The host-buffer queries run on streams of the library's own, which the caller cannot order behind an asynchronous update / refit it
 // enqueued on a stream of its own: they wait for it here (one flag test when nothing is pending).
 void require_synced_host(rc_scene* s) {
@@ -318,7 +312,7 @@ int rc_scene_destroy(rc_scene* s) {
         if (s->slots[i].recorded && s->slots[i].t1) (void)hipEventSynchronize(s->slots[i].t1);
     for (auto& c : s->call_ctx) if (c && c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto a : s->aux_streams) if (a) (void)hipStreamSynchronize(a);
-    if (s->async_pending) (void)hipStreamSynchronize(s->async_stream);  // an asynchronous update / refit nobody has waited for yet
+    if (s->state.async_work_pending()) (void)hipStreamSynchronize(s->async_stream);  // an asynchronous update / refit nobody has waited for yet
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     (void)hipGetLastError();
     if (s->ev0) (void)hipEventDestroy(s->ev0);
@@ -453,7 +447,7 @@ int rc_update_geometry_mesh(rc_scene* s, uint32_t handle, const float* verts, co
         Blas b;
         build_mesh_blas(s, verts, normals, uvs, nv, indices, nf, face_meta, false, b);
         s->blas[blas_idx - 1] = std::move(b);
-        s->dirty = true;
+        s->state.structural_edit();
     });
 }
 
@@ -490,7 +484,6 @@ int rc_add_instances_with_inverse(rc_scene* s, uint32_t blas_id, const float* xf
         sync_host_instances(s);
         if (blas_id >= s->blas.size()) throw RcError(RC_ERR_INVALID_ARGUMENT, "blas_id out of range");
         HandleRange r{(uint32_t)s->instances.size(), m};
-        s->mirror_edited = true;
         for (uint32_t i = 0; i < m; ++i) {  // :670-674
             RcInstanceDesc d;
             d.blas_index = blas_id + 1;
@@ -503,7 +496,7 @@ int rc_add_instances_with_inverse(rc_scene* s, uint32_t blas_id, const float* xf
         }
         uint32_t h = s->next_handle_id++;  // append_instances_with_handle! (:612-623)
         s->handle_to_range[h] = r;
-        s->dirty = true;
+        s->state.instances_pushed();
         if (handle) *handle = h;
     });
 }
@@ -519,13 +512,12 @@ int rc_update_transforms(rc_scene* s, uint32_t handle, const float* xforms, uint
         HandleRange& r = live_range(s, handle);
         if (m != r.count) throw RcError(RC_ERR_INVALID_ARGUMENT, "Transform count (" + std::to_string(m) + ") != instance count (" + std::to_string(r.count) + ")");
         if (!xforms) throw RcError(RC_ERR_INVALID_ARGUMENT, "xforms is NULL");
-        s->mirror_edited = true;
         for (uint32_t i = 0; i < m; ++i) {  // update_instance_transforms_offset_kernel! (src/instanced-bvh-kernels.jl:455-476)
             RcInstanceDesc& d = s->instances[r.first + i];
             memcpy(d.transform, xforms + 12 * (size_t)i, 48);
             rc_mat3x4_inverse(d.transform, d.inv_transform);
         }
-        s->transforms_dirty = true;
+        s->state.transforms_edited();
     });
 }
 
@@ -541,7 +533,7 @@ int rc_update_geometry(rc_scene* s, uint32_t handle, const float* verts, const u
         Blas b;
         build_from_device_faces(s, s->vert_stage.p, meta ? s->meta_stage.p : nullptr, n, b);
         s->blas[blas_idx - 1] = std::move(b);
-        s->dirty = true;
+        s->state.structural_edit();
     });
 }
 
@@ -550,7 +542,7 @@ int rc_delete(rc_scene* s, uint32_t handle, int* deleted) {
     int d = 0;
     if (s->handle_to_range.count(handle) && !s->deleted_handles.count(handle)) {  // :690-699
         s->deleted_handles.insert(handle);
-        s->dirty = true;
+        s->state.structural_edit();
         d = 1;
     }
     if (deleted) *deleted = d;
@@ -585,34 +577,26 @@ int rc_get_instances(rc_scene* s, uint32_t handle, rc_instance_desc* out, uint32
 int rc_sync(rc_scene* s, int* action) {
     if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
     if (action) *action = 0;
-    if (!s->dirty && !s->transforms_dirty && s->has_static) return RC_OK;  // :898-900, no device sync
+    const RcSyncPlan plan = s->state.sync_plan();
+    if (plan == RcSyncPlan::Noop) return RC_OK;  // :898-900, no device sync
     return guarded([&] {
         use_device(s);
-        if (s->has_static && !s->dirty && s->device_dirty && s->host_instances_stale) {
-            // rc_update_transforms_device since the last refit: the device descriptors are the new ones and the mirror is stale -- refit from
-            // them (the per-instance passes run again: they reproduce what the update kernel wrote); the mirror is refreshed when someone reads it
+        if (plan == RcSyncPlan::RefitFromDevice) {
+            // (the per-instance passes run again: they reproduce what the update kernel wrote; the mirror is refreshed when someone reads it)
             rc_wait_async_mutations(s);
             rc_refit_tlas(s, true, false);
-            note_device_commit(s);
-            if (action) *action = 1;
-            return;
+        } else {
+            sync_host_instances(s);
+            if (plan == RcSyncPlan::Rebuild) {  // rebuild_bvh! + rebuild_static_tlas! (:902-905, :911-915)
+                rc_ensure_blas_bounds(s);  // (root boxes an asynchronous geometry update left on the device)
+                if (!s->deleted_handles.empty()) compact_instances(s);
+                rc_build_tlas(s);
+            } else {  // refit_tlas! (:906-911): in place, the adapted buffers keep their identity
+                rc_refit_tlas(s);
+            }
         }
-        sync_host_instances(s);
-        if (s->dirty || !s->has_static) {  // rebuild_bvh! + rebuild_static_tlas! (:902-905, :911-915)
-            rc_ensure_blas_bounds(s);  // (root boxes an asynchronous geometry update left on the device)
-            if (!s->deleted_handles.empty()) compact_instances(s);
-            rc_build_tlas(s);
-            s->dirty = false;
-            s->transforms_dirty = false;
-            s->has_static = true;
-            if (action) *action = 2;
-        } else {  // refit_tlas! (:906-911): in place, the adapted buffers keep their identity
-            rc_refit_tlas(s);
-            s->transforms_dirty = false;
-            if (action) *action = 1;
-        }
-        s->mirror_edited = false;  // the device holds what the mirror holds
-        s->device_dirty = false;
+        s->state.synced_by(plan);
+        if (action) *action = plan == RcSyncPlan::Rebuild ? 2 : 1;
     });
 }
 
@@ -626,15 +610,15 @@ int rc_counts(rc_scene* s, uint32_t* n_live, uint32_t* n_total, uint32_t* n_geom
     if (n_live) *n_live = (uint32_t)s->instances.size() - pending;  // :2391-2398
     if (n_total) *n_total = (uint32_t)s->instances.size();
     if (n_geom) *n_geom = (uint32_t)s->blas.size();
-    if (n_prims) *n_prims = s->has_static ? s->n_flat_prims : 0;
-    if (n_tlas_nodes) *n_tlas_nodes = s->has_static ? s->n_tlas_nodes : 0;
-    if (n_blas_nodes) *n_blas_nodes = s->has_static ? s->n_flat_nodes : 0;
+    if (n_prims) *n_prims = s->state.tlas_present() ? s->n_flat_prims : 0;
+    if (n_tlas_nodes) *n_tlas_nodes = s->state.tlas_present() ? s->n_tlas_nodes : 0;
+    if (n_blas_nodes) *n_blas_nodes = s->state.tlas_present() ? s->n_flat_nodes : 0;
     return RC_OK;
 }
 
 int rc_world_bound(rc_scene* s, float out[6]) {
     if (!s || !out) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (s->bound_stale || s->captured_refit) {  // after rc_refit_device_async: wait for the refit, read the root back
+    if (s->state.world_bound_needs_read()) {  // after rc_refit_device_async: wait for the refit, read the root back
         const int rc = guarded([&] { rc_ensure_world_bound(s); });
         if (rc != RC_OK) return rc;
     }
@@ -1191,7 +1175,7 @@ int rc_scene_load(int device, const char* path, rc_scene** out) {
                 });
             }
         }
-        s->dirty = true;  // the TLAS and the flat arrays are rebuilt by the next rc_sync
+        s->state.structural_edit();  // the TLAS and the flat arrays are rebuilt by the next rc_sync
     });
     if (rc != RC_OK) { rc_scene_destroy(s); return rc; }
     *out = s;
@@ -1234,7 +1218,7 @@ int rc_update_transforms_device(rc_scene* s, uint32_t handle, const float* d_xfo
         require_device_resident(s, "rc_update_transforms_device writes the descriptors where the last rc_sync put them: the scene has pending host-side mutations, call rc_sync first");
         use_device(s);
         rc_update_instances_async(s, r.first, m, d_xforms, (hipStream_t)stream);
-        note_device_update(s);
+        s->state.device_update_enqueued();
     });
 }
 
@@ -1245,10 +1229,8 @@ static int commit_device_async(rc_scene* s, void* stream, const char* not_synced
     return guarded([&] {
         require_device_resident(s, not_synced);
         use_device(s);
-        // device_dirty: every change since the last refit came through rc_update_transforms_device, whose kernel has already written the
-        // per-instance data; otherwise the descriptors were rewritten through rc_instance_buffer_device and it is derived from them here
-        commit(s, !s->device_dirty, (hipStream_t)stream);
-        note_device_commit(s);
+        commit(s, s->state.commit_needs_per_instance_pass(), (hipStream_t)stream);
+        s->state.device_commit_enqueued();
     });
 }
 int rc_refit_device_async(rc_scene* s, void* stream) {
@@ -1266,8 +1248,8 @@ int rc_refit_or_rebuild_tlas_device_async(rc_scene* s, double ratio, void* strea
     return guarded([&] {
         require_device_resident(s, "scene has pending host-side mutations: call rc_sync (rc_refit_or_rebuild_tlas_device_async commits device-side updates only)");
         use_device(s);
-        rc_refit_or_rebuild_tlas_async(s, !s->device_dirty, ratio, (hipStream_t)stream);
-        note_device_commit(s);
+        rc_refit_or_rebuild_tlas_async(s, s->state.commit_needs_per_instance_pass(), ratio, (hipStream_t)stream);
+        s->state.device_commit_enqueued();
     });
 }
 // The cost the decision is made from, for a caller's own policy: one f64 to caller-owned device memory, on `stream`
@@ -1288,7 +1270,7 @@ int rc_tlas_quality(rc_scene* s, rc_tlas_quality_info* out) {
         rc_tlas_quality_read(s, &q);
         out->cost = q.cost; out->cost_built = q.cost_built;
         out->evaluations = q.evaluations; out->rebuilds = q.rebuilds; out->last_rebuilt = q.last_rebuilt;
-        out->armed = s->quality_armed ? 1u : 0u;
+        out->armed = s->state.quality_is_armed() ? 1u : 0u;
     });
 }
 
@@ -1310,8 +1292,8 @@ static void update_geometry_device(rc_scene* s, uint32_t handle, const float* d_
     use_device(s);
     rc_update_geometry_async(s, blas_idx, d_verts, d_meta, n, d_mesh_verts, d_mesh_normals, (hipStream_t)stream);
     b.n_nodes4 = 0;  // the BLAS4 was collapsed from the old tree
-    s->vf_order_valid = false;
-    note_device_update(s);
+    s->state.vf_order_invalidated();
+    s->state.device_update_enqueued();
 }
 
 int rc_update_geometry_device_async(rc_scene* s, uint32_t handle, const float* d_verts, const uint32_t* d_meta, uint32_t n, void* stream) {
@@ -1359,9 +1341,7 @@ int rc_set_option(rc_scene* s, const char* name, int64_t value) {
             std::lock_guard<std::mutex> g(s->launch_mu);
             s->capture_slots.clear();
             s->last_capture = -1;
-            if (s->captured_refit) { s->captured_refit = false; s->bound_stale = true; }  // (no replay can move the root box any more: one more read-back settles it)
-            if (s->captured_deform) { s->captured_deform = false; s->blas_bounds_stale = true; s->vf_order_valid = false; }  // (one more read-back / sort settles them)
-            if (s->captured_update) { s->captured_update = false; s->host_instances_stale = s->host_instances_stale || !s->mirror_edited; }
+            s->state.captures_released();
         }
     }
     else if (k == "release_capture") {  // ONE captured launch handed back: value = the token option "last_capture_token" returned right after that capture

@@ -1425,7 +1425,7 @@ void rc_launch_illumination_points(rc_scene* s, const RcRay* d_sources, uint32_t
 
 // RC_VF_SOURCES_BY_METADATA: the flat primitives' indices sorted by (metadata, index) -- and the sorted metadata themselves on the host --
 // cached until the next rebuild or geometry update.  Built on the scene's own stream, which also owns the sort scratch, behind every EAGER
-// asynchronous update (host wait, as the host-buffer queries do).  captured_deform: a graph that captured a geometry update re-sorts the
+// asynchronous update (host wait, as the host-buffer queries do).  A graph that captured a geometry update re-sorts the
 // primitives on every replay, at times the library does not see -- the order is rebuilt on every use, like the root boxes
 // (rc_ensure_blas_bounds); the caller has waited for the replay (raycore_mi355x.h).  for_stream: the stream the order is wanted for; while it
 // is being captured nothing can be sorted, read back or waited for.
@@ -1433,10 +1433,10 @@ void rc_launch_illumination_points(rc_scene* s, const RcRay* d_sources, uint32_t
 // the same words before, during and after the copy unless the primitives moved -- and then its caller had to wait for it first anyway.
 void rc_ensure_vf_order(rc_scene* s, hipStream_t for_stream) {
     std::lock_guard<std::mutex> g(s->launch_mu);
-    if (s->vf_order_valid && !s->captured_deform) return;
+    if (s->state.vf_order_current()) return;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (for_stream && hipStreamIsCapturing(for_stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive)
-        throw RcError(6, s->captured_deform
+        throw RcError(6, s->state.deform_captured()
                              ? "stale view-factor source order: a graph that captured rc_update_geometry_device_async may have re-sorted the primitives, and the order cannot be rebuilt while the stream is being captured -- release the graph (\"release_captures\") or address the sources by primitive"
                              : "stale view-factor source order: it cannot be built while the stream is being captured -- call rc_view_factors_device with RC_VF_SOURCES_BY_METADATA once before the capture");
     (void)hipGetLastError();
@@ -1454,7 +1454,7 @@ void rc_ensure_vf_order(rc_scene* s, hipStream_t for_stream) {
         RC_HIP(hipMemcpyAsync(s->vf_meta_sorted.data(), s->keys_b.p, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, s->stream));
         RC_HIP(hipStreamSynchronize(s->stream));  // the launches that read the order run on other streams
     }
-    s->vf_order_valid = true;
+    s->state.vf_order_built();
 }
 void rc_vf_source_range(rc_scene* s, uint32_t row_begin, uint32_t row_end, uint32_t& pos_begin, uint32_t& pos_end) {
     const auto& m = s->vf_meta_sorted;  // row r <=> metadata r + 1

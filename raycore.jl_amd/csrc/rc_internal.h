@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "rc_device.h"
+#include "rc_scene_state.h"
 #include "rc_stream_slots.h"
 
 struct RcError : std::runtime_error {
@@ -210,28 +211,8 @@ struct rc_scene {
     std::map<uint32_t, HandleRange> handle_to_range;
     std::set<uint32_t> deleted_handles;
     uint32_t next_handle_id = 1;
-    bool dirty = true, transforms_dirty = false, has_static = false;
-    bool host_instances_stale = false;  // descriptors were rewritten on the device (rc_instance_buffer_device + rc_refit_device)
-    // ---- host state of the mutable scene.  Who sets / who clears / who refuses:
-    //  dirty             set: push, delete, geometry update, load.        cleared: rebuilding rc_sync.          refused while set: every query, rc_update_transforms_device, rc_refit_device_async
-    //  transforms_dirty  set: rc_update_transforms(_device).              cleared: rc_sync, rc_refit_device_async, rc_rebuild_tlas_device_async.  refused while set: every query (RC_ERR_NOT_SYNCED)
-    //  mirror_edited     set: push, rc_update_transforms (the host mirror holds edits the device lacks).  cleared: rc_sync (upload).
-    //                    refused while set: rc_update_transforms_device, rc_refit_device_async; the mirror is never pulled from the device
-    //  device_dirty      set: rc_update_transforms_device (the DEVICE descriptors are newer than the last refit; the update kernel has written the
-    //                    per-instance data).  cleared: rc_refit_device_async, rc_rebuild_tlas_device_async, rc_sync.  Survives a pull of the mirror (a read is no mutation).
-    //                    rc_sync with device_dirty && host_instances_stale refits from the device; otherwise the mirror equals the device and is uploaded
-    //  host_instances_stale  set: rc_refit_device, rc_update_transforms_device, rc_refit_device_async.  cleared: sync_host_instances (pull), which every
-    //                    reader / editor of the mirror calls first.  Implies !mirror_edited
-    //  bound_stale       set: rc_refit_device_async, rc_rebuild_tlas_device_async.  cleared: rc_ensure_world_bound (read-back), rc_sync.  While set, a driver that needs the bound
-    //                    fails on a capturing stream
-    //  captured_update / captured_refit  set: the call was captured into a graph.  cleared: rebuilding rc_sync, option "release_captures".  While set,
-    //                    the mirror (unless mirror_edited) / the bound are re-read from the device on every use: replays happen unseen
-    //  async_pending + async_stream  set: an EAGER update / refit was enqueued there.  cleared: rc_wait_async_mutations (stream synchronise), which the
-    //                    host-buffer queries, the mirror pull, the bound read-back, rc_sync, rc_refit_device and rc_scene_destroy call first
-    bool mirror_edited = false, device_dirty = false;
-    bool bound_stale = false, captured_update = false, captured_refit = false;
-    bool async_pending = false;
-    hipStream_t async_stream = nullptr;
+    RcSceneState state;  // the flags every entry point consults, and their transitions: rc_scene_state.h
+    hipStream_t async_stream = nullptr;  // where the eager asynchronous call that state.async_work_pending() speaks of was enqueued
 
     // StaticTLAS (src/instanced-bvh.jl:155-168): the adapted form owned by rc_sync
     DevBuf<RcNode> tlas_nodes;
@@ -266,14 +247,10 @@ struct rc_scene {
         std::map<uint32_t, size_t> scan_bytes, sort_bytes;  // per item count, queried by eager calls
     } deform;
     // state of rc_refit_or_rebuild_tlas_async: an RcTlasQuality, then 2 x kQualityMaxBlocks partial sums.  Reserved, zeroed and disarmed by every
-    // rebuilding rc_sync (rc_build_tlas), beside the rebuild scratch.  quality_armed: the block's cost_built describes the tree the device
-    // holds -- set by the first rc_refit_or_rebuild_tlas_async after such a sync (eager: refit, unconditional rebuild, record); while set,
-    // rc_rebuild_tlas_async appends the record step
+    // rebuilding rc_sync (rc_build_tlas), beside the rebuild scratch.  Armed (state.quality_is_armed()): the block's cost_built describes the
+    // tree the device holds -- by the first rc_refit_or_rebuild_tlas_async after such a sync (eager: refit, unconditional rebuild, record);
+    // while armed, rc_rebuild_tlas_async appends the record step
     DevBuf<double> quality;
-    bool quality_armed = false;
-    // blas_bounds_stale  set: rc_update_geometry_async (the root boxes in d_descs are newer than descs / Blas::root_min,max).  cleared: rc_ensure_blas_bounds
-    //                    (read-back), rebuilding rc_sync.  captured_deform: the call was captured -- re-read on every use, like captured_refit
-    bool blas_bounds_stale = false, captured_deform = false;
     DevBuf<uint32_t> inst_leaf;        // instance -> sorted position (1-based) of its TLAS leaf: topology only, built by rc_build_tlas for k_update_instances
     DevBuf<uint32_t> tlas_remap;       // same for the TLAS's internal nodes (top levels too large for the full LDS kernels), kept for refits
     uint32_t tlas_top_k = 0;
@@ -375,10 +352,8 @@ struct rc_scene {
     DevBuf<unsigned long long> c4_counts, c4_offsets;
     DevBuf<uint32_t> slot_face;       // rc_add_mesh: source face of every compacted slot
     DevBuf<float> flat_attrs;         // 15 floats per flat primitive (normals 9, uv 6), built on demand after a rebuild
-    bool flat_attrs_valid = false;
     DevBuf<uint32_t> vf_order;        // flat primitive indices by ascending metadata (RC_VF_SOURCES_BY_METADATA), built on demand after a rebuild
     std::vector<uint32_t> vf_meta_sorted;  // the metadata in that order (host): which source positions fall into a range of matrix rows
-    bool vf_order_valid = false;
     DevBuf<uint32_t> compact_flags, compact_pos;  // rc_compact_hits scratch
     DevBuf<unsigned char> compact_tmp;
     DevBuf<uint32_t> collide_counts;  // collide_instances' per-leaf counts / prefix sums (the reference's `cache`)
@@ -506,7 +481,7 @@ void rc_note_stage_launch(rc_scene* s, hipStream_t stream);  // after a kernel o
 void rc_timing_fixed(rc_scene* s, float ms);
 float rc_timing_read(rc_scene* s);  // the calling thread's latest timed operation on the scene, else the scene's latest
 uint32_t rc_grid_blocks(rc_scene* s, uint64_t n_items, int block, int64_t per_cu);  // the grid rule of the persistent kernels (per_cu: TraceShape::kBlocksPerCu, rc_traverse_core.h)
-void rc_ensure_vf_order(rc_scene* s, hipStream_t for_stream = nullptr);  // builds vf_order / vf_meta_sorted if the scene has been rebuilt or its geometry updated since (captured_deform: on every use)
+void rc_ensure_vf_order(rc_scene* s, hipStream_t for_stream = nullptr);  // builds vf_order / vf_meta_sorted if the scene has been rebuilt or its geometry updated since (while a graph that captured a geometry update may live: on every use)
 void rc_vf_source_range(rc_scene* s, uint32_t row_begin, uint32_t row_end, uint32_t& pos_begin, uint32_t& pos_end);  // positions in the metadata order whose metadata - 1 is in [row_begin, row_end)
 // rc_multi.hip
 void rc_launch_vf_totals(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin,

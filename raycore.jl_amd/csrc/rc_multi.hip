@@ -317,7 +317,7 @@ void check_same_geometry(rc_scene* const* scenes, int n) {
     for (int g = 0; g < n; ++g) {
         rc_scene* s = scenes[g];
         if (!s) throw RcError(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
-        if (!s->has_static || s->dirty || s->transforms_dirty) throw RcError(RC_ERR_NOT_SYNCED, "scene has pending mutations: call rc_sync first");
+        if (!s->state.synced()) throw RcError(RC_ERR_NOT_SYNCED, "scene has pending mutations: call rc_sync first");
         rc_wait_async_mutations(s);  // the multi-device calls are host-buffer queries on the scenes' own streams
         rc_ensure_world_bound(s);    // (a replica refitted asynchronously: compare its current bound)
         if (s->n_flat_prims != scenes[0]->n_flat_prims || s->n_flat_nodes != scenes[0]->n_flat_nodes || s->n_static_instances != scenes[0]->n_static_instances ||
