@@ -33,7 +33,7 @@ def main():
     import raycore_jl_amd as rc
     from oracle import pyoracle
     from helpers import build_oracle, build_product
-    from test_gpu_view_factors_host import room_cfg
+    from scene_kit import room_cfg
 
     assert rc.device_count() > 0, "no GPU visible: the product has no CPU fallback"
     fake = None

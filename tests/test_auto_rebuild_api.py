@@ -8,30 +8,15 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import ROOT, header, julia_text, prototype
+from api_kit import rc  # noqa: F401
+
 PROTOS = {
     "rc_tlas_cost_device": (["rc_scene*", "double*", "void*"], [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rc_refit_or_rebuild_tlas_device_async": (["rc_scene*", "double", "void*"], [C.c_void_p, C.c_double, C.c_void_p]),
     "rc_tlas_quality": (["rc_scene*", "rc_tlas_quality_info*"], [C.c_void_p, C.c_void_p]),
 }
 RC_ERR_INVALID_ARGUMENT, RC_ERR_NO_DEVICE = 1, 3
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
-
-
-def prototype(name):
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert m, f"{name} is not declared in the header"
-    return [" ".join(a.split()[:-1]) for a in m.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", sorted(PROTOS))
@@ -82,7 +67,7 @@ def test_python_surface(rc):
 
 
 def test_julia_binding_has_the_methods():
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     for name in PROTOS:
         assert ":" + name in text
     assert re.search(r"ccall\(\(:rc_refit_or_rebuild_tlas_device_async, LIB\), Cint, \(Ptr\{Cvoid\}, Cdouble, Ptr\{Cvoid\}\)", text)

@@ -6,6 +6,8 @@ import subprocess
 
 import pytest
 
+from api_kit import header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -18,7 +20,7 @@ def rc():
 
 
 def header_symbols():
-    text = open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
+    text = header()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(rc_[a-z0-9_]+)\s*\(", text)))
 

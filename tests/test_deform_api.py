@@ -3,34 +3,18 @@ bindings match the header's prototypes, the library exports them, the Python and
 the same argument checks as everything else."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import header, julia_text, prototype
+from api_kit import rc  # noqa: F401
+
 C_TO_CTYPES = {"rc_scene*": C.c_void_p, "void*": C.c_void_p, "const float*": C.c_void_p, "const uint32_t*": C.c_void_p, "uint32_t": C.c_uint32}
 CALLS = {
     "rc_update_geometry_device_async": ["rc_scene*", "uint32_t", "const float*", "const uint32_t*", "uint32_t", "void*"],
     "rc_update_mesh_vertices_device_async": ["rc_scene*", "uint32_t", "const float*", "const float*", "uint32_t", "void*"],
 }
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
-
-
-def prototype(name):
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert m, f"{name} is not declared in the header"
-    return [" ".join(a.split()[:-1]) for a in m.group(1).split(",")]  # the types, parameter names dropped
 
 
 @pytest.mark.parametrize("name", sorted(CALLS))
@@ -77,7 +61,7 @@ def test_python_surface(rc):
 
 
 def test_julia_binding_has_the_methods(rc):
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     for name in CALLS:
         assert ":" + name in text
     assert re.search(r"Raycore\.update!\(t::MI355XTLAS, h(andle)?(::TLASHandle)?, d_verts::Ptr\{Cfloat\}, n(::Integer)?, stream::Ptr\{Cvoid\}", text)

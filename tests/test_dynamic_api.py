@@ -2,28 +2,14 @@
 header's prototypes, the wavefront frame takes `dynamic`, and without a GPU the new methods sit behind RC_ERR_NO_DEVICE like everything else."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import julia_text, prototype
+from api_kit import rc  # noqa: F401
 
 C_TO_CTYPES = {"rc_scene*": C.c_void_p, "uint32_t": C.c_uint32, "const float*": C.c_void_p, "void*": C.c_void_p}
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def prototype(name):
-    text = open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert m, f"{name} is not declared in the header"
-    return [" ".join(a.split()[:-1]) for a in m.group(1).split(",")]  # the types, parameter names dropped
 
 
 @pytest.mark.parametrize("name, c_args", [
@@ -51,7 +37,7 @@ def test_python_surface(rc):
 
 
 def test_julia_binding_has_the_device_method(rc):
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     assert re.search(r"function Raycore\.update_transforms!\(t::MI355XTLAS, h::TLASHandle, d_transforms::Ptr\{Float32\}", text)
     assert ":rc_update_transforms_device" in text and ":rc_refit_device_async" in text
 

@@ -2,16 +2,7 @@
 mesh whose attributes have their own index sets becomes a single-index mesh; merged vertices are numbered by first appearance."""
 import numpy as np
 
-
-def cube():
-    p = np.array([[x, y, z] for x in (0, 1) for y in (0, 1) for z in (0, 1)], np.float32)        # 8 corners, index = 4x + 2y + z
-    quads = [(0, 1, 3, 2, (-1, 0, 0)), (4, 6, 7, 5, (1, 0, 0)), (0, 4, 5, 1, (0, -1, 0)), (2, 3, 7, 6, (0, 1, 0)), (0, 2, 6, 4, (0, 0, -1)), (1, 5, 7, 3, (0, 0, 1))]
-    pf, nf, normals = [], [], []
-    for k, (a, b, c, d, n) in enumerate(quads):
-        normals.append(n)
-        pf += [(a, b, c), (a, c, d)]
-        nf += [(k, k, k), (k, k, k)]
-    return p, np.array(pf), np.array(normals, np.float32), np.array(nf)
+from scene_kit import cube
 
 
 def test_cube_with_per_face_normals_and_per_face_metadata():

@@ -11,23 +11,15 @@ import re
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import ROOT, header, julia_text
+from api_kit import rc  # noqa: F401
+
 NAME = "rc_final_gather_device"
 ARGS = ["rc_scene*", "const rc_ray*", "const rc_hit*", "uint64_t", "uint32_t", "float", "uint64_t", "uint32_t", "const uint32_t*", "uint64_t", "float",
         "const uint32_t*", "uint32_t", "uint64_t*", "uint32_t*", "void*"]
 CTYPES = {"uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": C.c_float}
 JL_ARGS = ["Ptr{Cvoid}", "Ptr{RTRay}", "Ptr{RTHitResult}", "UInt64", "UInt32", "Cfloat", "UInt64", "UInt32", "Ptr{UInt32}", "UInt64", "Cfloat", "Ptr{UInt32}",
            "UInt32", "Ptr{UInt64}", "Ptr{UInt32}", "Ptr{Cvoid}"]
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
 
 
 def test_symbol_matches_the_header(rc):
@@ -79,7 +71,7 @@ def test_python_surface(rc):
 
 
 def test_julia_binding_and_integration_line():
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     m = re.search(r"ccall\(\(:" + NAME + r", LIB\), Cint,\s*\(([^)]*)\)", text)
     assert m, f"no ccall of {NAME}"
     assert [t.strip() for t in m.group(1).split(",")] == JL_ARGS

@@ -7,6 +7,7 @@ import pytest
 import ao_model as am
 import gather_model as gm
 from helpers import build_oracle
+from scene_kit import distinct_x
 
 BIAS = 1e-3
 SEED = 0xA0
@@ -29,10 +30,6 @@ def world(oracle):
         for a in t:
             a.setflags(write=False)
     return o, rays, hits, lit, tables
-
-
-def distinct_x(n):
-    return (np.arange(1, n + 1, dtype=np.uint64) * np.uint64(2654435761) % np.uint64(1 << 32)).astype(np.uint32)
 
 
 @pytest.mark.parametrize("max_dist", DISTANCES)

@@ -5,15 +5,10 @@ import os
 import numpy as np
 import pytest
 
+from api_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
 
 
 def cfg_c1(rc):

@@ -15,7 +15,10 @@ import pytest
 
 import ao_model as am
 import bounce_model as bm
+from gpu_kit import POISON, check_words, dev, poisoned, words_of, zeroed
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_rays_equal, build_oracle, build_product
+from worlds import C3World, three_shapes
 
 pytestmark = pytest.mark.gpu
 
@@ -24,49 +27,16 @@ N_RAYS = 63_997  # 320 x 200 less three: n * S ends inside a 128-item chunk for 
 SEED = 0xA0
 S_MAX = 5
 DISTANCES = (np.inf, 1.0)
-POISON = 0xAB
-GUARD = 256      # poisoned bytes behind every output: nothing may be written past it
 DUMMY = np.array([0, 0, 0, 0, 0, 0, 1, 0], np.float32).view(np.uint32)
 
 
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def poisoned(nbytes):
-    import torch
-    return torch.full((nbytes + GUARD,), POISON, dtype=torch.uint8, device="cuda")
-
-
-def count_buffer(n_counts):
-    """n_counts zeroed u32 followed by the poisoned guard (the call accumulates: the caller zeroes)."""
-    out = poisoned(n_counts * 4)
-    out[:n_counts * 4] = 0
-    return out
-
-
-class World:
+class World(C3World):
     def __init__(self, rc, oracle, lattice, kernel=None):
-        self.cfg = rc.scenes.config_c3(lon=16, bands=9, lattice=lattice)
-        self.t, self.o = build_product(rc, self.cfg), build_oracle(oracle, self.cfg)
-        if kernel is not None:
-            self.t.set_option("kernel", kernel)
-        self.rays = rc.scenes.c3_primary_rays(self.cfg, 320, 200)[:N_RAYS]
-        self.hits = self.o.trace(self.rays, nthreads=16)
-        self.lit = self.hits["hit"] == 1
+        super().__init__(rc, oracle, lattice, kernel)
         self._seen = {}
-        # a degenerate input cannot pass: enough hits and misses; fully open, partly occluded (and, on the dense lattice, fully occluded)
+        # a degenerate input cannot pass: (enough hits and misses;) fully open, partly occluded (and, on the dense lattice, fully occluded)
         # slots; and a reach that matters -- all from the oracle alone, before anything is compared
-        lit, missed = int(self.lit.sum()), int((~self.lit).sum())
-        assert lit >= 1000 and missed >= 1000, (lit, missed)
+        lit = int(self.lit.sum())
         for dist in DISTANCES:
             c = self.want(S_MAX, max_dist=dist)[self.lit]
             full, zero = int((c == S_MAX).sum()), int((c == 0).sum())
@@ -74,7 +44,6 @@ class World:
             if lattice == (7, 7, 6) and dist == np.inf:
                 assert zero >= 20, zero
         assert not np.array_equal(self.want(S_MAX, max_dist=DISTANCES[0]), self.want(S_MAX, max_dist=DISTANCES[1]))
-        self.d_rays, self.d_hits = dev(self.rays), dev(self.hits)
 
     def seen(self, max_dist=np.inf, seed=SEED, depth=0, path_in=None, path_base=0, rays=None, hits=None):
         """(n, S_MAX) bool from the oracle alone: sample s of slot i is visible -- the model's rays, oracle.trace(mode="any"), the gate.
@@ -97,35 +66,20 @@ class World:
     def fused(self, samples, out=None, max_dist=np.inf, seed=SEED, depth=0, d_path_in=None, path_base=0, stream=None):
         """One call into a zeroed count buffer with a poisoned guard behind it (or into `out`); returns the tensor."""
         if out is None:
-            out = count_buffer(N_RAYS)
+            out = zeroed(N_RAYS, 4)
         self.t.ambient_occlusion_device(self.d_rays.data_ptr(), self.d_hits.data_ptr(), N_RAYS, samples, out.data_ptr(), max_dist=max_dist, seed=seed,
                                         depth=depth, bias=BIAS, d_path_in=d_path_in, path_base=path_base, stream=stream)
         return out
 
 
-def counts_of(out, n_counts):
-    got = out.cpu().numpy()
-    assert np.all(got[n_counts * 4:] == POISON), "bytes behind the counts were written"
-    return got[:n_counts * 4].view(np.uint32)
-
-
 def check(out, want, what):
     """`out`: a tensor from World.fused, `want`: (n,) counts."""
-    got = counts_of(out, want.size)
-    flat = np.asarray(want, np.uint32).reshape(-1)
-    bad = np.nonzero(got != flat)[0]
-    assert len(bad) == 0, f"{what}: {len(bad)} of {want.size} counts differ, first items {bad[:8]}: got {got[bad[:8]]} want {flat[bad[:8]]}"
+    check_words(out, want, np.uint32, what)
 
 
 @pytest.fixture(scope="module")
 def worlds(rc, oracle):
-    w = {"lds": World(rc, oracle, (3, 3, 2)),            # 18 instances: the whole top level in LDS
-         "partial": World(rc, oracle, (7, 7, 6)),        # 294 instances: only the top of the TLAS is staged
-         "plain": World(rc, oracle, (3, 3, 2), kernel=3)}  # the small scene again through the 256-thread kernel
-    assert w["lds"].t.n_instances() == 18 and w["partial"].t.n_instances() == 294
-    yield w
-    for x in w.values():
-        x.t.free()
+    yield from three_shapes(World, rc, oracle)
 
 
 # ---- 1: every count against the oracle, in the three shapes, for both reaches ----------------------------------------------------------
@@ -139,7 +93,7 @@ def test_counts_equal_the_oracles(worlds, shape, max_dist, samples):
     torch.cuda.synchronize()
     w.t.wait_for_gpu()  # (a stack overflow would be reported here)
     check(out, w.want(samples, max_dist=max_dist), f"{shape} S={samples} max_dist={max_dist}")
-    got = counts_of(out, N_RAYS)
+    got = words_of(out, N_RAYS, np.uint32)
     assert not got[~w.lit].any(), "a slot whose primary ray missed has visible samples"
     assert got.max() <= samples
 
@@ -241,7 +195,7 @@ def test_captured_call_follows_the_frame(worlds):
     t, S = w.t, 2
     s = torch.cuda.Stream()
     d_rays, d_hits = dev(w.rays), dev(w.hits)  # the captured call's own frame buffers
-    out = count_buffer(N_RAYS)
+    out = zeroed(N_RAYS, 4)
 
     def launch():
         t.ambient_occlusion_device(d_rays.data_ptr(), d_hits.data_ptr(), N_RAYS, S, out.data_ptr(), seed=SEED, bias=BIAS, stream=s.cuda_stream)
@@ -280,7 +234,7 @@ def test_two_streams_at_once(worlds):
     w = worlds["lds"]
     seeds, S = (SEED, 0xBEEF00000001), 2
     streams = [torch.cuda.Stream() for _ in seeds]
-    outs = [[count_buffer(N_RAYS) for _ in range(3)] for _ in seeds]
+    outs = [[zeroed(N_RAYS, 4) for _ in range(3)] for _ in seeds]
     torch.cuda.synchronize()  # the buffers are filled on the current stream: done before the other streams write them
     for rep in range(3):  # enqueued alternately, never waited for in between
         for k, seed in enumerate(seeds):
@@ -390,7 +344,7 @@ def test_singular_instance_and_nan_frames(rc, oracle):
             assert np.isnan(model_rays["d"].reshape(n, S, 3)[lit[::7]]).any(axis=2).all()
             assert np.all(model_rays["tmax"].reshape(n, S)[lit] == np.float32(dist))  # t_max = max_dist > 0 also on NaN frames: no gate
             d_rays, d_hits = dev(rays), dev(hits)
-            d_ar, d_ah, out = poisoned(n * S * 32), poisoned(n * S * 32), count_buffer(n)
+            d_ar, d_ah, out = poisoned(n * S * 32), poisoned(n * S * 32), zeroed(n, 4)
             t.ambient_occlusion_rays_device(d_rays.data_ptr(), d_hits.data_ptr(), n, S, d_ar.data_ptr(), max_dist=dist, seed=SEED, bias=BIAS)
             t.trace_device(d_ar.data_ptr(), d_ah.data_ptr(), n * S, mode="any")
             t.ambient_occlusion_device(d_rays.data_ptr(), d_hits.data_ptr(), n, S, out.data_ptr(), max_dist=dist, seed=SEED, bias=BIAS)

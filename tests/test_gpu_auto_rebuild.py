@@ -27,9 +27,9 @@ import numpy as np
 import pytest
 
 import auto_rebuild_model as model
+from dynamic_kit import LARGE, OracleFrame, PATHS, PATH_IDS, SMALL, camera_rays, dev_bytes, fresh_twin, hits_of, initial_xf, make_scene, sphere
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal
-from test_gpu_dynamic import LARGE, SMALL, camera_rays, dev_bytes, hits_of, initial_xf, make_scene, sphere
-from test_gpu_rebuild import PATH_IDS, PATHS, OracleFrame, fresh_twin
 
 pytestmark = pytest.mark.gpu
 
@@ -37,13 +37,6 @@ RATIO = model.RATIO
 REL = 1e-11
 RC_ERR_INVALID_ARGUMENT, RC_ERR_NOT_SYNCED = 1, 6
 N_FRAMES = len(model.KINDS)
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0
-    return raycore_jl_amd
 
 
 def close(a, b):

@@ -7,16 +7,11 @@ import numpy as np
 import pytest
 
 import bounce_model as bm
+from gpu_kit import dev
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 @pytest.fixture(scope="module")
@@ -25,11 +20,6 @@ def c3(rc, oracle):
     t, o = build_product(rc, cfg), build_oracle(oracle, cfg)
     yield cfg, t, o
     t.free()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
 
 
 def empty_records(n):

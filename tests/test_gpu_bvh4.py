@@ -3,17 +3,11 @@ produce a byte-identical BVHNode4 array, closest_hit4 / any_hit4 bit-identical h
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal
 
 pytestmark = pytest.mark.gpu
 INVALID = 0xFFFFFFFF
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 def soup(n, seed, scale=0.1):

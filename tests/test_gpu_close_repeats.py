@@ -10,19 +10,13 @@ import numpy as np
 import pytest
 
 import close_repeat_model as cm
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product
 
 pytestmark = pytest.mark.gpu
 
 W, H = 1280, 800
 STEP = np.array([0.02, 0.01, 0.0])       # the translating camera's travel per frame
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 def turned_in_place(eye, look_at, degrees):

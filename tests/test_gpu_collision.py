@@ -3,15 +3,10 @@ identical ContactPair array (content AND order), identical collide_instances_any
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 TRIS = np.array([[0, 0, 0, 1, 0, 0, 0, 1, 0], [0, 0, 1, 1, 0, 1, 0, 1, 1]], np.float32)
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 def both(rc, po, n, spread, seed, rot=False):

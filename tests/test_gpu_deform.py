@@ -33,111 +33,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from dynamic_kit import Spec, Want, deform, dev_bytes, frame_xf, hits_of, want_frame
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal
-from test_gpu_dynamic import LARGE, SMALL, camera_rays, dev_bytes, frame_xf, hits_of, initial_xf, records_differing
 
 pytestmark = pytest.mark.gpu
 
 N_FRAMES = 4
 RC_ERR_INVALID_ARGUMENT, RC_ERR_INVALID_HANDLE, RC_ERR_NOT_SYNCED, RC_ERR_GEOMETRY_CHANGED = 1, 2, 6, 8
 EXPORTS = ("nodes", "instances", "all_blas_nodes", "all_blas_prims", "blas_descriptors")
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0
-    return raycore_jl_amd
-
-
-def deform(soup, f):
-    """Frame f of the soup (f < 0: the soup itself)."""
-    if f < 0:
-        return np.ascontiguousarray(soup, dtype=np.float32)
-    v = np.asarray(soup, dtype=np.float64).reshape(-1, 3)
-    a = (0.8 + 0.5 * f) * v[:, 2] / 0.5
-    c, s = np.cos(a), np.sin(a)
-    out = np.stack([(c * v[:, 0] - s * v[:, 1]) * (1 + 0.4 * f), s * v[:, 0] + c * v[:, 1], v[:, 2] * (1 - 0.15 * f)], axis=1)
-    out = out.astype(np.float32).reshape(-1, 9)
-    return np.ascontiguousarray(np.roll(out, 7 * (f + 1), axis=0))
-
-
-class Spec:
-    """A scene: soups (soup 0 is the one that deforms), the instance ranges of its handles as (soup, first, end), lattice."""
-
-    def __init__(self, rc, name):
-        sc = rc.scenes
-        self.name = name
-        self.dims = LARGE if name == "864" else SMALL
-        self.xf = initial_xf(rc, self.dims)
-        n = len(self.xf)
-        self.soups = [sc.fan_sphere(40, 20, radius=0.5) if name == "top" else sc.fan_sphere(10, 6, radius=0.5)]
-        self.groups = [(0, 0, n)]
-        if name == "two":  # the deforming soup is shared by the first and the last handle
-            self.soups.append(sc.fan_sphere(16, 9, radius=0.45))
-            self.groups = [(0, 0, 60), (1, 60, 84), (0, 84, n)]
-        if name == "poles":  # 2 x 11 x 8 faces, 2 x 11 of them (one per pole quad) degenerate
-            self.soups = [sc.uv_sphere_grid(12, 9, radius=0.5)]
-        self.owner = np.zeros(n, dtype=np.int64)
-        for k, lo, hi in self.groups:
-            self.owner[lo:hi] = k
-        self.rays = camera_rays(rc, self.dims)
-
-    def soups_of(self, f):
-        return [deform(self.soups[0], f)] + self.soups[1:]
-
-    def build(self, rc, f=-1, xf=None):
-        """The scene with frame f's soup, built by the structural sync -> (scene, handles)."""
-        xf = self.xf if xf is None else xf
-        t = rc.TLAS()
-        ids = np.arange(len(xf), dtype=np.uint32)
-        geo = [t.add_geometry(s) for s in self.soups_of(f)]
-        hs = [t.push_instances(geo[k], xf[lo:hi], ids[lo:hi]) for k, lo, hi in self.groups]
-        t.sync()
-        assert t.last_sync_action == "rebuild"
-        return t, hs
-
-
-class Want:
-    """The oracle built from scratch."""
-
-    def __init__(self, oracle, soups, owner, xf, rays, metas=None):
-        o = oracle.Scene()
-        ids = [o.add_blas(s, None if metas is None else metas[k]) for k, s in enumerate(soups)]
-        for i, x in enumerate(xf):
-            o.add_instance(ids[owner[i]], x, i)
-        o.build()
-        self.nodes, self.instances, self.bound = o.tlas_nodes, o.instances, o.world_bound
-        self.blas_nodes, self.blas_prims, self.blas_descs = o.blas_nodes, o.blas_prims, o.blas_descs
-        self.closest = o.trace(rays, nthreads=8)
-        self.any = o.trace(rays, mode="any", nthreads=8)
-
-    def same_topology(self, other):
-        return all(np.array_equal(self.nodes[k], other.nodes[k]) for k in ("child0", "child1", "parent"))
-
-
-_want_cache = {}
-
-
-def want_frame(oracle, rc, spec, f):
-    """Frame f's oracle (f = -1: the undeformed scene) with the conditions on the inputs asserted on the oracle's output alone."""
-    key = (spec.name, f)
-    if key not in _want_cache:
-        w = Want(oracle, spec.soups_of(f), spec.owner, spec.xf, spec.rays)
-        if f >= 0:
-            prev, first = want_frame(oracle, rc, spec, f - 1), want_frame(oracle, rc, spec, -1)
-            n0 = int(w.blas_descs["primitives_offset"][1]) if len(w.blas_descs) > 1 else len(w.blas_prims)
-            moved = float(np.mean(w.blas_prims["meta"][:n0] != prev.blas_prims["meta"][:n0]))
-            hit_fraction = float(w.closest["hit"].mean())
-            changed = records_differing(w.closest, prev.closest) / len(w.closest)
-            print(f"inputs {spec.name} frame {f}: prims {len(w.blas_prims)} (before {len(prev.blas_prims)}), leaf slots with other metadata {moved:.3f}, "
-                  f"oracle hit fraction {hit_fraction:.3f}, records changed vs previous frame {changed:.3f}, TLAS topology as initially: {w.same_topology(first)}")
-            assert len(w.blas_prims) == len(prev.blas_prims), (spec.name, f)
-            assert moved >= 0.9, (spec.name, f, moved)
-            assert hit_fraction >= 0.2, (spec.name, f, hit_fraction)
-            assert changed >= 0.3, (spec.name, f, changed)
-        _want_cache[key] = w
-    return _want_cache[key]
 
 
 def refit_restatement(topo, fresh):
@@ -478,7 +382,7 @@ def test_wavefront_deform_frame(rc, oracle, mode):
 # ---- 6. the mesh form ------------------------------------------------------------------------------------------------------------------
 def test_mesh_vertices(rc, oracle):
     import torch
-    from test_oracle_mesh import grid_mesh
+    from scene_kit import grid_mesh
     v, f, nrm, uv = grid_mesh(24, seed=3)
     f[17] = [5, 5, 5]      # degenerate by index: whatever the vertices do
     f[100] = [7, 8, 7]
@@ -547,7 +451,7 @@ def test_mesh_vertices(rc, oracle):
 # ---- 7. argument errors leave the scene usable ---------------------------------------------------------------------------------------------
 def test_argument_errors_leave_the_scene_usable(rc):
     import torch
-    from test_oracle_mesh import grid_mesh
+    from scene_kit import grid_mesh
     v, f, nrm, uv = grid_mesh(8, seed=2)
     soup = rc.scenes.fan_sphere(10, 6, radius=0.5)
     t = rc.TLAS()

@@ -22,121 +22,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from dynamic_kit import LARGE, RC_ERR_INVALID_ARGUMENT, RC_ERR_INVALID_HANDLE, RC_ERR_NOT_SYNCED, SMALL, assert_same_scene, camera_rays, dev_bytes
+from dynamic_kit import frame_xf, hits_of, host_frame, initial_xf, make_scene, oracle_frame, oracle_scene_hits, sphere
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal
 
 pytestmark = pytest.mark.gpu
 
-SMALL = (6, 6, 4)     # 144 instances: at most kTlasLdsInst = 256 (kernel 5 would stage the whole TLAS in LDS: test_gpu_update_kernels.py)
-LARGE = (12, 12, 6)   # 864 instances: the TLAS's top is renumbered (tlas_top_k > 0) for kernel 6, which this file does not run either
 N_FRAMES = 4
-SCALED_FRAME = 2      # the frame whose linear part carries a non-uniform scale
-W = H = 256
-RC_ERR_INVALID_ARGUMENT, RC_ERR_INVALID_HANDLE, RC_ERR_NOT_SYNCED = 1, 2, 6
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0
-    return raycore_jl_amd
-
-
-def sphere(rc):
-    return rc.scenes.fan_sphere(10, 6, radius=0.5)
-
-
-def initial_xf(rc, dims):
-    return rc.scenes.lattice_transforms(*dims, 1.6, 3)[0]
-
-
-def frame_xf(rc, dims, f):
-    """Transforms of frame f: pitch 1.5 + 0.2 f, rotation seed 100 + 7 f; frame SCALED_FRAME stretches the local axes by (1.0, 0.7, 1.3)."""
-    xf = rc.scenes.lattice_transforms(*dims, 1.5 + 0.2 * f, 100 + 7 * f)[0]
-    if f == SCALED_FRAME:
-        m = xf.reshape(-1, 3, 4).copy()
-        m[:, :, :3] *= np.array([1.0, 0.7, 1.3], dtype=np.float32)
-        xf = np.ascontiguousarray(m.reshape(-1, 12))
-    return xf
-
-
-def camera_rays(rc, dims):
-    """A 256 x 256 pinhole view of the lattice from outside one of its corners (fixed per scene: the frames move under it)."""
-    ext = (np.array(dims, dtype=np.float64) - 1) * 1.8   # the lattice at the frames' mean pitch
-    centre = ext / 2
-    eye = centre + np.array([0.45, 0.3, 1.0]) * (0.95 * ext[:2].max() + 3.0)
-    return rc.scenes.pinhole_rays(W, H, eye, centre, fov_deg=45.0)
-
-
-_oracle_cache = {}
-
-
-def oracle_scene_hits(oracle, rc, xf, rays, mode="closest"):
-    o = oracle.Scene()
-    b = o.add_blas(sphere(rc))
-    for i, x in enumerate(xf):
-        o.add_instance(b, x, i)
-    o.build()
-    return o.trace(rays, mode=mode, nthreads=8)
-
-
-def records_differing(a, b):
-    return int(np.count_nonzero(np.any(a.view(np.uint32).reshape(len(a), -1) != b.view(np.uint32).reshape(len(b), -1), axis=1)))
-
-
-def oracle_frame(oracle, rc, dims, f):
-    """Closest hits of the oracle built from scratch with frame f's transforms (f = -1: the initial ones), with the conditions on the
-    inputs asserted on the oracle's output alone."""
-    key = (dims, f)
-    if key not in _oracle_cache:
-        rays = camera_rays(rc, dims)
-        want = oracle_scene_hits(oracle, rc, initial_xf(rc, dims) if f < 0 else frame_xf(rc, dims, f), rays)
-        if f >= 0:
-            prev = oracle_frame(oracle, rc, dims, f - 1)
-            hit_fraction = float(want["hit"].mean())
-            changed = records_differing(want, prev) / len(want)
-            print(f"inputs {dims} frame {f}: oracle hit fraction {hit_fraction:.3f}, records changed vs previous frame {changed:.3f}")
-            assert hit_fraction >= 0.2, (dims, f, hit_fraction)
-            assert changed >= 0.1, (dims, f, changed)
-        _oracle_cache[key] = want
-    return _oracle_cache[key]
-
-
-def make_scene(rc, dims, n_handles=1):
-    """One fan-sphere BLAS under the initial lattice, the instances split over n_handles handles (contiguous ranges)."""
-    xf = initial_xf(rc, dims)
-    n = len(xf)
-    ids = np.arange(n, dtype=np.uint32)
-    t = rc.TLAS()
-    cuts = [n * k // n_handles for k in range(n_handles + 1)]
-    blas = t.add_geometry(sphere(rc))
-    handles = [t.push_instances(blas, xf[cuts[k]:cuts[k + 1]], ids[cuts[k]:cuts[k + 1]]) for k in range(n_handles)]
-    t.sync()
-    assert (t.get_option("tlas_top_k") > 0) == (n > 256)  # which top-level layout the scene exercises
-    return t, handles, cuts
-
-
-def host_frame(twin, handles, cuts, xf, which=None):
-    for k, h in enumerate(handles):
-        if which is None or k in which:
-            twin.update_transforms(h, xf[cuts[k]:cuts[k + 1]])
-    twin.sync()
-    assert twin.last_sync_action == "refit"
-
-
-def assert_same_scene(got, want, what):
-    sg, sw = got.adapt(), want.adapt()
-    assert sg.nodes.tobytes() == sw.nodes.tobytes(), f"{what}: TLAS nodes differ"
-    assert sg.instances.tobytes() == sw.instances.tobytes(), f"{what}: instances differ"
-    bg, bw = got.world_bound(), want.world_bound()
-    assert bg.p_min.tobytes() == bw.p_min.tobytes() and bg.p_max.tobytes() == bw.p_max.tobytes(), f"{what}: world bound {bg.p_min} {bg.p_max} != {bw.p_min} {bw.p_max}"
-
-
-def dev_bytes(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def hits_of(rc, d_hits):
-    return d_hits.cpu().numpy().view(rc.HIT_DT)
 
 
 # ---- 1. update on the device, commit with sync() ---------------------------------------------------------------------------------------

@@ -8,16 +8,11 @@ condition 16) and beyond (singular, huge, tiny: never culled).  Everything is co
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product
+from scene_kit import grazing_rays
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 def xform(rot=None, scale=1.0, t=(0, 0, 0)):
@@ -42,22 +37,6 @@ def check(rc, t, o, rays, what):
     t.set_option("kernel", -1)
     t.set_option("entry_cull", 1)
     return want_c
-
-
-def grazing_rays(rc, centres, radii, seed, per_instance=400):
-    """Rays aimed to pass each sphere at distance radius * f for f around 1 (the geometry), around the cull sphere (~1.1) and far."""
-    g = rc.scenes.rng(seed)
-    fs = np.array([0.0, 0.5, 0.9, 0.99, 0.999, 1.0, 1.001, 1.01, 1.05, 1.08, 1.09, 1.1, 1.11, 1.12, 1.15, 1.2, 1.5, 3.0])
-    org, dirs = [], []
-    for c, r in zip(centres, radii):
-        for _ in range(per_instance):
-            d = g.normal(size=3); d /= np.linalg.norm(d)
-            u = np.cross(d, g.normal(size=3)); u /= np.linalg.norm(u)
-            f = g.choice(fs) * (1 + g.choice([0, 1e-6, -1e-6, 1e-4, -1e-4]))
-            p = np.asarray(c) + u * r * f                      # closest point of the ray to the centre
-            dist = g.choice([0.0, 0.3, 3.0, 50.0, 3000.0])     # origin before / inside / far from the instance
-            org.append(p - d * dist * g.choice([1, 1, 1, -1])); dirs.append(d)
-    return rc.scenes.make_rays(np.array(org), np.array(dirs))
 
 
 def test_grazing_a_lattice_of_spheres(rc, oracle):

@@ -8,11 +8,12 @@ instance finds a triangle.
 * Parity, bit for bit against the oracle and across the option settings, on batches that mix triangle lanes, entering lanes, culled
   entries that pop straight into the next TLAS leaf and exits that pop into one, with rays inside and outside the cull's regime.
 """
-import ctypes
 
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
+from gpu_kit import read_device
 from helpers import assert_hits_equal, build_oracle, build_product
 
 pytestmark = pytest.mark.gpu
@@ -20,19 +21,7 @@ pytestmark = pytest.mark.gpu
 N_RAYS = 4096
 
 
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
 # ---- 1. the traversal copy holds the spheres -------------------------------------------------------------------------------------------
-def read_device(ptr, dtype, count):
-    out = np.zeros(count, dtype=dtype)
-    hip = ctypes.CDLL("libamdhip64.so")
-    assert hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(int(ptr)), out.nbytes, 2) == 0
-    return out
 
 
 def leaf_records_hold_the_spheres(t, n, what):

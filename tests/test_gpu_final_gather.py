@@ -14,8 +14,11 @@ import pytest
 
 import bounce_model as bm
 import gather_model as gm
+from gpu_kit import POISON, check_words, dev, finish, poisoned, words_of, zeroed
+from gpu_kit import rc  # noqa: F401
 from helpers import build_oracle, build_product
-from test_gpu_view_factors_host import room_cfg
+from scene_kit import distinct_x, meta, room_cfg
+from worlds import C3World, three_shapes
 
 pytestmark = pytest.mark.gpu
 
@@ -25,58 +28,13 @@ SEED = 0xA0
 S_MAX = 5
 DISTANCES = (np.inf, 1.0)
 U32_MAX = gm.U32_MAX
-POISON = 0xAB
-GUARD = 256      # poisoned bytes behind every output: nothing may be written past it
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def poisoned(nbytes):
-    import torch
-    return torch.full((nbytes + GUARD,), POISON, dtype=torch.uint8, device="cuda")
-
-
-def zeroed(n, width):
-    """n zeroed words of `width` bytes followed by the poisoned guard (the call accumulates: the caller zeroes)."""
-    out = poisoned(n * width)
-    out[:n * width] = 0
-    return out
-
-
-def words_of(out, n, dtype):
-    got = out.cpu().numpy()
-    width = np.dtype(dtype).itemsize
-    assert np.all(got[n * width:] == POISON), "bytes behind an output were written"
-    return got[:n * width].view(dtype)
 
 
 def check(outs, want, what):
     """outs: (sums tensor, open tensor or None) of a call; want: (sums u64, open u32) of the model."""
     for out, w, dtype, name in ((outs[0], want[0], np.uint64, "sums"), (outs[1], want[1], np.uint32, "open")):
-        if out is None:
-            continue
-        got = words_of(out, len(w), dtype)
-        bad = np.nonzero(got != w)[0]
-        assert len(bad) == 0, f"{what}: {len(bad)} of {len(w)} {name} differ, first slots {bad[:8]}: got {got[bad[:8]]} want {w[bad[:8]]}"
-
-
-def distinct_x(n, salt=0):
-    """Distinct per primitive, over the whole u32 range and with 2^32 - 1 among them: a sum that reads another primitive's word cannot
-    equal the model's, and sums of a few samples pass 2^32."""
-    x = ((np.arange(1, n + 1, dtype=np.uint64) + np.uint64(salt)) * np.uint64(2654435761) % np.uint64(1 << 32)).astype(np.uint32)
-    x[0] = U32_MAX
-    assert len(set(x.tolist())) == n
-    return x
+        if out is not None:
+            check_words(out, w, dtype, f"{what} ({name})")
 
 
 def run_gather(t, d_rays, d_hits, n, samples, d_x, outs=None, with_open=True, miss_value=0, max_dist=np.inf, seed=SEED, depth=0, d_path_in=None,
@@ -90,25 +48,17 @@ def run_gather(t, d_rays, d_hits, n, samples, d_x, outs=None, with_open=True, mi
     return outs
 
 
-class World:
+class World(C3World):
     def __init__(self, rc, oracle, lattice, kernel=None):
-        self.cfg = rc.scenes.config_c3(lon=16, bands=9, lattice=lattice)
-        self.t, self.o = build_product(rc, self.cfg), build_oracle(oracle, self.cfg)
-        if kernel is not None:
-            self.t.set_option("kernel", kernel)
-        self.rays = rc.scenes.c3_primary_rays(self.cfg, 320, 200)[:N_RAYS]
-        self.hits = self.o.trace(self.rays, nthreads=16)
-        self.lit = self.hits["hit"] == 1
+        super().__init__(rc, oracle, lattice, kernel)
         self.prim_meta = self.o.blas_prims["meta"]
         self.n_prims = len(self.prim_meta)
         assert self.n_prims == self.t.n_primitives() == 256 and self.prim_meta.min() >= 1 and self.prim_meta.max() <= self.n_prims
-        self.x = distinct_x(self.n_prims)
+        self.x = distinct_x(self.n_prims, with_max=True)
         self._tables = {}
-        # a degenerate input cannot pass -- all from the oracle alone, before anything is compared: enough hits and misses; at the
+        # a degenerate input cannot pass -- all from the oracle alone, before anything is compared: (enough hits and misses;) at the
         # unbounded reach enough slots whose samples land on two or more different primitives' metadata; at either reach enough slots
         # with a sample that hits and a sample that escapes; sums that pass 2^32; and a reach that matters
-        lit, missed = int(self.lit.sum()), int((~self.lit).sum())
-        assert lit >= 1000 and missed >= 1000, (lit, missed)
         for dist in DISTANCES:
             meta, escaped = self.table(max_dist=dist)
             mixed = int(((meta >= 1).any(axis=1) & escaped.any(axis=1)).sum())
@@ -120,7 +70,7 @@ class World:
             assert self.want(S_MAX, max_dist=dist)[0].max() >= 1 << 32
             assert (meta[~self.lit] == -1).all() and not escaped[~self.lit].any()
         assert not np.array_equal(self.want(S_MAX, max_dist=DISTANCES[0])[0], self.want(S_MAX, max_dist=DISTANCES[1])[0])
-        self.d_rays, self.d_hits, self.d_x = dev(self.rays), dev(self.hits), dev(self.x)
+        self.d_x = dev(self.x)
 
     def table(self, max_dist=np.inf, seed=SEED, depth=0, path_in=None, path_base=0, rays=None, hits=None):
         """(meta, escaped), (n, S_MAX) each, from the oracle alone; computed once per argument set and read-only.  A sample does not
@@ -145,19 +95,7 @@ class World:
 
 @pytest.fixture(scope="module")
 def worlds(rc, oracle):
-    w = {"lds": World(rc, oracle, (3, 3, 2)),            # 18 instances: the whole top level in LDS
-         "partial": World(rc, oracle, (7, 7, 6)),        # 294 instances: only the top of the TLAS is staged
-         "plain": World(rc, oracle, (3, 3, 2), kernel=3)}  # the small scene again through the 256-thread kernel
-    assert w["lds"].t.n_instances() == 18 and w["partial"].t.n_instances() == 294
-    yield w
-    for x in w.values():
-        x.t.free()
-
-
-def finish(t):
-    import torch
-    torch.cuda.synchronize()
-    t.wait_for_gpu()  # (a stack overflow would be reported here)
+    yield from three_shapes(World, rc, oracle)
 
 
 # ---- 1: every word against the model, in the three shapes, for both reaches and both ends of miss_value -----------------------------------
@@ -219,13 +157,6 @@ def test_open_is_ambient_occlusion_and_optional(worlds, shape):
 
 
 # ---- 4, 6: a closed room -- the furnace, and metadata with gaps, duplicates, 0 and N + 50 -------------------------------------------------
-def meta(n):
-    """The products test's metadata: sources 5..39 share metadata 7, ten primitives have metadata 0, one has N + 50."""
-    m = np.arange(1, n + 1, dtype=np.uint32)
-    m[5:40] = 7
-    m[100:110] = 0
-    m[150] = n + 50
-    return m
 
 
 class Room:
@@ -273,7 +204,7 @@ def test_metadata_gaps_duplicates_and_out_of_range(rc, oracle):
     try:
         n = r.n_prims
         assert (r.meta == 0).sum() >= 100 and (r.meta == n + 50).sum() >= 10 and (r.meta == 7).sum() >= 100  # samples that land on each kind
-        x = distinct_x(n, salt=3)
+        x = distinct_x(n, salt=3, with_max=True)
         want = gm.reduce(r.meta, r.escaped, x, 99)
         dropped = ((r.meta == 0) | (r.meta == n + 50)).sum(axis=1)
         ones = gm.reduce(r.meta, r.escaped, np.ones(n, np.uint32))[0]
@@ -381,7 +312,7 @@ def test_captured_call_follows_its_inputs(worlds):
     with torch.cuda.graph(g, stream=s):
         launch()
     rays2, hits2 = np.ascontiguousarray(w.rays[::-1]), np.ascontiguousarray(w.hits[::-1])  # another frame: the same view, slots reversed
-    x2 = distinct_x(w.n_prims, salt=11)
+    x2 = distinct_x(w.n_prims, salt=11, with_max=True)
     want2 = w.want(S, x=x2, miss_value=9, rays=rays2, hits=hits2)
     assert not np.array_equal(want2[0], w.want(S, miss_value=9)[0]) and not np.array_equal(want2[0], w.want(S, x=x2, miss_value=9)[0][::-1])
     for rays, hits, x, want, what in ((w.rays, w.hits, w.x, w.want(S, miss_value=9), "replay"),
@@ -407,7 +338,7 @@ def test_captured_call_follows_its_inputs(worlds):
 def test_two_streams_at_once(worlds):
     import torch
     w = worlds["lds"]
-    xs, S = (w.x, distinct_x(w.n_prims, salt=21)), 2
+    xs, S = (w.x, distinct_x(w.n_prims, salt=21, with_max=True)), 2
     d_xs = [dev(x) for x in xs]
     streams = [torch.cuda.Stream() for _ in xs]
     outs = [[(zeroed(N_RAYS, 8), zeroed(N_RAYS, 4)) for _ in range(3)] for _ in xs]
@@ -503,7 +434,7 @@ def test_wavefront_final_gather(rc, worlds):
     wf.capture(s)
     for c in wf.gather_sums + wf.gather_open:
         c.fill_(0x7B)  # the replayed frame zeroes them itself
-    x2 = distinct_x(w.n_prims, salt=31)
+    x2 = distinct_x(w.n_prims, salt=31, with_max=True)
     d_x.copy_(torch.from_numpy(x2.view(np.int32).copy()).cuda())  # held by reference: the replay reads the new solution
     torch.cuda.synchronize()
     wf.replay()
@@ -552,7 +483,7 @@ def test_singular_instance_and_nan_frames(rc, oracle):
         _, nrm = o.hit_points(rays[lit[::7]], hits[lit[::7]])
         assert np.isnan(nrm).any(axis=1).all(), "the singular instance's frames are expected to be NaN"
         prim_meta = t.adapt().all_blas_prims["meta"]
-        x = distinct_x(t.n_primitives(), salt=41)
+        x = distinct_x(t.n_primitives(), salt=41, with_max=True)
         d_rays, d_hits, d_x = dev(rays), dev(hits), dev(x)
         for dist in DISTANCES:
             d_gr, d_gh = poisoned(n * S * 32), poisoned(n * S * 32)

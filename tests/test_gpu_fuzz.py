@@ -4,38 +4,11 @@ aimed at them -- device-built arrays byte-identical to the oracle's and hit reco
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product
+from scene_kit import hostile_transform
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-def hostile_transform(g, kind):
-    m = np.eye(4, dtype=np.float64)
-    a = g.normal(size=(3, 3))
-    q, _ = np.linalg.qr(a)
-    if kind == 0:      # rotation + uniform scale + translation
-        m[:3, :3] = q * g.uniform(0.3, 2.0)
-    elif kind == 1:    # mirror
-        m[:3, :3] = q @ np.diag([-1.0, 1.0, 1.0])
-    elif kind == 2:    # shear + anisotropic scale
-        m[:3, :3] = q @ np.diag(g.uniform(0.05, 5.0, 3)) + np.triu(g.normal(size=(3, 3)) * 0.5, 1)
-    elif kind == 3:    # flattened along one axis: singular, inverse = Inf / NaN
-        m[:3, :3] = q @ np.diag([1.0, 1.0, 0.0])
-    elif kind == 4:    # huge
-        m[:3, :3] = q * 1e6
-    elif kind == 5:    # tiny
-        m[:3, :3] = q * 1e-6
-    else:              # all-zero linear part
-        m[:3, :3] = 0.0
-    m[:3, 3] = g.uniform(-3, 3, 3)
-    return m.astype(np.float32)[:3, :].reshape(12)
 
 
 import os

@@ -12,33 +12,18 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_dynamic as dyn
-import test_gpu_rebuild as reb
+import dynamic_kit as dyn
+from gpu_kit import POISON_U32 as POISON, f32_tensor, finish, u32_of
+from gpu_kit import rc  # noqa: F401
 from helpers import build_oracle, build_product
+from scene_kit import single_cfg, small_cfg
 
 pytestmark = pytest.mark.gpu
 
 DIRS = np.array([[0, 0, 1], [0.3, 0.2, 1], [1, 0.1, 0.1],  # the third takes the other branch of the basis choice (|x| >= 0.9)
                  [0, -1, 0], [0, 0, 5]], np.float32)        # the last is not normalised
 GRIDS = (13, 24)  # 169 rays per direction: a 128-item chunk and a 64-lane wave straddle two directions
-POISON = 0xABABABAB
 RC_ERR_INVALID_ARGUMENT, RC_ERR_NOT_SYNCED = 1, 6
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-def f32_tensor(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def u32_of(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 class World:
@@ -79,16 +64,6 @@ class World:
         return out
 
 
-def small_cfg(rc, lattice):
-    return rc.scenes.config_c3(lon=16, bands=9, lattice=lattice, pitch=1.0)  # (a dense lattice: every direction of DIRS lights it)
-
-
-def single_cfg(rc):
-    sc = rc.scenes
-    verts = sc.fan_sphere(12, 7, centre=(0.2, -0.1, 0.3), radius=0.6)
-    return {"blas": [(verts, np.arange(1, len(verts) + 1, dtype=np.uint32))], "instances": [(1, sc.IDENTITY3x4[None], np.ones(1, np.uint32))]}
-
-
 @pytest.fixture(scope="module")
 def worlds(rc, oracle):
     w = {"lds": World(rc, oracle, small_cfg(rc, (3, 3, 2))),              # 18 instances: the whole top level in LDS
@@ -108,12 +83,6 @@ def worlds(rc, oracle):
         x.t.free()
 
 
-def finish(w):
-    import torch
-    torch.cuda.synchronize()
-    w.t.wait_for_gpu()  # (a stack overflow would be reported here)
-
-
 # ---- 1. every row against the oracle, in every shell ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", ["lds", "plain", "partial", "single"])
 @pytest.mark.parametrize("grid", GRIDS)
@@ -121,7 +90,7 @@ def finish(w):
 def test_rows_equal_the_oracles(worlds, shape, grid, n_dirs):
     w = worlds[shape]
     out = w.run(DIRS[:n_dirs], grid)
-    finish(w)
+    finish(w.t)
     got = u32_of(out).reshape(n_dirs, w.n)
     assert np.array_equal(got, w.want(DIRS[:n_dirs], grid)), f"{shape} grid {grid} D {n_dirs}"
 
@@ -131,7 +100,7 @@ def test_direction_order_is_free(worlds):
     w = worlds["lds"]
     order = [3, 0, 4, 2, 1]
     out = w.run(DIRS[order], 13)
-    finish(w)
+    finish(w.t)
     assert np.array_equal(u32_of(out).reshape(5, w.n), w.want(DIRS[order], 13))
 
 
@@ -141,7 +110,7 @@ def test_a_second_call_doubles_the_counts(worlds, shape):
     w = worlds[shape]
     out = w.run(DIRS, 13)
     w.run(DIRS, 13, out=out)
-    finish(w)
+    finish(w.t)
     assert np.array_equal(u32_of(out).reshape(5, w.n), 2 * w.want(DIRS, 13))
 
 
@@ -152,7 +121,7 @@ def test_row_stride_leaves_the_padding_alone(worlds):
     out = torch.from_numpy(np.full(5 * stride + 16, POISON, np.uint32).view(np.int32)).cuda()
     out[:5 * stride].view(5, stride)[:, :w.n] = 0
     w.run(DIRS, 24, out=out, row_stride=stride)
-    finish(w)
+    finish(w.t)
     got = u32_of(out)
     rows = got[:5 * stride].reshape(5, stride)
     assert np.array_equal(rows[:, :w.n], w.want(DIRS, 24))
@@ -174,7 +143,7 @@ def test_metadata_outside_1_to_n_is_dropped(rc, oracle):
     rays_hitting = [int((w.o.trace(w.o.ray_grid(d, 24), nthreads=8)["hit"] == 1).sum()) for d in DIRS]
     assert (want.sum(axis=1) > 0.05 * 24 * 24).all() and (want.sum(axis=1) < 0.6 * np.array(rays_hitting)).all(), (want.sum(axis=1), rays_hitting)
     out = w.run(DIRS, 24)
-    finish(w)
+    finish(w.t)
     assert np.array_equal(u32_of(out).reshape(5, w.n), want)
     w.t.free()
 
@@ -192,7 +161,7 @@ def test_groups_of_one_and_two_give_the_same_rows(worlds, shape):
             w.t.set_option("illum_scratch_bytes", cap)
             assert w.t.get_option("illum_scratch_bytes") == cap
             out = w.run(DIRS, 13)
-            finish(w)
+            finish(w.t)
             assert np.array_equal(u32_of(out), whole), f"illum_scratch_bytes = {cap}"
     finally:
         w.t.set_option("illum_scratch_bytes", default)
@@ -236,7 +205,7 @@ def test_degenerate_directions_give_the_one_direction_grids(rc, worlds):
         assert np.array_equal(got[d], one.cpu().numpy().view(np.uint32).reshape(-1, 8)), f"direction {dirs[d]}"
     # ... and the counts: nothing for the degenerate ones (a NaN ray hits nothing on either path), the oracle's for the third
     out = w.run(dirs, 13)
-    finish(w)
+    finish(w.t)
     rows = u32_of(out).reshape(3, w.n)
     for d in range(len(dirs)):
         assert np.array_equal(rows[d].astype(np.float32), rc.get_illumination(w.t, dirs[d], 13)), f"direction {dirs[d]}"
@@ -248,7 +217,7 @@ _pose_cache = {}
 # along an axis the columns line up and under a fifth of the rays hit, so the later frames are lit obliquely (checked in pose_rows).
 POSE_DIRS = {0: DIRS,
              1: np.array([[0.3, 0.2, 1], [-0.2, 0.1, -1], [0.4, 1, 0.3], [1, 0.3, 0.2], [0.5, -2, 0.5]], np.float32),
-             reb.TIE_FRAME: np.array([[0.3, 0.2, 1], [0.75, -3, 0.3], [1, 0.3, 0.2], [0.1, 1, 0.45], [-0.2, 0.1, -1]], np.float32)}
+             dyn.TIE_FRAME: np.array([[0.3, 0.2, 1], [0.75, -3, 0.3], [1, 0.3, 0.2], [0.1, 1, 0.45], [-0.2, 0.1, -1]], np.float32)}
 
 
 def pose_rows(oracle, rc, f, dirs, grid):
@@ -256,7 +225,7 @@ def pose_rows(oracle, rc, f, dirs, grid):
     if f not in _pose_cache:
         o = oracle.Scene()
         b = o.add_blas(dyn.sphere(rc))
-        for i, x in enumerate(reb.frame_xf(rc, dyn.SMALL, f)):
+        for i, x in enumerate(dyn.rebuild_frame_xf(rc, dyn.SMALL, f)):
             o.add_instance(b, x, i)
         o.build()
         _pose_cache[f] = o
@@ -274,12 +243,12 @@ def bound_of(o):
 def test_captured_frame_follows_the_scene_and_the_directions(rc, oracle, commit):
     import torch
     grid = 24
-    a = reb.Frames(rc, dyn.SMALL, 1)
+    a = dyn.Frames(rc, dyn.SMALL, 1)
     n = a.t.n_primitives()
     dir_sets = POSE_DIRS
     wants = {f: pose_rows(oracle, rc, f, dirs, grid) for f, dirs in dir_sets.items()}
     # the last pose has the widest pitch: its bound holds the others', so a grid laid out from an earlier bound would miss the rim
-    b0, b3 = bound_of(_pose_cache[0]), bound_of(_pose_cache[reb.TIE_FRAME])
+    b0, b3 = bound_of(_pose_cache[0]), bound_of(_pose_cache[dyn.TIE_FRAME])
     assert (b3[1] > b0[1] + 1.5).all(), (b0, b3)  # (the lattice grows away from the origin: the upper corner moves)
     d_dirs = f32_tensor(dir_sets[0])
     d_counts = torch.full((5 * n,), 0x55, dtype=torch.int32, device="cuda")
@@ -300,7 +269,7 @@ def test_captured_frame_follows_the_scene_and_the_directions(rc, oracle, commit)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=a.s):
         frame(torch.cuda.current_stream().cuda_stream)
-    for f in (1, reb.TIE_FRAME, 0):
+    for f in (1, dyn.TIE_FRAME, 0):
         with torch.cuda.stream(a.s):
             a.d_xf.copy_(a.frames[f])            # in place: the graph reads the tensors when it runs
             d_dirs.copy_(f32_tensor(dir_sets[f]))
@@ -318,8 +287,8 @@ def test_captured_frame_follows_the_scene_and_the_directions(rc, oracle, commit)
 def test_no_host_copy_of_the_bound_is_needed(rc, oracle):
     """After an eager asynchronous refit the host copy of the world bound is stale; the call neither waits for it nor reads it."""
     import torch
-    grid, f = 24, reb.TIE_FRAME
-    a = reb.Frames(rc, dyn.SMALL, 1)
+    grid, f = 24, dyn.TIE_FRAME
+    a = dyn.Frames(rc, dyn.SMALL, 1)
     n = a.t.n_primitives()
     want = pose_rows(oracle, rc, f, POSE_DIRS[f], grid)
     d_dirs = f32_tensor(POSE_DIRS[f])
@@ -348,7 +317,7 @@ def test_two_streams_into_two_matrices(worlds):
     for _ in range(3):
         outs.append((w.run(da, 24, stream=s1), w.run(db, 13, stream=s2)))
     s1.synchronize(); s2.synchronize()
-    finish(w)
+    finish(w.t)
     for oa, ob in outs:
         assert np.array_equal(u32_of(oa).reshape(5, w.n), w.want(da, 24))
         assert np.array_equal(u32_of(ob).reshape(5, w.n), w.want(db, 13))

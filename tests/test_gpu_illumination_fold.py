@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import build_oracle, build_product
 
 pytestmark = pytest.mark.gpu
@@ -21,13 +22,6 @@ GRID = 16
 PREFILL = np.array([0, 5, 16777215, 16777216, 0.5, -3, 3e7, np.inf, np.nan], dtype=np.float32)
 DISTINCT = np.arange(1, 10, dtype=np.uint32)
 REPEATING = np.array([3, 3, 7, 0, 12, 7, 1, 9, 3], dtype=np.uint32)  # 0 and 12 are outside 1..9: dropped; slots 2, 4, 5, 6, 8 take nothing
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 def board():

@@ -35,6 +35,7 @@ import numpy as np
 import pytest
 
 import lifecycle_model as lm
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_f32_bits_equal, assert_hits_equal
 
 pytestmark = pytest.mark.gpu
@@ -44,13 +45,6 @@ KERNELS = (0, 1, 3, 5, 6)
 REL = 1e-11  # the cost: tests/test_gpu_auto_rebuild.py's bound (sums of at most 700 positive f64 terms)
 FIRST_READS = ("trace", "exports", "world_bound", "collide", "save_load", "vf", "quality", "shading")
 EXPORTS = ("nodes", "instances", "all_blas_nodes", "all_blas_prims", "blas_descriptors")
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0
-    return raycore_jl_amd
 
 
 class Runner:

@@ -3,17 +3,11 @@ rc_shading_attributes_device against the oracle, bit for bit."""
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal
-from test_oracle_mesh import grid_mesh
+from scene_kit import grid_mesh
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 def both(rc, po, meshes, soups=()):
@@ -274,7 +268,7 @@ def test_face_view_mesh_through_expand_faceviews(rc, oracle):
     """A mesh with per-attribute index sets (cube: 8 positions, 6 per-face normals, one metadata value per face) goes through the host
     mirror's expand_faceviews (GeometryBasics' role in build_and_append_blas!, src/instanced-bvh.jl:581-590) and rc_add_mesh: the
     triangles come back with the face's normal on all three corners and the face's metadata, and match the oracle's mesh path."""
-    from test_expand_faceviews import cube
+    from scene_kit import cube
     p, pf, normals, nf = cube()
     meta = np.arange(101, 113, dtype=np.uint32)
     pos, faces, attr = rc.expand_faceviews(p, pf, normals=(normals, nf), face_meta=(meta, None))

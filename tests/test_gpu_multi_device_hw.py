@@ -7,8 +7,9 @@ also held against the oracle directly."""
 import numpy as np
 import pytest
 
+from api_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product, random_rays
-from test_gpu_view_factors_host import room_cfg
+from scene_kit import room_cfg
 
 # Nothing below has ever run (the builder's box has one GPU): a multi-rank RCCL call that never returns must end the run with a stack dump,
 # not hang the suite (pytest-timeout's thread method exits the process; signals do not interrupt a thread blocked inside the library).
@@ -24,12 +25,6 @@ def _n_dev():
 
 
 needs2 = pytest.mark.skipif(_n_dev() < 2, reason="needs >= 2 GPUs (the RCCL multi-rank branch cannot run on one device)")
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
 
 
 @needs2

@@ -8,16 +8,10 @@ import numpy as np
 import pytest
 
 import order_model as om
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 class Rig:

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product, random_rays
 
 pytestmark = pytest.mark.gpu
@@ -17,13 +18,6 @@ pytestmark = pytest.mark.gpu
 # Tests below that assert the DEFAULT shapes' plane counts / stack widths are skipped when a campaign runs the suite with RC_STACK16=0 (32-bit lane stacks as
 # the process default, profiles/r06_parity_campaigns.txt): the parity they check is covered there by the fuzz run under the same setting.
 default_stack_shape = pytest.mark.skipif(os.environ.get("RC_STACK16", "1") == "0", reason="asserts the 16-bit-stack shapes; RC_STACK16=0 is set")
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 UNIT_TRI = np.array([[0, 0, 0, 1, 0, 0, 0, 1, 0]], dtype=np.float32)

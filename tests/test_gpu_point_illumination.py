@@ -14,12 +14,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import dynamic_kit as dyn
 import point_source_model as pm
-import test_gpu_deform as dfm
-import test_gpu_dynamic as dyn
-import test_gpu_illumination_dirs as tdirs
-import test_gpu_rebuild as reb
+from gpu_kit import POISON_U32 as POISON, f32_tensor, finish, u32_of
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_rays_equal, build_oracle, build_product
+from scene_kit import single_cfg, small_cfg
 
 pytestmark = pytest.mark.gpu
 
@@ -27,25 +27,13 @@ GRIDS = (13, 24)  # 169 rays per source: a 128-item chunk and a 64-lane wave str
 SEED = 0x5EED0005
 AXIS = (0.3, 0.2, 1.0)
 LAMP = (0.25, -0.05, 0.2)  # inside the single sphere (tests/test_point_source_model.py: the furnace)
-POISON = 0xABABABAB
 RC_ERR_INVALID_ARGUMENT, RC_ERR_NOT_SYNCED = 1, 6
 HIT_DT = pm.bm.HIT_DT
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 def dev_bytes(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def u32_of(t):
-    return t.cpu().numpy().view(np.uint32)
 
 
 def zeros_u32(n):
@@ -142,15 +130,9 @@ class World:
         total = S * grid * grid
         d_hits = torch.zeros(total * 32, dtype=torch.uint8, device="cuda")
         self.t.trace_device(d_rays.data_ptr(), d_hits.data_ptr(), total, mode="closest")
-        finish(self)
+        finish(self.t)
         hits = d_hits.cpu().numpy().view(HIT_DT)
         return pm.counts_of(self.t.adapt().all_blas_prims["meta"], hits, S, grid, self.n)
-
-
-def finish(w):
-    import torch
-    torch.cuda.synchronize()
-    w.t.wait_for_gpu()  # (a stack overflow would be reported here)
 
 
 def rows_of(w, counts, S=None, row_stride=None):
@@ -164,10 +146,10 @@ SHAPES = ["lds", "plain", "partial", "single"]
 
 @pytest.fixture(scope="module")
 def worlds(rc, oracle):
-    w = {"lds": World(rc, oracle, tdirs.small_cfg(rc, (3, 3, 2))),              # 18 instances: the whole top level in LDS
-         "plain": World(rc, oracle, tdirs.small_cfg(rc, (3, 3, 2)), kernel=3),  # the same scene through the 256-thread shell
-         "partial": World(rc, oracle, tdirs.small_cfg(rc, (7, 7, 6))),          # 294 instances: only the TLAS's top is staged
-         "single": World(rc, oracle, tdirs.single_cfg(rc), sources=single_sources)}  # one instance: the TLAS root is a leaf
+    w = {"lds": World(rc, oracle, small_cfg(rc, (3, 3, 2))),              # 18 instances: the whole top level in LDS
+         "plain": World(rc, oracle, small_cfg(rc, (3, 3, 2)), kernel=3),  # the same scene through the 256-thread shell
+         "partial": World(rc, oracle, small_cfg(rc, (7, 7, 6))),          # 294 instances: only the TLAS's top is staged
+         "single": World(rc, oracle, single_cfg(rc), sources=single_sources)}  # one instance: the TLAS root is a leaf
     assert w["lds"].t.n_instances() == 18 and w["partial"].t.n_instances() == 294 and w["single"].t.n_instances() == 1
     assert w["partial"].t.get_option("tlas_top_k") > 0 and w["lds"].t.get_option("tlas_top_k") == 0
     # not vacuous, on the oracle's side alone: every row has hits, every source but the furnace's loses rays, the rows differ, and the
@@ -206,7 +188,7 @@ def test_stage_rays_equal_the_models(worlds, shape, grid):
 def test_counts_and_escaped_equal_the_models(worlds, shape, grid):
     w = worlds[shape]
     counts, escaped = w.run(grid)
-    finish(w)
+    finish(w.t)
     want, want_escaped, _ = w.want(grid)
     got, got_escaped = rows_of(w, counts), u32_of(escaped)[:w.S]
     assert np.array_equal(got, want), f"{shape} grid {grid}: rows {np.nonzero((got != want).any(axis=1))[0]} differ"
@@ -220,7 +202,7 @@ def test_counts_equal_the_composed_path(worlds, shape):
     w = worlds[shape]
     want, want_escaped, dropped = w.composed(24)
     counts, escaped = w.run(24)
-    finish(w)
+    finish(w.t)
     assert np.array_equal(rows_of(w, counts), want) and np.array_equal(u32_of(escaped)[:w.S], want_escaped) and not dropped.any()
 
 
@@ -240,7 +222,7 @@ def test_dropped_rays_are_accounted_for(rc, oracle):
     # not vacuous, on the oracle's side alone: every source has rays of all three kinds (the one outside sees little of the scene)
     assert (dropped > 0).all() and dropped.sum() > 100 and (want.sum(axis=1) > 0).all() and (want_escaped > 0).all(), (dropped, want.sum(axis=1), want_escaped)
     counts, escaped = w.run(24)
-    finish(w)
+    finish(w.t)
     got, got_escaped = rows_of(w, counts), u32_of(escaped)[:w.S]
     assert np.array_equal(got, want) and np.array_equal(got_escaped, want_escaped)
     assert (got.sum(axis=1, dtype=np.uint64) + got_escaped + dropped == 24 * 24).all()
@@ -256,7 +238,7 @@ def test_furnace(worlds, grid):
     w = worlds["single"]
     src = pm.make_sources([LAMP, LAMP, (0.2, -0.1, 0.3)], [(0, 0, 0), AXIS, (-1, 0, 0)])
     counts, escaped = w.run(grid, n_sources=3, d_src=dev_bytes(src))
-    finish(w)
+    finish(w.t)
     got = rows_of(w, counts, 3)
     assert not u32_of(escaped)[:3].any() and (got.sum(axis=1) == grid * grid).all()
     want = w.want(grid, src=src)
@@ -269,7 +251,7 @@ def test_a_second_call_doubles_the_counts(worlds, shape):
     w = worlds[shape]
     counts, escaped = w.run(13)
     w.run(13, counts=counts, escaped=escaped)
-    finish(w)
+    finish(w.t)
     want, want_escaped, _ = w.want(13)
     assert np.array_equal(rows_of(w, counts), 2 * want) and np.array_equal(u32_of(escaped)[:w.S], 2 * want_escaped)
 
@@ -283,7 +265,7 @@ def test_row_stride_leaves_the_padding_alone(worlds):
     esc = torch.from_numpy(np.full(w.S + 16, POISON, np.uint32).view(np.int32)).cuda()
     esc[:w.S] = 0
     w.run(24, counts=out, escaped=esc, row_stride=stride)
-    finish(w)
+    finish(w.t)
     got, got_escaped = u32_of(out), u32_of(esc)
     rows = got[:w.S * stride].reshape(w.S, stride)
     want, want_escaped, _ = w.want(24)
@@ -295,7 +277,7 @@ def test_row_stride_leaves_the_padding_alone(worlds):
 def test_without_escaped_the_counts_are_the_same(worlds, shape):
     w = worlds[shape]
     counts, _ = w.run(24, escaped=None)
-    finish(w)
+    finish(w.t)
     assert np.array_equal(rows_of(w, counts), w.want(24)[0])
 
 
@@ -311,7 +293,7 @@ def test_groups_of_one_and_two_give_the_same_rows(worlds, shape):
             w.t.set_option("illum_scratch_bytes", cap)
             for with_escaped in (True, None):
                 counts, escaped = w.run(13, escaped=with_escaped)
-                finish(w)
+                finish(w.t)
                 assert np.array_equal(rows_of(w, counts), want), f"illum_scratch_bytes = {cap}"
                 assert escaped is None or np.array_equal(u32_of(escaped)[:w.S], want_escaped), f"illum_scratch_bytes = {cap}"
     finally:
@@ -326,7 +308,7 @@ def test_split_calls_give_the_rows_of_the_one_call(worlds, shape):
     head, head_escaped = w.run(24, n_sources=2)
     tail, tail_escaped = w.run(24, n_sources=3, d_src=w.d_src[2 * 32:], first_source=2)
     wrong, _ = w.run(24, n_sources=3, d_src=w.d_src[2 * 32:], first_source=0)
-    finish(w)
+    finish(w.t)
     assert np.array_equal(rows_of(w, head, 2), want[:2]) and np.array_equal(u32_of(head_escaped)[:2], want_escaped[:2])
     assert np.array_equal(rows_of(w, tail, 3), want[2:5]) and np.array_equal(u32_of(tail_escaped)[:3], want_escaped[2:5])
     assert (rows_of(w, wrong, 3) != want[2:5]).any(axis=1).all(), "first_source does not reach the random numbers"
@@ -343,7 +325,7 @@ def test_two_streams_into_one_matrix(worlds):
         w.run(24, counts=counts, escaped=escaped, stream=s1)
         w.run(13, counts=counts, escaped=escaped, stream=s2)
     s1.synchronize(); s2.synchronize()
-    finish(w)
+    finish(w.t)
     a, b = w.want(24), w.want(13)
     assert np.array_equal(rows_of(w, counts), 3 * (a[0] + b[0])) and np.array_equal(u32_of(escaped)[:w.S], 3 * (a[1] + b[1]))
 
@@ -363,7 +345,7 @@ def pose_want(oracle, rc, f, grid):
     if f not in _pose_cache:
         o = oracle.Scene()
         b = o.add_blas(dyn.sphere(rc))
-        for i, x in enumerate(reb.frame_xf(rc, dyn.SMALL, f)):
+        for i, x in enumerate(dyn.rebuild_frame_xf(rc, dyn.SMALL, f)):
             o.add_instance(b, x, i)
         o.build()
         _pose_cache[f] = o
@@ -375,11 +357,11 @@ def pose_want(oracle, rc, f, grid):
 def test_captured_frame_follows_the_scene_and_the_lamps(rc, oracle):
     import torch
     grid = 24
-    a = reb.Frames(rc, dyn.SMALL, 1)
+    a = dyn.Frames(rc, dyn.SMALL, 1)
     n = a.t.n_primitives()
-    frames = (1, reb.TIE_FRAME, 0)
+    frames = (1, dyn.TIE_FRAME, 0)
     wants = {f: pose_want(oracle, rc, f, grid) for f in (0,) + frames}
-    assert not np.array_equal(wants[0][0], wants[1][0]) and not np.array_equal(wants[1][0], wants[reb.TIE_FRAME][0])
+    assert not np.array_equal(wants[0][0], wants[1][0]) and not np.array_equal(wants[1][0], wants[dyn.TIE_FRAME][0])
     d_src = dev_bytes(pose_sources(0))
     d_counts = torch.full((5 * n,), 0x55, dtype=torch.int32, device="cuda")
     d_escaped = torch.full((5,), 0x55, dtype=torch.int32, device="cuda")
@@ -423,11 +405,11 @@ def test_captured_frame_follows_the_scene_and_the_lamps(rc, oracle):
 # ---- 11. behind a device-side geometry update on the same stream, no host wait ----------------------------------------------------------------
 def test_after_a_geometry_update_on_the_same_stream(rc, oracle):
     import torch
-    spec = dfm.Spec(rc, "144")
+    spec = dyn.Spec(rc, "144")
     t, hs = spec.build(rc)
     f, grid = 3, 24
     o = oracle.Scene()
-    b = o.add_blas(dfm.deform(spec.soups[0], f))
+    b = o.add_blas(dyn.deform(spec.soups[0], f))
     for i, x in enumerate(spec.xf):
         o.add_instance(b, x, i)
     o.build()
@@ -437,7 +419,7 @@ def test_after_a_geometry_update_on_the_same_stream(rc, oracle):
     assert (want.sum(axis=1) > 0).all() and (want_escaped > 0).all() and not np.array_equal(want, before)
     n = t.n_primitives()
     s = torch.cuda.Stream()
-    d_soup = torch.from_numpy(dfm.deform(spec.soups[0], f)).cuda()
+    d_soup = torch.from_numpy(dyn.deform(spec.soups[0], f)).cuda()
     d_src, d_counts, d_escaped = dev_bytes(src), zeros_u32(3 * n), zeros_u32(3)
     for buf in (d_soup, d_src, d_counts, d_escaped):
         buf.record_stream(s)
@@ -461,7 +443,7 @@ def test_non_finite_sources_give_the_composed_rows(worlds, shape):
     d_src = dev_bytes(src)
     want, want_escaped, _ = w.composed(13, n_sources=5, d_src=d_src)
     counts, escaped = w.run(13, n_sources=5, d_src=d_src)
-    finish(w)
+    finish(w.t)
     assert np.array_equal(rows_of(w, counts, 5), want) and np.array_equal(u32_of(escaped)[:5], want_escaped)
     assert (want.sum(axis=1, dtype=np.uint64) + want_escaped == 169).all()
 
@@ -520,7 +502,7 @@ def test_errors_and_empty_work(rc, worlds):
     assert illum(t._h, src, S, 13, P(out), np_t) == RC_ERR_NOT_SYNCED and stage(t._h, src, S, 13, P(rays)) == RC_ERR_NOT_SYNCED
     t.sync()
     # transforms-dirty from the device, no refit yet
-    d_xf = tdirs.f32_tensor(dyn.frame_xf(rc, (2, 2, 1), 2))
+    d_xf = f32_tensor(dyn.frame_xf(rc, (2, 2, 1), 2))
     t.update_transforms_device(h, d_xf)
     assert illum(t._h, src, S, 13, P(out), np_t) == RC_ERR_NOT_SYNCED and stage(t._h, src, S, 13, P(rays)) == RC_ERR_NOT_SYNCED
     assert untouched()

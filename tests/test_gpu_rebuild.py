@@ -22,93 +22,14 @@ spheres in the rebuilt leaf records and kernels 3, 5 and 6 on the rebuilt tree a
 import numpy as np
 import pytest
 
+from dynamic_kit import Frames, LARGE, N_FRAMES, OracleFrame, PATHS, PATH_IDS, SMALL, TIE_FRAME, assert_same_scene, camera_rays, dev_bytes, fresh_twin
+from dynamic_kit import hits_of, initial_xf, make_scene, rebuild_frame_xf as frame_xf, rebuild_oracle_frame as oracle_frame, sphere
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal
-from test_gpu_dynamic import LARGE, SMALL, assert_same_scene, camera_rays, dev_bytes, hits_of, initial_xf, make_scene, records_differing, sphere
 
 pytestmark = pytest.mark.gpu
 
-N_FRAMES = 4
-SCALED_FRAME = 2      # the frame whose linear part carries a non-uniform scale
-TIE_FRAME = 3         # the frame with three coincident instances
 RC_ERR_INVALID_ARGUMENT, RC_ERR_NOT_SYNCED = 1, 6
-PATHS = [(SMALL, 1), (SMALL, 0), (LARGE, 0)]  # (lattice, tlas_rebuild_fused): the single-workgroup kernel applies up to 256 instances
-PATH_IDS = ["144-fused", "144-chain", "864-chain"]
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0
-    return raycore_jl_amd
-
-
-def frame_xf(rc, dims, f):
-    xf = rc.scenes.lattice_transforms(*dims, 1.5 + 0.2 * f, 100 + 7 * f)[0]
-    n = len(xf)
-    m = xf.reshape(n, 3, 4).copy()
-    if f == SCALED_FRAME:
-        m[:, :, :3] *= np.array([1.0, 0.7, 1.3], dtype=np.float32)
-    perm = np.random.Generator(np.random.Philox(key=900 + f)).permutation(n)
-    m[:, :, 3] = m[perm][:, :, 3]
-    if f == TIE_FRAME:
-        m[1] = m[0]
-        m[n - 1] = m[0]
-    return np.ascontiguousarray(m.reshape(n, 12))
-
-
-class OracleFrame:
-    def __init__(self, oracle, rc, xf, rays, blas=None, owner=None):
-        o = oracle.Scene()
-        blas = blas if blas is not None else [sphere(rc)]
-        ids = [o.add_blas(b) for b in blas]
-        for i, x in enumerate(xf):
-            o.add_instance(ids[0 if owner is None else owner[i]], x, i)
-        o.build()
-        self.nodes, self.instances, self.bound = o.tlas_nodes, o.instances, o.world_bound
-        self.closest = o.trace(rays, nthreads=8)
-        self.any = o.trace(rays, mode="any", nthreads=8)
-
-
-_oracle_cache = {}
-
-
-def oracle_frame(oracle, rc, dims, f):
-    """The oracle built from scratch with frame f's transforms (f = -1: the initial ones), with the conditions on the inputs asserted on
-    the oracle's output alone."""
-    key = (dims, f)
-    if key not in _oracle_cache:
-        want = OracleFrame(oracle, rc, initial_xf(rc, dims) if f < 0 else frame_xf(rc, dims, f), camera_rays(rc, dims))
-        if f >= 0:
-            prev = oracle_frame(oracle, rc, dims, f - 1)
-            n = len(want.instances)
-            moved = float(np.mean(want.nodes["child1"][n - 1:] != prev.nodes["child1"][n - 1:]))
-            hit_fraction = float(want.closest["hit"].mean())
-            changed = records_differing(want.closest, prev.closest) / len(want.closest)
-            print(f"inputs {dims} frame {f}: leaf slots with another instance {moved:.3f}, oracle hit fraction {hit_fraction:.3f}, "
-                  f"records changed vs previous frame {changed:.3f}")
-            assert moved >= 0.9, (dims, f, moved)
-            assert hit_fraction >= 0.2, (dims, f, hit_fraction)
-            assert changed >= 0.1, (dims, f, changed)
-        _oracle_cache[key] = want
-    return _oracle_cache[key]
-
-
-def fresh_twin(rc, xf, blas=None, owner=None, handles=None):
-    """A new scene with the same pushes and these transforms, built by the structural sync (`handles`: a list that receives the pushes')."""
-    t = rc.TLAS()
-    n = len(xf)
-    ids = np.arange(n, dtype=np.uint32)
-    blas = blas if blas is not None else [sphere(rc)]
-    owner = np.zeros(n, dtype=np.int64) if owner is None else np.asarray(owner)
-    for k, b in enumerate(blas):  # contiguous ranges per BLAS, in order
-        bi = t.add_geometry(b)
-        sel = owner == k
-        handle = t.push_instances(bi, xf[sel], ids[sel])
-        if handles is not None:
-            handles.append(handle)
-    t.sync()
-    assert t.last_sync_action == "rebuild"
-    return t
 
 
 def assert_scene_is_oracle(t, want, what):
@@ -128,34 +49,6 @@ def check_frame(rc, t, want, twin, rays, got, got_any, what):
     assert t.sync().last_sync_action == "noop", what  # the asynchronous rebuild left nothing pending
     assert_scene_is_oracle(t, want, what)
     assert_same_scene(t, twin, what)
-
-
-class Frames:
-    """The device buffers of one scene's animation on one stream."""
-
-    def __init__(self, rc, dims, fused):
-        import torch
-        self.torch, self.rc, self.dims = torch, rc, dims
-        self.t, (self.h,), _ = make_scene(rc, dims)
-        self.t.set_option("tlas_rebuild_fused", fused)
-        assert self.t.get_option("tlas_rebuild_fused") == fused
-        self.rays = camera_rays(rc, dims)
-        self.n = len(self.rays)
-        self.frames = [torch.from_numpy(frame_xf(rc, dims, f)).cuda() for f in range(N_FRAMES)]
-        self.d_xf = self.frames[0].clone()
-        self.d_rays = dev_bytes(torch, self.rays)
-        self.d_hits, self.d_any = (torch.zeros(self.n * 32, dtype=torch.uint8, device="cuda") for _ in range(2))
-        self.s = torch.cuda.Stream()
-        for buf in (self.d_xf, self.d_rays, self.d_hits, self.d_any, *self.frames):
-            buf.record_stream(self.s)
-        torch.cuda.synchronize()
-
-    def trace(self, st):
-        self.t.trace_device(self.d_rays.data_ptr(), self.d_hits.data_ptr(), self.n, stream=st)
-        self.t.trace_device(self.d_rays.data_ptr(), self.d_any.data_ptr(), self.n, mode="any", stream=st)
-
-    def hits(self):
-        return hits_of(self.rc, self.d_hits), hits_of(self.rc, self.d_any)
 
 
 # ---- 1. copy -> update -> rebuild -> trace on one stream, no host synchronisation between them -------------------------------------------

@@ -6,43 +6,21 @@ import numpy as np
 import pytest
 
 import bounce_model as bm
-from helpers import build_oracle, build_product
+from gpu_kit import POISON, check_words, f32_tensor, poisoned
+from gpu_kit import rc  # noqa: F401
+from helpers import build_product
+from worlds import C3World, three_shapes
 
 pytestmark = pytest.mark.gpu
 
 LIGHTS = np.array([[10, 10, 10], [-4, 6, 3], [3, 2.5, -6], [2, 20, 2]], np.float32)
 BIAS = 1e-3
 N_RAYS = 63_997  # 320 x 200 less three: n * L ends in the middle of a chunk for every L used here
-POISON = 0xAB
-GUARD = 256      # poisoned bytes behind every output: nothing may be written past n * L
 
 
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
-
-
-def poisoned(nbytes):
-    import torch
-    return torch.full((nbytes + GUARD,), POISON, dtype=torch.uint8, device="cuda")
-
-
-def lights_tensor(lights):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(lights, dtype=np.float32)).cuda()
-
-
-def oracle_visibility(o, rays, lights):
-    """(primary hits, visible[n, L]) from the oracle alone: trace, then per light shadow_rays, the reference's t_max > 0 gate and any_hit.
+def oracle_visibility(o, rays, want, lights):
+    """visible[n, L] from the oracle alone: its primary hits `want`, then per light shadow_rays, the reference's t_max > 0 gate and any_hit.
     On these clean worlds every hit's shadow ray passes the gate (tests/test_gpu_stage_fuzz.py has the scenes where it does not)."""
-    want = o.trace(rays, nthreads=16)
     lit = want["hit"] == 1
     vis = np.zeros((len(rays), len(lights)), np.uint8)
     for l, light in enumerate(lights):
@@ -50,24 +28,18 @@ def oracle_visibility(o, rays, lights):
         assert np.all(shadow_rays["tmax"][lit] > 0), f"light {l}: a hit slot's shadow ray has a t_max that is not > 0"
         shadow = o.trace(shadow_rays, mode="any", nthreads=16)
         vis[:, l] = lit & (shadow_rays["tmax"] > 0) & (shadow["hit"] == 0)
-    return want, vis
+    return vis
 
 
-class World:
+class World(C3World):
     def __init__(self, rc, oracle, lattice, kernel=None):
-        self.cfg = rc.scenes.config_c3(lon=16, bands=9, lattice=lattice)
-        self.t, self.o = build_product(rc, self.cfg), build_oracle(oracle, self.cfg)
-        if kernel is not None:
-            self.t.set_option("kernel", kernel)
-        self.rays = rc.scenes.c3_primary_rays(self.cfg, 320, 200)[:N_RAYS]
-        self.hits, self.visible = oracle_visibility(self.o, self.rays, LIGHTS)
-        # a degenerate input cannot pass: enough hits and misses, and every light both shadowed and seen
-        lit = self.hits["hit"] == 1
-        assert lit.sum() >= 1000 and (~lit).sum() >= 1000, (lit.sum(), (~lit).sum())
+        super().__init__(rc, oracle, lattice, kernel)
+        self.visible = oracle_visibility(self.o, self.rays, self.hits, LIGHTS)
+        # a degenerate input cannot pass: (enough hits and misses, and) every light both shadowed and seen
+        lit = self.lit
         for l in range(len(LIGHTS)):
             seen = int(self.visible[lit, l].sum())
             assert seen >= 100 and int(lit.sum()) - seen >= 100, (l, seen, int(lit.sum()) - seen)
-        self.d_rays, self.d_hits = dev(self.rays), dev(self.hits)
 
     def fused(self, lights_t, n_lights):
         """One call on the current stream into a poisoned buffer; returns the tensor (n * n_lights bytes + the guard)."""
@@ -78,22 +50,12 @@ class World:
 
 def check(out, want, what):
     """`out`: a tensor from World.fused, `want`: (n, L) bytes."""
-    got = out.cpu().numpy()
-    nl = want.size
-    assert np.all(got[nl:] == POISON), f"{what}: bytes behind the output were written"
-    bad = np.nonzero(got[:nl] != want.reshape(-1))[0]
-    assert len(bad) == 0, f"{what}: {len(bad)} of {nl} bytes differ, first items {bad[:8]}: got {got[bad[:8]]} want {want.reshape(-1)[bad[:8]]}"
+    check_words(out, want, np.uint8, what)
 
 
 @pytest.fixture(scope="module")
 def worlds(rc, oracle):
-    w = {"lds": World(rc, oracle, (3, 3, 2)),            # 18 instances: the whole top level in LDS
-         "partial": World(rc, oracle, (7, 7, 6)),        # 294 instances: only the top of the TLAS is staged
-         "plain": World(rc, oracle, (3, 3, 2), kernel=3)}  # the small scene again through the 256-thread kernel
-    assert w["lds"].t.n_instances() == 18 and w["partial"].t.n_instances() == 294
-    yield w
-    for x in w.values():
-        x.t.free()
+    yield from three_shapes(World, rc, oracle)
 
 
 # ---- (a), (c): every byte against the oracle, in the three shapes ------------------------------------------------------------------
@@ -102,7 +64,7 @@ def worlds(rc, oracle):
 def test_every_byte_matches_the_oracle(worlds, shape, n_lights):
     import torch
     w = worlds[shape]
-    out = w.fused(lights_tensor(LIGHTS[:n_lights]), n_lights)
+    out = w.fused(f32_tensor(LIGHTS[:n_lights]), n_lights)
     torch.cuda.synchronize()
     w.t.wait_for_gpu()  # (a stack overflow would be reported here)
     check(out, w.visible[:, :n_lights], f"{shape} L={n_lights}")
@@ -129,7 +91,7 @@ def test_composed_product_path_gives_the_same_bytes(worlds, shape):
                 torch.cuda.synchronize()
                 shadow = d_sh.cpu().numpy()[:n * 32].view(bm.HIT_DT)
                 composed[:, l] = (w.hits["hit"] == 1) & (shadow["hit"] == 0)
-            out = w.fused(lights_tensor(LIGHTS), len(LIGHTS))
+            out = w.fused(f32_tensor(LIGHTS), len(LIGHTS))
             torch.cuda.synchronize()
             check(out, composed, f"{shape} entry_cull={cull} against the composed path")
             check(out, w.visible, f"{shape} entry_cull={cull} against the oracle")
@@ -143,7 +105,7 @@ def test_empty_work_and_argument_checks(rc, worlds):
     from raycore_jl_amd._capi import lib
     w = worlds["lds"]
     f, h = lib().rc_shadow_visibility_device, w.t._h
-    d_l = lights_tensor(LIGHTS)
+    d_l = f32_tensor(LIGHTS)
     out = poisoned(N_RAYS * 4)
     r, hh, lp, op = w.d_rays.data_ptr(), w.d_hits.data_ptr(), d_l.data_ptr(), out.data_ptr()
     INV, NS = 1, 6
@@ -175,7 +137,7 @@ def test_captured_call_follows_the_lights(worlds):
     w = worlds["partial"]
     t, n, L = w.t, N_RAYS, len(LIGHTS)
     s = torch.cuda.Stream()
-    d_l = lights_tensor(LIGHTS)
+    d_l = f32_tensor(LIGHTS)
     d_hits = poisoned(n * 32)
     out = poisoned(n * L)
 
@@ -194,7 +156,7 @@ def test_captured_call_follows_the_lights(worlds):
     perm = [2, 0, 3, 1]
     for lights, cols, what in ((None, [0, 1, 2, 3], "replay"), (LIGHTS[perm], perm, "replay with permuted lights")):
         if lights is not None:
-            d_l.copy_(lights_tensor(lights))  # in place: the graph holds the tensor's address
+            d_l.copy_(f32_tensor(lights))  # in place: the graph holds the tensor's address
         out.fill_(POISON)
         d_hits.fill_(POISON)
         torch.cuda.synchronize()
@@ -214,7 +176,7 @@ def test_two_streams_at_once(worlds):
     w = worlds["lds"]
     sets = ([0, 1, 2], [3, 1])
     streams = [torch.cuda.Stream() for _ in sets]
-    d_ls = [lights_tensor(LIGHTS[c]) for c in sets]
+    d_ls = [f32_tensor(LIGHTS[c]) for c in sets]
     outs = [[poisoned(N_RAYS * len(c)) for _ in range(3)] for c in sets]
     torch.cuda.synchronize()  # the buffers are filled on the current stream: done before the other streams write them
     for rep in range(3):  # enqueued alternately, never waited for in between
@@ -253,7 +215,7 @@ def test_wavefront_fused_shadows(rc, worlds):
         del wf
     for b in range(depth):
         assert 0 < want[b].sum() < want[b].size, b
-    d_l = lights_tensor(LIGHTS)
+    d_l = f32_tensor(LIGHTS)
     s = torch.cuda.Stream()
     wf = rc.wavefront.WavefrontPaths(t, width, height, spp, depth, cam, lights=d_l, fused_shadows=True, seed=seed)
     assert wf.shadow_rays == [] and wf.shadow_hits == [] and len(wf.visible) == depth and wf.lights is d_l and wf.n_lights == L
@@ -276,7 +238,7 @@ def test_wavefront_fused_shadows(rc, worlds):
     perm = [1, 3, 0, 2]
     for lights, cols, what in ((None, [0, 1, 2, 3], "replay"), (LIGHTS[perm], perm, "replay after an in-place edit of the lights")):
         if lights is not None:
-            d_l.copy_(lights_tensor(lights))
+            d_l.copy_(f32_tensor(lights))
         for v in wf.visible:
             v.fill_(POISON)
         torch.cuda.synchronize()

@@ -9,7 +9,10 @@ import pytest
 
 import bounce_model as bm
 import soft_shadow_model as sm
-from helpers import build_oracle, build_product
+from gpu_kit import POISON, check_words, dev, f32_tensor, poisoned, words_of, zeroed
+from gpu_kit import rc  # noqa: F401
+from helpers import build_product
+from worlds import C3World, three_shapes
 
 pytestmark = pytest.mark.gpu
 
@@ -18,57 +21,18 @@ RADII = np.array([1.0, 0.5, 1.0], np.float32)
 BIAS = 1e-3
 N_RAYS = 63_997  # 320 x 200 less three: with L = 3, n * L * S ends inside a 128-item chunk for S = 2 and 5 (remainders 110 and 83)
 SEED = 0x50F7
-POISON = 0xAB
-GUARD = 256      # poisoned bytes behind every output: nothing may be written past it
 DUMMY = np.array([0, 0, 0, 0, 0, 0, 1, 0], np.float32).view(np.uint32)
 
 
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
-
-
-def f32_tensor(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-
-
-def poisoned(nbytes):
-    import torch
-    return torch.full((nbytes + GUARD,), POISON, dtype=torch.uint8, device="cuda")
-
-
-def count_buffer(n_counts):
-    """n_counts zeroed u32 followed by the poisoned guard (the call accumulates: the caller zeroes)."""
-    out = poisoned(n_counts * 4)
-    out[:n_counts * 4] = 0
-    return out
-
-
-class World:
+class World(C3World):
     def __init__(self, rc, oracle, lattice, kernel=None):
-        self.cfg = rc.scenes.config_c3(lon=16, bands=9, lattice=lattice)
-        self.t, self.o = build_product(rc, self.cfg), build_oracle(oracle, self.cfg)
-        if kernel is not None:
-            self.t.set_option("kernel", kernel)
-        self.rays = rc.scenes.c3_primary_rays(self.cfg, 320, 200)[:N_RAYS]
-        self.hits = self.o.trace(self.rays, nthreads=16)
-        self.lit = self.hits["hit"] == 1
+        super().__init__(rc, oracle, lattice, kernel)
         self._want = {}
-        # a degenerate input cannot pass: enough hits and misses, and for every light fully shadowed, fully lit and penumbra slots
-        assert self.lit.sum() >= 1000 and (~self.lit).sum() >= 1000, (self.lit.sum(), (~self.lit).sum())
+        # a degenerate input cannot pass: (enough hits and misses, and) for every light fully shadowed, fully lit and penumbra slots
         c = self.want(5)[self.lit]
         for l in range(len(LIGHTS)):
             zero, full = int((c[:, l] == 0).sum()), int((c[:, l] == 5).sum())
             assert zero >= 20 and full >= 20 and len(c) - zero - full >= 20, (l, zero, full, len(c) - zero - full)
-        self.d_rays, self.d_hits = dev(self.rays), dev(self.hits)
 
     def want(self, samples, lights=LIGHTS, radii=RADII, seed=SEED, depth=0, path_in=None, path_base=0):
         """(n, L) expected counts from the oracle alone: the model's rays, oracle.trace(mode="any"), the gate, the sum.  Computed once."""
@@ -84,7 +48,7 @@ class World:
     def fused(self, lights_t, radii_t, n_lights, samples, out=None, seed=SEED, depth=0, d_path_in=None, path_base=0, stream=None):
         """One call into a zeroed count buffer with a poisoned guard behind it (or into `out`); returns the tensor."""
         if out is None:
-            out = count_buffer(N_RAYS * n_lights)
+            out = zeroed(N_RAYS * n_lights, 4)
         self.t.soft_shadow_visibility_device(self.d_rays.data_ptr(), self.d_hits.data_ptr(), N_RAYS, lights_t.data_ptr(), radii_t.data_ptr(), n_lights,
                                              samples, out.data_ptr(), seed=seed, depth=depth, bias=BIAS, d_path_in=d_path_in, path_base=path_base,
                                              stream=stream)
@@ -99,29 +63,14 @@ class World:
         return out.cpu().numpy()[:N_RAYS * n_lights].reshape(N_RAYS, n_lights)
 
 
-def counts_of(out, n_counts):
-    got = out.cpu().numpy()
-    assert np.all(got[n_counts * 4:] == POISON), "bytes behind the counts were written"
-    return got[:n_counts * 4].view(np.uint32)
-
-
 def check(out, want, what):
     """`out`: a tensor from World.fused, `want`: (n, L) counts."""
-    got = counts_of(out, want.size)
-    flat = np.asarray(want, np.uint32).reshape(-1)
-    bad = np.nonzero(got != flat)[0]
-    assert len(bad) == 0, f"{what}: {len(bad)} of {want.size} counts differ, first items {bad[:8]}: got {got[bad[:8]]} want {flat[bad[:8]]}"
+    check_words(out, want, np.uint32, what)
 
 
 @pytest.fixture(scope="module")
 def worlds(rc, oracle):
-    w = {"lds": World(rc, oracle, (3, 3, 2)),            # 18 instances: the whole top level in LDS
-         "partial": World(rc, oracle, (7, 7, 6)),        # 294 instances: only the top of the TLAS is staged
-         "plain": World(rc, oracle, (3, 3, 2), kernel=3)}  # the small scene again through the 256-thread kernel
-    assert w["lds"].t.n_instances() == 18 and w["partial"].t.n_instances() == 294
-    yield w
-    for x in w.values():
-        x.t.free()
+    yield from three_shapes(World, rc, oracle)
 
 
 # ---- 1: every count against the oracle, in the three shapes -------------------------------------------------------------------------
@@ -136,7 +85,7 @@ def test_counts_equal_the_oracles(worlds, shape, n_lights, samples):
     w.t.wait_for_gpu()  # (a stack overflow would be reported here)
     want = w.want(samples)[:, :n_lights]  # (a sample depends on (seed, path, depth, l, s), not on how many lights there are)
     check(out, want, f"{shape} L={n_lights} S={samples}")
-    got = counts_of(out, N_RAYS * n_lights).reshape(N_RAYS, n_lights)
+    got = words_of(out, N_RAYS * n_lights, np.uint32).reshape(N_RAYS, n_lights)
     assert not got[~w.lit].any(), "a slot whose primary ray missed has visible samples"
     assert got.max() <= samples
 
@@ -258,7 +207,7 @@ def test_captured_call_follows_lights_and_radii(worlds):
     t, L, S = w.t, 3, 2
     s = torch.cuda.Stream()
     d_l, d_r = f32_tensor(LIGHTS), f32_tensor(RADII)
-    out = count_buffer(N_RAYS * L)
+    out = zeroed(N_RAYS * L, 4)
     torch.cuda.synchronize()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
@@ -295,7 +244,7 @@ def test_two_streams_at_once(worlds):
     seeds, L, S = (SEED, 0xBEEF00000001), 3, 2
     streams = [torch.cuda.Stream() for _ in seeds]
     d_l, d_r = f32_tensor(LIGHTS), f32_tensor(RADII)
-    outs = [[count_buffer(N_RAYS * L) for _ in range(3)] for _ in seeds]
+    outs = [[zeroed(N_RAYS * L, 4) for _ in range(3)] for _ in seeds]
     torch.cuda.synchronize()  # the buffers are filled on the current stream: done before the other streams write them
     for rep in range(3):  # enqueued alternately, never waited for in between
         for k, seed in enumerate(seeds):
@@ -378,4 +327,4 @@ def test_light_on_a_hit_point_is_gated(worlds):
     torch.cuda.synchronize()
     w.t.wait_for_gpu()
     check(out, want, "a light on a hit point")
-    assert counts_of(out, N_RAYS * 3).reshape(N_RAYS, 3)[k, 1] == 0
+    assert words_of(out, N_RAYS * 3, np.uint32).reshape(N_RAYS, 3)[k, 1] == 0

@@ -6,67 +6,14 @@ one ray pushes and pops in the same pass.  Everything is compared with the oracl
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product
+from scene_kit import BOUNDARY, GRID, LDS_STACK, MID_STACK, VIEWDIR, chain, chain_cfg, corner_rays, max_depth
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-MID_STACK, LDS_STACK = 16, 24  # kMidStack (kernels 5, 6, the 768-thread driver shells), kLdsStack (kernels 3, 0, the plain driver shell)
 KERNELS = ((-1, 1), (3, 1), (5, 1), (6, 1), (-1, 0), (3, 0), (5, 0), (6, 0))   # (kernel, stack16)
-
-
-def chain(levels, fat=0.3):
-    """The LBVH chain of test_deep_trees_use_the_stack_spill_path: three triangles per level, one leaf split off per level; rays through
-    the shared corner keep one pending far child per level."""
-    tris = []
-    for j in range(1, levels + 1):
-        for axis in range(3):
-            size = 2.0 ** (-j + 1)
-            p = np.full(3, fat * size); p[axis] = size
-            q = p.copy(); q[(axis + 1) % 3] += 0.5 * size * fat
-            r = np.full(3, -1e-4 * (1 + 0.5 * j))
-            tris.append(np.concatenate([r, p, q]))
-    return np.array(tris, dtype=np.float32)
-
-
-def chain_cfg(rc, verts, n_inst=4, fillers=0):
-    xf = np.tile(rc.scenes.IDENTITY3x4, (4, 1)).astype(np.float32)
-    xf[1, [0, 5, 10]] = 0.5
-    xf[2, [0, 5, 10]] = 0.25
-    xf[3, [3, 7, 11]] = [0.01, 0.0, 0.0]
-    xf = xf[:n_inst]
-    if fillers:  # small copies on a lattice inside [1, 2]^3: a top level too large for the LDS shells, clear of the corner
-        f = np.tile(rc.scenes.IDENTITY3x4, (fillers, 1)).astype(np.float32)
-        k = np.arange(fillers)
-        f[:, [0, 5, 10]] = 0.05
-        f[:, 3], f[:, 7], f[:, 11] = 1.0 + 0.14 * (k // 49), 1.0 + 0.14 * ((k // 7) % 7), 1.0 + 0.14 * (k % 7)
-        xf = np.concatenate([xf, f])
-    return {"blas": [(verts, None)], "instances": [(1, xf, np.arange(len(xf), dtype=np.uint32))]}
-
-
-def corner_rays(rc, n=20000, seed=12):
-    g = rc.scenes.rng(seed)
-    org = g.uniform(-0.2, 0.0, size=(n, 3))
-    d = rc.scenes.normalize(g.uniform(0.05, 1.0, size=(n, 3)))
-    return rc.scenes.make_rays(org, d)
-
-
-def max_depth(o, rays):
-    """The deepest stack any of `rays` has at the start of a traversal step (the initial INVALID entry and the top-level sentinel included):
-    what the product's kernel 1 reports as stat2.  From the oracle's per-step record of each ray."""
-    m = 1
-    for i in range(len(rays)):
-        dp = o.trace_events(rays[i], cap=8192)[1]
-        if len(dp) > 1:
-            m = max(m, int(dp[:-1].max()))
-    return m
 
 
 def product_max_depth(t, rays, want):
@@ -87,11 +34,6 @@ def compare_all_kernels(t, rays, want, want_any, what):
     t.set_option("kernel", -1); t.set_option("stack16", 1)
 
 
-# Prefixes of chain(8) (24 triangles) under the deep test's instances.  Whole levels under its 4 instances give maximum depths 14, 17, 20,
-# 23, 26; a prefix that ends inside a level, or 3 of the 4 instances, gives the values between (chosen with the oracle on the CPU; the
-# test asserts each through the oracle and through stat2).
-BOUNDARY = {14: (4, 11), 15: (3, 13), 16: (4, 13), 17: (4, 14), 18: (3, 16),
-            22: (4, 19), 23: (4, 20), 24: (3, 22), 25: (4, 22), 26: (4, 23)}
 assert sorted(BOUNDARY) == [d + k for d in (MID_STACK, LDS_STACK) for k in (-2, -1, 0, 1, 2)]
 
 
@@ -170,9 +112,6 @@ def test_push_then_pop_in_one_pass(rc, oracle):
     compare_all_kernels(t, rays, want, want_any, "push-then-pop")
     t.set_option("kernel", 0)
     assert_hits_equal(t.trace(rays), want, "push-then-pop k0")
-
-
-VIEWDIR, GRID = np.array([0.3, 0.2, 1.0], dtype=np.float32), 192
 
 
 @pytest.mark.parametrize("shell", ["lds", "plain", "partial"])

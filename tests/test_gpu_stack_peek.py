@@ -7,20 +7,14 @@ compared with the oracle bit for bit, closest and any, 16- and 32-bit stack entr
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_hits_equal, build_oracle, build_product
-from test_gpu_stack_boundary import BOUNDARY, GRID, LDS_STACK, MID_STACK, VIEWDIR, chain, chain_cfg, corner_rays, max_depth
+from scene_kit import BOUNDARY, GRID, LDS_STACK, MID_STACK, VIEWDIR, chain, chain_cfg, corner_rays, max_depth
 
 pytestmark = pytest.mark.gpu
 
 N_RAYS = 4096
 SHAPES = ((3, 1), (5, 1), (6, 1), (3, 0), (5, 0), (6, 0))   # (kernel, stack16)
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 @pytest.fixture(scope="module")

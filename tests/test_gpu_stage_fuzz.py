@@ -16,27 +16,18 @@ import numpy as np
 import pytest
 
 import bounce_model as bm
+from gpu_kit import GUARD, POISON, dev, poisoned
+from gpu_kit import rc  # noqa: F401
 from helpers import assert_f32_bits_equal, assert_hits_equal, assert_rays_equal, build_oracle, build_product
-from test_gpu_fuzz import hostile_transform
-from test_oracle_independent_f64 import scenes_module
-from test_oracle_mesh import grid_mesh
+from scene_kit import grid_mesh, hostile_transform, scenes_module
 
 gpu = pytest.mark.gpu
 
-POISON = 0xAB
-GUARD = 256
 BIASES = (1e-3, 0.0, -1e-3)
 SEEDS = list(range(24))
 FIXED = ["nan", "partial"]
 N_VIS = 3997           # rays of the fixed scenes: the largest n of the fused visibility cases
 OUTSIDE_LIGHT = np.array([6.0, 7.0, 5.0], np.float32)
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 # ---- scenes (numpy only) ----------------------------------------------------------------------------------------------------------
@@ -220,14 +211,6 @@ def test_scenes_cover_the_cases():
 
 
 # ---- device buffers ---------------------------------------------------------------------------------------------------------------
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def poisoned(nbytes):
-    import torch
-    return torch.full((nbytes + GUARD,), POISON, dtype=torch.uint8, device="cuda")
 
 
 def fetch(buf, nbytes, dtype, what):

@@ -9,16 +9,11 @@ holds about 2 GB of device memory while the scene lives."""
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 N_RAYS = 8192
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 def chain(levels, fat=0.3):

@@ -5,14 +5,9 @@ flat-array leak checks become the geometry / primitive / node counters of rc_cou
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0
-    return raycore_jl_amd
 
 
 def sphere(rc, n):

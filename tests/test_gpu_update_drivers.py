@@ -10,9 +10,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import test_gpu_deform as dfm
-import test_gpu_dynamic as dyn
-import test_gpu_rebuild as reb
+import dynamic_kit as dyn
+from gpu_kit import rc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,17 +21,10 @@ VIEWDIR = np.array([0.3, -0.2, -1.0], dtype=np.float32)
 GRID = 128
 
 
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0
-    return raycore_jl_amd
-
-
 # ---- 1. view factors after geometry updates -------------------------------------------------------------------------------------------------
 def vf_frame(verts, meta, f):
     """Frame f of the scene of test_view_factors_parity: deform() of tests/test_gpu_deform.py, the metadata rolled with the faces."""
-    return dfm.deform(verts, f), np.ascontiguousarray(np.roll(meta, 7 * (f + 1)))
+    return dyn.deform(verts, f), np.ascontiguousarray(np.roll(meta, 7 * (f + 1)))
 
 
 def test_view_factors_after_geometry_updates(rc, oracle):
@@ -145,9 +137,9 @@ def illumination_both_ways(rc, t, s):
 @pytest.mark.parametrize("fused", [1, 0])
 def test_illumination_after_device_rebuild(rc, oracle, fused):
     import torch
-    a = reb.Frames(rc, SMALL, fused)
-    f = reb.TIE_FRAME  # the widest pitch (the bound grows: a grid laid out from the old one misses the rim), permuted, three coincident instances
-    xf = reb.frame_xf(rc, SMALL, f)
+    a = dyn.Frames(rc, SMALL, fused)
+    f = dyn.TIE_FRAME  # the widest pitch (the bound grows: a grid laid out from the old one misses the rim), permuted, three coincident instances
+    xf = dyn.rebuild_frame_xf(rc, SMALL, f)
     o = oracle.Scene()
     b = o.add_blas(dyn.sphere(rc))
     for i, x in enumerate(xf):
@@ -166,17 +158,17 @@ def test_illumination_after_device_rebuild(rc, oracle, fused):
 
 def test_illumination_after_geometry_update(rc, oracle):
     import torch
-    spec = dfm.Spec(rc, "144")
+    spec = dyn.Spec(rc, "144")
     t, hs = spec.build(rc)
     f = 3
     o = oracle.Scene()
-    b = o.add_blas(dfm.deform(spec.soups[0], f))
+    b = o.add_blas(dyn.deform(spec.soups[0], f))
     for i, x in enumerate(spec.xf):
         o.add_instance(b, x, i)
     o.build()
     want = o.get_illumination(VIEWDIR, GRID, nthreads=8)
     s = torch.cuda.Stream()
-    d_soup = torch.from_numpy(dfm.deform(spec.soups[0], f)).cuda()
+    d_soup = torch.from_numpy(dyn.deform(spec.soups[0], f)).cuda()
     d_soup.record_stream(s)
     torch.cuda.synchronize()
     t.update_geometry_device_async(hs[-1], d_soup, stream=s.cuda_stream)

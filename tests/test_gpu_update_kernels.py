@@ -32,12 +32,11 @@ import numpy as np
 import pytest
 
 import cull_model as cm
-import test_gpu_deform as dfm
-import test_gpu_dynamic as dyn
-import test_gpu_rebuild as reb
+import dynamic_kit as dyn
+from gpu_kit import rc  # noqa: F401
+from gpu_kit import read_device
 from helpers import assert_hits_equal
-from test_gpu_entry_cull import grazing_rays
-from test_gpu_entry_fetch import read_device
+from scene_kit import grazing_rays
 
 LARGE, SMALL = dyn.LARGE, dyn.SMALL
 N_FRAMES = 4
@@ -57,12 +56,6 @@ def rcm():
     return raycore_jl_amd
 
 
-@pytest.fixture(scope="module")
-def rc(rcm):
-    assert rcm.device_count() > 0
-    return rcm
-
-
 # ---- the condition on the inputs, on the CPU alone ----------------------------------------------------------------------------------------
 _cache = {}
 
@@ -74,17 +67,17 @@ def cached(key, make):
 
 
 def spec_of(rcm, name):
-    return cached(("spec", name), lambda: dfm.Spec(rcm, name))
+    return cached(("spec", name), lambda: dyn.Spec(rcm, name))
 
 
 def oracle_state(oracle, rcm, kind, key, f):
     """-> (instances, BLAS descriptors, primitives) of the oracle built from scratch with frame f's inputs (f = -1: the initial ones)."""
     if kind == "deform":
-        w = dfm.want_frame(oracle, rcm, spec_of(rcm, key), f)
+        w = dyn.want_frame(oracle, rcm, spec_of(rcm, key), f)
         return w.instances, w.blas_descs, w.blas_prims
 
     def build():
-        xf = dyn.initial_xf(rcm, key) if f < 0 else (dyn if kind == "refit" else reb).frame_xf(rcm, key, f)
+        xf = dyn.initial_xf(rcm, key) if f < 0 else (dyn.frame_xf if kind == "refit" else dyn.rebuild_frame_xf)(rcm, key, f)
         o = oracle.Scene()
         b = o.add_blas(dyn.sphere(rcm))
         for i, x in enumerate(xf):
@@ -99,8 +92,8 @@ def oracle_closest(oracle, rcm, kind, key, f):
     if kind == "refit":
         return dyn.oracle_frame(oracle, rcm, key, f)
     if kind == "rebuild":
-        return reb.oracle_frame(oracle, rcm, key, f).closest
-    return dfm.want_frame(oracle, rcm, spec_of(rcm, key), f).closest
+        return dyn.rebuild_oracle_frame(oracle, rcm, key, f).closest
+    return dyn.want_frame(oracle, rcm, spec_of(rcm, key), f).closest
 
 
 def spheres_of(state):
@@ -117,7 +110,7 @@ def aimed_targets(oracle, rcm, name, f):
     spec = spec_of(rcm, name)
     _, descs, prims = oracle_state(oracle, rcm, "deform", name, f - 1)
     centre, radius, _ = cm.blas_radii(descs, prims)[0]
-    v = dfm.deform(spec.soups[0], f).astype(np.float64).reshape(-1, 3, 3)
+    v = dyn.deform(spec.soups[0], f).astype(np.float64).reshape(-1, 3, 3)
     dist = np.linalg.norm(v - centre, axis=2)
     far = v[np.arange(len(v)), dist.argmax(axis=1)]
     points = 0.8 * far + 0.2 * v.mean(axis=1)
@@ -153,7 +146,7 @@ UNREACHABLE = {("144", 1), ("864", 1), ("two", 1)}
 def aimed_want(oracle, rcm, name, f):
     """The oracle from scratch on the aimed rays of frame f (closest and any)."""
     spec = spec_of(rcm, name)
-    return cached(("aimed want", name, f), lambda: dfm.Want(oracle, spec.soups_of(f), spec.owner, spec.xf, aimed_rays(oracle, rcm, name, f)))
+    return cached(("aimed want", name, f), lambda: dyn.Want(oracle, spec.soups_of(f), spec.owner, spec.xf, aimed_rays(oracle, rcm, name, f)))
 
 
 def stale_sphere_count(prev_spheres, rays, hits, ids):
@@ -368,29 +361,29 @@ def test_matrix_after_refit(rc, oracle, dims):
 
 # ---- 2. update + rebuild_device_async -------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("dims, fused", reb.PATHS, ids=reb.PATH_IDS)
+@pytest.mark.parametrize("dims, fused", dyn.PATHS, ids=dyn.PATH_IDS)
 def test_matrix_after_rebuild(rc, oracle, dims, fused):
     import torch
-    a = reb.Frames(rc, dims, fused)
+    a = dyn.Frames(rc, dims, fused)
     batch = Batch(torch, a.rays, a.s)
     torch.cuda.synchronize()
     n_inst = len(a.frames[0])
     for f in range(N_FRAMES):
-        want = reb.oracle_frame(oracle, rc, dims, f)
-        twin = reb.fresh_twin(rc, reb.frame_xf(rc, dims, f))
+        want = dyn.rebuild_oracle_frame(oracle, rc, dims, f)
+        twin = dyn.fresh_twin(rc, dyn.rebuild_frame_xf(rc, dims, f))
         with torch.cuda.stream(a.s):
             a.d_xf.copy_(a.frames[f])
         a.t.update_transforms_device(a.h, a.d_xf, stream=a.s.cuda_stream)
         a.t.rebuild_device_async(stream=a.s.cuda_stream)
         enqueue_matrix(a.t, [batch], a.s)
         a.s.synchronize()
-        what = f"rebuild {reb.PATH_IDS[reb.PATHS.index((dims, fused))]} frame {f}"
+        what = f"rebuild {dyn.PATH_IDS[dyn.PATHS.index((dims, fused))]} frame {f}"
         first = check_matrix(rc, batch, want.closest, want.any, what)
         assert first == (twin.trace(a.rays).tobytes(), twin.trace(a.rays, mode="any").tobytes()), f"{what}: hits differ from the fresh twin's"
         assert_same_derived(a.t, twin, n_inst, what)
     side = default_dispatch_side(a.t)
     big = big_camera_rays(rc, dims, side)
-    w = cached(("big", "rebuild", dims, side), lambda: reb.OracleFrame(oracle, rc, reb.frame_xf(rc, dims, N_FRAMES - 1), big))
+    w = cached(("big", "rebuild", dims, side), lambda: dyn.OracleFrame(oracle, rc, dyn.rebuild_frame_xf(rc, dims, N_FRAMES - 1), big))
     check_default_dispatch(rc, a.t, a.s, big, w.closest, w.any, f"rebuild {dims} fused {fused}")
 
 
@@ -403,11 +396,11 @@ def test_matrix_after_geometry_update(rc, oracle, name, commit):
     spec = spec_of(rc, name)
     t, hs = spec.build(rc)
     n_inst = len(spec.xf)
-    first_want = dfm.want_frame(oracle, rc, spec, -1)
+    first_want = dyn.want_frame(oracle, rc, spec, -1)
     s = torch.cuda.Stream()
     camera = Batch(torch, spec.rays, s)
     aimed = Batch(torch, aimed_rays(oracle, rc, name, 2), s)
-    soups = [torch.from_numpy(dfm.deform(spec.soups[0], f)).cuda() for f in range(N_FRAMES)]
+    soups = [torch.from_numpy(dyn.deform(spec.soups[0], f)).cuda() for f in range(N_FRAMES)]
     d_soup = torch.empty_like(soups[0])
     for buf in (d_soup, *soups):
         buf.record_stream(s)
@@ -415,7 +408,7 @@ def test_matrix_after_geometry_update(rc, oracle, name, commit):
     commit_fn = t.refit_device_async if commit == "refit" else t.rebuild_device_async
     as_fresh = True
     for f in range(N_FRAMES):
-        want = dfm.want_frame(oracle, rc, spec, f)
+        want = dyn.want_frame(oracle, rc, spec, f)
         twin, _ = spec.build(rc, f)
         batches = [camera]
         extra = aimed_rays(oracle, rc, name, f) if f >= 1 else None  # (None also where no ray can tell a stale sphere: UNREACHABLE)
@@ -442,7 +435,7 @@ def test_matrix_after_geometry_update(rc, oracle, name, commit):
         assert_same_derived(t, twin, n_inst, what, same_topology=as_fresh)
     side = default_dispatch_side(t)
     big = big_camera_rays(rc, spec.dims, side)
-    w = cached(("big", "deform", name, side), lambda: dfm.Want(oracle, spec.soups_of(N_FRAMES - 1), spec.owner, spec.xf, big))
+    w = cached(("big", "deform", name, side), lambda: dyn.Want(oracle, spec.soups_of(N_FRAMES - 1), spec.owner, spec.xf, big))
     check_default_dispatch(rc, t, s, big, w.closest, w.any, f"{name} {commit}", any_records=as_fresh)
     if name == "144":  # the cull does spare entries on these rays (the counters of the stats kernel): the matrix did read the spheres
         set_shape(t, 5, 1, 1)
@@ -468,13 +461,13 @@ def test_captured_frames(rc, oracle, kind, key, kernel, s16):
         spec = spec_of(rc, key)
         t, hs = spec.build(rc)
         h, rays, n_inst = hs[-1], spec.rays, len(spec.xf)
-        src = [torch.from_numpy(dfm.deform(spec.soups[0], f)).cuda() for f in range(N_FRAMES)]
+        src = [torch.from_numpy(dyn.deform(spec.soups[0], f)).cuda() for f in range(N_FRAMES)]
         assert 0 < t.get_option("blas_top_k")
     else:
         t, (h,), cuts = dyn.make_scene(rc, key)
         twin, th, _ = dyn.make_scene(rc, key)
         rays, n_inst = dyn.camera_rays(rc, key), cuts[-1]
-        src = [torch.from_numpy((dyn if kind == "refit" else reb).frame_xf(rc, key, f)).cuda() for f in range(N_FRAMES)]
+        src = [torch.from_numpy((dyn.frame_xf if kind == "refit" else dyn.rebuild_frame_xf)(rc, key, f)).cuda() for f in range(N_FRAMES)]
     d_src = src[0].clone()
     batch = Batch(torch, rays, s, n_settings=1)
     for buf in (d_src, *src):
@@ -511,8 +504,8 @@ def test_captured_frames(rc, oracle, kind, key, kernel, s16):
             assert_hits_equal(got_c, dyn.oracle_frame(oracle, rc, key, f), f"{what}: closest vs oracle")
             assert (got_c.tobytes(), got_a.tobytes()) == (twin.trace(rays).tobytes(), twin.trace(rays, mode="any").tobytes()), f"{what}: hits differ from the host twin's"
         else:
-            want = reb.oracle_frame(oracle, rc, key, f) if kind == "rebuild" else dfm.want_frame(oracle, rc, spec, f)
-            twin = reb.fresh_twin(rc, reb.frame_xf(rc, key, f)) if kind == "rebuild" else spec.build(rc, f)[0]
+            want = dyn.rebuild_oracle_frame(oracle, rc, key, f) if kind == "rebuild" else dyn.want_frame(oracle, rc, spec, f)
+            twin = dyn.fresh_twin(rc, dyn.rebuild_frame_xf(rc, key, f)) if kind == "rebuild" else spec.build(rc, f)[0]
             assert_hits_equal(got_c, want.closest, f"{what}: closest vs oracle")
             assert_hits_equal(got_a, want.any, f"{what}: any vs oracle")
         assert_same_derived(t, twin, n_inst, what)

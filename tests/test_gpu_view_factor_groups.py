@@ -12,8 +12,11 @@ import numpy as np
 import pytest
 
 import vf_groups_model as model
-from helpers import assert_rays_equal, build_oracle, build_product
-from test_gpu_view_factors_host import room_cfg
+from gpu_kit import dev_u32, dev_u64, u64_of
+from gpu_kit import rc  # noqa: F401
+from helpers import assert_rays_equal, build_oracle
+from scene_kit import meta, room_cfg
+from worlds import VfWorld, room_world
 
 pytestmark = pytest.mark.gpu
 
@@ -21,33 +24,11 @@ U32_MAX = model.U32_MAX
 RC_ERR_INVALID_ARGUMENT = 1
 
 
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-def dev_u32(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x, np.uint32).view(np.int32)).cuda()
-
-
-def dev_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).cuda()
-
-
-def u64_of(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-class World:
+class World(VfWorld):
     """One scene in the product and in the oracle; the model's traces are computed once per (rays, seed, sampling, shard) and only read."""
 
     def __init__(self, rc, oracle, cfg):
-        self.rc, self.t, self.o = rc, build_product(rc, cfg), build_oracle(oracle, cfg)
-        self.n = self.t.n_primitives()
+        super().__init__(rc, oracle, cfg)
         assert self.n == len(self.o.blas_prims)
         self._traced = {}
 
@@ -74,10 +55,7 @@ class World:
 
 @pytest.fixture(scope="module")
 def room(rc, oracle):
-    w = World(rc, oracle, room_cfg(rc))
-    assert w.n == 192
-    yield w
-    w.t.free()
+    yield from room_world(World, rc, oracle)
 
 
 def room_groups(n, G):
@@ -183,12 +161,6 @@ def test_composed_path_on_the_device(rc, room, sampling):
 
 
 # ---- 5. irregular metadata, excluded groups, the analytic cube ------------------------------------------------------------------------------
-def meta(n):
-    m = np.arange(1, n + 1, dtype=np.uint32)
-    m[5:40] = 7
-    m[100:110] = 0
-    m[150] = n + 50
-    return m
 
 
 @pytest.mark.parametrize("sampling", ["uniform", "cosine"])
@@ -382,7 +354,7 @@ def test_captured_call_follows_rewritten_groups_and_weights(rc, oracle):
 
 def test_after_a_geometry_update_on_the_same_stream(rc, oracle):
     import torch
-    import test_gpu_deform as dfm
+    import dynamic_kit as dyn
     sc = rc.scenes
     verts = np.concatenate([sc.fan_sphere(12, 7, centre=(0, 0, 0), radius=0.5), sc.box_room((-1.5, -1.5, -1.5), (1.5, 1.5, 1.5), 2)])
     n = len(verts)
@@ -390,7 +362,7 @@ def test_after_a_geometry_update_on_the_same_stream(rc, oracle):
     t = rc.TLAS()
     h = t.push_instances(t.add_geometry(verts, m), sc.IDENTITY3x4[None], np.zeros(1, np.uint32))
     t.sync()
-    new_verts, new_meta = dfm.deform(verts, 1), np.ascontiguousarray(np.roll(m, 14))
+    new_verts, new_meta = dyn.deform(verts, 1), np.ascontiguousarray(np.roll(m, 14))
     o = oracle.Scene()
     o.add_instance(o.add_blas(new_verts, new_meta), sc.IDENTITY3x4, 0)
     o.build()

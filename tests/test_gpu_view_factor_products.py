@@ -10,8 +10,10 @@ import numpy as np
 import pytest
 
 import vf_products_model as model
-from helpers import build_oracle, build_product
-from test_gpu_view_factors_host import room_cfg
+from gpu_kit import dev_u32, dev_u64, finish, u64_of
+from gpu_kit import rc  # noqa: F401
+from scene_kit import bounce_inputs, distinct_x, full_range_x, meta, room_cfg
+from worlds import VfWorld, room_world
 
 pytestmark = pytest.mark.gpu
 
@@ -20,68 +22,8 @@ RC_ERR_INVALID_ARGUMENT = 1
 
 
 @pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-class World:
-    """One scene in the product and in the oracle; the oracle's matrices are computed once per (rays, seed) and are read-only."""
-
-    def __init__(self, rc, oracle, cfg):
-        self.rc, self.t, self.o = rc, build_product(rc, cfg), build_oracle(oracle, cfg)
-        self.n = self.t.n_primitives()
-        self._m = {}
-
-    def M(self, rays, seed):
-        if (rays, seed) not in self._m:
-            m = self.o.view_factors(rays, seed=seed, nthreads=8)
-            assert m.shape == (self.n, self.n) and m.dtype == np.uint32
-            m.setflags(write=False)
-            self._m[rays, seed] = m
-        return self._m[rays, seed]
-
-
-@pytest.fixture(scope="module")
 def room(rc, oracle):
-    w = World(rc, oracle, room_cfg(rc))
-    assert w.n == 192
-    yield w
-    w.t.free()
-
-
-def full_range_x(n, seed):
-    x = np.random.default_rng(seed).integers(0, 1 << 32, n, dtype=np.uint32)
-    x[:3] = (U32_MAX, 0, 1 << 31)
-    return x
-
-
-def distinct_x(n):
-    """Distinct per primitive in every byte lane: a sum that takes a lane of another source or of another group cannot equal the model's."""
-    x = (np.arange(1, n + 1, dtype=np.uint64) * np.uint64(2654435761) % np.uint64(1 << 32)).astype(np.uint32)
-    assert len(set(x.tolist())) == n
-    return x
-
-
-def dev_u32(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x, np.uint32).view(np.int32)).cuda()
-
-
-def dev_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).cuda()
-
-
-def u64_of(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def finish(w):
-    import torch
-    torch.cuda.synchronize()
-    w.t.wait_for_gpu()  # (a stack overflow would be reported here)
+    yield from room_world(VfWorld, rc, oracle)
 
 
 # ---- 1. identity with the matrix, in every shell ------------------------------------------------------------------------------------------
@@ -153,7 +95,7 @@ def test_shards_nulls_and_accumulation(rc, room):
     only = torch.zeros(2 * n, dtype=torch.int64, device="cuda")
     t.view_factor_products_device(d_x.data_ptr(), only.data_ptr(), None, 96, 11)
     t.view_factor_products_device(d_x.data_ptr(), None, only.data_ptr() + 8 * n, 96, 11)
-    finish(room)
+    finish(room.t)
     got = u64_of(only)
     assert np.array_equal(got[:n], w_mx) and np.array_equal(got[n:], w_mtx)
     # ranges are clamped, empty ranges enqueue nothing
@@ -161,10 +103,10 @@ def test_shards_nulls_and_accumulation(rc, room):
     t.view_factor_products_device(d_x.data_ptr(), only.data_ptr(), only.data_ptr() + 8 * n, 96, 11, src=(n, n + 5))
     t.view_factor_products_device(d_x.data_ptr(), only.data_ptr(), only.data_ptr() + 8 * n, 96, 11, rays=(96, 200))
     t.view_factor_products_device(d_x.data_ptr(), only.data_ptr(), only.data_ptr() + 8 * n, 96, 11, src=(7, 7))
-    finish(room)
+    finish(room.t)
     assert np.array_equal(u64_of(only), before)
     t.view_factor_products_device(d_x.data_ptr(), only.data_ptr(), only.data_ptr() + 8 * n, 96, 11, src=(0, n + 1000), rays=(0, 1 << 20))
-    finish(room)
+    finish(room.t)
     assert np.array_equal(u64_of(only)[:n], 2 * w_mx) and np.array_equal(u64_of(only)[n:], 2 * w_mtx)
     # the error contract
     L = lib()
@@ -172,21 +114,13 @@ def test_shards_nulls_and_accumulation(rc, room):
     assert L.rc_view_factor_products_device(t._h, 96, 11, 0, n, 0, 96, None, ptr(only.data_ptr()), None, None) == RC_ERR_INVALID_ARGUMENT
     assert L.rc_view_factor_products_device(None, 96, 11, 0, n, 0, 96, ptr(d_x.data_ptr()), ptr(only.data_ptr()), None, None) == RC_ERR_INVALID_ARGUMENT
     assert L.rc_view_factor_products(t._h, 96, 11, None, ptr(only.data_ptr()), None) == RC_ERR_INVALID_ARGUMENT
-    finish(room)
+    finish(room.t)
     assert np.array_equal(u64_of(only)[:n], 2 * w_mx)
 
 
 # ---- 4. metadata with gaps, duplicates, 0 and N + 50 -----------------------------------------------------------------------------------
-def meta(n):
-    m = np.arange(1, n + 1, dtype=np.uint32)
-    m[5:40] = 7
-    m[100:110] = 0
-    m[150] = n + 50
-    return m
-
-
 def test_metadata_gaps_duplicates_and_out_of_range(rc, oracle):
-    w = World(rc, oracle, room_cfg(rc, meta))
+    w = VfWorld(rc, oracle, room_cfg(rc, meta))
     M = w.M(128, 5)
     assert M[6].sum() > 0 and not M[8:39].any() and int(M.sum(dtype=np.uint64)) < 128 * w.n  # rays from and onto metadata 0 / N + 50 are dropped
     x = full_range_x(w.n, 4)
@@ -202,7 +136,7 @@ def test_metadata_gaps_duplicates_and_out_of_range(rc, oracle):
 # ---- 5. an instanced scene -------------------------------------------------------------------------------------------------------------------
 def test_instanced_scene(rc, oracle):
     """Hits are counted by the metadata of the hit primitive whatever instance it sits in (src/kernels.jl:93-97)."""
-    w = World(rc, oracle, rc.scenes.config_c3(lon=8, bands=5, lattice=(2, 2, 2)))
+    w = VfWorld(rc, oracle, rc.scenes.config_c3(lon=8, bands=5, lattice=(2, 2, 2)))
     M = w.M(64, 9)
     x = full_range_x(w.n, 5)
     mx, mtx = rc.view_factor_products(w.t, x, 64, seed=9)
@@ -233,17 +167,10 @@ def test_two_streams_at_once(rc, room):
         for v, (w_mx, w_mtx) in zip((v1, v2), wants):
             g = u64_of(v)
             assert np.array_equal(g[:n], w_mx) and np.array_equal(g[n:], w_mtx), rep
-    finish(room)
+    finish(room.t)
 
 
 # ---- 7. a captured bounce, replayed ---------------------------------------------------------------------------------------------------------
-def bounce_inputs(n, seed):
-    rng = np.random.default_rng(seed)
-    e = rng.integers(0, 1 << 24, n, dtype=np.uint32)
-    e[::17] = 0
-    rho = rng.integers(0, 65537, n, dtype=np.uint32)
-    rho[:4] = (0, 65536, 1, 65535)
-    return e, rho
 
 
 def test_captured_bounce_replayed(rc, oracle):
@@ -251,7 +178,7 @@ def test_captured_bounce_replayed(rc, oracle):
     one eager step; five replays are five bounces."""
     import torch
     from raycore_jl_amd.api import bounce_step
-    w = World(rc, oracle, room_cfg(rc))  # a scene of its own: the captured launches are released with it
+    w = VfWorld(rc, oracle, room_cfg(rc))  # a scene of its own: the captured launches are released with it
     t, n = w.t, w.n
     R, seed = 48, 31
     M = w.M(R, seed)
@@ -308,7 +235,7 @@ def test_view_factor_bounces_equal_the_model(rc, room, k):
     out = rc.view_factor_bounces(room.t, d_e, d_rho, k, rays_per_triangle=R, seed=seed, stream=st)
     st.synchronize()
     assert out.dtype == torch.int64 and out.is_cuda and np.array_equal(out.cpu().numpy().astype(np.uint32), want)
-    finish(room)
+    finish(room.t)
 
 
 def test_radiosity(rc, room):

@@ -5,17 +5,11 @@ for metadata with gaps / duplicates / out-of-range ids, and at C5's full size th
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import build_oracle, build_product
-from test_gpu_view_factors_host import room_cfg
+from scene_kit import room_cfg
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
 
 
 def sums(m):

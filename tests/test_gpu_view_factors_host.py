@@ -6,24 +6,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from gpu_kit import rc  # noqa: F401
 from helpers import build_oracle, build_product
+from scene_kit import room_cfg
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-def room_cfg(rc, meta=None):
-    sc = rc.scenes
-    verts = np.concatenate([sc.fan_sphere(12, 7, centre=(0, 0, 0), radius=0.5), sc.box_room((-1.5, -1.5, -1.5), (1.5, 1.5, 1.5), 2)])
-    n = len(verts)
-    m = np.arange(1, n + 1, dtype=np.uint32) if meta is None else meta(n)
-    return {"blas": [(verts, m)], "instances": [(1, sc.IDENTITY3x4[None], np.zeros(1, np.uint32))]}
 
 
 @pytest.fixture(scope="module")

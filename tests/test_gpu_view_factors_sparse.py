@@ -12,8 +12,10 @@ import pytest
 
 import vf_products_model as dense
 import vf_sparse_model as model
-from helpers import build_oracle, build_product
-from test_gpu_view_factors_host import room_cfg
+from gpu_kit import dev_u32, dev_u64, finish, u32_of, u64_of
+from gpu_kit import rc  # noqa: F401
+from scene_kit import bounce_inputs, full_range_x, meta, room_cfg
+from worlds import VfWorld, room_world
 
 pytestmark = pytest.mark.gpu
 
@@ -22,29 +24,13 @@ RC_ERR_INVALID_ARGUMENT, RC_ERR_NOT_SYNCED = 1, 6
 GUARD = 0x5A5A5A5A
 
 
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    assert raycore_jl_amd.device_count() > 0, "no GPU visible: the product has no CPU fallback"
-    return raycore_jl_amd
-
-
-class World:
+class World(VfWorld):
     """One scene in the product and in the oracle.  The oracle's matrices and the product's default build of each are computed once per
     (rays, seed) and are read-only."""
 
     def __init__(self, rc, oracle, cfg):
-        self.rc, self.t, self.o = rc, build_product(rc, cfg), build_oracle(oracle, cfg)
-        self.n = self.t.n_primitives()
-        self._m, self._csr = {}, {}
-
-    def M(self, rays, seed):
-        if (rays, seed) not in self._m:
-            m = self.o.view_factors(rays, seed=seed, nthreads=8)
-            assert m.shape == (self.n, self.n) and m.dtype == np.uint32
-            m.setflags(write=False)
-            self._m[rays, seed] = m
-        return self._m[rays, seed]
+        super().__init__(rc, oracle, cfg)
+        self._csr = {}
 
     def csr(self, rays, seed):
         if (rays, seed) not in self._csr:
@@ -55,21 +41,9 @@ class World:
         return self._csr[rays, seed]
 
 
-def meta(n):
-    """The products test's metadata: sources 5..39 share metadata 7 (row 6), ten sources have metadata 0, one has N + 50."""
-    m = np.arange(1, n + 1, dtype=np.uint32)
-    m[5:40] = 7
-    m[100:110] = 0
-    m[150] = n + 50
-    return m
-
-
 @pytest.fixture(scope="module")
 def room(rc, oracle):
-    w = World(rc, oracle, room_cfg(rc))
-    assert w.n == 192
-    yield w
-    w.t.free()
+    yield from room_world(World, rc, oracle)
 
 
 @pytest.fixture(scope="module")
@@ -84,36 +58,6 @@ def lattice(rc, oracle):
     w = World(rc, oracle, rc.scenes.config_c3(lon=8, bands=5, lattice=(2, 2, 2)))
     yield w
     w.t.free()
-
-
-def full_range_x(n, seed):
-    x = np.random.default_rng(seed).integers(0, 1 << 32, n, dtype=np.uint32)
-    x[:3] = (U32_MAX, 0, 1 << 31)
-    return x[:n]
-
-
-def dev_u32(x):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(x, np.uint32).view(np.int32)).cuda()
-
-
-def dev_u64(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64)).cuda()
-
-
-def u64_of(t):
-    return t.cpu().numpy().view(np.uint64)
-
-
-def u32_of(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def finish(w):
-    import torch
-    torch.cuda.synchronize()
-    w.t.wait_for_gpu()  # (a stack overflow would be reported here)
 
 
 class DeviceCsr:
@@ -264,7 +208,7 @@ def test_capacity_contract(rc, room):
     # the counting call: NULL arrays
     d = DeviceCsr(n, 0)
     d.build(t, R, seed, null_arrays=True)
-    finish(room)
+    finish(room.t)
     row_ptr, got_nnz, cols, vals = d.read()
     assert got_nnz == nnz and np.array_equal(row_ptr, want_ptr)
     assert (cols == GUARD).all() and (vals == GUARD).all()
@@ -272,7 +216,7 @@ def test_capacity_contract(rc, room):
     for capacity in (nnz - 5, nnz, nnz + 3, 1):
         d = DeviceCsr(n, capacity)
         d.build(t, R, seed)
-        finish(room)
+        finish(room.t)
         row_ptr, got_nnz, cols, vals = d.read()
         k = min(capacity, nnz)
         assert got_nnz == nnz and np.array_equal(row_ptr, want_ptr), capacity
@@ -300,7 +244,7 @@ def test_capacity_contract(rc, room):
     assert L.rc_view_factors_sparse_device(t._h, R, seed, 0, n, None, ptr(d.cols.data_ptr()), ptr(d.vals.data_ptr()), 16, ptr(h), None) == RC_ERR_INVALID_ARGUMENT
     assert L.rc_view_factors_sparse_device(t._h, R, seed, 0, n, ptr(h), None, ptr(d.vals.data_ptr()), 16, ptr(h), None) == RC_ERR_INVALID_ARGUMENT
     assert L.rc_view_factors_sparse_device(t._h, R, seed, 0, n, ptr(h), ptr(d.cols.data_ptr()), ptr(d.vals.data_ptr()), 16, None, None) == RC_ERR_INVALID_ARGUMENT
-    finish(room)
+    finish(room.t)
 
 
 # ---- 7. an instanced scene -------------------------------------------------------------------------------------------------------------------
@@ -331,7 +275,7 @@ def test_two_streams_at_once(rc, room):
             row_ptr, nnz, cols, vals = d.read()
             assert nnz == len(w[1]) and np.array_equal(row_ptr, w[0]), rep
             assert np.array_equal(cols[:nnz], w[1]) and np.array_equal(vals[:nnz], w[2]), rep
-    finish(room)
+    finish(room.t)
 
 
 def test_build_refuses_a_capturing_stream(rc, room):
@@ -352,7 +296,7 @@ def test_build_refuses_a_capturing_stream(rc, room):
     del g
     torch.cuda.synchronize()
     assert (u32_of(d.cols) == GUARD).all()
-    finish(room)
+    finish(room.t)
 
 
 # ---- 9. the products on traced matrices ----------------------------------------------------------------------------------------------------
@@ -387,7 +331,7 @@ def test_products_on_traced_matrices(rc, room, gaps, lattice, which):
     torch.cuda.synchronize()
     t.view_factor_sparse_products_device(n, row_ptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), d_x.data_ptr(), acc.data_ptr(), None)
     t.view_factor_sparse_products_device(n, row_ptr.data_ptr(), cols.data_ptr(), vals.data_ptr(), d_x.data_ptr(), None, acc.data_ptr() + 8 * n)
-    finish(w)
+    finish(w.t)
     got = u64_of(acc)
     assert np.array_equal(got[:n], start[:n] + w_mx) and np.array_equal(got[n:], start[n:] + w_mtx)
     both = torch.zeros(2 * n, dtype=torch.int64, device="cuda")
@@ -397,7 +341,7 @@ def test_products_on_traced_matrices(rc, room, gaps, lattice, which):
         bp, bc, bv = b.device_arrays()
         t.view_factor_sparse_products_device(r1 - r0, bp.data_ptr(), bc.data_ptr() if b.nnz else None, bv.data_ptr() if b.nnz else None, d_x.data_ptr(),
                                              both.data_ptr(), both.data_ptr() + 8 * n, row_offset=r0)
-        finish(w)
+        finish(w.t)
         if r1 > r0:
             one = rc.view_factor_sparse_products(b, x)
             s_mx, s_mtx = model.spmv(tuple(b), x, row_offset=r0)
@@ -411,7 +355,7 @@ def test_products_on_traced_matrices(rc, room, gaps, lattice, which):
     assert L.rc_view_factor_sparse_products_device(t._h, n, 0, *args, ptr(d_x.data_ptr()), None, None, None) == RC_ERR_INVALID_ARGUMENT
     assert L.rc_view_factor_sparse_products_device(t._h, n, 0, *args, None, ptr(both.data_ptr()), None, None) == RC_ERR_INVALID_ARGUMENT
     assert L.rc_view_factor_sparse_products_device(t._h, n, 0, None, *args[1:], ptr(d_x.data_ptr()), ptr(both.data_ptr()), None, None) == RC_ERR_INVALID_ARGUMENT
-    finish(w)
+    finish(w.t)
     assert np.array_equal(u64_of(both)[:n], w_mx)
 
 
@@ -464,17 +408,10 @@ def test_products_on_handmade_matrices(rc, room):
     got = rc.view_factor_sparse_products(rc.SparseViewFactors.from_arrays(t, *block, n=4100, row_offset=r0), x)
     want = model.spmv(block, x, row_offset=r0)
     assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and not got[0][:r0].any() and not got[0][r1:].any()
-    finish(room)
+    finish(room.t)
 
 
 # ---- 11. bounces and radiosity on the matrix -----------------------------------------------------------------------------------------------
-def bounce_inputs(n, seed):
-    rng = np.random.default_rng(seed)
-    e = rng.integers(0, 1 << 24, n, dtype=np.uint32)
-    e[::17] = 0
-    rho = rng.integers(0, 65537, n, dtype=np.uint32)
-    rho[:4] = (0, 65536, 1, 65535)
-    return e, rho
 
 
 @pytest.mark.parametrize("k", [0, 1, 5])
@@ -501,7 +438,7 @@ def test_bounces_on_the_matrix_equal_the_retraced_ones(rc, room, k):
     # a block of rows is no matrix to bounce on
     with pytest.raises(ValueError, match="all rows"):
         rc.view_factor_bounces(rc.view_factors_sparse(room.t, R, seed=seed, rows=(0, 10)), e, rho, k)
-    finish(room)
+    finish(room.t)
 
 
 def test_captured_sparse_bounce_replayed(rc, room):
@@ -532,7 +469,7 @@ def test_captured_sparse_bounce_replayed(rc, room):
     want = dense.bounces(M, R, e_np, rho_np, 5)
     assert np.array_equal(x.cpu().numpy().astype(np.uint32), want) and (want != e_np).any()
     del g
-    finish(room)
+    finish(room.t)
 
 
 def test_radiosity_on_the_matrix(rc, room):
@@ -546,4 +483,4 @@ def test_radiosity_on_the_matrix(rc, room):
     got, scale = rc.radiosity(room.t, e, rho, K, return_scale=True, matrix=csr)
     assert scale == w_scale and got.dtype == np.float64 and np.array_equal(got, want)
     assert (got > e + 0.1).any()  # the bounces matter
-    finish(room)
+    finish(room.t)

@@ -3,36 +3,20 @@ bindings match the header's prototypes, the library exports them, the header sta
 and Julia layers carry them, and get_illumination_dirs validates its arguments before it touches a device."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import header, julia_text, prototype
+from api_kit import rc  # noqa: F401
+
 C_TO_CTYPES = {"rc_scene*": C.c_void_p, "void*": C.c_void_p, "const float*": C.c_void_p, "uint32_t*": C.c_void_p, "rc_ray*": C.c_void_p,
                "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
 PROTOTYPES = {"rc_get_illumination_dirs_device": ["rc_scene*", "const float*", "uint32_t", "uint32_t", "uint32_t*", "uint64_t", "void*"],
               "rc_generate_ray_grid_dirs_device": ["rc_scene*", "const float*", "uint32_t", "uint32_t", "rc_ray*", "void*"]}
 JULIA_TYPES = {"rc_get_illumination_dirs_device": ["Ptr{Cvoid}", "Ptr{Float32}", "UInt32", "UInt32", "Ptr{UInt32}", "UInt64", "Ptr{Cvoid}"],
                "rc_generate_ray_grid_dirs_device": ["Ptr{Cvoid}", "Ptr{Float32}", "UInt32", "UInt32", "Ptr{RTRay}", "Ptr{Cvoid}"]}
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
-
-
-def prototype(name):
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert m, f"{name} is not declared in the header"
-    return [" ".join(a.split()[:-1]) for a in m.group(1).split(",")]  # the types, parameter names dropped
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
@@ -86,7 +70,7 @@ def test_python_surface(rc):
 
 
 def test_julia_binding_has_the_methods():
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     for name, types in JULIA_TYPES.items():
         m = re.search(r"ccall\(\(:" + name + r", LIB\), Cint,\s*\(([^)]*)\)", text)
         assert m, name

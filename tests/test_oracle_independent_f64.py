@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from helpers import build_oracle
+from scene_kit import scenes_module
 
 
 def f64_closest(verts, prim_meta_unused, instances, rays, chunk=64):
@@ -107,16 +108,6 @@ def check_scene(po, cfg, rays, tol_uv, what):
     assert worst <= 1.0, f"{what}: barycentrics off by {worst:.3g} x (1e-5 + {tol_uv:g} x conditioning)"
     print(f"{what}: {int(clear.sum())} clear hits, {int(clear_miss.sum())} clear misses, max t error {dt.max():.2e}, barycentric error {worst:.2f} of tolerance")
     return int(clear.sum()), int(clear_miss.sum()), float(dt.max()), worst
-
-
-def scenes_module():
-    import importlib.util
-    import os
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "raycore.jl_amd", "scenes.py")
-    spec = importlib.util.spec_from_file_location("rc_scenes_only", path)   # scene generators only: no HIP library needed
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
 
 
 def test_c1_every_ray_against_f64_plane_intersection(oracle):

@@ -3,22 +3,7 @@ Triangle{UInt32} record and the shading epilogue.  Pinned by the reference's own
 tangents NaN, default uv (0,0),(1,0),(1,1), metadata = face index before the degenerate filter or face_meta[first vertex]."""
 import numpy as np
 
-
-def grid_mesh(n, seed=0, with_uv=True):
-    """(n+1)^2 vertex grid over [0,1]^2 with a bumpy z, 2 n^2 faces, analytic-ish normals."""
-    g = np.random.default_rng(seed)
-    xs, ys = np.meshgrid(np.linspace(0, 1, n + 1), np.linspace(0, 1, n + 1), indexing="ij")
-    z = 0.1 * np.sin(6 * xs) * np.cos(5 * ys)
-    verts = np.stack([xs, ys, z], -1).reshape(-1, 3).astype(np.float32)
-    nrm = g.normal(size=verts.shape).astype(np.float32)
-    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
-    uv = np.stack([xs, ys], -1).reshape(-1, 2).astype(np.float32) if with_uv else None
-    idx = lambda i, j: i * (n + 1) + j
-    faces = []
-    for i in range(n):
-        for j in range(n):
-            faces += [[idx(i, j), idx(i + 1, j), idx(i + 1, j + 1)], [idx(i, j), idx(i + 1, j + 1), idx(i, j + 1)]]
-    return verts, np.array(faces, np.uint32), nrm, uv
+from scene_kit import grid_mesh
 
 
 def test_mesh_equals_soup_geometry(oracle):

@@ -1,15 +1,9 @@
 """Independent checks of the oracle itself: BVH traversal vs an all-pairs brute-force Moeller-Trumbore,
 structural invariants of the LBVH, determinism of the drivers."""
 import numpy as np
-import pytest
 
+from api_kit import rc  # noqa: F401
 from helpers import build_oracle, random_rays
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
 
 
 def small_scene(rc):

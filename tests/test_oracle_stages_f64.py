@@ -23,9 +23,8 @@ Measured on these inputs (x86-64, the oracle as committed):
 NORMAL_BOUND = 4e-6: above 4 x the worst case of either family, below 1/1000 of the mutant's median on the shear family."""
 import numpy as np
 
-from test_gpu_fuzz import hostile_transform
-from test_oracle_independent_f64 import scenes_module
-from test_oracle_mesh import grid_mesh
+from scene_kit import grid_mesh, hostile_transform, scenes_module
+
 
 NORMAL_BOUND = 4e-6
 EPS = 2.0 ** -24           # half an ulp of 1.0f: the relative error of one correctly rounded float32 operation

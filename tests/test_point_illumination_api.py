@@ -10,7 +10,9 @@ import re
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import ROOT, header, julia_text
+from api_kit import rc  # noqa: F401
+
 C_TO_CTYPES = {"uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
 PROTOTYPES = {"rc_point_source_rays_device": ["rc_scene*", "const rc_ray*", "uint32_t", "uint32_t", "uint64_t", "uint32_t", "rc_ray*", "void*"],
               "rc_get_illumination_points_device": ["rc_scene*", "const rc_ray*", "uint32_t", "uint32_t", "uint64_t", "uint32_t", "uint32_t*", "uint64_t",
@@ -18,16 +20,6 @@ PROTOTYPES = {"rc_point_source_rays_device": ["rc_scene*", "const rc_ray*", "uin
 JULIA_TYPES = {"rc_point_source_rays_device": ["Ptr{Cvoid}", "Ptr{RTRay}", "UInt32", "UInt32", "UInt64", "UInt32", "Ptr{RTRay}", "Ptr{Cvoid}"],
                "rc_get_illumination_points_device": ["Ptr{Cvoid}", "Ptr{RTRay}", "UInt32", "UInt32", "UInt64", "UInt32", "Ptr{UInt32}", "UInt64", "Ptr{UInt32}",
                                                      "Ptr{Cvoid}"]}
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
@@ -78,7 +70,7 @@ def test_python_surface(rc):
 
 
 def test_julia_binding_and_documents():
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     for name, types in JULIA_TYPES.items():
         m = re.search(r"ccall\(\(:" + name + r", LIB\), Cint,\s*\(([^)]*)\)", text)
         assert m, name

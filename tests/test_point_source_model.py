@@ -7,19 +7,13 @@ import pytest
 import bounce_model as bm
 import point_source_model as pm
 from helpers import build_oracle
+from scene_kit import single_cfg
 
 F32 = np.float32
 GRIDS = (13, 24, 64)
 SEED = 5
 AXIS = (0.3, 0.2, 1.0)
 LAMP = (0.25, -0.05, 0.2)
-
-
-def single_cfg(rc):
-    """The closed single-instance sphere of tests/test_gpu_illumination_dirs.py (single_cfg)."""
-    sc = rc.scenes
-    verts = sc.fan_sphere(12, 7, centre=(0.2, -0.1, 0.3), radius=0.6)
-    return {"blas": [(verts, np.arange(1, len(verts) + 1, dtype=np.uint32))], "instances": [(1, sc.IDENTITY3x4[None], np.ones(1, np.uint32))]}
 
 
 @pytest.mark.parametrize("grid", GRIDS)

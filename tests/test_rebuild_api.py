@@ -2,29 +2,16 @@
 exports it, the Python and Julia layers carry it, and without a GPU it sits behind the same argument checks as everything else."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import header, julia_text, prototype
+from api_kit import rc  # noqa: F401
+
 NAME = "rc_rebuild_tlas_device_async"
 C_ARGS = ["rc_scene*", "void*"]
 C_TO_CTYPES = {"rc_scene*": C.c_void_p, "void*": C.c_void_p}
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def prototype(name):
-    text = open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert m, f"{name} is not declared in the header"
-    return [" ".join(a.split()[:-1]) for a in m.group(1).split(",")]  # the types, parameter names dropped
 
 
 def test_symbol_matches_the_header(rc):
@@ -42,7 +29,7 @@ def test_library_exports_the_symbol(rc):
 
 def test_header_documents_the_call():
     """The comment in front of the declaration cites the reference's rebuild and states the bound of the single-workgroup path."""
-    text = open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
+    text = header()
     at = text.index("int " + NAME)
     comment = text[text.rindex("/*", 0, at):at]
     for needle in ("rebuild_bvh!", "build_tlas_topology", "256 instances", "tlas_rebuild_fused", "RC_ERR_NOT_SYNCED", "capturing stream"):
@@ -60,7 +47,7 @@ def test_python_surface(rc):
 
 
 def test_julia_binding_has_the_method(rc):
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     assert ":" + NAME in text
     assert re.search(r"Raycore\.rebuild_bvh!\(t::MI355XTLAS, stream::Ptr\{Cvoid\}\)", text)
 

@@ -3,34 +3,18 @@ library exports it, the Python and Julia layers carry it, WavefrontPaths validat
 without a GPU the call sits behind the same argument checks as everything else."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import header, julia_text, prototype
+from api_kit import rc  # noqa: F401
+
 NAME = "rc_shadow_visibility_device"
 C_TO_CTYPES = {"rc_scene*": C.c_void_p, "void*": C.c_void_p, "const rc_ray*": C.c_void_p, "const rc_hit*": C.c_void_p, "const float*": C.c_void_p,
                "uint8_t*": C.c_void_p, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": C.c_float}
 ARGS = ["rc_scene*", "const rc_ray*", "const rc_hit*", "uint64_t", "const float*", "uint32_t", "float", "uint8_t*", "void*"]
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
-
-
-def prototype(name):
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert m, f"{name} is not declared in the header"
-    return [" ".join(a.split()[:-1]) for a in m.group(1).split(",")]  # the types, parameter names dropped
 
 
 def test_symbol_matches_the_header(rc):
@@ -69,7 +53,7 @@ def test_python_surface(rc):
 
 
 def test_julia_binding_has_the_method(rc):
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     assert ":" + NAME in text
     m = re.search(r"ccall\(\(:" + NAME + r", LIB\), Cint,\s*\(([^)]*)\)", text)
     assert m

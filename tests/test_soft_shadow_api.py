@@ -9,7 +9,9 @@ import re
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import ROOT, header, julia_text, prototype
+from api_kit import rc  # noqa: F401
+
 C_TO_CTYPES = {"rc_scene*": C.c_void_p, "void*": C.c_void_p, "const rc_ray*": C.c_void_p, "const rc_hit*": C.c_void_p, "const float*": C.c_void_p,
                "const uint32_t*": C.c_void_p, "rc_ray*": C.c_void_p, "uint32_t*": C.c_void_p, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
                "float": C.c_float}
@@ -20,23 +22,6 @@ JL_HEAD = ["Ptr{Cvoid}", "Ptr{RTRay}", "Ptr{RTHitResult}", "UInt64", "Ptr{Float3
            "UInt64", "Cfloat"]
 JL_ARGS = {"rc_soft_shadow_rays_device": JL_HEAD + ["Ptr{RTRay}", "Ptr{Cvoid}"], "rc_soft_shadow_visibility_device": JL_HEAD + ["Ptr{UInt32}", "Ptr{Cvoid}"]}
 NAMES = sorted(ARGS)
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
-
-
-def prototype(name):
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-    assert m, f"{name} is not declared in the header"
-    return [" ".join(a.split()[:-1]) for a in m.group(1).split(",")]  # the types, parameter names dropped
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -90,7 +75,7 @@ def test_python_surface(rc):
 
 @pytest.mark.parametrize("name", NAMES)
 def test_julia_binding_has_the_method(name):
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     m = re.search(r"ccall\(\(:" + name + r", LIB\), Cint,\s*\(([^)]*)\)", text)
     assert m, f"no ccall of {name}"
     assert [t.strip() for t in m.group(1).split(",")] == JL_ARGS[name]

@@ -9,7 +9,9 @@ import re
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from api_kit import ROOT, header, julia_text
+from api_kit import rc  # noqa: F401
+
 PROTOTYPES = {
     "rc_view_factor_sampled_rays_device": ["rc_scene*", "uint64_t", "uint32_t", "uint32_t", "uint32_t", "uint32_t", "rc_ray*", "void*"],
     "rc_view_factor_groups_device": ["rc_scene*", "uint32_t", "uint64_t", "uint32_t", "uint32_t", "uint32_t", "uint32_t", "uint32_t", "const uint32_t*", "uint32_t",
@@ -22,16 +24,6 @@ JL_ARGS = {
 }
 CTYPES = {"uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
 RC_ERR_INVALID_ARGUMENT = 1
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "raycore_mi355x.h")).read()
 
 
 @pytest.mark.parametrize("name", sorted(PROTOTYPES))
@@ -84,7 +76,7 @@ def test_python_surface(rc):
 
 
 def test_julia_binding_and_integration_line():
-    text = open(os.path.join(ROOT, "raycore.jl_amd", "julia", "RaycoreMI355X.jl")).read()
+    text = julia_text()
     integration = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     for name, jl in JL_ARGS.items():
         m = re.search(r"ccall\(\(:" + name + r", LIB\), Cint,\s*\(([^)]*)\)", text)

@@ -10,14 +10,9 @@ import numpy as np
 import pytest
 
 import vf_groups_model as model
+from api_kit import rc  # noqa: F401
 from helpers import build_oracle
-from test_gpu_view_factors_host import room_cfg
-
-
-@pytest.fixture(scope="module")
-def rc():
-    import raycore_jl_amd
-    return raycore_jl_amd
+from scene_kit import room_cfg
 
 
 @pytest.fixture(scope="module")

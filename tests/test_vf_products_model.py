@@ -6,7 +6,7 @@ import pytest
 
 import vf_products_model as model
 from helpers import build_oracle
-from test_gpu_view_factors_host import room_cfg
+from scene_kit import room_cfg
 
 R, SEED = 192, 77
 U32_MAX = model.U32_MAX
