@@ -984,6 +984,63 @@ int rc_final_gather_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* 
                            uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias,
                            const uint32_t* d_x, uint32_t miss_value, uint64_t* d_sum, uint32_t* d_open, void* stream);
 
+/* ---- Form factors between instances: view-factor sources in WORLD space.  The view-factor family above shoots its rays from the
+ * untransformed primitives of each BLAS, as the reference does (src/kernels.jl:80-104): on a scene of one identity instance that is the
+ * scene, on every other scene the sources are not where the tracer sees the bodies.  These four calls place every source by its
+ * instance and name every hit by (instance, primitive): "how much of body A's emission reaches body B" is one launch, the bodies may be
+ * instances of one mesh, and the call may run behind a device-side move of B with no host wait.
+ * 1. THE PLACED-PRIMITIVE INDEX SPACE.  A placed primitive is a pair (instance i, local primitive l).  i is the 0-based position in the
+ *    instance array: rc_export_instances' order and rc_hit::instance_id.  l is the 0-based position inside the instance's BLAS in its
+ *    sorted order: the flat index is prims_offset(i) + l, and the traversal core reports prim = l + 1.  Its index is q = base[i] + l, where
+ *    base is the exclusive prefix sum of the instances' primitive counts over the instance array; P = base[n_inst] is the scene's
+ *    placed-primitive count.  base (n_inst + 1 u32) is built by the rebuilding rc_sync -- structure changes only there; device-side
+ *    transform and geometry updates keep every count: rc_update_geometry_device_async commits only on an equal face count --, kept on the
+ *    host and on the device, and re-derived by rc_scene_load.  A scene whose P reaches 2^32 keeps working for everything else; these
+ *    four calls return RC_ERR_INVALID_ARGUMENT on it.
+ * 2. THE PLACED RAY of (q, ray index, seed, sampling).  World triangle: p_k = transform_point(T_i, v_k) in f32, per row
+ *    ((m0 * x + m1 * y) + m2 * z) + m3, no contraction; T_i is the instance's FORWARD `transform` as it is in device memory WHEN THE
+ *    KERNEL RUNS.  Ray: exactly the ray of rc_view_factor_sampled_rays_device applied to (p_1, p_2, p_3): the normal is that of the
+ *    transformed vertices in their order -- a mirroring instance flips it, a non-uniform scale bends it correctly --, the origin is
+ *    pt + normal * 0.01f in WORLD units, the samplings are the same two.  Philox counter: (ray_idx, flat primitive index, i, 0), key =
+ *    seed; word 2 is the only difference from the per-triangle family, so instance 0 with an identity transform draws the sibling's
+ *    numbers.  THE CALLER'S CONTRACT: sources are placed by `transform`, hits are found through `inv_transform`; a caller who supplied
+ *    an inverse of its own (rc_add_instances_with_inverse) owns their agreement.  Singular transforms are outside the contract, as
+ *    everywhere else.
+ * 3. THE RULE, with no metadata in it.  a = the source's q.  For a hit, b = base[hit instance] + prim - 1.  ga = groups[a], gb = groups[b],
+ *    wa = weights ? weights[a] : 1.  A source with ga >= G contributes nothing.  A miss: escaped[ga] += wa, if escaped is given.  A hit
+ *    with b != a and gb < G: matrix[ga * G + gb] += wa.  Any other hit adds nothing.  u64 modulo 2^64, exact in any order: any partition
+ *    of placed primitives x rays gives the same words.  d_groups / d_weights: P u32 each, indexed by q, read WHEN THE KERNEL RUNS.  Both
+ *    outputs ACCUMULATE.
+ *
+ * rc_placed_primitive_bases: the host copy of base; *count = n_inst + 1, out may be NULL to ask for the count, capacity in words (the
+ * idiom of the exports).
+ * rc_placed_triangles_device: 9 f32 per placed primitive for [placed_begin, placed_begin + n), the world triangle of 2. -- for areas, for a
+ * model on the host, for a caller's own kernels.  One kernel, no scratch.
+ * rc_placed_view_factor_rays_device, the composed stage, sibling of rc_view_factor_sampled_rays_device: writes the placed rays
+ * [ray_begin, ray_begin + n_rays) of placed primitive placed_prim.  The output feeds rc_trace_closest_device unchanged.
+ * rc_placed_view_factor_groups_device, the fused driver, sibling of rc_view_factor_groups_device.  WORK-ITEM LAYOUT: item w = placed
+ * primitive placed_begin + w / n_ray, ray ray_begin + w % n_ray, n_ray = the clamped ray range's length; the ray is generated when a lane
+ * takes the item -- bit for bit the stage's, the same device function makes both -- and never stored.  placed_end is clamped to P and
+ * ray_end to rays_per_triangle; an empty range enqueues nothing.  1 <= n_groups <= 65535.  d_matrix: G * G u64, row = the source's group;
+ * d_escaped: G u64, may be NULL.  The kernel counts into private copies of the G * G (+ G) words while they fit 256 MiB and a fold adds
+ * them, and adds straight onto the caller's words above that: the same words either way.  Scratch is per stream.  Legal on a capturing
+ * stream that has run the call eagerly once, and behind rc_update_transforms_device -> rc_refit_device_async (or the rebuilds) and
+ * behind rc_update_geometry_device_async on the same stream with no host wait: a replay reads the CURRENT transforms, groups and weights.
+ * Errors, all before anything is enqueued and with the outputs untouched: RC_ERR_INVALID_ARGUMENT (NULL scene, d_groups, d_matrix, d_rays,
+ * or d_verts with n != 0; sampling above RC_VF_SAMPLING_COSINE; n_groups outside 1..65535; placed_prim >= P; placed_begin + n > P;
+ * capacity below n_inst + 1; P >= 2^32), RC_ERR_NOT_SYNCED in the states in which rc_view_factor_groups_device returns it.  A stack
+ * overflow is reported by rc_wait.
+ * Placed forms of the dense matrix, the totals, the products, the sparse matrix and the bounce solve do not exist yet.
+ * Register and scratch figures of the new kernel shells and the cost against the sibling: docs/EXPERIMENTS.md, "Form factors between
+ * instances". */
+int rc_placed_primitive_bases(rc_scene* scene, uint32_t* out, uint32_t capacity, uint32_t* count);
+int rc_placed_triangles_device(rc_scene* scene, uint32_t placed_begin, uint32_t n, float* d_verts, void* stream);
+int rc_placed_view_factor_rays_device(rc_scene* scene, uint64_t seed, uint32_t sampling, uint32_t placed_prim, uint32_t ray_begin,
+                                      uint32_t n_rays, rc_ray* d_rays, void* stream);
+int rc_placed_view_factor_groups_device(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin,
+                                        uint32_t placed_end, uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups,
+                                        const uint32_t* d_weights, uint64_t* d_matrix, uint64_t* d_escaped, void* stream);
+
 /* ---- Ambient occlusion: how open is the hemisphere above every hit?  `samples` cosine-weighted any_hit rays of length max_dist per hit; the
  * visible fraction count / samples is the cosine-weighted openness of the point (with max_dist = +Inf its sky-view factor, the per-point form
  * of what rc_get_illumination_device and rc_view_factor_totals answer per triangle).

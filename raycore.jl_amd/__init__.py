@@ -11,7 +11,9 @@ from .api import (BLAS4, CONTACT_DT, CollisionResult, ContactPair, collide_insta
                   get_centroid, get_illumination, get_illumination_dirs, get_illumination_points, point_sources, hits_from_grid, typed_hit_metadata, mat4_to_mat3x4, sync, trace_rays, view_factors, view_factors_multi, view_factor_totals, view_factor_totals_multi, multi_prepare, trace_multi, get_illumination_multi,
                   world_bound, expand_faceviews, ambient_occlusion, final_gather, irradiance, irradiance_scale, view_factor_products, view_factor_bounces, radiosity, radiosity_scale,
                   view_factors_sparse, view_factor_sparse_products, SparseViewFactors,
-                  view_factor_groups, form_factors, form_factor_weights, form_factors_from_counts, primitive_areas)
+                  view_factor_groups, form_factors, form_factor_weights, form_factors_from_counts, primitive_areas,
+                  placed_primitive_count, placed_primitive_areas, placed_groups, placed_view_factor_groups, placed_form_factors,
+                  instance_form_factors)
 
 
 def device_count():

@@ -150,6 +150,10 @@ SYMBOLS = [
     ("rc_final_gather_device", _int, [_vp, _vp, _vp, _u64, _u32, C.c_float, _u64, _u32, _vp, _u64, C.c_float, _vp, _u32, _vp, _vp, _vp]),
     ("rc_point_source_rays_device", _int, [_vp, _vp, _u32, _u32, _u64, _u32, _vp, _vp]),
     ("rc_get_illumination_points_device", _int, [_vp, _vp, _u32, _u32, _u64, _u32, _vp, _u64, _vp, _vp]),
+    ("rc_placed_primitive_bases", _int, [_vp, _vp, _u32, _pu32]),
+    ("rc_placed_triangles_device", _int, [_vp, _u32, _u32, _vp, _vp]),
+    ("rc_placed_view_factor_rays_device", _int, [_vp, _u64, _u32, _u32, _u32, _u32, _vp, _vp]),
+    ("rc_placed_view_factor_groups_device", _int, [_vp, _u32, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
 ]
 
 _lib = None

@@ -657,6 +657,43 @@ class TLAS:
                                                  ptr(groups_ptr), int(n_groups), ptr(weights_ptr) if weights_ptr else None, ptr(matrix_ptr),
                                                  ptr(escaped_ptr) if escaped_ptr else None, ptr(stream) if stream else None))
 
+    def placed_primitive_bases(self):
+        """The placed-primitive table (rc_placed_primitive_bases): n_inst + 1 uint32, base[i] = the primitives of the instances before i in
+        the instance array's order; base[-1] = P, the scene's placed-primitive count.  Placed primitive q = base[i] + l is primitive l
+        (0-based, in the BLAS's sorted order) of instance i."""
+        n = C.c_uint32(0)
+        check(lib().rc_placed_primitive_bases(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        check(lib().rc_placed_primitive_bases(self._h, ptr(out), n.value, C.byref(n)))
+        return out
+
+    def placed_triangles_device(self, d_verts, placed_begin=0, n=None, stream=None):
+        """The world triangles of placed primitives [placed_begin, placed_begin + n) (rc_placed_triangles_device; default: to the last): 9 f32
+        each at d_verts, the local vertices under the instance's forward transform as it is in device memory when the kernel runs."""
+        if n is None:
+            n = int(self.placed_primitive_bases()[-1]) - int(placed_begin)
+        check(lib().rc_placed_triangles_device(self._h, int(placed_begin), int(n), ptr(d_verts), ptr(stream) if stream else None))
+
+    def placed_view_factor_rays_device(self, d_rays, placed_prim, n_rays, seed=0, sampling="uniform", ray_begin=0, stream=None):
+        """The sampled view-factor rays of one PLACED primitive (rc_placed_view_factor_rays_device): view_factor_sampled_rays_device's ray
+        of the world triangle, with the instance in the third word of the random-number counter."""
+        check(lib().rc_placed_view_factor_rays_device(self._h, int(seed), vf_sampling(sampling), int(placed_prim), int(ray_begin), int(n_rays), ptr(d_rays),
+                                                      ptr(stream) if stream else None))
+
+    def placed_view_factor_groups_device(self, groups_ptr, n_groups, matrix_ptr, rays_per_triangle, seed, sampling="uniform", weights_ptr=None,
+                                         escaped_ptr=None, placed=None, rays=None, stream=None):
+        """Weighted counts between GROUPS of PLACED primitives (rc_placed_view_factor_groups_device): view_factor_groups_device with the
+        sources in world space.  groups_ptr / weights_ptr (may be None: weight 1): P u32 each, indexed by placed primitive q, read when the
+        kernel runs; matrix_ptr: n_groups x n_groups u64, row = source group; escaped_ptr: n_groups u64 or None.  Both outputs are
+        ACCUMULATED: a ray from placed primitive a (group ga, weight wa) that hits placed primitive b != a of group gb adds wa to
+        matrix[ga, gb], one that hits nothing adds wa to escaped[ga]; a group >= n_groups excludes the primitive.  placed / rays:
+        (begin, end) ranges of placed primitives and of ray indices (default: all) -- the shards of one job add up to the whole."""
+        s0, s1 = (0, 0xFFFFFFFF) if placed is None else placed
+        r0, r1 = (0, int(rays_per_triangle)) if rays is None else rays
+        check(lib().rc_placed_view_factor_groups_device(self._h, int(rays_per_triangle), int(seed), vf_sampling(sampling), int(s0), int(s1), int(r0), int(r1),
+                                                        ptr(groups_ptr), int(n_groups), ptr(weights_ptr) if weights_ptr else None, ptr(matrix_ptr),
+                                                        ptr(escaped_ptr) if escaped_ptr else None, ptr(stream) if stream else None))
+
     def view_factors_sparse_device(self, row_ptr_ptr, cols_ptr, vals_ptr, capacity, nnz_ptr, rays_per_triangle, seed, rows=None, stream=None):
         """Rows `rows` = (begin, end) (default: all; end is clamped to N) of the view-factor matrix in canonical CSR on the device
         (rc_view_factors_sparse_device), OVERWRITTEN: row_ptr_ptr: rows + 1 u64 starting at 0; cols_ptr / vals_ptr: `capacity` u32 each
@@ -1365,6 +1402,80 @@ def form_factors(accel, groups, rays_per_triangle=10000, seed=0, n_groups=None):
     w = form_factor_weights(primitive_areas(accel), rays_per_triangle)
     matrix, escaped = view_factor_groups(accel, groups, rays_per_triangle, seed, weights=w, sampling="cosine", n_groups=n_groups, return_escaped=True)
     return form_factors_from_counts(matrix, escaped, groups, w, rays_per_triangle)
+
+
+def placed_primitive_count(accel):
+    """P, the number of placed primitives of the scene: the sum over the instances of their BLAS's primitive count."""
+    return int(_owner(accel).placed_primitive_bases()[-1])
+
+
+def placed_primitive_areas(accel):
+    """The areas of the scene's PLACED primitives as float64, indexed by placed primitive q, from the world triangles
+    (rc_placed_triangles_device): |cross(p2 - p1, p3 - p1)| / 2 in float64."""
+    import torch
+    t = _owner(accel)
+    P = int(t.placed_primitive_bases()[-1])
+    torch.cuda.synchronize(t.device)
+    d_v = torch.empty(max(9 * P, 1), dtype=torch.float32, device=f"cuda:{t.device}")
+    t.placed_triangles_device(d_v.data_ptr(), 0, P)
+    torch.cuda.synchronize(t.device)
+    v = d_v.cpu().numpy()[:9 * P].reshape(P, 3, 3).astype(np.float64)
+    return 0.5 * np.linalg.norm(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]), axis=1)
+
+
+def placed_groups(accel, per_instance=None):
+    """The `groups` of placed_view_factor_groups from one group number per instance (uint32, length n_inst; a value >= n_groups leaves
+    the instance out), expanded to P entries by np.repeat over the bases.  per_instance=None: every instance is its own group."""
+    g = None if per_instance is None else _u32_vector(per_instance, "per_instance")
+    bases = _owner(accel).placed_primitive_bases().astype(np.int64)
+    n_inst = len(bases) - 1
+    if g is None:
+        g = np.arange(n_inst, dtype=np.uint32)
+    if len(g) != n_inst:
+        raise ValueError(f"per_instance must hold one group per instance: {len(g)} values for {n_inst} instances")
+    return np.repeat(g, np.diff(bases))
+
+
+def placed_view_factor_groups(accel, groups, rays_per_triangle=10000, seed=0, weights=None, sampling="uniform", n_groups=None, return_escaped=False):
+    """view_factor_groups with the sources in WORLD space (rc_placed_view_factor_groups_device): the (G, G) uint64 array [source group,
+    hit group] between groups of PLACED primitives.  groups[q] / weights[q] belong to placed primitive q = base[i] + l -- primitive l of
+    instance i, placed_primitive_bases() -- so length P, not N; placed_groups() makes them from one number per instance.  Every placed
+    primitive shoots rays_per_triangle rays from where its instance's transform puts it; a ray that hits its own placed primitive is
+    not counted, one that hits nothing is counted in `escaped`.  No metadata takes part.  Arguments and errors as view_factor_groups."""
+    g, w, word, G = check_groups_arguments(groups, weights, rays_per_triangle, seed, sampling, n_groups)
+    import torch
+    t = _owner(accel)
+    P = int(t.placed_primitive_bases()[-1])
+    if len(g) != P:
+        raise ValueError(f"groups must hold one value per placed primitive: {len(g)} values for {P} placed primitives")
+    dev = f"cuda:{t.device}"
+    torch.cuda.synchronize(t.device)  # (the call runs on the default stream: behind whatever the caller enqueued on streams of its own)
+    d_g = torch.from_numpy(g.view(np.int32)).to(dev) if P else None
+    d_w = torch.from_numpy(w.view(np.int32)).to(dev) if (w is not None and P) else None
+    out = torch.zeros(G * G + G, dtype=torch.int64, device=dev)
+    if P:
+        t.placed_view_factor_groups_device(d_g.data_ptr(), G, out.data_ptr(), int(rays_per_triangle), int(seed), word,
+                                           d_w.data_ptr() if d_w is not None else None, out.data_ptr() + 8 * G * G)
+    torch.cuda.synchronize(t.device)
+    t.wait_for_gpu()  # (reports a traversal stack overflow)
+    words = out.cpu().numpy().view(np.uint64)
+    matrix, escaped = words[:G * G].reshape(G, G).copy(), words[G * G:].copy()
+    return (matrix, escaped) if return_escaped else matrix
+
+
+def placed_form_factors(accel, groups, rays_per_triangle=10000, seed=0, n_groups=None):
+    """form_factors between groups of PLACED primitives: (F, escaped), float64.  Cosine sampling with
+    form_factor_weights(placed_primitive_areas(accel), R); the quotients are form_factors_from_counts'."""
+    check_groups_arguments(groups, None, rays_per_triangle, seed, "cosine", n_groups)
+    w = form_factor_weights(placed_primitive_areas(accel), rays_per_triangle)
+    matrix, escaped = placed_view_factor_groups(accel, groups, rays_per_triangle, seed, weights=w, sampling="cosine", n_groups=n_groups, return_escaped=True)
+    return form_factors_from_counts(matrix, escaped, groups, w, rays_per_triangle)
+
+
+def instance_form_factors(accel, rays_per_triangle=10000, seed=0):
+    """Form factors between the scene's INSTANCES: (F, escaped), F the n_inst x n_inst float64 matrix of placed_form_factors with every
+    instance its own group (at most 65535 instances)."""
+    return placed_form_factors(accel, placed_groups(accel), rays_per_triangle, seed)
 
 
 def _is_tensor(a):

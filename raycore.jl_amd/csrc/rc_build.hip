@@ -1344,6 +1344,15 @@ void rc_build_tlas(rc_scene* s) {
     RC_HIP(hipMemsetAsync(s->blas_cull_bits.p, 0, sizeof(uint32_t) * (nb ? nb : 1), s->stream));
     if (nb && tp) hipLaunchKernelGGL(k_cull_radius, dim3(grid_for(tp)), dim3(kBlock), 0, s->stream, s->flat_prims.p, tp, s->d_descs.p, nb, s->blas_cull_bits.p);
     s->n_static_instances = n;
+    {   // the placed-primitive table: the exclusive prefix sum of the instances' primitive counts (what k_inst_recs writes to RcInstRec::n_prims)
+        s->placed_base.assign((size_t)n + 1u, 0u);
+        uint64_t placed = 0;
+        for (uint32_t i = 0; i < n; ++i) { s->placed_base[i] = (uint32_t)placed; placed += s->blas[s->instances[i].blas_index - 1u].n_prims; }
+        s->placed_base[n] = (uint32_t)placed;
+        s->n_placed = placed;
+        s->d_placed_base.reserve((size_t)n + 1u);
+        RC_HIP(hipMemcpyAsync(s->d_placed_base.p, s->placed_base.data(), sizeof(uint32_t) * ((size_t)n + 1u), hipMemcpyHostToDevice, s->stream));
+    }
     for (auto& b : s->blas) b.root_on_device = false;
     s->state.tlas_built(n == 0);
     if (n == 0) {  // :969-977

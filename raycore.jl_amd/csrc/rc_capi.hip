@@ -1712,6 +1712,56 @@ int rc_view_factor_sampled_rays_device(rc_scene* s, uint64_t seed, uint32_t samp
     });
 }
 
+// ---- form factors between instances: the placed-primitive table, the two stages and the fused driver (PlacedViewFactorGroupsJob, rc_drivers.hip) ----
+// The placed calls index in 32 bits: a scene whose placed-primitive count reaches 2^32 keeps working for everything else.
+static void require_placed(rc_scene* s, const char* who) {
+    require_synced(s);
+    if (s->n_placed >> 32) throw RcError(RC_ERR_INVALID_ARGUMENT, std::string(who) + ": the scene's placed-primitive count reaches 2^32");
+}
+int rc_placed_primitive_bases(rc_scene* s, uint32_t* out, uint32_t capacity, uint32_t* count) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    return guarded([&] {
+        require_placed(s, "rc_placed_primitive_bases");
+        if (count) *count = (uint32_t)s->placed_base.size();
+        if (!out) return;
+        if (capacity < s->placed_base.size()) throw RcError(RC_ERR_INVALID_ARGUMENT, "export buffer too small");
+        if (!s->placed_base.empty()) memcpy(out, s->placed_base.data(), sizeof(uint32_t) * s->placed_base.size());
+    });
+}
+int rc_placed_triangles_device(rc_scene* s, uint32_t placed_begin, uint32_t n, float* d_verts, void* stream) {
+    if (!s || (n && !d_verts)) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded([&] {
+        use_device(s);
+        require_placed(s, "rc_placed_triangles_device");
+        if ((uint64_t)placed_begin + n > s->n_placed) throw RcError(RC_ERR_INVALID_ARGUMENT, "rc_placed_triangles_device: placed range out of bounds");
+        rc_launch_placed_triangles(s, placed_begin, n, d_verts, (hipStream_t)stream);
+    });
+}
+int rc_placed_view_factor_rays_device(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t placed_prim, uint32_t ray_begin, uint32_t n_rays, rc_ray* d_rays,
+                                      void* stream) {
+    if (!s || !d_rays) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (sampling > RC_VF_SAMPLING_COSINE) return fail(RC_ERR_INVALID_ARGUMENT, "rc_placed_view_factor_rays_device: sampling must be RC_VF_SAMPLING_UNIFORM or RC_VF_SAMPLING_COSINE");
+    return guarded([&] {
+        use_device(s);
+        require_placed(s, "rc_placed_view_factor_rays_device");
+        if (placed_prim >= s->n_placed) throw RcError(RC_ERR_INVALID_ARGUMENT, "placed_prim out of range");
+        rc_launch_placed_view_factor_rays(s, seed, sampling, placed_prim, ray_begin, n_rays, reinterpret_cast<RcRay*>(d_rays), (hipStream_t)stream);
+    });
+}
+int rc_placed_view_factor_groups_device(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
+                                        uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
+                                        uint64_t* d_matrix, uint64_t* d_escaped, void* stream) {
+    if (!s || !d_groups || !d_matrix) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (sampling > RC_VF_SAMPLING_COSINE) return fail(RC_ERR_INVALID_ARGUMENT, "rc_placed_view_factor_groups_device: sampling must be RC_VF_SAMPLING_UNIFORM or RC_VF_SAMPLING_COSINE");
+    if (n_groups < 1 || n_groups > 65535) return fail(RC_ERR_INVALID_ARGUMENT, "rc_placed_view_factor_groups_device: n_groups must lie in 1..65535");
+    return guarded([&] {
+        use_device(s);
+        require_placed(s, "rc_placed_view_factor_groups_device");
+        rc_launch_placed_vf_groups(s, rays_per_triangle, seed, sampling, placed_begin, placed_end, ray_begin, ray_end, d_groups, n_groups, d_weights,
+                                   reinterpret_cast<unsigned long long*>(d_matrix), reinterpret_cast<unsigned long long*>(d_escaped), (hipStream_t)stream);
+    });
+}
+
 int rc_hit_points_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, float* d_points, float* d_normals, void* stream) {
     if (!s || !d_rays || !d_hits || !d_points) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
     return guarded([&] {

@@ -397,12 +397,13 @@ __device__ inline float3_ cosine_hemisphere_dir(const float3_ n, float u1, float
 // cosine_hemisphere_dir(normal, xi1, xi2), the function of the bounce, AO and point-source stages applied to the triangle's unit normal
 // with the third and fourth Philox words, not renormalised: the direction density of a Lambertian surface, so the counts are FORM
 // factors.  t_min = 0, t_max = inf.  The sampling is a template parameter: the cosine path carries no f64 acos, the uniform path no disk mapping.
+// `placed`: the third counter word, 0 in the per-triangle family; the placed family (below) passes the source's instance.
 template <bool COSINE>
-__device__ inline RcRay view_factor_ray(const RcPrim& tri, uint32_t src, uint32_t ray_idx, RcPhiloxKey key) {
+__device__ inline RcRay view_factor_ray(const RcPrim& tri, uint32_t src, uint32_t ray_idx, RcPhiloxKey key, uint32_t placed = 0u) {
     float3_ p1 = mk3(tri.v[0], tri.v[1], tri.v[2]), p2 = mk3(tri.v[3], tri.v[4], tri.v[5]), p3 = mk3(tri.v[6], tri.v[7], tri.v[8]);
     float3_ normal = normalize3(cross3(sub3(p2, p1), sub3(p3, p1)));  // GB.orthogonal_vector + normalize (:86-87)
     uint32_t rnd[4];
-    philox4x32_10(ray_idx, src, 0u, 0u, key.k0, key.k1, rnd);
+    philox4x32_10(ray_idx, src, placed, 0u, key.k0, key.k1, rnd);
     float r1 = u32_to_unit(rnd[0]), r2 = u32_to_unit(rnd[1]), xi1 = u32_to_unit(rnd[2]), xi2 = u32_to_unit(rnd[3]);
     // random_triangle_point (src/math.jl:158-174)
     float sqrt_r1 = __builtin_sqrtf(r1);
@@ -1134,6 +1135,139 @@ struct ViewFactorGroupsJob {
     __device__ inline ViewFactorGroupsSink sink(const SceneView& v) const { return ViewFactorGroupsSink{v, sh, n_groups, groups, weights, matrix, escaped, h}; }
 };
 
+// ---- form factors between instances: the groups job with its sources placed in world space, counted per PLACED primitive ------------------
+// A placed primitive is a pair (instance i, local primitive l): i = the 0-based position in the instance array (RcHit::instance_id), l = the
+// 0-based position inside the instance's BLAS in its sorted order -- the flat index is inst[i].prims_offset + l, the traversal core reports
+// prim = l + 1.  Its index is q = base[i] + l, base = the exclusive prefix sum of RcInstRec::n_prims over the instance array (n_inst + 1
+// words, rc_scene::d_placed_base, built by rc_build_tlas: structure changes only there); P = base[n_inst].
+// q -> i: the upper bound in base.  Every BLAS has a primitive, so base is strictly increasing and the i with base[i] <= q < base[i + 1] is
+// unique.  The search never reads past base[n_inst - 1] and answers an instance below n_inst whatever q is (the launchers hand out q < P).
+__device__ __forceinline__ uint32_t placed_instance(const uint32_t* base, uint32_t n_inst, uint32_t q) {
+    uint32_t lo = 0, hi = n_inst - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (base[mid + 1u] <= q) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+// The scene arrays a placed source reads, all as they are WHEN THE KERNEL RUNS: behind k_update_instances on the same stream `instances`
+// holds the new forward transforms.
+struct PlacedView {
+    const RcInstanceDesc* instances;  // 108-byte records, 4-byte aligned: the 12 transform words are dword loads
+    const RcInstRec* inst;
+    const RcPrim* prims;
+    const uint32_t* base;
+    uint32_t n_inst;
+};
+// The world triangle of placed primitive q: p_k = transform_point(T_i, v_k) with T_i the instance's FORWARD transform, in xf_point's
+// operation order ((m0 * x + m1 * y) + m2 * z) + m3 per row, no contraction.  `flat` and `i` are what the Philox counter needs.
+__device__ inline RcPrim placed_triangle(const PlacedView& pv, uint32_t q, uint32_t& flat, uint32_t& i) {
+    i = placed_instance(pv.base, pv.n_inst, q);
+    flat = pv.inst[i].prims_offset + (q - pv.base[i]);
+    const float* m = pv.instances[i].transform;
+    const RcPrim local = pv.prims[flat];
+    RcPrim tri;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float3_ p = xf_point(m, mk3(local.v[3 * k], local.v[3 * k + 1], local.v[3 * k + 2]));
+        tri.v[3 * k] = p.x; tri.v[3 * k + 1] = p.y; tri.v[3 * k + 2] = p.z;
+    }
+    tri.meta = local.meta;
+    return tri;
+}
+// The placed ray of (q, ray index): view_factor_ray<COSINE> on the world triangle -- the normal is that of the transformed vertices in
+// their order, so a mirroring instance flips it and a non-uniform scale bends it correctly; the origin is pt + normal * 0.01f in WORLD
+// units -- with the Philox counter (ray_idx, flat primitive index, i, 0): word 2 is the only difference from the per-triangle family, so
+// instance 0 under an identity transform draws the sibling's numbers.  Shared by the stage kernel and the fused driver's source.
+template <bool COSINE>
+__device__ inline RcRay placed_view_factor_ray(const PlacedView& pv, uint32_t q, uint32_t ray_idx, RcPhiloxKey key) {
+    uint32_t flat, i;
+    const RcPrim tri = placed_triangle(pv, q, flat, i);
+    return view_factor_ray<COSINE>(tri, flat, ray_idx, key, i);
+}
+// The two composed stages: the world triangles of placed primitives [placed_begin, placed_begin + n), 9 f32 each; and the rays
+// [ray_begin, ray_begin + n_ray) of one placed primitive.
+__global__ void k_placed_triangles(PlacedView pv, uint32_t placed_begin, uint32_t n, float* out) {
+    for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x) {
+        uint32_t flat, i;
+        const RcPrim tri = placed_triangle(pv, placed_begin + (uint32_t)t, flat, i);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out[9u * t + k] = tri.v[k];
+    }
+}
+template <bool COSINE>
+__global__ void k_placed_view_factor_rays(PlacedView pv, RcPhiloxKey key, uint32_t q, uint32_t ray_begin, uint32_t n_ray, RcRay* out) {
+    for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < n_ray; t += (uint64_t)gridDim.x * blockDim.x)
+        store_ray(out, t, placed_view_factor_ray<COSINE>(pv, q, ray_begin + (uint32_t)t, key));
+}
+// The fused driver's source: work item w = placed primitive sh.src_begin + w / n_ray, ray sh.ray_begin + w % n_ray.  With n_ray >= 64 a wave
+// holds one or two sources: the search and the transform loads are near-uniform and cache-resident, once per ray against hundreds of node
+// visits.  With n_ray = 1 a wave's 64 lanes hold 64 sources of possibly several instances; every lane searches for itself.
+template <bool COSINE>
+struct PlacedViewFactorSource {
+    PlacedView pv;
+    VfShard sh;
+    __device__ inline RcRay operator()(uint64_t w) const {
+        return placed_view_factor_ray<COSINE>(pv, sh.src_begin + (uint32_t)(w / sh.n_ray), sh.ray_begin + (uint32_t)(w % sh.n_ray), sh.key);
+    }
+    static constexpr bool kPrefetch = false;
+};
+// The counting rule, P = the placed-primitive count, G = n_groups, no metadata in it: a = the source's q, for a hit b = base[hit instance] +
+// prim - 1, ga = groups[a], gb = groups[b], wa = weights ? weights[a] : 1.  A source with ga >= G contributes nothing.  A miss:
+// escaped[ga] += wa, if escaped is given.  A hit with b != a and gb < G: matrix[ga * G + gb] += wa.  Any other hit adds nothing.  u64 adds
+// modulo 2^64, exact in any order.  a comes from w alone and b needs ONE load (base[instance]) where the metadata sink reads two `meta`
+// words; the counting itself is ViewFactorGroupsSink's: one wave_add into the copies, or two onto the caller's words, folded by FoldAddU64Groups.
+struct PlacedGroupsSink {
+    const uint32_t* base;
+    VfShard sh;
+    uint32_t n_groups;
+    const uint32_t* groups;       // P words, indexed by q
+    const uint32_t* weights;      // P words or nullptr: every source weighs 1
+    unsigned long long* matrix;   // as ViewFactorGroupsSink's
+    unsigned long long* escaped;
+    CopyHist h;
+    __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
+        const uint32_t a = sh.src_begin + (uint32_t)(w / sh.n_ray);
+        const uint32_t ga = groups[a];
+        bool counted = false, escape = false;
+        uint32_t j = 0, wa = 0;
+        if (ga < n_groups) {
+            if (hit) {
+                const uint32_t b = base[instance] + prim - 1u;
+                if (b != a) {
+                    const uint32_t gb = groups[b];
+                    if (gb < n_groups) { counted = true; j = ga * n_groups + gb; }
+                }
+            } else if (escaped) { counted = true; escape = true; j = ga; }
+            if (counted) wa = weights ? weights[a] : 1u;
+        }
+        if (h.n8) {  // (uniform over the launch: every finishing lane reaches the same wave_add)
+            if (escape) j += n_groups * n_groups;
+            wave_add(matrix + h.base(h.copy()), counted ? h.slot(j) : 0u, wa, counted);
+        } else {
+            wave_add(matrix, j, wa, counted && !escape);
+            if (escaped) wave_add(escaped, j, wa, escape);
+        }
+    }
+};
+template <bool COSINE>
+struct PlacedViewFactorGroupsJob {
+    const RcInstanceDesc* instances;
+    const uint32_t* base;
+    VfShard sh;
+    uint32_t n_groups;
+    const uint32_t* groups;
+    const uint32_t* weights;
+    unsigned long long* matrix;
+    unsigned long long* escaped;
+    CopyHist h;
+    __device__ inline PlacedViewFactorSource<COSINE> source(const SceneView& v) const {
+        return PlacedViewFactorSource<COSINE>{PlacedView{instances, v.inst, v.prims, base, v.n_inst}, sh};
+    }
+    __device__ inline PlacedGroupsSink sink(const SceneView&) const { return PlacedGroupsSink{base, sh, n_groups, groups, weights, matrix, escaped, h}; }
+};
+
 // Diffuse bounce: output slot i continues the path of source slot s (s = i, or d_src[i] for i < count, or d_src[i % count] round robin
 // with k = i / count), from hit_point + normal * bias in a cosine-weighted direction about the geometric normal.  The uniforms are
 // Philox4x32-10(counter = (lo32 path, hi32 path, k, 0x424E0000 | bounce), key = seed): a path's bounce does not depend on compaction,
@@ -1334,13 +1468,16 @@ void for_row_groups(rc_scene* s, uint32_t n_rows, uint64_t cells, CopyHist h, Ea
     for (uint32_t r0 = 0; r0 < n_rows; r0 += (uint32_t)group) each(r0, (uint32_t)std::min<uint64_t>(group, n_rows - r0));
 }
 // The shard of a view-factor call: the rays [ray_begin, ray_end) below rays_per_triangle of the source positions [src_begin, src_end) below
-// the flat primitive count.  Returns its item count, 0 for an empty shard.
-uint64_t vf_shard(const rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin, uint32_t ray_end, VfShard& sh) {
-    src_end = std::min(src_end, s->n_flat_prims);
+// n_sources (the flat primitive count; the placed family's P).  Returns its item count, 0 for an empty shard.
+uint64_t vf_shard(uint32_t n_sources, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin, uint32_t ray_end, VfShard& sh) {
+    src_end = std::min(src_end, n_sources);
     ray_end = std::min(ray_end, rays_per_triangle);
     if (src_begin >= src_end || ray_begin >= ray_end) return 0;
     sh = VfShard{rc_philox_key(seed), src_begin, ray_begin, ray_end - ray_begin};
     return (uint64_t)(src_end - src_begin) * sh.n_ray;
+}
+uint64_t vf_shard(const rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t src_begin, uint32_t src_end, uint32_t ray_begin, uint32_t ray_end, VfShard& sh) {
+    return vf_shard(s->n_flat_prims, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, sh);
 }
 }  // namespace
 
@@ -1511,17 +1648,16 @@ void rc_launch_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t see
 // surface groups").  Both paths give the same words.  d_groups, d_weights and the scene are read when the kernel runs.  1 <= G <= 65535
 // (checked by the caller): wave_add indexes in 32 bits.
 constexpr unsigned long long kVfGroupsCopyBytes = 256ull << 20;
-template <bool COSINE>
-static void launch_vf_groups(rc_scene* s, const VfShard& sh, uint64_t total, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
-                             unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream) {
+// make(matrix, h): the job that counts into `matrix` under the copy layout h ({0}: the caller's own words).
+template <class MakeJob>
+static void launch_vf_groups(rc_scene* s, uint64_t total, uint32_t n_groups, unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream, MakeJob make) {
     DriverLaunch launch(s, stream, total);
     const uint32_t gg = n_groups * n_groups, n = gg + (d_escaped ? n_groups : 0u);
     CopyHist h = CopyHist::of(n);
     const bool copies = sizeof(unsigned long long) * h.words() <= kVfGroupsCopyBytes;
     unsigned long long* scratch = copies ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
     if (!copies) h = CopyHist{0u};
-    launch.go<false>(ViewFactorGroupsJob<COSINE>{sh, n_groups, d_groups, d_weights, copies ? scratch : d_matrix, d_escaped, h}, Nothing(),
-                     [&] { if (copies) rc_hist_fold(stream, scratch, h, n, FoldAddU64Groups{{}, d_matrix, d_escaped, gg}); });
+    launch.go<false>(make(copies ? scratch : d_matrix, h), Nothing(), [&] { if (copies) rc_hist_fold(stream, scratch, h, n, FoldAddU64Groups{{}, d_matrix, d_escaped, gg}); });
 }
 void rc_launch_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t src_begin, uint32_t src_end,
                          uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
@@ -1529,7 +1665,33 @@ void rc_launch_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
     VfShard sh;
     const uint64_t total = vf_shard(s, rays_per_triangle, seed, src_begin, src_end, ray_begin, ray_end, sh);
     if (!total) return;
-    (sampling ? launch_vf_groups<true> : launch_vf_groups<false>)(s, sh, total, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream);
+    if (sampling) launch_vf_groups(s, total, n_groups, d_matrix, d_escaped, stream, [&](unsigned long long* m, CopyHist h) { return ViewFactorGroupsJob<true>{sh, n_groups, d_groups, d_weights, m, d_escaped, h}; });
+    else launch_vf_groups(s, total, n_groups, d_matrix, d_escaped, stream, [&](unsigned long long* m, CopyHist h) { return ViewFactorGroupsJob<false>{sh, n_groups, d_groups, d_weights, m, d_escaped, h}; });
+}
+
+// Form factors between instances (rc_placed_*): the scene arrays of a placed source, the two composed stages, and rc_launch_vf_groups with
+// PlacedViewFactorGroupsJob over placed primitives [placed_begin, placed_end) clamped to P -- the same copy bound, scratch and fold.
+// The callers have checked P < 2^32 and the ranges of the stages.
+static PlacedView placed_view(const rc_scene* s) {
+    return PlacedView{s->d_instances.p, s->inst_recs.p, s->flat_prims.p, s->d_placed_base.p, s->n_static_instances};
+}
+void rc_launch_placed_triangles(rc_scene* s, uint32_t placed_begin, uint32_t n, float* d_verts, hipStream_t stream) {
+    launch_stage(s, stream, n, k_placed_triangles, placed_view(s), placed_begin, n, d_verts);
+}
+void rc_launch_placed_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t placed_prim, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out, hipStream_t stream) {
+    launch_stage(s, stream, n_ray, sampling ? k_placed_view_factor_rays<true> : k_placed_view_factor_rays<false>, placed_view(s), rc_philox_key(seed), placed_prim,
+                 ray_begin, n_ray, d_out);
+}
+void rc_launch_placed_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
+                                uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
+                                unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream) {
+    VfShard sh;
+    const uint64_t total = vf_shard((uint32_t)s->n_placed, rays_per_triangle, seed, placed_begin, placed_end, ray_begin, ray_end, sh);
+    if (!total) return;
+    const RcInstanceDesc* instances = s->d_instances.p;
+    const uint32_t* base = s->d_placed_base.p;
+    if (sampling) launch_vf_groups(s, total, n_groups, d_matrix, d_escaped, stream, [&](unsigned long long* m, CopyHist h) { return PlacedViewFactorGroupsJob<true>{instances, base, sh, n_groups, d_groups, d_weights, m, d_escaped, h}; });
+    else launch_vf_groups(s, total, n_groups, d_matrix, d_escaped, stream, [&](unsigned long long* m, CopyHist h) { return PlacedViewFactorGroupsJob<false>{instances, base, sh, n_groups, d_groups, d_weights, m, d_escaped, h}; });
 }
 
 // Rows [row_begin, row_end) of the view-factor matrix in canonical CSR (rc_view_factors_sparse_device), all on `stream`, no host wait.

@@ -222,6 +222,11 @@ struct rc_scene {
     DevBuf<uint32_t> blas_cull_bits;   // per BLAS: radius (float bits) of the sphere about the root box's centre that holds every leaf box
     DevBuf<float4> inst_cull;          // per instance: (c_w, A), (B, -, -, -): the entry-cull sphere, k_inst_recs (rc_build.hip)
     uint32_t n_static_instances = 0;
+    // the placed-primitive table (raycore_mi355x.h, "Form factors between instances"): base[i] = the primitives of the instances before i,
+    // n_static_instances + 1 words on the host and on the device.  Built by rc_build_tlas: structure changes only there
+    std::vector<uint32_t> placed_base;
+    DevBuf<uint32_t> d_placed_base;
+    uint64_t n_placed = 0;             // P = base[n_inst] before it is cut to 32 bits: at 2^32 and above the placed calls refuse the scene
     DevBuf<RcNode> flat_nodes;
     uint32_t n_flat_nodes = 0;
     DevBuf<uint32_t> tlas_flags;       // arrival counters of rc_refit_tlas_async (n - 1 words; `flags` below belongs to the builds on the scene's own stream)
@@ -499,6 +504,13 @@ void rc_launch_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t sampling, u
 void rc_launch_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t src_begin, uint32_t src_end,
                          uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
                          unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream);
+// Form factors between instances (rc_drivers.hip): the world triangles of placed primitives (9 f32 each), the sampled rays of one placed
+// primitive, and rc_launch_vf_groups over placed primitives.  The callers have checked s->n_placed < 2^32 and the stages' ranges.
+void rc_launch_placed_triangles(rc_scene* s, uint32_t placed_begin, uint32_t n, float* d_verts, hipStream_t stream);
+void rc_launch_placed_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t sampling, uint32_t placed_prim, uint32_t ray_begin, uint32_t n_ray, RcRay* d_out, hipStream_t stream);
+void rc_launch_placed_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
+                                uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
+                                unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream);
 void rc_multi_prepare_impl(rc_scene* const* scenes, int n_scenes, float out_ms[4]);
 int rc_multi_ranks_impl(rc_scene* const* scenes, int n_scenes);
 void rc_view_factor_totals_multi_impl(rc_scene* const* scenes, int n_scenes, uint32_t rays_per_triangle, uint64_t seed, uint64_t* out_received, uint64_t* out_emitted);

@@ -345,6 +345,36 @@ view_factor_groups_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, seed
                            d_matrix::Ptr{UInt64}, d_escaped::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_view_factor_groups_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, UInt32, Ptr{UInt32}, UInt32, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
                 a.owner.ptr, rays_per_triangle, seed, sampling, src_begin, src_end, ray_begin, ray_end, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream))
+"The placed-primitive table: `n_inst + 1` UInt32, `base[i + 1]` (1-based Julia index) = the primitives of the instances before 0-based
+instance `i` in the instance array's order; the last entry is P.  Placed primitive `q = base + l` is primitive `l` (0-based, in the BLAS's
+sorted order) of that instance: the index space of the three calls below."
+function placed_primitive_bases(a::MI355XStaticTLAS)
+    n = Ref{UInt32}(0)
+    check(ccall((:rc_placed_primitive_bases, LIB), Cint, (Ptr{Cvoid}, Ptr{UInt32}, UInt32, Ref{UInt32}), a.owner.ptr, C_NULL, 0, n))
+    out = Vector{UInt32}(undef, n[])
+    check(ccall((:rc_placed_primitive_bases, LIB), Cint, (Ptr{Cvoid}, Ptr{UInt32}, UInt32, Ref{UInt32}), a.owner.ptr, out, n[], n))
+    out
+end
+"The world triangles of placed primitives `[placed_begin, placed_begin + n)`, 9 Float32 each: the local vertices under the instance's forward
+transform as it is in device memory when the kernel runs."
+placed_triangles_device!(a::MI355XStaticTLAS, placed_begin::Integer, n::Integer, d_verts::Ptr{Float32}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_placed_triangles_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt32, Ptr{Float32}, Ptr{Cvoid}), a.owner.ptr, placed_begin, n, d_verts, stream))
+"The sampled view-factor rays of one PLACED primitive: `view_factor_sampled_rays_device!`'s ray of the world triangle, with the instance in
+the third word of the Philox counter (instance 0 under an identity transform draws the sibling's numbers)."
+placed_view_factor_rays_device!(a::MI355XStaticTLAS, seed::UInt64, sampling::Integer, placed_prim::Integer, ray_begin::Integer, n_rays::Integer,
+                                d_rays::Ptr{RTRay}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_placed_view_factor_rays_device, LIB), Cint, (Ptr{Cvoid}, UInt64, UInt32, UInt32, UInt32, UInt32, Ptr{RTRay}, Ptr{Cvoid}),
+                a.owner.ptr, seed, sampling, placed_prim, ray_begin, n_rays, d_rays, stream))
+"One shard (placed primitives [placed_begin, placed_end) x rays [ray_begin, ray_end)) of the weighted counts between GROUPS of PLACED
+primitives, ACCUMULATED into `d_matrix` (G x G UInt64, row = source group, row-major) and `d_escaped` (G UInt64, may be C_NULL): the sources
+are in world space.  `d_groups` / `d_weights` (may be C_NULL): P UInt32 each, indexed by placed primitive `q`; a group >= G excludes the
+primitive.  The rule has no metadata in it: a ray from `a` that hits placed primitive `b != a` adds `a`'s weight to `matrix[ga, gb]`, a miss to
+`escaped[ga]`.  Legal behind the device-side transform and geometry updates on the same stream with no host wait."
+placed_view_factor_groups_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, seed::UInt64, sampling::Integer, placed_begin::Integer,
+                                  placed_end::Integer, ray_begin::Integer, ray_end::Integer, d_groups::Ptr{UInt32}, n_groups::Integer,
+                                  d_weights::Ptr{UInt32}, d_matrix::Ptr{UInt64}, d_escaped::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_placed_view_factor_groups_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, UInt32, Ptr{UInt32}, UInt32, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
+                a.owner.ptr, rays_per_triangle, seed, sampling, placed_begin, placed_end, ray_begin, ray_end, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream))
 """
     view_factors_sparse(accel; rays_per_triangle, seed) -> (row_ptr::Vector{UInt64}, cols::Vector{UInt32}, vals::Vector{UInt32})
 
