@@ -217,7 +217,7 @@ int rc_trace_any_device_batches(rc_scene* scene, const rc_ray* const* d_rays, rc
  * then in one launch of eight; default 1), "order_close_repeats" (1 = a launch with a remembered batch's ray origins and nearly its directions -- jittered re-renders of a still view -- continues that batch's history like an exact repeat; 0 = exact repeats only; default 1),
  * "cost_thr" (its initial reporting threshold), "entry_cull" (1 = an instance whose conservative sphere the ray's segment misses is
  * not entered: the reference's traversal of it would test no triangle; 0 = off, 1 = closest_hit and the drivers (default),
- * 2 = any_hit batches too), "vf_chunk_bytes" (device block per row chunk of the host-matrix view factors), "illum_scratch_bytes" (rc_get_illumination_dirs_device: histogram scratch per launch, which bounds its group of directions; default 256 MiB), "vf_first_touch" (ROWS on several devices: each device's
+ * 2 = any_hit batches too), "vf_chunk_bytes" (device block per row chunk of the host-matrix view factors), "illum_scratch_bytes" (rc_get_illumination_dirs_device: histogram scratch per launch, which bounds its group of directions; default 256 MiB), "placed_copy_bytes" (rc_placed_view_factor_products_device: d_mtx is counted into private copies while 16 copies of P u64 fit, added straight onto the caller's words above; 0 = always straight; default 256 MiB; changes no result), "vf_first_touch" (ROWS on several devices: each device's
  * host thread joins the device's NUMA node and faults in its own row block; default 1), "release_captures" (set to 1 when the hipGraphs that
  * captured launches of this scene have been destroyed: frees their stack spill regions and counter slots, 16 per scene; get: how many are held),
  * "blas_top" (1 = a scene with a single BLAS keeps that BLAS's top internal
@@ -951,6 +951,38 @@ int rc_point_source_rays_device(rc_scene* scene, const rc_ray* d_sources, uint32
 int rc_get_illumination_points_device(rc_scene* scene, const rc_ray* d_sources, uint32_t n_sources, uint32_t grid, uint64_t seed,
                                       uint32_t first_source, uint32_t* d_counts, uint64_t row_stride, uint32_t* d_escaped, void* stream);
 
+/* ---- Radiosity between instances: the matrix of counts between PLACED primitives APPLIED TO A VECTOR, without the matrix -- the step of
+ * B <- E + rho .* (M * B) ./ R per surface element of an INSTANCED scene.  rc_view_factor_products_device answers in metadata space: instances
+ * of one mesh share metadata and its sources are shot from BLAS-local coordinates, so on an instanced scene it describes another scene.  This
+ * call is its form in the index space of "Form factors between instances" (below): 1. the placed-primitive index space, q = base[i] + l,
+ * P = base[n_inst]; 2. the placed ray -- the source is that family's, unchanged: the rays are bit for bit those of
+ * rc_placed_view_factor_rays_device, with the same two samplings.  With sampling = RC_VF_SAMPLING_COSINE, M[a, b] / R estimates the Lambertian
+ * form factor F_ab, so the iteration over placed primitives is the radiosity equation; RC_VF_SAMPLING_UNIFORM shoots the reference's
+ * directions.
+ * THE RULE, with no metadata in it.  Item w = placed primitive placed_begin + w / n_ray, ray ray_begin + w % n_ray, n_ray = the clamped ray
+ * range's length.  a = the source's q.  For a hit, b = base[hit instance] + prim - 1.  A hit with b != a:
+ *     mx [a] += x[b]        (M  x)[a]
+ *     mtx[b] += x[a]        (M^T x)[b]
+ * A miss: escaped[a] += 1.  A hit on the source itself adds nothing.  All adds are u64 modulo 2^64, exact in any order: any partition of
+ * placed primitives x rays gives the same words.  d_x: P u32, indexed by q, read WHEN THE KERNEL RUNS and only for counted rays; d_x == NULL
+ * means x = 1: mx is then the count of a source's rays that hit another placed primitive (the placed `emitted`) and mtx the placed
+ * `received`, so the totals need no call of their own, and mx[a] + escaped[a] + the self hits of a = the rays of a.  d_mx, d_mtx, d_escaped:
+ * P u64 each, every one may be NULL.  All outputs ACCUMULATE.
+ * placed_end is clamped to P and ray_end to rays_per_triangle; an empty range, or all three outputs NULL, enqueues nothing.  d_mtx is the
+ * hot vector: the kernel counts it into 16 private copies of P u64 while they fit option "placed_copy_bytes" (default 256 MiB: P <= 2 M) and a
+ * fold adds them, and adds straight onto the caller's words above that -- P is 2 x 10^7 on a 4800-instance scene, where the copies would be
+ * 2.5 GB: the same words either way.  d_mx and d_escaped are per source and are added onto the caller's words.  Scratch is per stream;
+ * shards accumulate on one stream or concurrently on several.  Legal on a capturing stream that has run the call eagerly once, and behind
+ * rc_update_transforms_device -> rc_refit_device_async (or the rebuilds) and behind rc_update_geometry_device_async on the same stream with
+ * no host wait: a replay reads the CURRENT transforms and x.
+ * Errors, all before anything is enqueued and with the outputs untouched: RC_ERR_INVALID_ARGUMENT (NULL scene; sampling above
+ * RC_VF_SAMPLING_COSINE; P >= 2^32), RC_ERR_NOT_SYNCED in the states in which rc_placed_view_factor_groups_device returns it.  A stack
+ * overflow is reported by rc_wait.
+ * Register and scratch figures of the six new kernel shells: docs/EXPERIMENTS.md, "Radiosity between instances". */
+int rc_placed_view_factor_products_device(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin,
+                                          uint32_t placed_end, uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_x, uint64_t* d_mx,
+                                          uint64_t* d_mtx, uint64_t* d_escaped, void* stream);
+
 /* ---- Final gather: how much of a per-triangle solution arrives at every hit point?  The step between the analysis half (a u32 per
  * primitive indexed by metadata - 1: rc_view_factor_products_device's x, a radiosity iterate) and the per-hit half: the hemisphere samples of
  * rc_ambient_occlusion_device (declared below), traced for the CLOSEST hit -- closest_hit, src/instanced-bvh.jl:1902-2024 -- and the field
@@ -1030,7 +1062,8 @@ int rc_final_gather_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* 
  * or d_verts with n != 0; sampling above RC_VF_SAMPLING_COSINE; n_groups outside 1..65535; placed_prim >= P; placed_begin + n > P;
  * capacity below n_inst + 1; P >= 2^32), RC_ERR_NOT_SYNCED in the states in which rc_view_factor_groups_device returns it.  A stack
  * overflow is reported by rc_wait.
- * Placed forms of the dense matrix, the totals, the products, the sparse matrix and the bounce solve do not exist yet.
+ * The placed totals, products and bounce solve: rc_placed_view_factor_products_device ("Radiosity between instances", declared ahead of the
+ * final gather).  Placed forms of the dense matrix and of the sparse matrix do not exist yet.
  * Register and scratch figures of the new kernel shells and the cost against the sibling: docs/EXPERIMENTS.md, "Form factors between
  * instances". */
 int rc_placed_primitive_bases(rc_scene* scene, uint32_t* out, uint32_t capacity, uint32_t* count);

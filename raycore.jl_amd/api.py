@@ -694,6 +694,20 @@ class TLAS:
                                                         ptr(groups_ptr), int(n_groups), ptr(weights_ptr) if weights_ptr else None, ptr(matrix_ptr),
                                                         ptr(escaped_ptr) if escaped_ptr else None, ptr(stream) if stream else None))
 
+    def placed_view_factor_products_device(self, x_ptr, mx_ptr, mtx_ptr, rays_per_triangle, seed, sampling="uniform", escaped_ptr=None, placed=None,
+                                           rays=None, stream=None):
+        """The matrix of counts between PLACED primitives applied to a device vector without the matrix
+        (rc_placed_view_factor_products_device): view_factor_products_device with the sources in world space and a choice of sampling.
+        x_ptr: P u32 indexed by placed primitive q, or None for x = 1 (the placed totals); mx_ptr / mtx_ptr / escaped_ptr: P u64 each (every
+        one may be None), ACCUMULATED: a ray from placed primitive a that hits placed primitive b != a adds x[b] to mx[a] and x[a] to
+        mtx[b], one that hits nothing adds 1 to escaped[a]; modulo 2^64.  No metadata takes part.  placed / rays: (begin, end) ranges of
+        placed primitives and of ray indices (default: all) -- the shards of one job add up to the whole."""
+        s0, s1 = (0, 0xFFFFFFFF) if placed is None else placed
+        r0, r1 = (0, int(rays_per_triangle)) if rays is None else rays
+        check(lib().rc_placed_view_factor_products_device(self._h, int(rays_per_triangle), int(seed), vf_sampling(sampling), int(s0), int(s1), int(r0), int(r1),
+                                                          ptr(x_ptr) if x_ptr else None, ptr(mx_ptr) if mx_ptr else None, ptr(mtx_ptr) if mtx_ptr else None,
+                                                          ptr(escaped_ptr) if escaped_ptr else None, ptr(stream) if stream else None))
+
     def view_factors_sparse_device(self, row_ptr_ptr, cols_ptr, vals_ptr, capacity, nnz_ptr, rays_per_triangle, seed, rows=None, stream=None):
         """Rows `rows` = (begin, end) (default: all; end is clamped to N) of the view-factor matrix in canonical CSR on the device
         (rc_view_factors_sparse_device), OVERWRITTEN: row_ptr_ptr: rows + 1 u64 starting at 0; cols_ptr / vals_ptr: `capacity` u32 each
@@ -1767,6 +1781,130 @@ def radiosity(accel, emission, reflectance, bounces, rays_per_triangle=10000, se
     if matrix is not None and not isinstance(matrix, SparseViewFactors):
         raise ValueError("matrix must be a SparseViewFactors (view_factors_sparse's result)")
     x = view_factor_bounces(accel if matrix is None else matrix, e_q, rho_q, bounces, rays_per_triangle, seed, stream)
+    b = x.astype(np.float64) / scale
+    return (b, scale) if return_scale else b
+
+
+def check_placed_products_arguments(x, rays_per_triangle, seed, sampling):
+    """The arguments of placed_view_factor_products / placed_view_factor_totals (x = None), checked before any device is touched:
+    (x as contiguous uint32 or None, the sampling word)."""
+    if x is not None:
+        if not isinstance(x, np.ndarray) or x.dtype != np.uint32 or x.ndim != 1:
+            raise ValueError("x must be a one-dimensional uint32 array with one value per placed primitive")
+        x = np.ascontiguousarray(x)
+    if isinstance(rays_per_triangle, bool) or not isinstance(rays_per_triangle, (int, np.integer)) or not 0 <= int(rays_per_triangle) <= U32_MAX:
+        raise ValueError("rays_per_triangle must be an integer in 0..2^32 - 1")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64):
+        raise ValueError("seed must be an integer in 0..2^64 - 1")
+    return x, vf_sampling(sampling)
+
+
+def _placed_products(accel, x, rays_per_triangle, seed, word):
+    """Upload, one rc_placed_view_factor_products_device over everything, download: (mx, mtx, escaped) as uint64 of length P."""
+    import torch
+    t = _owner(accel)
+    P = int(t.placed_primitive_bases()[-1])
+    if x is not None and len(x) != P:
+        raise ValueError(f"x must hold one value per placed primitive: {len(x)} values for {P} placed primitives")
+    dev = f"cuda:{t.device}"
+    torch.cuda.synchronize(t.device)  # (the call runs on the default stream: behind whatever the caller enqueued on streams of its own)
+    d_x = torch.from_numpy(x.view(np.int32)).to(dev) if (x is not None and P) else None
+    out = torch.zeros(3 * max(P, 1), dtype=torch.int64, device=dev)
+    if P:
+        t.placed_view_factor_products_device(d_x.data_ptr() if d_x is not None else None, out.data_ptr(), out.data_ptr() + 8 * P, int(rays_per_triangle), int(seed),
+                                             word, out.data_ptr() + 16 * P)
+    torch.cuda.synchronize(t.device)
+    t.wait_for_gpu()  # (reports a traversal stack overflow)
+    words = out.cpu().numpy().view(np.uint64)
+    return words[:P].copy(), words[P:2 * P].copy(), words[2 * P:3 * P].copy()
+
+
+def placed_view_factor_products(accel, x, rays_per_triangle=10000, seed=0, sampling="uniform", return_escaped=False):
+    """view_factor_products with the sources in WORLD space (rc_placed_view_factor_products_device): (mx, mtx[, escaped]), uint64 vectors of
+    length P with mx = M @ x and mtx = M.T @ x modulo 2^64, M[a, b] = the rays of placed primitive a that hit placed primitive b != a
+    first -- placed_view_factor_groups(accel, arange(P), ...) is that matrix.  x: uint32, length P, indexed by placed primitive
+    q = base[i] + l (placed_primitive_bases()).  escaped[a] = the rays of a that hit nothing.  sampling "cosine": M / R estimates the
+    Lambertian form factors between the placed primitives.  No metadata takes part.  Costs the tracing only.
+    ValueError for a wrong length, an x that is not uint32, or an unknown sampling."""
+    x, word = check_placed_products_arguments(x, rays_per_triangle, seed, sampling)
+    if x is None:
+        raise ValueError("x must be a one-dimensional uint32 array with one value per placed primitive")
+    mx, mtx, escaped = _placed_products(accel, x, rays_per_triangle, seed, word)
+    return (mx, mtx, escaped) if return_escaped else (mx, mtx)
+
+
+def placed_view_factor_totals(accel, rays_per_triangle=10000, seed=0, sampling="uniform"):
+    """view_factor_totals per PLACED primitive: (received, emitted, escaped), uint64 vectors of length P -- the rays that arrive at placed
+    primitive q from another one, the rays of q that hit another one, and the rays of q that hit nothing.  placed_view_factor_products with
+    x = 1 (the C call takes NULL for it): emitted[q] + escaped[q] + the hits of q on itself = rays_per_triangle."""
+    _, word = check_placed_products_arguments(None, rays_per_triangle, seed, sampling)
+    mx, mtx, escaped = _placed_products(accel, None, rays_per_triangle, seed, word)
+    return mtx, mx, escaped
+
+
+def placed_view_factor_bounces(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, sampling="cosine", stream=None):
+    """view_factor_bounces over PLACED primitives: `bounces` steps of
+
+        x_0 = e,    x_{k+1}[q] = min(2^32 - 1, e[q] + (((M x_k)[q] // R) * rho[q] >> 16))
+
+    in integers on the device, with M the matrix of placed_view_factor_products (sources in world space, hits named by (instance,
+    primitive)) and R = rays_per_triangle.  With sampling "cosine" (the default) M / R estimates the Lambertian form factors between the
+    surface elements, so this is the radiosity equation of an instanced scene; "uniform" shoots the reference's directions.  The same
+    seed is used every bounce: the iteration with that one matrix, exact, independent of the order of the device's adds.
+    emission: u32 per placed primitive (length P, indexed by q = base[i] + l); reflectance: 0..65536, 16.16 fixed point.  Both are numpy
+    integer arrays or device int64 / int32 torch tensors.  Each bounce is zero -> placed_view_factor_products_device (mx only) -> an
+    elementwise torch update (placed_bounce_step), all on `stream` with no host wait between bounces.  Returns x: a uint32 numpy array for
+    numpy input, else an int64 tensor on the device, ready on `stream`.  ValueError as view_factor_bounces, and for an unknown sampling."""
+    e, rho = check_bounce_arguments(emission, reflectance, bounces, rays_per_triangle)
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64):
+        raise ValueError("seed must be an integer in 0..2^64 - 1")
+    word = vf_sampling(sampling)
+    import torch
+    t = _owner(accel)
+    P = int(t.placed_primitive_bases()[-1])
+    if len(e) != P:
+        raise ValueError(f"emission and reflectance must hold one value per placed primitive: {len(e)} values for {P} placed primitives")
+    dev = torch.device("cuda", t.device)
+    on_host = not _is_tensor(e)
+    ts = stream if isinstance(stream, torch.cuda.Stream) else (torch.cuda.ExternalStream(int(stream), device=dev) if stream else torch.cuda.current_stream(dev))
+    with torch.cuda.stream(ts):
+        e, rho = (torch.from_numpy(a).to(dev) if not _is_tensor(a) else a.to(dev) for a in (e, rho))
+        for a in (e, rho):
+            a.record_stream(ts)  # (a caller's tensor, or its int64 copy made on the stream the caller was on)
+        x = e.clone()
+        x32 = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+        mx = torch.empty(max(P, 1), dtype=torch.int64, device=dev)
+        for _ in range(int(bounces)):
+            placed_bounce_step(t, e, rho, x, x32, mx, int(rays_per_triangle), int(seed), word, ts.cuda_stream)
+    if on_host:
+        ts.synchronize()
+        t.wait_for_gpu()  # (reports a traversal stack overflow)
+        return x.cpu().numpy().astype(np.uint32)
+    return x
+
+
+def placed_bounce_step(t, e, rho, x, x32, mx, rays_per_triangle, seed, sampling, stream):
+    """bounce_step over placed primitives: one bounce of placed_view_factor_bounces on the current torch stream, whose raw handle is
+    `stream`.  x (int64, values in u32, length P) is replaced by the next iterate; x32 (int32) and mx (int64) are scratch of the same
+    length.  Nothing here waits for the device, so a loop of steps may be captured into a graph (after one eager step)."""
+    import torch
+    n = x.numel()
+    x32[:n].copy_(x.view(torch.int32).view(n, 2)[:, 0])  # the low words: x as u32
+    mx.zero_()
+    t.placed_view_factor_products_device(x32.data_ptr(), mx.data_ptr(), None, rays_per_triangle, seed, sampling, stream=stream)
+    nxt = e + ((torch.div(mx[:n], rays_per_triangle, rounding_mode="floor") * rho) >> 16)  # (M x)[q] < 2^63: non-negative in int64
+    x.copy_(nxt.clamp_(max=U32_MAX))
+
+
+def placed_radiosity(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, sampling="cosine", stream=None, return_scale=False):
+    """Radiosity per surface element of an INSTANCED scene by `bounces` steps of B <- E + rho .* (M B) / R in float terms: radiosity() on top
+    of placed_view_factor_bounces.  emission: float array >= 0, reflectance: float array in [0, 1), one value per PLACED primitive
+    (ValueError otherwise).  With sampling "cosine" (the default) M / R estimates the form factors F_ab, so the fixed point is the
+    radiosity equation's; the per-triangle radiosity() is uniform-only.  Quantisation and scaling back: radiosity_scale.
+    return_scale: also return the scale (result = integer iterate / scale)."""
+    vf_sampling(sampling)
+    scale, e_q, rho_q = radiosity_scale(emission, reflectance)
+    x = placed_view_factor_bounces(accel, e_q, rho_q, bounces, rays_per_triangle, seed, sampling, stream)
     b = x.astype(np.float64) / scale
     return (b, scale) if return_scale else b
 

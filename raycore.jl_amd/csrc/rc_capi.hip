@@ -1352,6 +1352,7 @@ int rc_set_option(rc_scene* s, const char* name, int64_t value) {
     }
     else if (k == "vf_chunk_bytes") s->opt.vf_chunk_bytes = value < 4096 ? 4096 : (value > (int64_t(4) << 30) ? (int64_t(4) << 30) : value);
     else if (k == "illum_scratch_bytes") s->opt.illum_scratch_bytes = value < 1 ? 1 : (value > (int64_t(4) << 30) ? (int64_t(4) << 30) : value);  // (a launch always gets one direction's worth)
+    else if (k == "placed_copy_bytes") s->opt.placed_copy_bytes = value < 0 ? 0 : (value > (int64_t(16) << 30) ? (int64_t(16) << 30) : value);  // (0: mtx always straight onto the caller's words)
     else if (k == "vf_sparse_scratch_bytes") s->opt.vf_sparse_scratch_bytes = value < 8 ? 8 : (value > (int64_t(16) << 30) ? (int64_t(16) << 30) : value);  // (a chunk always gets one whole row)
     else if (k == "timeline_ptr") s->opt.timeline_ptr = value;  // dev instrumentation: the caller owns the buffer and its size (8 x u64 per wave of the launch)
     else if (k == "debug_set_overflow") {  // test hook: raise the sticky stack-overflow word as a kernel would (no LBVH is deep enough to do it for real)
@@ -1426,6 +1427,7 @@ int rc_get_option(rc_scene* s, const char* name, int64_t* value) {
     }
     else if (k == "vf_chunk_bytes") *value = s->opt.vf_chunk_bytes;
     else if (k == "illum_scratch_bytes") *value = s->opt.illum_scratch_bytes;
+    else if (k == "placed_copy_bytes") *value = s->opt.placed_copy_bytes;
     else if (k == "vf_sparse_scratch_bytes") *value = s->opt.vf_sparse_scratch_bytes;
     else if (k == "blas_top_k") *value = s->blas_top_k;
     else if (k == "tlas_top_k") *value = s->tlas_top_k;
@@ -1759,6 +1761,20 @@ int rc_placed_view_factor_groups_device(rc_scene* s, uint32_t rays_per_triangle,
         require_placed(s, "rc_placed_view_factor_groups_device");
         rc_launch_placed_vf_groups(s, rays_per_triangle, seed, sampling, placed_begin, placed_end, ray_begin, ray_end, d_groups, n_groups, d_weights,
                                    reinterpret_cast<unsigned long long*>(d_matrix), reinterpret_cast<unsigned long long*>(d_escaped), (hipStream_t)stream);
+    });
+}
+
+// Radiosity between instances: the matrix of counts between placed primitives applied to a vector, the escapes beside it
+// (PlacedViewFactorProductsJob, rc_drivers.hip).  d_x == NULL is x = 1: the placed totals.  All three outputs NULL: nothing to do.
+int rc_placed_view_factor_products_device(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
+                                          uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_x, uint64_t* d_mx, uint64_t* d_mtx, uint64_t* d_escaped, void* stream) {
+    if (!s) return fail(RC_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (sampling > RC_VF_SAMPLING_COSINE) return fail(RC_ERR_INVALID_ARGUMENT, "rc_placed_view_factor_products_device: sampling must be RC_VF_SAMPLING_UNIFORM or RC_VF_SAMPLING_COSINE");
+    return guarded([&] {
+        use_device(s);
+        require_placed(s, "rc_placed_view_factor_products_device");
+        rc_launch_placed_vf_products(s, rays_per_triangle, seed, sampling, placed_begin, placed_end, ray_begin, ray_end, d_x, reinterpret_cast<unsigned long long*>(d_mx),
+                                     reinterpret_cast<unsigned long long*>(d_mtx), reinterpret_cast<unsigned long long*>(d_escaped), (hipStream_t)stream);
     });
 }
 

@@ -1267,6 +1267,52 @@ struct PlacedViewFactorGroupsJob {
     }
     __device__ inline PlacedGroupsSink sink(const SceneView&) const { return PlacedGroupsSink{base, sh, n_groups, groups, weights, matrix, escaped, h}; }
 };
+// Radiosity between instances: the P x P matrix of counts between PLACED primitives applied to a vector without the matrix
+// (rc_placed_view_factor_products_device).  The rule, no metadata in it: a = the source's q; for a hit b = base[hit instance] + prim - 1.  A
+// hit with b != a adds x[b] to mx[a] = (M x)[a] and x[a] to mtx[b] = (M^T x)[b]; a miss adds 1 to escaped[a]; a hit on the source itself
+// adds nothing.  x == nullptr is x = 1: mx and mtx are then the placed `emitted` and `received`, so the totals need no job of their own.
+// u64 adds modulo 2^64, exact in any order.  x is read for counted rays only.  mtx is the hot vector: it goes through the copy histogram
+// like ViewFactorProductsSink's while the copies fit (h.n8 != 0, uniform over the launch), and straight onto the caller's words above that
+// (h = {0}).  mx and escaped are per source, nearly wave-uniform in their target: wave_add / wave_count onto the caller's words.  Called
+// under phased_trace's `if (fin)` like its siblings: every finishing lane reaches the same three calls, and both helpers read only lanes
+// they have just balloted.
+struct PlacedProductsSink {
+    const uint32_t* base;
+    VfShard sh;
+    const uint32_t* x;            // P words, indexed by q, or nullptr: every x is 1
+    unsigned long long* mtx;      // one histogram of scratch words (h.n8 != 0), the caller's P words (h.n8 == 0), or nullptr
+    CopyHist h;
+    unsigned long long* mx;       // [P] or nullptr
+    unsigned long long* escaped;  // [P] or nullptr
+    __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
+        const uint32_t a = sh.src_begin + (uint32_t)(w / sh.n_ray);
+        uint32_t b = a;
+        if (hit) b = base[instance] + prim - 1u;
+        const bool counted = b != a;
+        // (h = {0}: base() is 0 and the index is b itself -- one wave_add for both layouts)
+        if (mtx) wave_add(mtx + h.base(h.copy()), h.n8 ? h.slot(b) : b, counted ? (x ? x[a] : 1u) : 0u, counted);
+        if (mx) wave_add(mx, a, counted ? (x ? x[b] : 1u) : 0u, counted);
+        if (escaped) wave_count(escaped, (unsigned long long)a, !hit);
+    }
+};
+template <bool COSINE>
+struct PlacedViewFactorProductsJob {
+    const RcInstanceDesc* instances;
+    const uint32_t* base;
+    VfShard sh;
+    const uint32_t* x;
+    unsigned long long* mtx;
+    CopyHist h;
+    unsigned long long* mx;
+    unsigned long long* escaped;
+    __device__ inline PlacedViewFactorSource<COSINE> source(const SceneView& v) const {
+        return PlacedViewFactorSource<COSINE>{PlacedView{instances, v.inst, v.prims, base, v.n_inst}, sh};
+    }
+    __device__ inline PlacedProductsSink sink(const SceneView&) const { return PlacedProductsSink{base, sh, x, mtx, h, mx, escaped}; }
+};
+// As for ViewFactorTotalsJob: the uniform job's plain shell has 36 bytes of private segment with the integer form of the stack position.
+template <>
+struct JobShapeFlags<PlacedViewFactorProductsJob<false>> { static constexpr unsigned kPlain = ShapePtrStack, kLds = 0u, kPartial = 0u; };
 
 // Diffuse bounce: output slot i continues the path of source slot s (s = i, or d_src[i] for i < count, or d_src[i % count] round robin
 // with k = i / count), from hit_point + normal * bias in a cosine-weighted direction about the geometric normal.  The uniforms are
@@ -1692,6 +1738,32 @@ void rc_launch_placed_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_
     const uint32_t* base = s->d_placed_base.p;
     if (sampling) launch_vf_groups(s, total, n_groups, d_matrix, d_escaped, stream, [&](unsigned long long* m, CopyHist h) { return PlacedViewFactorGroupsJob<true>{instances, base, sh, n_groups, d_groups, d_weights, m, d_escaped, h}; });
     else launch_vf_groups(s, total, n_groups, d_matrix, d_escaped, stream, [&](unsigned long long* m, CopyHist h) { return PlacedViewFactorGroupsJob<false>{instances, base, sh, n_groups, d_groups, d_weights, m, d_escaped, h}; });
+}
+// Radiosity between instances (rc_placed_view_factor_products_device): the products of the same shard with the device vector d_x (P u32,
+// nullptr: x = 1), ACCUMULATED into d_mx / d_mtx / d_escaped (P u64 each, device; each may be nullptr).  d_mtx takes the copy histogram and
+// FoldAddU64 of rc_launch_vf_products while 8 bytes x the copies' words fit option "placed_copy_bytes" -- P reaches 2 x 10^7 on the
+// 4800-instance scene, where 16 copies are 2.5 GB --, and is added straight onto the caller's words above that, the way launch_vf_groups
+// does.  Both paths give the same words.  Nothing is read on the host.
+template <bool COSINE>
+static void launch_placed_vf_products(rc_scene* s, const VfShard& sh, uint64_t total, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx,
+                                      unsigned long long* d_escaped, hipStream_t stream) {
+    DriverLaunch launch(s, stream, total);
+    const uint32_t P = (uint32_t)s->n_placed;
+    CopyHist h = CopyHist::of(P);
+    const bool copies = d_mtx && sizeof(unsigned long long) * h.words() <= (unsigned long long)s->opt.placed_copy_bytes;
+    unsigned long long* scratch = copies ? rc_hist_scratch<unsigned long long>(launch.guard, h).hist : nullptr;
+    if (!copies) h = CopyHist{0u};
+    const PlacedView pv = placed_view(s);  // (the kernel's own SceneView supplies inst, prims and n_inst)
+    launch.go<false>(PlacedViewFactorProductsJob<COSINE>{pv.instances, pv.base, sh, d_x, copies ? scratch : d_mtx, h, d_mx, d_escaped}, Nothing(),
+                     [&] { if (copies) rc_hist_fold(stream, scratch, h, P, FoldAddU64{{}, d_mtx}); });
+}
+void rc_launch_placed_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
+                                  uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx,
+                                  unsigned long long* d_escaped, hipStream_t stream) {
+    VfShard sh;
+    const uint64_t total = vf_shard((uint32_t)s->n_placed, rays_per_triangle, seed, placed_begin, placed_end, ray_begin, ray_end, sh);
+    if (!total || (!d_mx && !d_mtx && !d_escaped)) return;
+    (sampling ? launch_placed_vf_products<true> : launch_placed_vf_products<false>)(s, sh, total, d_x, d_mx, d_mtx, d_escaped, stream);
 }
 
 // Rows [row_begin, row_end) of the view-factor matrix in canonical CSR (rc_view_factors_sparse_device), all on `stream`, no host wait.

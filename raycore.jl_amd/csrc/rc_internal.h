@@ -162,6 +162,7 @@ struct TraceOptions {
     int64_t vf_first_touch = 1;          // ROWS on several devices: each device's host thread joins the device's NUMA node and faults in its own row block (rc_multi.hip)
     int64_t vf_chunk_bytes = 192 << 20;  // host-matrix view factors (rc_multi.hip): device block per row chunk -- large enough for full-rate launches and 2-D copies, small enough that the exposed first trace / last copy are a few ms
     int64_t illum_scratch_bytes = 256 << 20;  // rc_get_illumination_dirs_device: private histogram copies of one launch's group of directions: a bound on memory, the measured curve only falls with larger groups (docs/EXPERIMENTS.md); at least one direction's worth is always used
+    int64_t placed_copy_bytes = 256 << 20;  // rc_placed_view_factor_products_device: the private copies of mtx (16 x P u64) are used while they fit, above it mtx is added straight onto the caller's words; 0 = always straight (docs/EXPERIMENTS.md, "Radiosity between instances").  Changes no word of the result
     int64_t vf_sparse_scratch_bytes = 256 << 20;  // rc_view_factors_sparse*: the key array (8 bytes per ray) of one chunk of whole matrix rows; a single row above it gets a chunk of its own (docs/EXPERIMENTS.md, "Sparse view-factor matrix").  Changes no word of the result
     int64_t tlas_rebuild_fused = 1;  // rc_rebuild_tlas_device_async on scenes of at most kTlasLdsInst instances: 1 = one workgroup builds the whole TLAS in LDS (k_rebuild_tlas_fused), 0 = the chain of rc_build_tlas's kernels
     int64_t timeline_ptr = 0;  // dev: device address of 8 x u64 per wave (n_cus x 24 waves) that kernel 5 fills with its waves' event times; 0 = off
@@ -511,6 +512,10 @@ void rc_launch_placed_view_factor_rays(rc_scene* s, uint64_t seed, uint32_t samp
 void rc_launch_placed_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
                                 uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_groups, uint32_t n_groups, const uint32_t* d_weights,
                                 unsigned long long* d_matrix, unsigned long long* d_escaped, hipStream_t stream);
+// Radiosity between instances: rc_launch_vf_products over placed primitives, with a choice of sampling and the escapes; d_x may be nullptr (x = 1)
+void rc_launch_placed_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
+                                  uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx,
+                                  unsigned long long* d_escaped, hipStream_t stream);
 void rc_multi_prepare_impl(rc_scene* const* scenes, int n_scenes, float out_ms[4]);
 int rc_multi_ranks_impl(rc_scene* const* scenes, int n_scenes);
 void rc_view_factor_totals_multi_impl(rc_scene* const* scenes, int n_scenes, uint32_t rays_per_triangle, uint64_t seed, uint64_t* out_received, uint64_t* out_emitted);

@@ -375,6 +375,17 @@ placed_view_factor_groups_device!(a::MI355XStaticTLAS, rays_per_triangle::Intege
                                   d_weights::Ptr{UInt32}, d_matrix::Ptr{UInt64}, d_escaped::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_placed_view_factor_groups_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, UInt32, Ptr{UInt32}, UInt32, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
                 a.owner.ptr, rays_per_triangle, seed, sampling, placed_begin, placed_end, ray_begin, ray_end, d_groups, n_groups, d_weights, d_matrix, d_escaped, stream))
+"One shard (placed primitives [placed_begin, placed_end) x rays [ray_begin, ray_end)) of the matrix of counts between PLACED primitives applied
+to a device vector without the matrix, ACCUMULATED: a ray from placed primitive `a` that hits placed primitive `b != a` adds `x[b]` to `mx[a]`
+and `x[a]` to `mtx[b]`, one that hits nothing adds 1 to `escaped[a]` (0-based `a`, `b`); UInt64 modulo 2^64.  `d_x`: P UInt32 indexed by placed
+primitive, or C_NULL for x = 1 (then `mx` / `mtx` are the placed totals emitted / received).  `d_mx`, `d_mtx`, `d_escaped`: P UInt64 each, every
+one may be C_NULL.  With cosine sampling `M[a, b] / R` estimates the form factor F_ab: the product is the step of a radiosity iteration over
+the surface elements of an instanced scene.  Legal behind the device-side transform and geometry updates on the same stream with no host wait."
+placed_view_factor_products_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, seed::UInt64, sampling::Integer, placed_begin::Integer,
+                                    placed_end::Integer, ray_begin::Integer, ray_end::Integer, d_x::Ptr{UInt32}, d_mx::Ptr{UInt64},
+                                    d_mtx::Ptr{UInt64}, d_escaped::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_placed_view_factor_products_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, UInt32, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
+                a.owner.ptr, rays_per_triangle, seed, sampling, placed_begin, placed_end, ray_begin, ray_end, d_x, d_mx, d_mtx, d_escaped, stream))
 """
     view_factors_sparse(accel; rays_per_triangle, seed) -> (row_ptr::Vector{UInt64}, cols::Vector{UInt32}, vals::Vector{UInt32})
 
