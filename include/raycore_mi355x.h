@@ -983,6 +983,39 @@ int rc_placed_view_factor_products_device(rc_scene* scene, uint32_t rays_per_tri
                                           uint32_t placed_end, uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_x, uint64_t* d_mx,
                                           uint64_t* d_mtx, uint64_t* d_escaped, void* stream);
 
+/* ---- Sparse matrix between placed primitives: the matrix that rc_placed_view_factor_products_device applies, KEPT, as CSR -- the placed
+ * form of rc_view_factors_sparse_device.  The products above retrace all P x R rays for every bounce; a solve of tens of bounces builds the
+ * matrix once and then pays one pass over nnz x 8 bytes per bounce.  A placed row has at most min(R, P - 1) non-zeros, so the CSR exists
+ * where P x P words cannot (P is 2 x 10^7 on a 4800-instance scene).
+ * Mp[a, b] = the number of the R = rays_per_triangle placed rays of placed primitive a (bit for bit those of
+ * rc_placed_view_factor_rays_device, either sampling) whose closest hit is placed primitive b = base[hit instance] + prim - 1 with b != a:
+ * the rule of rc_placed_view_factor_products_device, no metadata in it.  Misses and hits on the source itself are in no entry; the diagonal
+ * is empty.  It is what rc_placed_view_factor_groups_device counts with every placed primitive its own group.
+ * The call OVERWRITES its outputs with rows [placed_begin, placed_end) of Mp (placed_end is clamped to P) under rc_view_factors_sparse_device's
+ * contract: d_row_ptr holds rows + 1 u64 offsets starting at 0 and is always the true one, *d_nnz is the true count, entries below
+ * `capacity` are the correct first entries, nothing is written at or beyond `capacity`, NULL d_cols / d_vals with capacity == 0 is the
+ * counting call; d_cols (0-based placed primitive) strictly ascending within a row, every d_vals >= 1.  The arrays are a function of (scene,
+ * rays_per_triangle, seed, sampling, row range) alone: the job is cut into chunks of whole consecutive rows whose rays x 8 bytes fit
+ * option "vf_sparse_scratch_bytes" (a single larger row gets a chunk of its own), and neither the option nor the shape of any kernel
+ * changes a word.  Row blocks of a partition of [0, P) concatenate.
+ * THE MATRIX IS A SNAPSHOT.  The build reads the instances' transforms as they are WHEN ITS KERNELS RUN.  After the instances move (or the
+ * geometry deforms) the arrays still describe the OLD placement; nothing tracks that, and rebuilding the matrix is the caller's job.
+ * THE PRODUCTS are rc_view_factor_sparse_products_device, which reads only the arrays: n_rows = the block's rows, row_offset = placed_begin,
+ * x and the outputs of length P.  With the CSR of the same (rays_per_triangle, seed, sampling) its sums equal
+ * rc_placed_view_factor_products_device's d_mx and d_mtx bit for bit.  There is no host-array form.
+ * Everything runs on the caller's stream with no host wait between the steps; scratch is per stream, two streams may build at once.  Legal
+ * behind rc_update_transforms_device -> rc_refit_device_async (or the rebuilds) and behind rc_update_geometry_device_async on the same
+ * stream with no host wait.  NOT capturable: RC_ERR_NOT_SYNCED on a stream that is being captured.
+ * Errors, all before anything is enqueued and with the outputs untouched: RC_ERR_INVALID_ARGUMENT (NULL scene, d_row_ptr or d_nnz; NULL
+ * d_cols / d_vals with capacity > 0; sampling above RC_VF_SAMPLING_COSINE; P >= 2^32; a chunk whose rays reach 2^32 or whose keys need
+ * more than 64 bits), RC_ERR_NOT_SYNCED in the states in which rc_placed_view_factor_products_device returns it.  A stack overflow is
+ * reported by rc_wait.
+ * Register and scratch figures of the six new kernel shells and the measured build, product and break-even figures:
+ * docs/EXPERIMENTS.md, "Sparse matrix between placed primitives". */
+int rc_placed_view_factors_sparse_device(rc_scene* scene, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin,
+                                         uint32_t placed_end, uint64_t* d_row_ptr, uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity,
+                                         uint64_t* d_nnz, void* stream);
+
 /* ---- Final gather: how much of a per-triangle solution arrives at every hit point?  The step between the analysis half (a u32 per
  * primitive indexed by metadata - 1: rc_view_factor_products_device's x, a radiosity iterate) and the per-hit half: the hemisphere samples of
  * rc_ambient_occlusion_device (declared below), traced for the CLOSEST hit -- closest_hit, src/instanced-bvh.jl:1902-2024 -- and the field
@@ -1063,7 +1096,8 @@ int rc_final_gather_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* 
  * capacity below n_inst + 1; P >= 2^32), RC_ERR_NOT_SYNCED in the states in which rc_view_factor_groups_device returns it.  A stack
  * overflow is reported by rc_wait.
  * The placed totals, products and bounce solve: rc_placed_view_factor_products_device ("Radiosity between instances", declared ahead of the
- * final gather).  Placed forms of the dense matrix and of the sparse matrix do not exist yet.
+ * final gather); the matrix itself as CSR: rc_placed_view_factors_sparse_device (declared behind it).  A placed form of the dense matrix
+ * does not exist yet.
  * Register and scratch figures of the new kernel shells and the cost against the sibling: docs/EXPERIMENTS.md, "Form factors between
  * instances". */
 int rc_placed_primitive_bases(rc_scene* scene, uint32_t* out, uint32_t capacity, uint32_t* count);

@@ -13,7 +13,8 @@ from .api import (BLAS4, CONTACT_DT, CollisionResult, ContactPair, collide_insta
                   view_factors_sparse, view_factor_sparse_products, SparseViewFactors,
                   view_factor_groups, form_factors, form_factor_weights, form_factors_from_counts, primitive_areas,
                   placed_primitive_count, placed_primitive_areas, placed_groups, placed_view_factor_groups, placed_form_factors,
-                  instance_form_factors, placed_view_factor_products, placed_view_factor_totals, placed_view_factor_bounces, placed_radiosity)
+                  instance_form_factors, placed_view_factor_products, placed_view_factor_totals, placed_view_factor_bounces, placed_radiosity,
+                  placed_view_factors_sparse, check_placed_sparse_arguments, check_placed_bounce_matrix)
 
 
 def device_count():

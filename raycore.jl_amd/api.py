@@ -718,6 +718,17 @@ class TLAS:
                                                   ptr(cols_ptr) if cols_ptr else None, ptr(vals_ptr) if vals_ptr else None, int(capacity),
                                                   ptr(nnz_ptr), ptr(stream) if stream else None))
 
+    def placed_view_factors_sparse_device(self, row_ptr_ptr, cols_ptr, vals_ptr, capacity, nnz_ptr, rays_per_triangle, seed, sampling="uniform",
+                                          rows=None, stream=None):
+        """Rows `rows` = (begin, end) (default: all; end is clamped to P) of the matrix of counts between PLACED primitives in canonical CSR
+        on the device (rc_placed_view_factors_sparse_device), OVERWRITTEN: view_factors_sparse_device's arguments and capacity contract,
+        with placed rows and columns and a choice of sampling.  The matrix is a SNAPSHOT of the placement at the time its kernels run.
+        Everything runs on `stream`; not capturable.  The products are view_factor_sparse_products_device."""
+        r0, r1 = (0, 0xFFFFFFFF) if rows is None else rows
+        check(lib().rc_placed_view_factors_sparse_device(self._h, int(rays_per_triangle), int(seed), vf_sampling(sampling), int(r0), int(r1),
+                                                         ptr(row_ptr_ptr), ptr(cols_ptr) if cols_ptr else None, ptr(vals_ptr) if vals_ptr else None,
+                                                         int(capacity), ptr(nnz_ptr), ptr(stream) if stream else None))
+
     def view_factor_sparse_products_device(self, n_rows, row_ptr_ptr, cols_ptr, vals_ptr, x_ptr, mx_ptr, mtx_ptr, row_offset=0, stream=None):
         """The products of a device CSR block with a device vector (rc_view_factor_sparse_products_device), ACCUMULATED modulo 2^64:
         mx[row_offset + r] += sum_k vals[k] x[cols[k]], mtx[cols[k]] += vals[k] x[row_offset + r]; mx_ptr / mtx_ptr: u64 vectors, either
@@ -1519,13 +1530,15 @@ class SparseViewFactors(tuple):
     owner runs the kernels), `n` (columns = length of x), `row_offset` (the matrix row of the block's first row), `rays_per_triangle` and
     `seed` it was traced with (None for a handmade matrix), `nnz` (the true count: larger than len(cols) after a build whose capacity was
     too small).  view_factors_sparse returns one whose arrays are ALSO still on the device (device_arrays()); one made from numpy arrays
-    is uploaded on first use."""
+    is uploaded on first use.  `placed`: rows and columns are PLACED primitives (placed_view_factors_sparse's result, n = P), and then
+    `sampling` is the RC_VF_SAMPLING_* word it was traced with; False and None for every other matrix."""
 
-    def __new__(cls, row_ptr, cols, vals, accel, n, row_offset=0, rays_per_triangle=None, seed=None, nnz=None, device=None):
+    def __new__(cls, row_ptr, cols, vals, accel, n, row_offset=0, rays_per_triangle=None, seed=None, nnz=None, device=None, sampling=None, placed=False):
         self = super().__new__(cls, (row_ptr, cols, vals))
         self.accel, self.n, self.row_offset, self.rays_per_triangle, self.seed = accel, int(n), int(row_offset), rays_per_triangle, seed
         self.nnz = int(len(cols) if nnz is None else nnz)
         self._device = device
+        self.sampling, self.placed = sampling, bool(placed)
         return self
 
     @classmethod
@@ -1842,6 +1855,55 @@ def placed_view_factor_totals(accel, rays_per_triangle=10000, seed=0, sampling="
     return mtx, mx, escaped
 
 
+def check_placed_sparse_arguments(rays_per_triangle, seed, sampling, rows, capacity):
+    """The arguments of placed_view_factors_sparse, checked before the library is touched: check_sparse_arguments' rules and a known
+    sampling.  Returns the sampling word."""
+    check_sparse_arguments(rays_per_triangle, seed, rows, capacity)
+    return vf_sampling(sampling)
+
+
+def placed_view_factors_sparse(accel, rays_per_triangle=10000, seed=0, sampling="uniform", rows=None, capacity=None):
+    """The matrix that placed_view_factor_products applies, KEPT, sparse (rc_placed_view_factors_sparse_device): the canonical CSR
+    (row_ptr uint64, cols uint32, vals uint32) of rows `rows` = (begin, end) (default: all; end is clamped to P) of M[a, b] = the rays of
+    placed primitive a that hit placed primitive b != a first -- placed_view_factor_groups(accel, arange(P), ...) is that matrix dense.
+    Rows and columns are placed primitives q = base[i] + l (placed_primitive_bases()); no metadata takes part; the diagonal is empty.  A
+    row has at most min(rays_per_triangle, P - 1) entries.  capacity: as view_factors_sparse (None: a counting call, then a filling call).
+    The result is a SparseViewFactors with placed = True, n = P, row_offset = rows[0] and the sampling word; the arrays stay on the device
+    for view_factor_sparse_products, placed_view_factor_bounces and placed_radiosity.
+    THE MATRIX IS A SNAPSHOT of the placement at the time of the call: after the instances move it describes the old placement, and
+    building it again is the caller's job."""
+    word = check_placed_sparse_arguments(rays_per_triangle, seed, sampling, rows, capacity)
+    import torch
+    t = _owner(accel)
+    P = int(t.placed_primitive_bases()[-1])
+    r0, r1 = (0, P) if rows is None else (min(int(rows[0]), P), min(int(rows[1]), P))
+    dev = torch.device("cuda", t.device)
+    st = torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev):
+        head = torch.zeros(r1 - r0 + 2, dtype=torch.int64, device=dev)  # row_ptr[rows + 1], then nnz
+        nnz_ptr = head.data_ptr() + 8 * (r1 - r0 + 1)
+        if capacity is None:
+            t.placed_view_factors_sparse_device(head.data_ptr(), None, None, 0, nnz_ptr, rays_per_triangle, seed, word, (r0, r1), st.cuda_stream)
+            capacity = int(head[-1].item())
+        entries = torch.zeros((2, max(int(capacity), 1)), dtype=torch.int32, device=dev)
+        t.placed_view_factors_sparse_device(head.data_ptr(), entries[0].data_ptr() if capacity else None, entries[1].data_ptr() if capacity else None,
+                                            int(capacity), nnz_ptr, rays_per_triangle, seed, word, (r0, r1), st.cuda_stream)
+        st.synchronize()
+        t.wait_for_gpu()  # (reports a traversal stack overflow)
+        nnz = int(head[-1].item())
+        filled = min(nnz, int(capacity))
+        d_row_ptr, d_cols, d_vals = head[:r1 - r0 + 1], entries[0, :filled], entries[1, :filled]
+        host = (d_row_ptr.cpu().numpy().view(np.uint64), d_cols.cpu().numpy().view(np.uint32), d_vals.cpu().numpy().view(np.uint32))
+    return SparseViewFactors(*host, t, P, r0, int(rays_per_triangle), int(seed), nnz, (d_row_ptr, d_cols, d_vals), sampling=word, placed=True)
+
+
+def check_placed_bounce_matrix(matrix):
+    """The matrix of placed_view_factor_bounces: placed_view_factors_sparse's result with all P rows, complete."""
+    if not isinstance(matrix, SparseViewFactors) or not matrix.placed:
+        raise ValueError("the matrix must be placed_view_factors_sparse's result: rows and columns must be placed primitives")
+    check_bounce_matrix(matrix)
+
+
 def placed_view_factor_bounces(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, sampling="cosine", stream=None):
     """view_factor_bounces over PLACED primitives: `bounces` steps of
 
@@ -1854,14 +1916,25 @@ def placed_view_factor_bounces(accel, emission, reflectance, bounces, rays_per_t
     emission: u32 per placed primitive (length P, indexed by q = base[i] + l); reflectance: 0..65536, 16.16 fixed point.  Both are numpy
     integer arrays or device int64 / int32 torch tensors.  Each bounce is zero -> placed_view_factor_products_device (mx only) -> an
     elementwise torch update (placed_bounce_step), all on `stream` with no host wait between bounces.  Returns x: a uint32 numpy array for
-    numpy input, else an int64 tensor on the device, ready on `stream`.  ValueError as view_factor_bounces, and for an unknown sampling."""
+    numpy input, else an int64 tensor on the device, ready on `stream`.  ValueError as view_factor_bounces, and for an unknown sampling.
+    `accel` may be the MATRIX instead: a placed SparseViewFactors holding all P rows (placed_view_factors_sparse(accel, R, seed, sampling)).
+    Then nothing is traced: each bounce is zero -> view_factor_sparse_products_device (mx only) -> the same update (bounce_step_sparse), with
+    the matrix's own accel and rays_per_triangle (the three keyword arguments are not read), word for word the retraced result for the
+    placement the matrix was built in -- the matrix is a snapshot.  ValueError for a matrix that is not placed, is truncated, does not hold
+    all P rows, or whose n differs from len(emission)."""
+    matrix = accel if isinstance(accel, SparseViewFactors) else None
+    if matrix is not None:
+        check_placed_bounce_matrix(matrix)
+        accel, rays_per_triangle, seed, sampling = matrix.accel, matrix.rays_per_triangle, matrix.seed, matrix.sampling
     e, rho = check_bounce_arguments(emission, reflectance, bounces, rays_per_triangle)
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64):
         raise ValueError("seed must be an integer in 0..2^64 - 1")
     word = vf_sampling(sampling)
+    if matrix is not None and len(e) != matrix.n:
+        raise ValueError(f"emission and reflectance must hold one value per placed primitive: {len(e)} values for {matrix.n} placed primitives")
     import torch
     t = _owner(accel)
-    P = int(t.placed_primitive_bases()[-1])
+    P = int(t.placed_primitive_bases()[-1]) if matrix is None else matrix.n
     if len(e) != P:
         raise ValueError(f"emission and reflectance must hold one value per placed primitive: {len(e)} values for {P} placed primitives")
     dev = torch.device("cuda", t.device)
@@ -1875,7 +1948,10 @@ def placed_view_factor_bounces(accel, emission, reflectance, bounces, rays_per_t
         x32 = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
         mx = torch.empty(max(P, 1), dtype=torch.int64, device=dev)
         for _ in range(int(bounces)):
-            placed_bounce_step(t, e, rho, x, x32, mx, int(rays_per_triangle), int(seed), word, ts.cuda_stream)
+            if matrix is None:
+                placed_bounce_step(t, e, rho, x, x32, mx, int(rays_per_triangle), int(seed), word, ts.cuda_stream)
+            else:
+                bounce_step_sparse(matrix, e, rho, x, x32, mx, ts.cuda_stream)
     if on_host:
         ts.synchronize()
         t.wait_for_gpu()  # (reports a traversal stack overflow)
@@ -1896,15 +1972,19 @@ def placed_bounce_step(t, e, rho, x, x32, mx, rays_per_triangle, seed, sampling,
     x.copy_(nxt.clamp_(max=U32_MAX))
 
 
-def placed_radiosity(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, sampling="cosine", stream=None, return_scale=False):
+def placed_radiosity(accel, emission, reflectance, bounces, rays_per_triangle=10000, seed=0, sampling="cosine", stream=None, return_scale=False, matrix=None):
     """Radiosity per surface element of an INSTANCED scene by `bounces` steps of B <- E + rho .* (M B) / R in float terms: radiosity() on top
     of placed_view_factor_bounces.  emission: float array >= 0, reflectance: float array in [0, 1), one value per PLACED primitive
     (ValueError otherwise).  With sampling "cosine" (the default) M / R estimates the form factors F_ab, so the fixed point is the
     radiosity equation's; the per-triangle radiosity() is uniform-only.  Quantisation and scaling back: radiosity_scale.
-    return_scale: also return the scale (result = integer iterate / scale)."""
+    return_scale: also return the scale (result = integer iterate / scale).
+    matrix: the placed SparseViewFactors of placed_view_factors_sparse(accel, rays_per_triangle, seed, sampling) -- the bounces then apply it
+    instead of tracing (placed_view_factor_bounces); the result is the same while the instances are where they were when it was built."""
     vf_sampling(sampling)
     scale, e_q, rho_q = radiosity_scale(emission, reflectance)
-    x = placed_view_factor_bounces(accel, e_q, rho_q, bounces, rays_per_triangle, seed, sampling, stream)
+    if matrix is not None and not isinstance(matrix, SparseViewFactors):
+        raise ValueError("matrix must be a SparseViewFactors (placed_view_factors_sparse's result)")
+    x = placed_view_factor_bounces(accel if matrix is None else matrix, e_q, rho_q, bounces, rays_per_triangle, seed, sampling, stream)
     b = x.astype(np.float64) / scale
     return (b, scale) if return_scale else b
 

@@ -1777,6 +1777,23 @@ int rc_placed_view_factor_products_device(rc_scene* s, uint32_t rays_per_triangl
                                      reinterpret_cast<unsigned long long*>(d_mtx), reinterpret_cast<unsigned long long*>(d_escaped), (hipStream_t)stream);
     });
 }
+// The matrix those products apply, kept: placed rows [placed_begin, placed_end) in canonical CSR on the device (rc_launch_placed_vf_sparse,
+// rc_drivers.hip).  rc_view_factors_sparse_device's contract and its refusal of a capturing stream; no source order to ensure.
+int rc_placed_view_factors_sparse_device(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
+                                         uint64_t* d_row_ptr, uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, uint64_t* d_nnz, void* stream) {
+    if (!s || !d_row_ptr || !d_nnz || (capacity && (!d_cols || !d_vals))) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (sampling > RC_VF_SAMPLING_COSINE) return fail(RC_ERR_INVALID_ARGUMENT, "rc_placed_view_factors_sparse_device: sampling must be RC_VF_SAMPLING_UNIFORM or RC_VF_SAMPLING_COSINE");
+    return guarded([&] {
+        use_device(s);
+        require_placed(s, "rc_placed_view_factors_sparse_device");
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (stream && hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusActive)
+            throw RcError(RC_ERR_NOT_SYNCED, "rc_placed_view_factors_sparse_device: the matrix cannot be built while the stream is being captured (the build sorts and sizes its scratch on the host) -- build it before the capture; rc_view_factor_sparse_products_device may be captured");
+        (void)hipGetLastError();
+        rc_launch_placed_vf_sparse(s, rays_per_triangle, seed, sampling, placed_begin, placed_end, reinterpret_cast<unsigned long long*>(d_row_ptr), d_cols, d_vals,
+                                   capacity, reinterpret_cast<unsigned long long*>(d_nnz), (hipStream_t)stream);
+    });
+}
 
 int rc_hit_points_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, float* d_points, float* d_normals, void* stream) {
     if (!s || !d_rays || !d_hits || !d_points) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");

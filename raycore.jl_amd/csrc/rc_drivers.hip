@@ -1313,6 +1313,38 @@ struct PlacedViewFactorProductsJob {
 // As for ViewFactorTotalsJob: the uniform job's plain shell has 36 bytes of private segment with the integer form of the stack position.
 template <>
 struct JobShapeFlags<PlacedViewFactorProductsJob<false>> { static constexpr unsigned kPlain = ShapePtrStack, kLds = 0u, kPartial = 0u; };
+// The sparse matrix between placed primitives (rc_placed_view_factors_sparse_device): ViewFactorPairsJob with the placed source and the
+// counting rule of PlacedProductsSink.  A chunk is whole consecutive rows, one source per row: sh.src_begin IS the chunk's first row, so
+// item w belongs to chunk row w / n_ray.  One plain u64 store per finished ray at pairs[w], w below the launch's item count, no atomics:
+// (chunk row << col_bits) | b for a hit with b = base[instance] + prim - 1 != a, `sentinel` for a miss or a hit on the source itself.
+struct PlacedPairsSink {
+    const uint32_t* base;
+    uint32_t src_begin, n_ray, col_bits;
+    unsigned long long sentinel;
+    unsigned long long* pairs;
+    __device__ inline void operator()(uint64_t w, bool hit, float, float, float, uint32_t prim, int instance) const {
+        const uint32_t row = (uint32_t)(w / n_ray), a = src_begin + row;
+        unsigned long long key = sentinel;
+        if (hit) {
+            const uint32_t b = base[instance] + prim - 1u;
+            if (b != a) key = ((unsigned long long)row << col_bits) | b;
+        }
+        pairs[w] = key;
+    }
+};
+template <bool COSINE>
+struct PlacedViewFactorPairsJob {
+    const RcInstanceDesc* instances;
+    const uint32_t* base;
+    VfShard sh;  // (whole rows: ray_begin = 0)
+    uint32_t col_bits;
+    unsigned long long sentinel;
+    unsigned long long* pairs;
+    __device__ inline PlacedViewFactorSource<COSINE> source(const SceneView& v) const {
+        return PlacedViewFactorSource<COSINE>{PlacedView{instances, v.inst, v.prims, base, v.n_inst}, sh};
+    }
+    __device__ inline PlacedPairsSink sink(const SceneView&) const { return PlacedPairsSink{base, sh.src_begin, sh.n_ray, col_bits, sentinel, pairs}; }
+};
 
 // Diffuse bounce: output slot i continues the path of source slot s (s = i, or d_src[i] for i < count, or d_src[i % count] round robin
 // with k = i / count), from hit_point + normal * bias in a cosine-weighted direction about the geometric normal.  The uniforms are
@@ -1769,48 +1801,33 @@ void rc_launch_placed_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint6
 // Rows [row_begin, row_end) of the view-factor matrix in canonical CSR (rc_view_factors_sparse_device), all on `stream`, no host wait.
 // The sources are addressed in metadata order (the caller has called rc_ensure_vf_order): a range of rows is a contiguous range of source
 // positions, and metadata 0 or above N lie outside every range.  The job is cut HERE, on the host, into chunks of WHOLE rows whose rays x 8
-// bytes fit option "vf_sparse_scratch_bytes" (a single row above it gets a chunk of its own).  Per chunk: the trace stores one key per ray
-// (ViewFactorPairsJob); a radix sort over the bits that can vary -- ceil(log2 rows of the chunk) + ceil(log2 N) + the sentinel's --; a
-// run-length encoding whose run count stays on the device; k_vf_sparse_append.  The chunks are whole rows in ascending order, so what they
-// append is the sorted result.  d_row_ptr holds the rows' COUNTS until an exclusive scan behind the last chunk turns them into offsets.
+// bytes fit option "vf_sparse_scratch_bytes" (a single row above it gets a chunk of its own).  Per chunk (vf_sparse_chain, shared with the
+// placed family): the trace stores one key per ray (ViewFactorPairsJob); a radix sort over the bits that can vary -- ceil(log2 rows of
+// the chunk) + ceil(log2 N) + the sentinel's --; a run-length encoding whose run count stays on the device; k_vf_sparse_append.  The
+// chunks are whole rows in ascending order, so what they append is the sorted result.  d_row_ptr holds the rows' COUNTS until an exclusive scan behind the last chunk turns them into offsets.
 // The running nnz alternates between *d_nnz and d_row_ptr[rows] (which no count uses), so that the append kernel reads one word and
 // writes another; the last chunk writes *d_nnz.  Every word that crosses a chunk boundary lives in the caller's arrays: the scratch is
 // the stream's (rc_totals_scratch), sized once for the largest chunk, and holds nothing between two launches.
 namespace {
-struct SparseChunk { uint32_t row0, row1, pos0, pos1; };
+struct SparseChunk { uint32_t row0, row1, pos0, pos1; };  // matrix rows [row0, row1) = source positions [pos0, pos1)
 uint32_t ceil_log2(uint64_t n) { uint32_t b = 0; while (b < 64u && (1ull << b) < n) ++b; return b; }
 size_t round16(size_t b) { return (b + 15u) & ~(size_t)15u; }
-}  // namespace
-void rc_launch_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t row_begin, uint32_t row_end, unsigned long long* d_row_ptr,
-                         uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, unsigned long long* d_nnz, hipStream_t stream) {
-    const uint32_t np = s->n_flat_prims, R = rays_per_triangle;
-    if (row_end > np) row_end = np;
-    if (row_begin > row_end) row_begin = row_end;
-    const uint32_t rows = row_end - row_begin;
-    // the plan: chunks of whole rows
-    std::vector<SparseChunk> chunks;
-    const uint64_t max_items = std::max<uint64_t>((uint64_t)s->opt.vf_sparse_scratch_bytes / 8u, 1u);
+// What follows the plan, the same for both families (rc_launch_vf_sparse, rc_launch_placed_vf_sparse): the limits of every chunk (before
+// anything is enqueued), the zeroed counts, the scratch sized for the largest chunk, and per chunk trace -> sort -> run-length encoding ->
+// append, with the scan behind the last one.  `chunks`: whole rows in ascending order, rows within [row_begin, row_begin + rows); n_cols:
+// the matrix's column count.  trace(launch, sh, chunk, col_bits, sentinel, keys, behind) launches the family's pairs job over the chunk's
+// items (sh: the chunk's source positions, all R rays) with `behind` as the launch's last step.
+template <class Trace>
+void vf_sparse_chain(rc_scene* s, const char* who, const std::vector<SparseChunk>& chunks, uint32_t R, uint64_t seed, uint64_t n_cols, uint32_t row_begin, uint32_t rows,
+                     unsigned long long* d_row_ptr, uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, unsigned long long* d_nnz, hipStream_t stream, Trace trace) {
+    const uint32_t col_bits = ceil_log2(n_cols);
     uint64_t most_items = 0;
-    if (rows && R) {
-        uint32_t p0 = 0, p1 = 0;
-        rc_vf_source_range(s, row_begin, row_end, p0, p1);
-        const std::vector<uint32_t>& m = s->vf_meta_sorted;
-        for (uint32_t i = p0; i < p1;) {
-            SparseChunk c{m[i] - 1u, 0u, i, i};
-            while (i < p1) {
-                uint32_t j = i;
-                while (j < p1 && m[j] == m[i]) ++j;  // the sources of one row
-                if (((uint64_t)(j - i) * R) >> 32) throw RcError(1, "rc_view_factors_sparse: one row's sources x rays_per_triangle reaches 2^32");
-                if (i != c.pos0 && (uint64_t)(j - c.pos0) * R > max_items) break;
-                c.row1 = m[i];
-                i = j;
-            }
-            c.pos1 = i;
-            most_items = std::max<uint64_t>(most_items, (uint64_t)(c.pos1 - c.pos0) * R);
-            chunks.push_back(c);
-        }
+    for (const SparseChunk& c : chunks) {
+        const uint64_t items = (uint64_t)(c.pos1 - c.pos0) * R;
+        if (items >> 32) throw RcError(1, std::string(who) + ": a chunk's sources x rays_per_triangle reaches 2^32");
+        if (ceil_log2(c.row1 - c.row0) + col_bits + 1u > 64u) throw RcError(1, std::string(who) + ": a chunk's (row, column) keys need more than 64 bits");
+        most_items = std::max(most_items, items);
     }
-    const uint32_t col_bits = ceil_log2(np);
     RC_HIP(hipMemsetAsync(d_row_ptr, 0, sizeof(unsigned long long) * ((size_t)rows + 1u), stream));
     RC_HIP(hipMemsetAsync(d_nnz, 0, sizeof(unsigned long long), stream));
     if (chunks.empty()) return;
@@ -1820,7 +1837,6 @@ void rc_launch_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
     for (const SparseChunk& c : chunks) {
         const uint64_t items = (uint64_t)(c.pos1 - c.pos0) * R;
         const int end_bit = (int)(ceil_log2(c.row1 - c.row0) + col_bits + 1u);
-        if (end_bit > 64) throw RcError(1, "rc_view_factors_sparse: a chunk's (row, column) keys need more than 64 bits");
         size_t b = 0;
         RC_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, b, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, items, 0, end_bit, stream));
         tmp_bytes = std::max(tmp_bytes, b);
@@ -1840,8 +1856,8 @@ void rc_launch_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
     const size_t n_chunks = chunks.size();
     for (size_t ci = 0; ci < n_chunks; ++ci) {
         const SparseChunk& c = chunks[ci];
-        VfShard sh;
-        const uint64_t items = vf_shard(s, R, seed, c.pos0, c.pos1, 0u, R, sh);  // (whole rows of a non-empty chunk: never 0)
+        const VfShard sh{rc_philox_key(seed), c.pos0, 0u, R};  // whole rows of a non-empty chunk
+        const uint64_t items = (uint64_t)(c.pos1 - c.pos0) * R;
         const uint32_t row_bits = ceil_log2(c.row1 - c.row0);
         const unsigned long long sentinel = 1ull << (row_bits + col_bits);
         DriverLaunch launch(s, stream, items);
@@ -1852,24 +1868,86 @@ void rc_launch_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed,
         uint32_t* n_runs = reinterpret_cast<uint32_t*>(base + 2u * key_bytes + len_bytes);
         unsigned long long* scanned = reinterpret_cast<unsigned long long*>(base + 2u * key_bytes + len_bytes + 16u);
         void* tmp = base + 2u * key_bytes + len_bytes + 16u + ptr_bytes;
-        launch.go<false>(
-            ViewFactorPairsJob{sh, c.row0, col_bits, sentinel, keys, s->vf_order.p}, Nothing(), [&] {
-                size_t b = tmp_bytes;
-                RC_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, b, (const unsigned long long*)keys, sorted, items, 0, (int)(row_bits + col_bits + 1u), stream));
+        trace(launch, sh, c, col_bits, sentinel, keys, [&] {
+            size_t b = tmp_bytes;
+            RC_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, b, (const unsigned long long*)keys, sorted, items, 0, (int)(row_bits + col_bits + 1u), stream));
+            b = tmp_bytes;
+            RC_HIP(::rocprim::run_length_encode(tmp, b, (const unsigned long long*)sorted, (unsigned int)items, keys, lengths, n_runs, stream));
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + 255u) / 256u, (uint64_t)std::max(s->n_cus, 1) * 8u);
+            hipLaunchKernelGGL(k_vf_sparse_append, dim3(blocks), dim3(256), 0, stream, (const unsigned long long*)keys, (const uint32_t*)lengths,
+                               (const uint32_t*)n_runs, sentinel, col_bits, c.row0 - row_begin, (const unsigned long long*)running[(n_chunks - ci) & 1u],
+                               running[(n_chunks - ci - 1u) & 1u], d_cols, d_vals, (unsigned long long)capacity, d_row_ptr);
+            RC_HIP(hipGetLastError());
+            if (ci + 1u == n_chunks) {  // counts -> offsets
                 b = tmp_bytes;
-                RC_HIP(::rocprim::run_length_encode(tmp, b, (const unsigned long long*)sorted, (unsigned int)items, keys, lengths, n_runs, stream));
-                const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + 255u) / 256u, (uint64_t)std::max(s->n_cus, 1) * 8u);
-                hipLaunchKernelGGL(k_vf_sparse_append, dim3(blocks), dim3(256), 0, stream, (const unsigned long long*)keys, (const uint32_t*)lengths,
-                                   (const uint32_t*)n_runs, sentinel, col_bits, c.row0 - row_begin, (const unsigned long long*)running[(n_chunks - ci) & 1u],
-                                   running[(n_chunks - ci - 1u) & 1u], d_cols, d_vals, (unsigned long long)capacity, d_row_ptr);
-                RC_HIP(hipGetLastError());
-                if (ci + 1u == n_chunks) {  // counts -> offsets
-                    b = tmp_bytes;
-                    RC_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, b, (const unsigned long long*)d_row_ptr, scanned, (int)(rows + 1u), stream));
-                    RC_HIP(hipMemcpyAsync(d_row_ptr, scanned, sizeof(unsigned long long) * ((size_t)rows + 1u), hipMemcpyDeviceToDevice, stream));
-                }
-            });
+                RC_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, b, (const unsigned long long*)d_row_ptr, scanned, (int)(rows + 1u), stream));
+                RC_HIP(hipMemcpyAsync(d_row_ptr, scanned, sizeof(unsigned long long) * ((size_t)rows + 1u), hipMemcpyDeviceToDevice, stream));
+            }
+        });
     }
+}
+}  // namespace
+void rc_launch_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t row_begin, uint32_t row_end, unsigned long long* d_row_ptr,
+                         uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, unsigned long long* d_nnz, hipStream_t stream) {
+    const uint32_t np = s->n_flat_prims, R = rays_per_triangle;
+    if (row_end > np) row_end = np;
+    if (row_begin > row_end) row_begin = row_end;
+    const uint32_t rows = row_end - row_begin;
+    // the plan: chunks of whole rows
+    std::vector<SparseChunk> chunks;
+    const uint64_t max_items = std::max<uint64_t>((uint64_t)s->opt.vf_sparse_scratch_bytes / 8u, 1u);
+    if (rows && R) {
+        uint32_t p0 = 0, p1 = 0;
+        rc_vf_source_range(s, row_begin, row_end, p0, p1);
+        const std::vector<uint32_t>& m = s->vf_meta_sorted;
+        for (uint32_t i = p0; i < p1;) {
+            SparseChunk c{m[i] - 1u, 0u, i, i};
+            while (i < p1) {
+                uint32_t j = i;
+                while (j < p1 && m[j] == m[i]) ++j;  // the sources of one row
+                if (((uint64_t)(j - i) * R) >> 32) throw RcError(1, "rc_view_factors_sparse: one row's sources x rays_per_triangle reaches 2^32");
+                if (i != c.pos0 && (uint64_t)(j - c.pos0) * R > max_items) break;
+                c.row1 = m[i];
+                i = j;
+            }
+            c.pos1 = i;
+            chunks.push_back(c);
+        }
+    }
+    const uint32_t* order = s->vf_order.p;
+    vf_sparse_chain(s, "rc_view_factors_sparse", chunks, R, seed, np, row_begin, rows, d_row_ptr, d_cols, d_vals, capacity, d_nnz, stream,
+                    [&](DriverLaunch& launch, const VfShard& sh, const SparseChunk& c, uint32_t col_bits, unsigned long long sentinel, unsigned long long* keys, auto behind) {
+                        launch.go<false>(ViewFactorPairsJob{sh, c.row0, col_bits, sentinel, keys, order}, Nothing(), behind);
+                    });
+}
+
+// Rows [placed_begin, placed_end) (clamped to P) of the matrix between PLACED primitives in canonical CSR
+// (rc_placed_view_factors_sparse_device): Mp[a, b] = the rays of placed primitive a that hit placed primitive b != a first, the matrix that
+// rc_launch_placed_vf_products applies.  Row a has exactly one source, placed primitive a, so the plan needs no metadata order: chunks of
+// max(1, option "vf_sparse_scratch_bytes" / (8 R)) consecutive rows, a row is never split.  The trace is PlacedViewFactorPairsJob, everything
+// behind it is vf_sparse_chain.  The transforms are read when the kernels run; nothing is read on the host.  The caller has checked P < 2^32.
+void rc_launch_placed_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
+                                unsigned long long* d_row_ptr, uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, unsigned long long* d_nnz, hipStream_t stream) {
+    const uint32_t P = (uint32_t)s->n_placed, R = rays_per_triangle;
+    if (placed_end > P) placed_end = P;
+    if (placed_begin > placed_end) placed_begin = placed_end;
+    const uint32_t rows = placed_end - placed_begin;
+    std::vector<SparseChunk> chunks;
+    if (rows && R) {
+        const uint64_t max_items = std::max<uint64_t>((uint64_t)s->opt.vf_sparse_scratch_bytes / 8u, 1u);
+        const uint32_t per_chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(max_items / R, 1u), rows);
+        for (uint32_t r0 = placed_begin; r0 < placed_end;) {
+            const uint32_t r1 = r0 + std::min(per_chunk, placed_end - r0);
+            chunks.push_back(SparseChunk{r0, r1, r0, r1});
+            r0 = r1;
+        }
+    }
+    const PlacedView pv = placed_view(s);  // (the kernel's own SceneView supplies inst, prims and n_inst)
+    vf_sparse_chain(s, "rc_placed_view_factors_sparse_device", chunks, R, seed, P, placed_begin, rows, d_row_ptr, d_cols, d_vals, capacity, d_nnz, stream,
+                    [&](DriverLaunch& launch, const VfShard& sh, const SparseChunk&, uint32_t col_bits, unsigned long long sentinel, unsigned long long* keys, auto behind) {
+                        if (sampling) launch.go<false>(PlacedViewFactorPairsJob<true>{pv.instances, pv.base, sh, col_bits, sentinel, keys}, Nothing(), behind);
+                        else launch.go<false>(PlacedViewFactorPairsJob<false>{pv.instances, pv.base, sh, col_bits, sentinel, keys}, Nothing(), behind);
+                    });
 }
 
 // mx += M x, mtx += M^T x for rows [row_offset, row_offset + n_rows) of a CSR block (k_vf_sparse_products): nothing is read on the host, so

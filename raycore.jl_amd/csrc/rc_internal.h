@@ -516,6 +516,10 @@ void rc_launch_placed_vf_groups(rc_scene* s, uint32_t rays_per_triangle, uint64_
 void rc_launch_placed_vf_products(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
                                   uint32_t ray_begin, uint32_t ray_end, const uint32_t* d_x, unsigned long long* d_mx, unsigned long long* d_mtx,
                                   unsigned long long* d_escaped, hipStream_t stream);
+// The sparse matrix between placed primitives: rc_launch_vf_sparse over placed rows [placed_begin, placed_end), with a choice of sampling;
+// its products are rc_launch_vf_sparse_products
+void rc_launch_placed_vf_sparse(rc_scene* s, uint32_t rays_per_triangle, uint64_t seed, uint32_t sampling, uint32_t placed_begin, uint32_t placed_end,
+                                unsigned long long* d_row_ptr, uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity, unsigned long long* d_nnz, hipStream_t stream);
 void rc_multi_prepare_impl(rc_scene* const* scenes, int n_scenes, float out_ms[4]);
 int rc_multi_ranks_impl(rc_scene* const* scenes, int n_scenes);
 void rc_view_factor_totals_multi_impl(rc_scene* const* scenes, int n_scenes, uint32_t rays_per_triangle, uint64_t seed, uint64_t* out_received, uint64_t* out_emitted);

@@ -386,6 +386,16 @@ placed_view_factor_products_device!(a::MI355XStaticTLAS, rays_per_triangle::Inte
                                     d_mtx::Ptr{UInt64}, d_escaped::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
     check(ccall((:rc_placed_view_factor_products_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, UInt32, UInt32, Ptr{UInt32}, Ptr{UInt64}, Ptr{UInt64}, Ptr{UInt64}, Ptr{Cvoid}),
                 a.owner.ptr, rays_per_triangle, seed, sampling, placed_begin, placed_end, ray_begin, ray_end, d_x, d_mx, d_mtx, d_escaped, stream))
+"Rows [placed_begin, placed_end) of the matrix those products apply, KEPT, as canonical CSR in device arrays on `stream`: entry (a, b) = the
+rays of placed primitive `a` that hit placed primitive `b != a` first (0-based).  `d_row_ptr`: rows + 1 UInt64 from 0; `d_cols`, `d_vals`:
+`capacity` UInt32 each, C_NULL with capacity 0 to count; `d_nnz`: one UInt64, always the true count.  The matrix is a SNAPSHOT of the
+placement when the kernels run: after the instances move, rebuilding it is the caller's job.  Its products are
+`view_factor_sparse_products_device!` with `n_rows` = the block's rows and `row_offset = placed_begin`.  Not capturable."
+placed_view_factors_sparse_device!(a::MI355XStaticTLAS, rays_per_triangle::Integer, seed::UInt64, sampling::Integer, placed_begin::Integer,
+                                   placed_end::Integer, d_row_ptr::Ptr{UInt64}, d_cols::Ptr{UInt32}, d_vals::Ptr{UInt32}, capacity::Integer,
+                                   d_nnz::Ptr{UInt64}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_placed_view_factors_sparse_device, LIB), Cint, (Ptr{Cvoid}, UInt32, UInt64, UInt32, UInt32, UInt32, Ptr{UInt64}, Ptr{UInt32}, Ptr{UInt32}, UInt64, Ptr{UInt64}, Ptr{Cvoid}),
+                a.owner.ptr, rays_per_triangle, seed, sampling, placed_begin, placed_end, d_row_ptr, d_cols, d_vals, capacity, d_nnz, stream))
 """
     view_factors_sparse(accel; rays_per_triangle, seed) -> (row_ptr::Vector{UInt64}, cols::Vector{UInt32}, vals::Vector{UInt32})
 
