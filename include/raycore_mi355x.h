@@ -1016,6 +1016,59 @@ int rc_placed_view_factors_sparse_device(rc_scene* scene, uint32_t rays_per_tria
                                          uint32_t placed_end, uint64_t* d_row_ptr, uint32_t* d_cols, uint32_t* d_vals, uint64_t capacity,
                                          uint64_t* d_nnz, void* stream);
 
+/* ---- Placed final gather: carry a solution per PLACED primitive to the hit points.  The placed family (rc_placed_view_factor_groups_device,
+ * rc_placed_view_factor_products_device, rc_placed_view_factors_sparse_device and the bounce solves on them) returns one value per placed
+ * primitive q = base[i] + l (section 1 of "Form factors between instances" below).  rc_final_gather_device (the next block) cannot read
+ * such a vector: it indexes x by metadata - 1, and every instance of a mesh shares its metadata.  These two calls index by q instead: two
+ * instances of one mesh carry different values.
+ *
+ * rc_placed_hit_indices_device, a stage: d_q[i] = base[d_hits[i].instance_id] + (d_hits[i].primitive_id - the first flat primitive of
+ * that instance's BLAS) for a record with hit != 0, RC_INVALID_ID for a record with hit == 0.  d_hits: n records, d_q: n u32.  The radiosity
+ * of the surface a camera ray sees is B[d_q[i]], one gather on the caller's side; applied to the hit records of
+ * rc_ambient_occlusion_rays_device's rays (declared last in this header) it is the lookup step of the composed path.
+ * One kernel, no scratch; legal wherever
+ * rc_hit_points_device is, a capturing stream and the same stream behind the device-side updates included.  Records that were not written
+ * by this library's closest-hit calls are outside the contract, as for rc_hit_points_device.  Errors: rc_hit_points_device's
+ * (RC_ERR_INVALID_ARGUMENT for a NULL scene, d_hits or d_q, also with n == 0; RC_ERR_NOT_SYNCED in the same states), and
+ * RC_ERR_INVALID_ARGUMENT on a scene whose P >= 2^32.
+ *
+ * rc_placed_final_gather_device, the fused driver: rc_final_gather_device's contract everywhere except the lookup rule.  The same items
+ * (j = i * samples + s), the same rays -- ray(i, s) is bit for bit the ray rc_ambient_occlusion_rays_device writes at slot i * samples + s --,
+ * the same d_rays, d_hits, n, samples, max_dist, seed, depth, d_path_in, path_base, bias and miss_value.  d_x: P u32 indexed by q, P the
+ * scene's placed-primitive count, read WHEN THE KERNEL RUNS and for counted samples only: a captured call follows a solution that changes
+ * between replays.  d_sum: n u64.  d_open: n u32, may be NULL.
+ * Identity with the composed path (the rays, rc_trace_closest_device, rc_placed_hit_indices_device on the sample hits, a lookup and a
+ * sum), exact, no tolerance, and with no metadata in it:
+ *   d_sum[i]  += sum over s of  live(i,s) && H.hit ? x[base[H.instance_id] + l(H)]  :  live(i,s) && !H.hit ? miss_value : 0
+ *   d_open[i] += sum over s of  live(i,s) && !H.hit
+ * where live(i,s) and H are rc_final_gather_device's, and l(H) is the hit's 0-based position inside its instance's BLAS: the traversal core
+ * reports prim = l + 1, so the index is base[instance] + prim - 1, one load where the metadata rule reads two.  EVERY hit is counted: the
+ * index is below P always, there is no "outside 1..N" case.  Sums are modulo 2^64: integer adds, exact in any order, so the words do not
+ * depend on scheduling, kernel shape or sharding.
+ * Consequences: d_open equals what rc_final_gather_device and rc_ambient_occlusion_device add for the same arguments; and on a scene whose
+ * metadata lies in 1..N the call with x_placed[q] = x[metadata(q) - 1] gives rc_final_gather_device's words for x.
+ * x IS WHATEVER THE CALLER HANDS IN.  Nothing tracks whether the instances moved since a placed solution was made; a solution per placed
+ * primitive keeps its meaning while base does, and base changes only in the rebuilding rc_sync.  Until the illumination drivers count per
+ * placed primitive the caller supplies the emission of a placed solve itself (one value per instance expanded over the bases, say).
+ * The call ACCUMULATES into d_sum and d_open: the caller zeroes them, and accumulation over calls with different `seed` or `depth` is
+ * legal.  Items are claimed in natural order; the entry cull follows rc_trace_closest_device.
+ * No allocation, copy, event, memset, host synchronisation or scene-owned scratch: re-entrant across streams, and captured on a capturing
+ * stream under the rules of the other driver launches (one capture slot; the stream must have run the call eagerly before).  Legal behind
+ * rc_update_transforms_device -> rc_refit_device_async (or the rebuilds) and behind rc_update_geometry_device_async on the same stream
+ * with no host wait: base does not change there, and a replay reads the CURRENT scene and the current x.  A stack overflow is reported by
+ * rc_wait.  n == 0 or samples == 0: succeeds, nothing is enqueued.
+ * Errors, all before anything is enqueued, rc_final_gather_device's in its order: RC_ERR_INVALID_ARGUMENT (NULL scene, checked first and
+ * with or without a device; samples >= 65536; depth >= 65536; max_dist not > 0 -- NaN included, +Inf is legal; n * samples >= 2^32,
+ * products that wrap in 64 bits included; NULL d_rays, d_hits, d_sum or d_x while there is work), RC_ERR_NOT_SYNCED (the rules of
+ * rc_shadow_visibility_device).  Then RC_ERR_INVALID_ARGUMENT for P >= 2^32: it sits where rc_placed_view_factor_products_device checks
+ * it, behind the device and the sync state, and no test can reach it (such a scene does not fit a device).
+ * Register and scratch figures of the new kernel shells and the cost against rc_final_gather_device:
+ * docs/EXPERIMENTS.md, "Placed final gather". */
+int rc_placed_hit_indices_device(rc_scene* scene, const rc_hit* d_hits, uint64_t n, uint32_t* d_q, void* stream);
+int rc_placed_final_gather_device(rc_scene* scene, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist,
+                                  uint64_t seed, uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias,
+                                  const uint32_t* d_x, uint32_t miss_value, uint64_t* d_sum, uint32_t* d_open, void* stream);
+
 /* ---- Final gather: how much of a per-triangle solution arrives at every hit point?  The step between the analysis half (a u32 per
  * primitive indexed by metadata - 1: rc_view_factor_products_device's x, a radiosity iterate) and the per-hit half: the hemisphere samples of
  * rc_ambient_occlusion_device (declared below), traced for the CLOSEST hit -- closest_hit, src/instanced-bvh.jl:1902-2024 -- and the field

@@ -14,7 +14,8 @@ from .api import (BLAS4, CONTACT_DT, CollisionResult, ContactPair, collide_insta
                   view_factor_groups, form_factors, form_factor_weights, form_factors_from_counts, primitive_areas,
                   placed_primitive_count, placed_primitive_areas, placed_groups, placed_view_factor_groups, placed_form_factors,
                   instance_form_factors, placed_view_factor_products, placed_view_factor_totals, placed_view_factor_bounces, placed_radiosity,
-                  placed_view_factors_sparse, check_placed_sparse_arguments, check_placed_bounce_matrix)
+                  placed_view_factors_sparse, check_placed_sparse_arguments, check_placed_bounce_matrix,
+                  placed_hit_indices, placed_final_gather, placed_irradiance)
 
 
 def device_count():

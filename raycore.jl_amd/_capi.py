@@ -156,6 +156,8 @@ SYMBOLS = [
     ("rc_placed_view_factor_groups_device", _int, [_vp, _u32, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     ("rc_placed_view_factor_products_device", _int, [_vp, _u32, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("rc_placed_view_factors_sparse_device", _int, [_vp, _u32, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp]),
+    ("rc_placed_hit_indices_device", _int, [_vp, _vp, _u64, _vp, _vp]),
+    ("rc_placed_final_gather_device", _int, [_vp, _vp, _vp, _u64, _u32, C.c_float, _u64, _u32, _vp, _u64, C.c_float, _vp, _u32, _vp, _vp, _vp]),
 ]
 
 _lib = None

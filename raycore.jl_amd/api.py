@@ -729,6 +729,23 @@ class TLAS:
                                                          ptr(row_ptr_ptr), ptr(cols_ptr) if cols_ptr else None, ptr(vals_ptr) if vals_ptr else None,
                                                          int(capacity), ptr(nnz_ptr), ptr(stream) if stream else None))
 
+    def placed_hit_indices_device(self, d_hits, n, d_q, stream=None):
+        """The placed primitive each hit record names (rc_placed_hit_indices_device): d_q (device pointer, n u32) gets
+        q = base[instance_id] + (primitive_id - the first flat primitive of the instance's BLAS) for a hit and RC_INVALID_ID (2^32 - 1)
+        for a miss.  B[q] is then the placed solution's value on the surface the ray sees.  One stage kernel, capturable."""
+        check(lib().rc_placed_hit_indices_device(self._h, ptr(d_hits), int(n), ptr(d_q), ptr(stream) if stream else None))
+
+    def placed_final_gather_device(self, d_rays, d_hits, n, samples, d_x, d_sum, d_open=None, miss_value=0, max_dist=float("inf"), seed=0, depth=0,
+                                   bias=1e-3, d_path_in=None, path_base=0, stream=None):
+        """The final gather of a field per PLACED primitive in one traversal launch (rc_placed_final_gather_device): final_gather_device's
+        items, rays and outputs, with d_x a device pointer to P u32 indexed by placed primitive q (placed_radiosity's result, say), read
+        when the kernel runs.  d_sum (n u64) is ACCUMULATED -- sum[i] += x[base[instance] + l] of what each sample of hit i's hemisphere
+        hits first, miss_value for a sample that reaches max_dist --, and d_open (n u32, may be None) with the samples that escape.  No
+        metadata takes part: every hit is counted, and two instances of one mesh carry different values.  The caller zeroes the outputs."""
+        check(lib().rc_placed_final_gather_device(self._h, ptr(d_rays), ptr(d_hits), int(n), int(samples), float(max_dist), int(seed), int(depth),
+                                                  ptr(d_path_in) if d_path_in else None, int(path_base), float(bias), ptr(d_x), int(miss_value),
+                                                  ptr(d_sum), ptr(d_open) if d_open else None, ptr(stream) if stream else None))
+
     def view_factor_sparse_products_device(self, n_rows, row_ptr_ptr, cols_ptr, vals_ptr, x_ptr, mx_ptr, mtx_ptr, row_offset=0, stream=None):
         """The products of a device CSR block with a device vector (rc_view_factor_sparse_products_device), ACCUMULATED modulo 2^64:
         mx[row_offset + r] += sum_k vals[k] x[cols[k]], mtx[cols[k]] += vals[k] x[row_offset + r]; mx_ptr / mtx_ptr: u64 vectors, either
@@ -1211,6 +1228,75 @@ def irradiance(accel, rays, hits, b, samples, sky=0.0, max_dist=float("inf"), se
     if isinstance(samples, bool) or samples != int(samples) or int(samples) < 1:
         raise ValueError("samples must be an integer in [1, 65536)")
     sums, opened = final_gather(accel, rays, hits, b_q, samples, max_dist=max_dist, miss_value=sky_q, seed=seed, bias=bias)
+    e = sums.astype(np.float64) / (int(samples) * scale)
+    return (e, opened) if return_open else e
+
+
+def check_placed_x(x, n=None):
+    """x of placed_final_gather: a uint32 vector (of length n, once the placed-primitive count is known)."""
+    if not isinstance(x, np.ndarray) or x.dtype != np.uint32 or x.ndim != 1:
+        raise ValueError("x must be a one-dimensional uint32 array with one value per placed primitive")
+    if n is not None and len(x) != n:
+        raise ValueError(f"x must hold one value per placed primitive: {len(x)} values for {n} placed primitives")
+    return np.ascontiguousarray(x)
+
+
+def placed_hit_indices(accel, hits):
+    """The placed primitive each hit record names (rc_placed_hit_indices_device): (n,) uint32, q = base[instance_id] + the primitive's
+    position inside its instance's BLAS for a hit, 2^32 - 1 (RC_INVALID_ID) for a miss.  hits: the HIT_DT records a closest-hit trace
+    returned.  B[q] is a placed solution's value on the surface each ray sees.  Upload, one placed_hit_indices_device call, download."""
+    h = np.ascontiguousarray(hits)
+    if h.dtype != HIT_DT or h.ndim != 1:
+        raise ValueError("hits must be a one-dimensional HIT_DT array")
+    import torch
+    t = _owner(accel)
+    n = len(h)
+    dev = f"cuda:{t.device}"
+    torch.cuda.synchronize(t.device)  # (the call runs on the default stream: behind whatever the caller enqueued on streams of its own)
+    d_hits = torch.from_numpy(h.view(np.uint8).reshape(-1).copy()).to(dev) if n else torch.zeros(32, dtype=torch.uint8, device=dev)
+    d_q = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    t.placed_hit_indices_device(d_hits.data_ptr(), n, d_q.data_ptr())
+    torch.cuda.synchronize(t.device)
+    return d_q.cpu().numpy().view(np.uint32)[:n].copy()
+
+
+def placed_final_gather(accel, rays, hits, x, samples, max_dist=float("inf"), miss_value=0, seed=0, bias=1e-3):
+    """final_gather for a field per PLACED primitive (rc_placed_final_gather_device).  x: uint32, one value per placed primitive, indexed by
+    q = base[i] + l (placed_primitive_bases(); placed_radiosity's result, say): two instances of one mesh carry different values, and no
+    metadata takes part -- every hit is counted.  Returns (sums, open) as final_gather does: sums (n,) uint64 -- x summed over what the
+    `samples` cosine-weighted samples of each hit's hemisphere hit first, miss_value for every sample that reaches max_dist --, and open
+    (n,) uint32, the samples that escape: final_gather's and ambient_occlusion()'s counts.  Upload, one placed_final_gather_device call,
+    download."""
+    r, h, samples, max_dist, miss_value = _gather_inputs(rays, hits, samples, max_dist, miss_value)
+    check_placed_x(x)
+    import torch
+    t = _owner(accel)
+    x = check_placed_x(x, int(t.placed_primitive_bases()[-1]))
+    n = len(r)
+    dev = f"cuda:{t.device}"
+    torch.cuda.synchronize(t.device)  # (the call runs on the default stream: behind whatever the caller enqueued on streams of its own)
+    d_rays = torch.from_numpy(r.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_hits = torch.from_numpy(h.view(np.uint8).reshape(-1).copy()).to(dev)
+    d_x = torch.from_numpy(x.view(np.int32).copy()).to(dev)
+    sums = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    opened = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    t.placed_final_gather_device(d_rays.data_ptr(), d_hits.data_ptr(), n, samples, d_x.data_ptr(), sums.data_ptr(), opened.data_ptr(),
+                                 miss_value=miss_value, max_dist=max_dist, seed=seed, bias=bias)
+    torch.cuda.synchronize(t.device)
+    t.wait_for_gpu()  # (reports a traversal stack overflow)
+    return sums.cpu().numpy().view(np.uint64)[:n].copy(), opened.cpu().numpy().view(np.uint32)[:n].copy()
+
+
+def placed_irradiance(accel, rays, hits, b, samples, sky=0.0, max_dist=float("inf"), seed=0, bias=1e-3, return_open=False):
+    """irradiance() for a field per PLACED primitive: the cosine-weighted mean of b over the hemisphere above every hit, float64 (n,), with
+    b (float, >= 0) holding one value per placed primitive q = base[i] + l -- placed_radiosity's result: the IRRADIANCE at the point in
+    b's units, `sky` for a direction that reaches max_dist; multiply by the local reflectance for the reflected radiosity.  0 where the
+    ray missed.  The quantisation is irradiance()'s (irradiance_scale, one step 1 / scale = max(max b, sky) / (2^32 - 1), floor); the sums
+    are exact integers (placed_final_gather).  return_open: also return the open counts.  samples must be >= 1."""
+    scale, b_q, sky_q = irradiance_scale(b, sky)
+    if isinstance(samples, bool) or samples != int(samples) or int(samples) < 1:
+        raise ValueError("samples must be an integer in [1, 65536)")
+    sums, opened = placed_final_gather(accel, rays, hits, b_q, samples, max_dist=max_dist, miss_value=sky_q, seed=seed, bias=bias)
     e = sums.astype(np.float64) / (int(samples) * scale)
     return (e, opened) if return_open else e
 

@@ -1905,6 +1905,30 @@ int rc_final_gather_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hi
     });
 }
 
+// The placed final gather: rc_final_gather_device's checks in its order, then the placed calls' refusal of P >= 2^32 where
+// rc_placed_view_factor_products_device makes it (require_placed: behind the device and the sync state)
+int rc_placed_final_gather_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, uint64_t n, uint32_t samples, float max_dist, uint64_t seed,
+                                  uint32_t depth, const uint32_t* d_path_in, uint64_t path_base, float bias, const uint32_t* d_x, uint32_t miss_value,
+                                  uint64_t* d_sum, uint32_t* d_open, void* stream) {
+    if (int e = ambient_occlusion_args("rc_placed_final_gather_device", s, d_rays, d_hits, n, samples, max_dist, depth, d_sum)) return e;
+    if (n && samples && !d_x) return fail(RC_ERR_INVALID_ARGUMENT, "rc_placed_final_gather_device: NULL argument");
+    const AoParams q{reinterpret_cast<const RcRay*>(d_rays), reinterpret_cast<const RcHit*>(d_hits), d_path_in, path_base, samples, rc_philox_key(seed), depth, bias, max_dist};
+    return guarded([&] {
+        use_device(s);
+        require_placed(s, "rc_placed_final_gather_device");
+        rc_launch_placed_final_gather(s, q, n, d_x, miss_value, d_sum, d_open, (hipStream_t)stream);
+    });
+}
+// The placed primitive each hit record names (k_placed_hit_indices, rc_drivers.hip): rc_hit_points_device's rules
+int rc_placed_hit_indices_device(rc_scene* s, const rc_hit* d_hits, uint64_t n, uint32_t* d_q, void* stream) {
+    if (!s || !d_hits || !d_q) return fail(RC_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded([&] {
+        use_device(s);
+        require_placed(s, "rc_placed_hit_indices_device");
+        rc_launch_placed_hit_indices(s, reinterpret_cast<const RcHit*>(d_hits), n, d_q, (hipStream_t)stream);
+    });
+}
+
 int rc_bounce_rays_device(rc_scene* s, const rc_ray* d_rays, const rc_hit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                           const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n_out, uint64_t seed, uint32_t bounce, float bias,
                           rc_ray* d_out, void* stream) {

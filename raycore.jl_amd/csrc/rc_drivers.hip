@@ -718,6 +718,17 @@ __global__ void k_hit_points(SceneView v, const RcRay* rays, const RcHit* hits, 
     }
 }
 
+// The placed index of a hit record (rc_placed_hit_indices_device): q = base[instance_id] + (primitive_id - the instance's first flat
+// primitive), base = rc_scene::d_placed_base (the index space of "form factors between instances" below); RC_INVALID_ID for a miss.
+__global__ void k_placed_hit_indices(SceneView v, const uint32_t* base, const RcHit* hits, uint64_t n, uint32_t* out) {
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const RcHit h = hits[i];
+        uint32_t q = 0xFFFFFFFFu;  // RC_INVALID_ID
+        if (h.hit) q = base[h.instance_id] + (h.primitive_id - v.inst[h.instance_id].prims_offset);
+        out[i] = q;
+    }
+}
+
 // generate_shadow_rays! for one point light (:288-333): slot i of the output belongs to ray i; misses get the
 // reference's dummy ray (o = 0, d = (0,0,1), t_max = 0), hits a ray from hit_point + normal*bias toward the light with
 // t_max = distance, ready for rc_trace_any_device.
@@ -958,6 +969,43 @@ struct GatherJob {
     uint32_t* open;
     __device__ inline HitItemSource<AoItems> source(const SceneView& v) const { return {v, {q}}; }  // (v: the kernel's own by-value parameter)
     __device__ inline GatherSink sink(const SceneView& v) const { return GatherSink{v.inst, v.prims, v.n_prims, x, miss_value, q.samples, sum, open}; }
+};
+// The placed final gather (rc_placed_final_gather_device): GatherSink with x indexed by PLACED primitive (the index space of "form factors
+// between instances" below: q = base[instance] + l, base = rc_scene::d_placed_base).  No metadata in the rule: the traversal core reports
+// prim = l + 1, so b = base[instance] + prim - 1 -- ONE load where GatherSink reads two -- and b < P always: every hit is counted.
+//   a hit:               sum[i] += x[b]
+//   no hit and t > 0:    sum[i] += miss_value, open[i] += 1 (open may be null)
+//   a dead item:         nothing
+struct PlacedGatherSink {
+    const uint32_t* base;
+    const uint32_t* x;  // P words, indexed by q
+    uint32_t miss_value, samples;
+    unsigned long long* sum;
+    uint32_t* open;
+    __device__ inline void operator()(uint64_t j, bool hit, float t, float, float, uint32_t prim, int instance) const {
+        const uint32_t i = (uint32_t)j / samples;
+        bool counted = false;
+        uint32_t value = 0;
+        if (hit) {
+            counted = true;
+            value = x[base[instance] + prim - 1u];
+        } else if (t > 0.0f) {
+            counted = true;
+            value = miss_value;
+            if (open) __hip_atomic_fetch_add(open + i, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        wave_add(sum, i, value, counted);
+    }
+};
+struct PlacedGatherJob {
+    AoParams q;
+    const uint32_t* base;
+    const uint32_t* x;
+    uint32_t miss_value;
+    unsigned long long* sum;
+    uint32_t* open;
+    __device__ inline HitItemSource<AoItems> source(const SceneView& v) const { return {v, {q}}; }  // (v: the kernel's own by-value parameter)
+    __device__ inline PlacedGatherSink sink(const SceneView&) const { return PlacedGatherSink{base, x, miss_value, q.samples, sum, open}; }
 };
 
 // ---- illumination from point sources: get_illumination (src/kernels.jl:112-124) for lamps at a finite position ---------------------------
@@ -2025,6 +2073,14 @@ void rc_launch_ambient_occlusion(rc_scene* s, const AoParams& q, uint64_t n, uin
 // (miss_value for an escaped sample) into d_sum[i] and the escaped samples into d_open[i] (may be null).
 void rc_launch_final_gather(rc_scene* s, const AoParams& q, uint64_t n, const uint32_t* d_x, uint32_t miss_value, uint64_t* d_sum, uint32_t* d_open, hipStream_t stream) {
     if (n * q.samples) DriverLaunch(s, stream, n * q.samples).go<false>(GatherJob{q, d_x, miss_value, reinterpret_cast<unsigned long long*>(d_sum), d_open});
+}
+// The placed final gather: the same launch with d_x indexed by placed primitive (PlacedGatherSink); and the placed index of hit records.
+void rc_launch_placed_final_gather(rc_scene* s, const AoParams& q, uint64_t n, const uint32_t* d_x, uint32_t miss_value, uint64_t* d_sum, uint32_t* d_open, hipStream_t stream) {
+    if (n * q.samples)
+        DriverLaunch(s, stream, n * q.samples).go<false>(PlacedGatherJob{q, s->d_placed_base.p, d_x, miss_value, reinterpret_cast<unsigned long long*>(d_sum), d_open});
+}
+void rc_launch_placed_hit_indices(rc_scene* s, const RcHit* d_hits, uint64_t n, uint32_t* d_q, hipStream_t stream) {
+    launch_stage(s, stream, n, k_placed_hit_indices, rc_scene_view_static(s), s->d_placed_base.p, d_hits, n, d_q);
 }
 
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,

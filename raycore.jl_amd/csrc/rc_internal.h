@@ -582,6 +582,10 @@ void rc_launch_ambient_occlusion(rc_scene* s, const AoParams& q, uint64_t n, uin
 // Final gather: the ambient-occlusion driver's items and rays traced for the closest hit; ACCUMULATES x[meta - 1] of every sample's hit
 // (miss_value for a sample that escapes) into sum[i] (u64) and the escaped samples into open[i] (may be null).  Same limits; d_x: n_prims u32
 void rc_launch_final_gather(rc_scene* s, const AoParams& q, uint64_t n, const uint32_t* d_x, uint32_t miss_value, uint64_t* d_sum, uint32_t* d_open, hipStream_t stream);
+// Placed final gather: the same launch with d_x indexed by placed primitive (P u32; x[base[instance] + prim - 1] of every sample's hit), and
+// the stage that names a hit record's placed primitive (RC_INVALID_ID for a miss).  The callers have checked s->n_placed < 2^32.
+void rc_launch_placed_final_gather(rc_scene* s, const AoParams& q, uint64_t n, const uint32_t* d_x, uint32_t miss_value, uint64_t* d_sum, uint32_t* d_open, hipStream_t stream);
+void rc_launch_placed_hit_indices(rc_scene* s, const RcHit* d_hits, uint64_t n, uint32_t* d_q, hipStream_t stream);
 // Diffuse (cosine-weighted) bounce rays, slot-aligned or gathered through d_src / *d_src_count (read on the device); n < 2^32, bounce < 2^16
 void rc_launch_bounce_rays(rc_scene* s, const RcRay* d_rays, const RcHit* d_hits, const uint32_t* d_src, const uint32_t* d_src_count, int wrap,
                            const uint32_t* d_path_in, uint32_t* d_path_out, uint64_t path_base, uint64_t n, uint64_t seed, uint32_t bounce, float bias,

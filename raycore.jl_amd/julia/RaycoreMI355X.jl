@@ -683,6 +683,20 @@ final_gather_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitR
                  UInt32, Ptr{UInt64}, Ptr{UInt32}, Ptr{Cvoid}),
                 a.owner.ptr, d_rays, d_hits, n, samples, max_dist, seed, depth, d_path_in, path_base, bias, d_x, miss_value, d_sum, d_open,
                 stream))
+"The placed primitive each hit record names: `d_q[i]` (0-based, n UInt32) = `base[instance_id] + (primitive_id - the first flat primitive of the instance's BLAS)` for a hit, `0xffffffff` for a miss; `B[d_q[i] + 1]` is a placed solution's value on the surface ray `i` sees."
+placed_hit_indices_device!(a::MI355XStaticTLAS, d_hits::Ptr{RTHitResult}, n::Integer, d_q::Ptr{UInt32}; stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_placed_hit_indices_device, LIB), Cint, (Ptr{Cvoid}, Ptr{RTHitResult}, UInt64, Ptr{UInt32}, Ptr{Cvoid}),
+                a.owner.ptr, d_hits, n, d_q, stream))
+"Final gather of a field per PLACED primitive in one traversal launch: `final_gather_device!` with `d_x` holding one UInt32 per placed primitive `q = base[instance] + l` (a placed radiosity solve's result), so two instances of one mesh carry different values; no metadata takes part and every hit is counted. `d_sum` and `d_open` as there (ACCUMULATED: zero them first)."
+placed_final_gather_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n::Integer, samples::Integer,
+                            d_x::Ptr{UInt32}, d_sum::Ptr{UInt64}; d_open::Ptr{UInt32} = Ptr{UInt32}(C_NULL), miss_value::Integer = 0,
+                            max_dist::Float32 = Inf32, seed::UInt64 = UInt64(0), depth::Integer = 0, bias::Float32 = 1f-3,
+                            d_path_in::Ptr{UInt32} = Ptr{UInt32}(C_NULL), path_base::Integer = 0, stream::Ptr{Cvoid} = C_NULL) =
+    check(ccall((:rc_placed_final_gather_device, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{RTRay}, Ptr{RTHitResult}, UInt64, UInt32, Cfloat, UInt64, UInt32, Ptr{UInt32}, UInt64, Cfloat, Ptr{UInt32},
+                 UInt32, Ptr{UInt64}, Ptr{UInt32}, Ptr{Cvoid}),
+                a.owner.ptr, d_rays, d_hits, n, samples, max_dist, seed, depth, d_path_in, path_base, bias, d_x, miss_value, d_sum, d_open,
+                stream))
 "Diffuse (cosine-weighted) bounce rays: slot-aligned, or gathered through `d_src` / `d_src_count` (a device count; `wrap` = round robin)."
 bounce_rays_device!(a::MI355XStaticTLAS, d_rays::Ptr{RTRay}, d_hits::Ptr{RTHitResult}, n_out::Integer, d_out::Ptr{RTRay};
                     seed::UInt64 = UInt64(0), bounce::Integer = 0, bias::Float32 = 1f-3, d_src::Ptr{UInt32} = Ptr{UInt32}(C_NULL),

@@ -117,7 +117,12 @@ class WavefrontPaths:
     gather_sums[b] (int64, n) and gather_open[b] (int32, n) on the frame's stream and runs one final_gather_device with
     max_dist=distance, depth=b, d_path_in=path_ids[b] and the frame's seed and bias: sum i is x summed over what the `samples` hemisphere
     samples of slot i of hits[b] hit first (miss_value for one that escapes), open i the samples that escape -- the ambient-occlusion
-    stage's rays, so with equal samples and distance gather_open[b] equals ao_counts[b].  With samples == 0 the frame is what it was."""
+    stage's rays, so with equal samples and distance gather_open[b] equals ao_counts[b].  With samples == 0 the frame is what it was.
+
+    Placed final gather: with_placed_final_gather(x, samples, distance=inf, miss_value=0), the same stage with x an int32 tensor holding one
+    u32 per PLACED primitive (indexed by q = base[instance] + l: placed_radiosity's result, say) and one placed_final_gather_device per
+    depth.  A frame has ONE gather stage, metadata or placed: both switches write the gather_* fields and the flag gather_placed, and the
+    last one called wins."""
 
     def __init__(self, accel, width, height, samples, depth, camera, light=None, seed=0, bias=1e-3, compact=True, dynamic=None, rebuild=False,
                  deform=None, lights=None, fused_shadows=False, shadow_samples=1, light_radii=None):
@@ -170,6 +175,7 @@ class WavefrontPaths:
         self.rebuild_ratio = 1.5
         self.ao_samples, self.ao_distance, self.ao_counts = 0, math.inf, []
         self.gather_samples, self.gather_distance, self.gather_miss, self.gather_x, self.gather_sums, self.gather_open = 0, math.inf, 0, None, [], []
+        self.gather_placed = False  # which call the gather stage makes: final_gather_device, or placed_final_gather_device (with_placed_final_gather)
         self.deform = list(deform) if deform else []
         dev = torch.device("cuda", accel.device)
         rec = lambda: torch.zeros(self.n * 32, dtype=torch.uint8, device=dev)  # noqa: E731
@@ -231,21 +237,38 @@ class WavefrontPaths:
         frame.  ValueError for samples outside [0, 65536), a distance that is not > 0, a miss_value that is no u32,
         width*height*samples*samples >= 2^32 or an x of another kind -- all before a tensor is made.  A captured frame keeps the stage it
         was captured with, so it is refused here."""
+        return self._set_gather(False, x, samples, distance, miss_value)
+
+    def with_placed_final_gather(self, x, samples, distance=math.inf, miss_value=0):
+        """with_final_gather for a field per PLACED primitive: x is an int32 tensor of placed_primitive_count words on the accel's device
+        (u32 values, indexed by placed primitive q = base[instance] + l), and each depth runs one placed_final_gather_device instead.  The
+        same checks, buffers (gather_sums, gather_open) and refusal of a captured frame.  The frame has one gather stage: this call
+        replaces a with_final_gather stage and the other way round."""
+        return self._set_gather(True, x, samples, distance, miss_value)
+
+    def _set_gather(self, placed, x, samples, distance, miss_value):
+        """The body of the two gather switches: `placed` picks the index space of x and the call run() makes."""
         samples, distance, miss_value = check_gather_arguments(self.n, samples, distance, miss_value)
+        name = "with_placed_final_gather" if placed else "with_final_gather"
         if self._graph_stream is not None:
-            raise RaycoreError(1, "WavefrontPaths.with_final_gather: this frame is already captured")
+            raise RaycoreError(1, f"WavefrontPaths.{name}: this frame is already captured")
         import torch
         dev = torch.device("cuda", self.accel.device)
         if samples:
             if not isinstance(x, torch.Tensor) or x.dtype != torch.int32 or x.dim() != 1 or x.device != dev or not x.is_contiguous():
                 raise ValueError("x must be a contiguous one-dimensional int32 tensor on the accel's device")
-            if x.numel() != self.accel.n_primitives():
+            if placed:
+                count = int(self.accel.placed_primitive_bases()[-1])
+                if x.numel() != count:
+                    raise ValueError(f"x must hold one value per placed primitive: {x.numel()} values for {count} placed primitives")
+            elif x.numel() != self.accel.n_primitives():
                 raise ValueError(f"x must hold one value per primitive: {x.numel()} values for {self.accel.n_primitives()} primitives")
         sums = [torch.zeros(self.n, dtype=torch.int64, device=dev) for _ in range(self.depth)] if samples else []
         opened = [torch.zeros(self.n, dtype=torch.int32, device=dev) for _ in range(self.depth)] if samples else []
         torch.cuda.current_stream(dev).synchronize()  # (as in the constructor: a frame may run on another stream than the allocating one)
         self.gather_samples, self.gather_distance, self.gather_miss = samples, distance, miss_value
         self.gather_x, self.gather_sums, self.gather_open = (x if samples else None), sums, opened
+        self.gather_placed = bool(placed) and samples > 0
         self._streams = set()  # the new buffers are recorded on a stream at its next run()
         return self
 
@@ -304,10 +327,11 @@ class WavefrontPaths:
                 with torch.cuda.stream(s):  # the call accumulates: zero on the frame's stream, whichever stream is current
                     self.gather_sums[b].zero_()
                     self.gather_open[b].zero_()
-                a.final_gather_device(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.gather_samples, self.gather_x.data_ptr(),
-                                      self.gather_sums[b].data_ptr(), self.gather_open[b].data_ptr(), miss_value=self.gather_miss,
-                                      max_dist=self.gather_distance, seed=self.seed, depth=b, bias=self.bias,
-                                      d_path_in=self.path_ids[b].data_ptr(), stream=st)
+                gather = a.placed_final_gather_device if self.gather_placed else a.final_gather_device
+                gather(self.rays[b].data_ptr(), self.hits[b].data_ptr(), n, self.gather_samples, self.gather_x.data_ptr(),
+                       self.gather_sums[b].data_ptr(), self.gather_open[b].data_ptr(), miss_value=self.gather_miss,
+                       max_dist=self.gather_distance, seed=self.seed, depth=b, bias=self.bias,
+                       d_path_in=self.path_ids[b].data_ptr(), stream=st)
             if b + 1 >= self.depth:
                 break
             src = cnt = None
